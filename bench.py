@@ -8,6 +8,8 @@ on N MI355X GPUs of one node, one process per GPU.
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
   python bench.py --gpus N ...      (no launcher: the parent, which never touches a GPU, starts the N rank processes itself)
+  python bench.py --dump-outputs DIR  (also write the last timed step's loss and gradients as DIR/*.npy: same inputs every run,
+                                       so two builds can be compared output for output)
 
 A "step" = one fwd+bwd of one micro-batch of 32 x 1024 synthetic tokens per GPU through the fused
 lm_head+cross-entropy loss, including the per-step fp32->bf16 weight casts (what autocast does
@@ -206,6 +208,30 @@ def pmc_traffic(family, config, tokens, n_layers):
     return {'traffic_note': f'profiles/{os.path.basename(PMC_PROFILE)} could not be used: {type(e).__name__}: {e}'}
 
 
+DUMP_SAMPLE = 1 << 17  # gradient elements kept per parameter: at most 64 MB in all for every config of CONFIGS
+
+
+def dump_outputs(out_dir, model, loss):
+  """What the timed path hands its caller after its last step, as float32 / float64 .npy files: ``loss.npy`` (the step's mean
+  cross-entropy) and ``grad.<parameter name>.npy`` (the flat fp32 gradient the step wrote, mean over ranks in a data-parallel
+  run).  A gradient of more than DUMP_SAMPLE elements is sampled at DUMP_SAMPLE flat indices drawn without replacement by a
+  generator seeded with the parameter's name, in ascending order - the same elements in every run and every build."""
+  import zlib
+  os.makedirs(out_dir, exist_ok=True)
+  files = {'loss': np.array(loss, dtype=np.float64)}
+  for name, p in model.named_parameters():
+    g = p.main_grad.reshape(-1)
+    if g.numel() > DUMP_SAMPLE:
+      idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(g.numel(), DUMP_SAMPLE, replace=False))
+      g = g[torch.from_numpy(idx).to(g.device)]
+    files['grad.' + name] = g.float().cpu().numpy()
+  total = sum(v.nbytes for v in files.values())
+  if total > 64 << 20:
+    raise RuntimeError(f'--dump-outputs would write {total / 2**20:.1f} MiB (limit 64 MiB)')
+  for name, v in files.items():
+    np.save(os.path.join(out_dir, name + '.npy'), v)
+
+
 def spawn_ranks(n):
   """`python bench.py --gpus N` without a launcher: start the N rank processes (one per GPU) as children with the
   torch.distributed.run environment and hand back the worst exit code.  The parent never initialises HIP (importing torch
@@ -268,7 +294,12 @@ def main():
                        'two ranks on one device); the printed rate is NOT a throughput measurement and says so')
   ap.add_argument('--doc-mask', action='store_true',
                   help='BASELINE configs[4]: document-boundary attention masks (random documents, mean length ~256)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed steps, write what the last timed step computed (loss, a fixed sample of every parameter gradient) '
+                       'to DIR/<name>.npy')
   a = ap.parse_args()
+  if a.steps < 1:
+    ap.error('--steps must be at least 1')
 
   if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
     raise SystemExit(spawn_ranks(a.gpus))
@@ -426,6 +457,8 @@ def main():
   # FREEZE_AFTER + 1 - must land in the warm-up, whatever --warmup says)
   warm = max(a.warmup, ddp.FREEZE_AFTER + 1) if ddp_on else a.warmup
   elapsed, per_rank, last_loss = timed(warm, a.steps)
+  if a.dump_outputs and rank == 0:
+    dump_outputs(a.dump_outputs, model, last_loss)
   fpt = flops_per_token(c, hidden, pairs_per_token)
 
   def line(elapsed, last_loss):

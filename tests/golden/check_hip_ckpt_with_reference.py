@@ -3,8 +3,9 @@
 tests/test_model_gpu.py::test_engine_checkpoint_has_the_reference_layout writes the checkpoint of a HipEngine run
 (2 optimizer steps of the ckpt.npz fixture on an MI355X) to gpurun_out/hip_ckpt_step_2.pth together with the losses of its own
 next 4 micro-steps (hip_ckpt_cont.npz).  This script resumes the REFERENCE engine (engine/engine.py:56-60,86-89, CPU fp32)
-from that file, runs the same 4 micro-steps and compares; on success it installs both files under tests/golden/, where
-tests/test_oracle_golden.py::test_reference_resumes_hip_checkpoint repeats the check whenever /root/reference is present.
+from that file, runs the same 4 micro-steps and compares; on success it installs both files under tests/golden/ together with
+the reference's own losses (hip_ckpt_ref_resume.npz), which tests/test_oracle_golden.py::test_reference_resumes_hip_checkpoint
+checks the CPU oracle against without the reference.
 
   PYTHONDONTWRITEBYTECODE=1 python tests/golden/check_hip_ckpt_with_reference.py [dir with hip_ckpt_step_2.pth]
 """
@@ -47,6 +48,8 @@ def main():
   print('HipEngine continuing by itself                        :', np.round(hip, 6), ' rel', np.array2string(np.abs(got - hip) / hip, precision=2))
   print('reference engine resumed from ITS OWN checkpoint      :', np.round(ref, 6), ' rel', np.array2string(np.abs(got - ref) / ref, precision=2))
   assert (np.abs(got - hip) / hip).max() <= 1e-4 and (np.abs(got - ref) / ref).max() <= 1e-4
+  np.savez(os.path.join(HERE, 'hip_ckpt_ref_resume.npz'), losses=got)
+  print('wrote tests/golden/hip_ckpt_ref_resume.npz')
   if os.path.abspath(src) != HERE:
     shutil.copy(ck, os.path.join(HERE, 'hip_ckpt_step_2.pth'))
     shutil.copy(cont, os.path.join(HERE, 'hip_ckpt_cont.npz'))

@@ -195,6 +195,37 @@ def test_bench_metric_definition(monkeypatch):
       assert tr.get('traffic', 0) > tr.get('algorithmic_bytes', 1) > 0, (fam, tr)
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+  """bench.py --dump-outputs: loss.npy (float64) and one float32 grad.<name>.npy per parameter, the whole gradient when it is small,
+  else a sample at the same flat indices in every run; at most 64 MiB for every config of bench.CONFIGS."""
+  import bench
+  from plainlm_amd.transformer import ModelConfig, Transformer
+  with torch.device('meta'):
+    for c in bench.CONFIGS.values():
+      m = Transformer(ModelConfig(vocab_size=c['vocab_size'], seq_len=c['seq_len'], dim=c['d_model'], expand=8 / 3, n_layers=c['n_layers'],
+                                  n_heads=c['n_heads'], mlp='glu'))
+      assert 8 + sum(4 * min(p.numel(), bench.DUMP_SAMPLE) for p in m.parameters()) <= 64 << 20
+  torch.manual_seed(0)
+  model = Transformer(ModelConfig(vocab_size=256, seq_len=64, dim=128, expand=8 / 3, n_layers=2, n_heads=2, mlp='glu'))
+  flat = model.enable_main_grad()
+  flat.copy_(torch.randn(flat.numel()))
+  monkeypatch.setattr(bench, 'DUMP_SAMPLE', 1000)
+  bench.dump_outputs(str(tmp_path / 'a'), model, 5.25)
+  bench.dump_outputs(str(tmp_path / 'b'), model, 5.25)
+  names = [n for n, _ in model.named_parameters()]
+  assert sorted(os.listdir(tmp_path / 'a')) == sorted(['loss.npy'] + [f'grad.{n}.npy' for n in names])
+  loss = np.load(tmp_path / 'a' / 'loss.npy')
+  assert loss.dtype == np.float64 and loss.shape == () and loss == 5.25
+  for n, p in model.named_parameters():
+    a, b = np.load(tmp_path / 'a' / f'grad.{n}.npy'), np.load(tmp_path / 'b' / f'grad.{n}.npy')
+    assert a.dtype == np.float32 and np.array_equal(a, b)
+    g = p.main_grad.reshape(-1).numpy()
+    if g.size <= 1000:
+      assert np.array_equal(a, g)
+    else:
+      assert a.shape == (1000,) and np.isin(a, g).all() and len(np.unique(a)) == 1000
+
+
 def test_bucket_plan_160m_engine_layout():
   """FlatAdamW's placement at the 160M size: [25 norm weights | embed_tokens | 12 x (w_qkv, w_out, fc1, fc2) | lm_head].
   Walking it from the end (the order gradients become ready): lm_head alone goes first, the layers follow in <= 64 MiB

@@ -266,21 +266,40 @@ def test_bf16_mode_engine_tracks_the_reference_trajectory(mdl, golden_dir):
   assert 1e-7 < rel.max() <= 1e-4, rel  # rounding is on (non-zero) and harmless (<= 1e-4), also after the updates
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='needs the reference checkout (build container only)')
 def test_reference_resumes_hip_checkpoint(golden_dir):
   """SURVEY section 8f N4, HipEngine -> reference: tests/golden/hip_ckpt_step_2.pth was written on an MI355X by HipEngine
-  (test_engine_checkpoint_has_the_reference_layout); the REFERENCE engine (imported in a child process so that its
-  top-level packages do not shadow ours) resumes from it with engine/engine.py:56-60,86-89 and reproduces, within 1e-4,
-  both HipEngine's own continuation and the continuation the reference got from its own checkpoint."""
-  import subprocess
-  import sys
-  if not os.path.exists(os.path.join(golden_dir, 'hip_ckpt_step_2.pth')):
-    pytest.skip('no HipEngine checkpoint fixture yet')
-  env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1')
-  r = subprocess.run([sys.executable, os.path.join(golden_dir, 'check_hip_ckpt_with_reference.py'), golden_dir], env=env,
-                     capture_output=True, text=True, timeout=600)
-  assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-  assert 'reference engine resumed from the HipEngine checkpoint' in r.stdout
+  (test_engine_checkpoint_has_the_reference_layout); the REFERENCE engine resumed from it with engine/engine.py:56-60,86-89
+  and its next 4 micro-step losses are stored in hip_ckpt_ref_resume.npz (tests/golden/check_hip_ckpt_with_reference.py).
+  Those losses reproduce, within 1e-4, both HipEngine's own continuation and the continuation the reference got from its own
+  checkpoint; and the CPU oracle engine, resumed from the same file through the reference's checkpoint layout (model
+  state_dict, torch AdamW state in (decay, no-decay) group order, scheduler iter), reproduces the reference's losses."""
+  z = np.load(os.path.join(golden_dir, 'ckpt.npz'))
+  hip = np.load(os.path.join(golden_dir, 'hip_ckpt_cont.npz'))['losses']
+  ref = np.load(os.path.join(golden_dir, 'hip_ckpt_ref_resume.npz'))['losses']
+  own = z['losses'][4:]
+  assert ref.shape == hip.shape == own.shape == (4,)
+  assert (np.abs(ref - hip) / hip).max() <= 1e-4 and (np.abs(ref - own) / own).max() <= 1e-4
+  ck = torch.load(os.path.join(golden_dir, 'hip_ckpt_step_2.pth'), map_location='cpu', weights_only=False)
+  assert set(ck) == {'step', 'state_dict', 'optimizer', 'scheduler', 'scaler'} and ck['step'] == 2
+  cfg = O.OracleConfig(vocab_size=128, seq_len=32, dim=64, n_layers=2, n_heads=1)
+  names = list(ck['state_dict'])
+  assert names == O.param_names(cfg)
+  eng = O.OracleEngine(ck['state_dict'], cfg, lr=3e-3, weight_decay=0.1, beta1=0.9, beta2=0.95, grad_clip=1.0, accum=2,
+                       steps_budget=8, warmup_steps=2)
+  decay = O.decay_mask(names)
+  order = [n for n in names if decay[n]] + [n for n in names if not decay[n]]
+  groups = ck['optimizer']['param_groups']
+  assert [g['weight_decay'] for g in groups] == [0.1, 0.0] and sum(len(g['params']) for g in groups) == len(order)
+  for i, n in enumerate(order):
+    st = ck['optimizer']['state'][i]
+    assert st['exp_avg'].shape == eng.params[n].shape and int(st['step']) == 2, n
+    eng.m[n], eng.v[n] = st['exp_avg'].clone(), st['exp_avg_sq'].clone()
+  eng.opt_step = 2
+  eng.sched_iter = ck['scheduler']['iter']
+  eng.lr = O.warmup_cosine_lr(eng.sched_iter, 0.0, 3e-3, 1e-5, 2, 8)
+  tok = torch.from_numpy(z['tokens'])
+  got = np.array([eng.step({'input_ids': tok[i]}).item() for i in range(4, 8)])
+  assert (np.abs(got - ref) / ref).max() <= 2e-6, (got, ref)
 
 
 def test_lr_schedules_vs_reference(golden_dir):
