@@ -529,7 +529,9 @@ def attn_fwd(qkv_rot, B, T, nh, doc_start=None, plan=None):
   return out, lse
 
 
-def attn_bwd(qkv, out, dout, lse, rope_cos, rope_sin, B, T, nh, doc_start=None, plan=None):
+def attn_bwd(qkv, out, dout, lse, rope_cos, rope_sin, B, T, nh, doc_start=None, plan=None, return_delta=False):
+  """dqkv w.r.t. the UN-rotated projection.  return_delta: also return the kernels' delta = rowsum(dO * O), fp32 [B, nh, T] (the hd = 64
+  families store it negated for their dK/dV kernel; it is returned here with the plain sign)."""
   _need(dout, BF16, 'attn_bwd.dout', 2)
   hd = qkv.shape[1] // (3 * nh)
   if doc_start is not None and plan is None:
@@ -540,6 +542,8 @@ def attn_bwd(qkv, out, dout, lse, rope_cos, rope_sin, B, T, nh, doc_start=None, 
   with _Timed('attn_bwd', 2.0 * attn_flops(B, T, nh, hd, doc_start) if PROFILE is not None else 0.0):
     _lib.check(_lib.load().plm_attn_bwd(_p(qkv), _p(out), _p(dout), _p(lse), _p(rope_cos), _p(rope_sin), _p(doc_start), _p(plan),
                                         _p(dqkv), _p(delta), B, T, nh, hd, _stream()), 'plm_attn_bwd')
+  if return_delta:
+    return dqkv, (-delta if hd == 64 else delta)
   return dqkv
 
 

@@ -23,6 +23,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import cpu_ref as O  # noqa: E402
+from oracle import parity as PB  # noqa: E402
 
 LOSS_RTOL = 1e-4
 
@@ -106,8 +107,14 @@ def test_attention_bench_grid_vs_oracle(ops, B, T, nh, masked):
   out2, lse2 = ops.attn_fwd(qrot, B, T, nh, dsg)
   dqkv2 = ops.attn_bwd(qrot, out2, dout.cuda(), lse2, cg, sg, B, T, nh, dsg)
   assert torch.equal(out, out2) and torch.equal(lse, lse2) and torch.equal(dqkv, dqkv2)
-  out_c, dqkv_c = out.float().cpu(), dqkv.float().cpu()
+  out_c, dqkv_c, qrot_c = out.float().cpu(), dqkv.float().cpu(), qrot.cpu()
   worst = {'out': 0.0, 'dq': 0.0, 'dk': 0.0, 'dv': 0.0}
+  budget = {}  # oracle/parity.py's metrics: row-local and per-(row, head) projection worst over the batch, whole-tensor projection summed over it
+  dots = {n: [0.0, 0.0] for n in worst}
+
+  def keep(key, val):
+    budget[key] = max(budget.get(key, 0.0), val)
+
   for b in range(B):
     rows = slice(b * T, (b + 1) * T)
     leaf = qkv[rows].float().requires_grad_(True)
@@ -117,9 +124,30 @@ def test_attention_bench_grid_vs_oracle(ops, B, T, nh, masked):
     worst['out'] = max(worst['out'], relerr(out_c[rows], ref))
     for i, n in enumerate(('dq', 'dk', 'dv')):
       worst[n] = max(worst[n], relerr(dqkv_c[rows, i * d:(i + 1) * d], leaf.grad[:, i * d:(i + 1) * d]))
+    # the budget's reference starts from the rotated bf16 q, k the kernels saw (fp32 here: fp64 at this size would cost the suite ~20 s)
+    rot = qrot_c[rows].float().requires_grad_(True)
+    qr, kr, vr = (t.reshape(1, T, nh, 64) for t in rot.split(d, dim=1))
+    ref_r = O.attention(qr, kr, vr, None if ds is None else ds[b:b + 1]).reshape(T, d)
+    ref_r.backward(dout[rows].float())
+    pairs = {'out': (out_c[rows], ref_r.detach())}
+    pairs.update({n: (dqkv_c[rows, i * d:(i + 1) * d], rot.grad[:, i * d:(i + 1) * d]) for i, n in enumerate(('dq', 'dk', 'dv'))})
+    pairs = {n: (PB.heads(g, 1, T, nh, 64), PB.heads(r, 1, T, nh, 64)) for n, (g, r) in pairs.items()}
+    for n in ('dq', 'dk'):  # gradient w.r.t. the un-rotated projection, as the kernels return it
+      pairs[n] = (pairs[n][0], PB.rope64(pairs[n][1], cos, sin, -1.0))
+    gscale = max(pairs[n][1].abs().max().item() for n in ('dq', 'dk', 'dv'))
+    for n, (g, r) in pairs.items():
+      sc = None if n == 'out' else gscale
+      keep('row_' + n, PB.row_local(g, r, sc))
+      keep('proj_slice_' + n, PB.projection(g, r, sc)[1])
+      dots[n][0] += (g.flatten() @ r.flatten()).item()
+      dots[n][1] += (r.flatten() @ r.flatten()).item()
+  for n, (gr, rr) in dots.items():
+    budget['proj_' + n] = abs(gr / rr - 1.0)
   print(f'attention B={B} T={T} nh={nh} masked={masked}: worst rel-to-max per batch row {worst}')
+  print(f'parity bench grid B={B} T={T} nh={nh} masked={masked}: ' + ' '.join(f'{k}={v:.2e}' for k, v in budget.items()))
   assert worst['out'] <= 1.6e-2, worst
   assert max(worst['dq'], worst['dk'], worst['dv']) <= 2e-2, worst
+  assert not PB.violations(budget), PB.violations(budget)
 
 
 # --------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import cpu_ref as O  # noqa: E402
+from oracle import parity as PB  # noqa: E402
 
 
 @pytest.fixture(scope='module')
@@ -566,6 +567,12 @@ def _attn_ref(qkv, B, T, nh, doc_start, hd=64):
   return O.attention(qr, kr, v, doc_start).reshape(B * T, nh * hd)
 
 
+def _budget(qrot, dout, B, T, nh, ds, tag, hd=64, out=None, lse=None, dqkv=None, delta=None):
+  """oracle/parity.py's error budget (row-local, projection, LSE, delta) against fp64 from the bf16 operands the kernels saw."""
+  ref = PB.reference(qrot, dout, B, T, nh, hd, ds, out=out, rope=O.rope_table(hd, T))
+  return PB.check(PB.kernel_result(B, T, nh, hd, out, lse, dqkv, delta), ref, tag)
+
+
 def _random_docs(B, T, seed):
   rng = np.random.default_rng(seed)
   out = []
@@ -602,6 +609,7 @@ def test_attention_fwd_bwd(ops, B, T, nh, masked):
   close(dv, gv, 2e-2, 'attention dV')
   close(dk, gk, 2e-2, 'attention dK')
   close(dq, gq, 2e-2, 'attention dQ')
+  _budget(qrot, dout, B, T, nh, ds, f'B={B} T={T} nh={nh} masked={masked}', out=out, lse=lse, dqkv=dqkv)
 
 
 def _plan_ref(ds, T, nh, split_min=8):
@@ -713,6 +721,7 @@ def test_attention_doc_mask_structures(ops, kind):
       assert got.float().abs().max().item() <= 1e-2 * leaf.grad[:, 2 * d:].abs().max().item()
       continue
     close(got.float(), want, 2e-2, f'attention d{name} [{kind}]')
+  _budget(qrot, dout, B, T, nh, ds, kind, out=out, lse=lse, dqkv=dqkv)
   out2, lse2 = ops.attn_fwd(qrot, B, T, nh, dsg)
   dqkv2 = ops.attn_bwd(qrot, out2, dout.cuda(), lse2, cos, sin, B, T, nh, dsg)
   assert torch.equal(out, out2) and torch.equal(lse, lse2) and torch.equal(dqkv, dqkv2)
@@ -791,6 +800,7 @@ def test_attention_doc_masks_random_shapes(ops):
     for name, got, want in zip('qkv', dqkv.split(d, dim=1), leaf.grad.split(d, dim=1)):
       err = (got.float().cpu() - want).abs().max().item()
       assert err <= 2e-2 * max(want.abs().max().item(), 0.05 * scale), (tag, name, err)  # (short documents: dQ / dK are nearly zero, judged on dV's scale)
+    _budget(qrot, dout, B, T, nh, ds, tag, out=out, lse=lse, dqkv=dqkv)
 
 
 @pytest.mark.parametrize('hd', [32, 128])
@@ -815,6 +825,7 @@ def test_attention_other_head_dims(ops, hd, B, T, nh, masked):
   dqkv = ops.attn_bwd(qrot, out, dout.cuda(), lse, cos, sin, B, T, nh, dsg)
   for name, got, want in zip('qkv', dqkv.split(d, dim=1), leaf.grad.split(d, dim=1)):
     close(got.float(), want, 2e-2, f'attention d{name} (hd {hd})')
+  _budget(qrot, dout, B, T, nh, ds, f'hd {hd} B={B} T={T} nh={nh} masked={masked}', hd=hd, out=out, lse=lse, dqkv=dqkv)
   out2, lse2 = ops.attn_fwd(qrot, B, T, nh, dsg)
   assert torch.equal(out, out2) and torch.equal(dqkv, ops.attn_bwd(qrot, out2, dout.cuda(), lse2, cos, sin, B, T, nh, dsg))
 
@@ -877,8 +888,72 @@ def test_attention_softmax_rescale_branch(ops):
   qkv = bf(qkv)
   ref = _attn_ref(qkv, B, T, nh, None)
   cos, sin = (t.cuda() for t in O.rope_table(64, T))
-  out, _ = ops.attn_fwd(ops.rope_qk_(qkv.cuda(), cos, sin, B, T, nh), B, T, nh)
+  qrot = ops.rope_qk_(qkv.cuda(), cos, sin, B, T, nh)
+  out, lse = ops.attn_fwd(qrot, B, T, nh)
   close(out.float(), ref, 1.6e-2, 'attention with max jump')
+  _budget(qrot, torch.zeros(B * T, d, dtype=torch.bfloat16), B, T, nh, None, 'max jump', out=out, lse=lse)
+
+
+def _stat_case(ops, hd, B, T, nh, masked):
+  g = torch.Generator().manual_seed(7 * T + hd + nh + masked)
+  d = nh * hd
+  qkv = bf(torch.randn(B * T, 3 * d, generator=g))
+  dout = bf(torch.randn(B * T, d, generator=g))
+  ds = O.doc_start_from_lengths(_random_docs(B, T, 5 * T + hd), T) if masked else None
+  cos, sin = (t.cuda() for t in O.rope_table(hd, T))
+  qrot = ops.rope_qk_(qkv.cuda(), cos, sin, B, T, nh)
+  return dout, ds, None if ds is None else ds.cuda(), cos, sin, qrot
+
+
+_STAT_CASES = [(64, 2, 320, 2, False), (64, 1, 1024, 2, False), (64, 2, 512, 2, True), (64, 3, 836, 2, True),
+               (32, 2, 200, 3, False), (32, 2, 512, 2, True), (128, 2, 200, 3, False), (128, 2, 512, 2, True)]
+
+
+@pytest.mark.parametrize('hd,B,T,nh,masked', _STAT_CASES)
+def test_attention_lse_vs_fp64(ops, hd, B, T, nh, masked):
+  """The forward's base-2 LSE [B, nh, T] against fp64 logsumexp(q k^T / sqrt(hd)) * log2(e), to fp32 level in absolute log2 units: every
+  family (causal, document-masked, the generic hd 32 / 128 kernels).  Every row sees at least its own key, so every LSE is finite."""
+  dout, ds, dsg, cos, sin, qrot = _stat_case(ops, hd, B, T, nh, masked)
+  out, lse = ops.attn_fwd(qrot, B, T, nh, dsg)
+  assert torch.isfinite(lse).all()
+  _budget(qrot, dout, B, T, nh, ds, f'lse hd {hd} B={B} T={T} nh={nh} masked={masked}', hd=hd, lse=lse)
+
+
+@pytest.mark.parametrize('hd,B,T,nh,masked', _STAT_CASES)
+def test_attention_delta_vs_fp64(ops, hd, B, T, nh, masked):
+  """The backward's delta = rowsum(dO * O) [B, nh, T] against fp64 from the kernel's own bf16 out, relative to rowsum |dO * O|."""
+  dout, ds, dsg, cos, sin, qrot = _stat_case(ops, hd, B, T, nh, masked)
+  out, lse = ops.attn_fwd(qrot, B, T, nh, dsg)
+  _, delta = ops.attn_bwd(qrot, out, dout.cuda(), lse, cos, sin, B, T, nh, dsg, return_delta=True)
+  _budget(qrot, dout, B, T, nh, ds, f'delta hd {hd} B={B} T={T} nh={nh} masked={masked}', hd=hd, out=out, delta=delta)
+
+
+@pytest.mark.parametrize('B,T,nh,layout', [(2, 512, 2, 'causal'), (2, 1024, 2, 'split'), (100, 1024, 1, 'random')])
+def test_attention_bwd_decoupled_from_fwd(ops, B, T, nh, layout):
+  """The backward fed the fp64 reference's out (rounded to bf16) and LSE instead of the forward's: a backward leaning on a quirk of the
+  forward's out / lse would show here.  Causal; long documents whose heaviest 128-row tiles the plan splits into 64-row items; 800 tiles,
+  a plan in tile order (past the sort's limit).  Same budget as with the forward's own out / lse."""
+  g = torch.Generator().manual_seed(11 * T + B)
+  d = nh * 64
+  qkv = bf(torch.randn(B * T, 3 * d, generator=g))
+  dout = bf(torch.randn(B * T, d, generator=g))
+  ds = None
+  if layout == 'split':
+    ds = O.doc_start_from_lengths([[700, 325], [T + 1]], T)
+    _, items, _ = _plan_ref(ds.numpy(), T, nh)
+    assert any(it[3] >> 30 for it in items)  # the plan really has split items
+  elif layout == 'random':
+    ds = O.doc_start_from_lengths(_random_docs(B, T, T), T)
+    assert B * ((T + 127) // 128) > 768
+  dsg = None if ds is None else ds.cuda()
+  cos, sin = O.rope_table(64, T)
+  qrot = ops.rope_qk_(qkv.cuda(), cos.cuda(), sin.cuda(), B, T, nh)
+  ref = PB.reference(qrot, dout, B, T, nh, 64, ds, rope=(cos, sin))
+  out_ref = bf(PB.to_rows(ref['out']))
+  ref['delta'], ref['delta_abs'] = PB.delta_reference(PB.heads(out_ref, B, T, nh, 64), PB.heads(dout, B, T, nh, 64))
+  dqkv, delta = ops.attn_bwd(qrot, out_ref.cuda(), dout.cuda(), ref['lse'].float().cuda(), cos.cuda(), sin.cuda(), B, T, nh, dsg,
+                             return_delta=True)
+  PB.check(PB.kernel_result(B, T, nh, 64, dqkv=dqkv, delta=delta), ref, f'decoupled backward B={B} T={T} nh={nh} {layout}')
 
 
 def test_attention_golden(ops, golden_dir):
