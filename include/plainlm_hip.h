@@ -252,6 +252,37 @@ typedef struct plm_adamw_item {
 int plm_adamw_cast_multi(const plm_adamw_item* items, int count, float lr, float beta1, float beta2, float eps,
                          float weight_decay, float bc1, float bc2, const float* clip_coef_dev, void* stream);
 
+/* The reference's other optimizers (optim/init_optim.py:7-70) on the same two launch shapes, selected by h->kind.  g is
+ * pre-multiplied by *clip_coef_dev (NULL = 1) as in plm_adamw_f32; the flat and the multi-tensor form give the same bits
+ * per element.  Scalars are host-computed per group and step:
+ *   PLM_OPTIM_NADAMW   torch.optim.NAdam(decoupled_weight_decay=True):
+ *     p *= decay ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; d = sqrt(v / bc2) + eps ;
+ *     p -= coef_grad * g / d + coef_avg * m / d
+ *     (coef_grad = lr (1 - mu_t) / (1 - prod mu), coef_avg = lr mu_{t+1} / (1 - prod mu * mu_{t+1}); needs m and v)
+ *   PLM_OPTIM_SGD      torch.optim.SGD(momentum, dampening, weight_decay), nesterov off (coupled L2):
+ *     d = g + weight_decay p ; momentum != 0: m = first ? d : momentum m + (1-dampening) d, p -= lr m ;
+ *     momentum == 0: p -= lr d (m is neither read nor written and may be NULL); v must be NULL
+ *   PLM_OPTIM_SIGNSGD  the reference's optim/signSGD.py:
+ *     p *= decay ; m = momentum (first ? g : m) + (1-dampening) g ; p -= lr sign(m)  (sign(0) = 0); v must be NULL
+ * `first` = 1 initialises the momentum buffer (SGD: torch's missing momentum_buffer; signSGD: the missing 'm').
+ * decay = 1 - lr * weight_decay, rounded once from the host's double, as torch passes it to p.mul_().  The multi-tensor form
+ * takes plm_adamw_item lists (v = NULL for SGD / signSGD) and writes the bf16 shadows like plm_adamw_cast_multi.  An unknown
+ * kind, a missing or superfluous state buffer, or a shape / alignment plm_adamw_cast_multi would refuse gives PLM_E_INVALID
+ * before anything is launched. */
+#define PLM_OPTIM_NADAMW 1
+#define PLM_OPTIM_SGD 2
+#define PLM_OPTIM_SIGNSGD 3
+typedef struct plm_optim_hparams {
+  int kind;   /* PLM_OPTIM_* */
+  int first;  /* 1: initialise the momentum buffer this step (SGD / signSGD) */
+  float lr, weight_decay, decay, beta1, beta2, eps, momentum, dampening;
+  float bc2, coef_grad, coef_avg; /* NAdamW */
+} plm_optim_hparams;
+int plm_optim_f32(const plm_optim_hparams* h, float* p, const float* g, float* m, float* v, int64_t n,
+                  const float* clip_coef_dev, void* stream);
+int plm_optim_cast_multi(const plm_optim_hparams* h, const plm_adamw_item* items, int count, const float* clip_coef_dev,
+                         void* stream);
+
 /* Leave `n` CUs free when sizing the persistent GEMM grids (one workgroup per CU, static tile schedule), so that
  * concurrently running RCCL collectives do not push GEMM workgroups into a second round.  Process-wide; 0 = whole chip. */
 int plm_set_cu_reserve(int n);

@@ -139,17 +139,33 @@ def initialize_scheduler(optimizer, cfg):
 
 
 def intialize_optimizer(param_groups, cfg, model=None):
-  """(sic) optim/init_optim.py:7-21 — AdamW is the only optimizer on the shipped configs' path.
-  ``fused_optim: True`` (the shipped configs) selects FlatAdamW: clip + AdamW on flat buffers with our kernels;
-  ``False`` keeps torch.optim.AdamW on the per-parameter views."""
-  if cfg.optim != 'adamw':
-    raise NotImplementedError(f'Not implemented optim: {cfg.optim}.')
-  if bool(getattr(cfg, 'fused_optim', True)) and model is not None:
-    from .optim import FlatAdamW
-    return FlatAdamW(model, param_groups, lr=cfg.lr, betas=[cfg.beta1, cfg.beta2], eps=getattr(cfg, 'eps', 1e-8),
-                     weight_decay=cfg.weight_decay)
-  return torch.optim.AdamW(param_groups, lr=cfg.lr, betas=[cfg.beta1, cfg.beta2], weight_decay=cfg.weight_decay,
-                           eps=getattr(cfg, 'eps', 1e-8))
+  """(sic) optim/init_optim.py:7-70: adamw, nadamw, sgd and signSGD.
+  ``fused_optim: True`` (the shipped configs) with a model selects the flat optimizers of plainlm_amd.optim (clip + update on flat
+  buffers with our kernels); ``False`` keeps the torch optimizers on the per-parameter views (for signSGD: optim.SignSGD, the
+  reference's arithmetic).  The reference also passes ``fused=cfg.fused_optim`` to torch.optim.NAdam, which torch 2.10 does not
+  accept; for NAdam ``fused_optim`` here selects only our flat path against torch's.  sfo_adamw needs the schedulefree package
+  and is not implemented."""
+  name = cfg.optim
+  if name not in ('adamw', 'nadamw', 'sgd', 'signSGD'):
+    raise NotImplementedError(f'Not implemented optim: {name}.')
+  if name in ('sgd', 'signSGD') and not hasattr(cfg, 'dampening'):
+    raise ValueError(f"optim '{name}' needs the config key 'dampening' (the reference reads cfg.dampening)")
+  eps = getattr(cfg, 'eps', 1e-8)
+  flat = bool(getattr(cfg, 'fused_optim', True)) and model is not None
+  from . import optim as O
+  if name == 'adamw':
+    if flat:
+      return O.FlatAdamW(model, param_groups, lr=cfg.lr, betas=[cfg.beta1, cfg.beta2], eps=eps, weight_decay=cfg.weight_decay)
+    return torch.optim.AdamW(param_groups, lr=cfg.lr, betas=[cfg.beta1, cfg.beta2], weight_decay=cfg.weight_decay, eps=eps)
+  if name == 'nadamw':
+    if flat:
+      return O.FlatNAdamW(model, param_groups, lr=cfg.lr, betas=[cfg.beta1, cfg.beta2], eps=eps, weight_decay=cfg.weight_decay)
+    return torch.optim.NAdam(param_groups, lr=cfg.lr, betas=[cfg.beta1, cfg.beta2], weight_decay=cfg.weight_decay,
+                             decoupled_weight_decay=True, eps=eps)
+  kw = dict(lr=cfg.lr, momentum=cfg.beta1, dampening=cfg.dampening, weight_decay=cfg.weight_decay)
+  if name == 'sgd':
+    return O.FlatSGD(model, param_groups, **kw) if flat else torch.optim.SGD(param_groups, **kw)
+  return O.FlatSignSGD(model, param_groups, **kw) if flat else O.SignSGD(param_groups, **kw)
 
 
 def doc_start_from_lengths(docs_lengths, seq_len):

@@ -628,6 +628,59 @@ def adamw_cast_multi_(items, lr, beta1, beta2, eps, weight_decay, step, clip_coe
   return table
 
 
+_OPTIM_KINDS = {'nadamw': _lib.OPTIM_NADAMW, 'sgd': _lib.OPTIM_SGD, 'signSGD': _lib.OPTIM_SIGNSGD}
+
+
+def optim_hparams(kind, lr, weight_decay=0.0, first=False, beta1=0.0, beta2=0.0, eps=0.0, momentum=0.0, dampening=0.0, bc2=1.0,
+                  coef_grad=0.0, coef_avg=0.0):
+  """struct plm_optim_hparams for optim_ / optim_cast_multi_.  kind: 'nadamw' | 'sgd' | 'signSGD' (an int is passed through as is).
+  decay = 1 - lr * weight_decay is formed here in double and rounded once, the value torch hands to p.mul_()."""
+  k = _OPTIM_KINDS[kind] if isinstance(kind, str) else int(kind)
+  return _lib.OptimHparams(k, int(bool(first)), lr, weight_decay, 1.0 - lr * weight_decay, beta1, beta2, eps, momentum, dampening, bc2,
+                           coef_grad, coef_avg)
+
+
+def nadam_scalars(lr, beta1, beta2, momentum_decay, step, mu_product):
+  """torch.optim.NAdam's per-step host scalars for step `step` (1-based), given the product of the earlier steps' mu.
+  Returns (bc2, coef_grad, coef_avg, mu_product including this step's mu)."""
+  mu = beta1 * (1.0 - 0.5 * 0.96 ** (step * momentum_decay))
+  mu_next = beta1 * (1.0 - 0.5 * 0.96 ** ((step + 1) * momentum_decay))
+  mu_product = mu_product * mu
+  return 1.0 - beta2 ** step, lr * (1.0 - mu) / (1.0 - mu_product), lr * mu_next / (1.0 - mu_product * mu_next), mu_product
+
+
+def optim_(hp, p, g, m, v, clip_coef=None):
+  """One NAdamW / SGD / signSGD step on a flat fp32 span (hp from optim_hparams).  m / v: None where the kind has no such buffer."""
+  for t, n in ((p, 'p'), (g, 'g'), (m, 'm'), (v, 'v')):
+    if t is not None:
+      _need(t, F32, 'optim.' + n)
+      if t.numel() != p.numel():
+        raise ValueError(f'optim.{n}: {t.numel()} elements, p has {p.numel()}')
+  _lib.check(_lib.load().plm_optim_f32(C.byref(hp), _p(p), _p(g), _p(m), _p(v), p.numel(), _p(clip_coef), _stream()), 'plm_optim_f32')
+
+
+def optim_cast_multi_(hp, items, clip_coef=None, table=None):
+  """optim_ on a list of Linear weights that also writes their bf16 shadows: items = [(p, g, m, v, dst, dst_t)] as for adamw_cast_multi_,
+  with v (and m for SGD without momentum) None.  Returns the ctypes item table; pass it back as `table` on later steps."""
+  if table is None:
+    table = (_lib.AdamwItem * len(items))()
+    for i, (p, g, m, v, dst, dst_t) in enumerate(items):
+      for t, n in ((p, 'p'), (g, 'g'), (m, 'm'), (v, 'v')):
+        if t is not None:
+          _need(t, F32, 'optim_cast_multi.' + n, 2)
+          if t.shape != p.shape:
+            raise ValueError(f'optim_cast_multi.{n}: shape {tuple(t.shape)}, p has {tuple(p.shape)}')
+      R, Cc = p.shape
+      if dst.dtype != BF16 or tuple(dst.shape) != (R, Cc) or not dst.is_contiguous() or not dst.is_cuda:
+        raise ValueError('optim_cast_multi.dst: need contiguous bf16 [rows, cols] on the GPU')
+      if dst_t.dtype != BF16 or dst_t.dim() != 2 or dst_t.shape[0] != Cc or dst_t.shape[1] < R or dst_t.stride(1) != 1 or not dst_t.is_cuda:
+        raise ValueError('optim_cast_multi.dst_t: need bf16 [cols, >= rows] on the GPU')
+      ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+      table[i] = _lib.AdamwItem(p.data_ptr(), g.data_ptr(), ptr(m), ptr(v), dst.data_ptr(), dst_t.data_ptr(), R, Cc, dst_t.stride(0))
+  _lib.check(_lib.load().plm_optim_cast_multi(C.byref(hp), table, len(table), _p(clip_coef), _stream()), 'plm_optim_cast_multi')
+  return table
+
+
 # ---- probes -------------------------------------------------------------------------------
 def probe_ds_read_tr16():
   out = torch.empty(256, dtype=torch.int32, device='cuda')

@@ -1,4 +1,4 @@
-"""Optimizer tail on the gfx950 kernels (engine/engine.py:126-135, optim/init_optim.py:14-21).
+"""Optimizer tail on the gfx950 kernels (engine/engine.py:126-135, optim/init_optim.py:7-70).
 
 ``FlatAdamW`` is a ``torch.optim.AdamW`` subclass, so ``engine.optimizer`` keeps the reference's interface
 (``param_groups`` with per-group ``lr`` written by the LR schedule, ``state_dict()`` / ``load_state_dict()`` in
@@ -11,18 +11,65 @@ torch's layout: per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq``), but
 
 Arithmetic matches ``torch.optim.AdamW`` (decoupled decay ``p *= 1 - lr*wd``; bias-corrected moments;
 ``denom = sqrt(v)/sqrt(bc2) + eps``) and ``torch.nn.utils.clip_grad_norm_``.
+
+The reference's other optimizers get the same treatment (same layout, clip and shadow emission, torch-layout state):
+``FlatNAdamW`` (``torch.optim.NAdam(decoupled_weight_decay=True)``: ``step`` / ``mu_product`` / ``exp_avg`` / ``exp_avg_sq``),
+``FlatSGD`` (``torch.optim.SGD``, nesterov off: ``momentum_buffer``) and ``FlatSignSGD`` (``SignSGD`` below, the arithmetic of the
+reference's optim/signSGD.py: ``m``).
 """
+
+import os
 
 import torch
 
 from . import ops
 
 
-class FlatAdamW(torch.optim.AdamW):
-  def __init__(self, model, param_groups, lr, betas, eps, weight_decay):
-    super().__init__(param_groups, lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, fused=False, foreach=False)
+class SignSGD(torch.optim.Optimizer):
+  """signSGD / signum with the reference's arithmetic (optim/signSGD.py), per parameter and step:
+  ``p *= 1 - lr*wd``; ``m`` starts as a copy of the first gradient and is then updated ``m = momentum*m + (1 - dampening)*g``
+  on every step, the first one included (so the first ``m`` is ``(momentum + 1 - dampening)*g``); ``p -= lr*sign(m)``.
+  State: ``m`` per parameter (no ``step``).  Parameters without a gradient are skipped."""
+
+  def __init__(self, params, lr, momentum=0.0, dampening=0.0, weight_decay=0.1):
+    for name, val, hi in (('learning rate', lr, None), ('momentum', momentum, 1.0), ('dampening', dampening, 1.0),
+                          ('weight decay', weight_decay, None)):
+      if not (val >= 0.0 and (hi is None or val <= hi)):
+        raise ValueError(f'SignSGD: invalid {name}: {val}')
+    super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay))
+
+  @torch.no_grad()
+  def step(self, closure=None):
+    loss = None
+    if closure is not None:
+      with torch.enable_grad():
+        loss = closure()
+    for group in self.param_groups:
+      lr, mom, damp, wd = group['lr'], group['momentum'], group['dampening'], group['weight_decay']
+      for p in group['params']:
+        if p.grad is None:
+          continue
+        st = self.state[p]
+        p.mul_(1 - lr * wd)
+        if 'm' not in st:
+          st['m'] = p.grad.detach().clone()
+        m = st['m']
+        m.mul_(mom).add_(p.grad, alpha=1.0 - damp)
+        p.add_(m.sign(), alpha=-lr)
+    return loss
+
+
+class _FlatTail:
+  """What every flat optimizer shares, mixed in front of its torch class: the flat re-layout of parameters, gradients and state
+  buffers (one span per parameter group), the model's gradient span table, the shadow-emitting launch plan, ``clip_and_step``,
+  ``step`` and ``zero_grad``.  Subclasses name their per-parameter state buffers (``_state_names``, torch's keys) and implement
+  ``_group_hparams`` / ``_publish_state`` / ``_restore_host_state``; ``_update_multi`` / ``_update_flat`` launch the update."""
+
+  _state_names = ()
+
+  def _lay_out(self, model):
     if getattr(model, '_flat_grad', None) is None:
-      raise RuntimeError('FlatAdamW needs model.enable_main_grad() first (flat gradient buffer)')
+      raise RuntimeError(f'{type(self).__name__} needs model.enable_main_grad() first (flat gradient buffer)')
     self.model = model
     dev = model._flat_grad.device
     # Re-lay parameters and gradients group by group so that every group is ONE contiguous span.
@@ -31,8 +78,9 @@ class FlatAdamW(torch.optim.AdamW):
       raise ValueError('param_groups must cover every model parameter exactly once')
     total = sum(p.numel() for p in order)
     self.flat_p = torch.empty(total, dtype=torch.float32, device=dev)
-    self.flat_m = torch.zeros(total, dtype=torch.float32, device=dev)
-    self.flat_v = torch.zeros(total, dtype=torch.float32, device=dev)
+    # state buffers, padded to two (the kernels' m and v; None where the optimizer has no such buffer)
+    bufs = [torch.zeros(total, dtype=torch.float32, device=dev) for _ in self._state_names]
+    self._state_bufs = bufs + [None] * (2 - len(bufs))
     self.flat_g = model._flat_grad
     if self.flat_g.numel() != total:
       raise ValueError('flat gradient buffer does not match the parameter groups')
@@ -55,7 +103,7 @@ class FlatAdamW(torch.optim.AdamW):
         p.data = self.flat_p[off:off + n].view(p.shape)
         p.main_grad = self.flat_g[off:off + n].view(p.shape)
         spans_by_param[id(p)] = (off, n)
-        self._views[id(p)] = (self.flat_m[off:off + n].view(p.shape), self.flat_v[off:off + n].view(p.shape))
+        self._views[id(p)] = tuple(b[off:off + n].view(p.shape) if b is not None else None for b in self._state_bufs)
         off += n
       self.group_spans[gi] = (lo, off)
     # the model's span table (used by the gradient reducer) follows parameters() order
@@ -64,12 +112,10 @@ class FlatAdamW(torch.optim.AdamW):
     self._scratch = torch.empty(4096, dtype=torch.float32, device=dev)
     self._step_count = 0
     self.last_grad_norm = None
-    self._publish_state()
     # SURVEY section 8f N1, second half: the Linear weights' update also writes their bf16 shadows (W and W^T), so the training step has
     # no stand-alone weight cast (what autocast does per forward, engine/engine.py:75).  Per weight-decay group: the Linear weights
     # of the group (one fused launch) + the rest of its span (embed_tokens / the norm weights: flat kernel).  PLM_ADAMW_SHADOWS=0
     # restores the flat kernel for everything + invalidated shadows.
-    import os
     self.emits_shadows = os.environ.get('PLM_ADAMW_SHADOWS', '1') != '0' and hasattr(model, 'linear_modules')
     self._fused = [None] * len(self.param_groups)  # per group: (linear modules, item tensors, ctypes table or None, leftover [(lo, hi)])
     if self.emits_shadows:
@@ -82,8 +128,7 @@ class FlatAdamW(torch.optim.AdamW):
         for lin in lins:
           w = lin.weight
           lin.stale_item()  # allocates the shadow buffers
-          mview, vview = self._views[id(w)]
-          items.append((w.data, w.main_grad, mview, vview, lin._shadow[0], lin._shadow[1]))
+          items.append(self._item(lin))
           taken.append(spans_by_param[id(w)])
         lo, hi = self.group_spans[gi]
         rest, cur = [], lo
@@ -95,12 +140,18 @@ class FlatAdamW(torch.optim.AdamW):
           rest.append((cur, hi))
         self._fused[gi] = (lins, items, None, rest)
 
-  def _publish_state(self):
-    """torch-layout per-parameter state backed by views of the flat moment buffers."""
-    for g in self.param_groups:
-      for p in g['params']:
-        m, v = self._views[id(p)]
-        self.state[p] = {'step': torch.tensor(float(self._step_count)), 'exp_avg': m, 'exp_avg_sq': v}
+  def _item(self, lin):
+    return (lin.weight.data, lin.weight.main_grad) + self._views[id(lin.weight)] + (lin._shadow[0], lin._shadow[1])
+
+  def _update_multi(self, group, hp, items, clip, table):
+    return ops.optim_cast_multi_(hp, items, clip, table)
+
+  def _update_flat(self, group, hp, a, b, clip):
+    m, v = (t[a:b] if t is not None else None for t in self._state_bufs)
+    ops.optim_(hp, self.flat_p[a:b], self.flat_g[a:b], m, v, clip)
+
+  def _after_step(self):
+    self._publish_state()
 
   @torch.no_grad()
   def clip_and_step(self, max_norm=None):
@@ -116,22 +167,20 @@ class FlatAdamW(torch.optim.AdamW):
     for gi, (g, (lo, hi)) in enumerate(zip(self.param_groups, self.group_spans)):
       if hi == lo:
         continue
-      b1, b2 = g['betas']
+      hp = self._group_hparams(gi, g)
       spans = [(lo, hi)]
       if self._fused[gi] is not None:
         lins, items, table, spans = self._fused[gi]
         if any(lin._shadow[0] is not it[4] or lin.weight.data_ptr() != it[0].data_ptr() for lin, it in zip(lins, items)):
           # a shadow buffer or a weight was re-allocated behind our back (model moved, weights re-laid): rebuild the cached table
-          items = [(lin.weight.data, lin.weight.main_grad) + self._views[id(lin.weight)] + (lin._shadow[0], lin._shadow[1]) for lin in lins]
+          items = [self._item(lin) for lin in lins]
           table = None
-        table = ops.adamw_cast_multi_(items, float(g['lr']), b1, b2, g['eps'], g['weight_decay'], self._step_count, clip, table)
+        table = self._update_multi(g, hp, items, clip, table)
         self._fused[gi] = (lins, items, table, spans)
         fresh.extend(lins)
       for a, b in spans:
-        ops.adamw_(self.flat_p[a:b], self.flat_g[a:b], self.flat_m[a:b], self.flat_v[a:b], float(g['lr']), b1, b2,
-                   g['eps'], g['weight_decay'], self._step_count, clip)
-    for st in self.state.values():
-      st['step'].fill_(float(self._step_count))
+        self._update_flat(g, hp, a, b, clip)
+    self._after_step()
     self.model.invalidate_shadows()  # raw-pointer update: torch's version counters did not move
     for lin in fresh:                # ... except where this step has just written the shadows itself
       lin.mark_fresh()
@@ -139,7 +188,7 @@ class FlatAdamW(torch.optim.AdamW):
   @torch.no_grad()
   def step(self, closure=None):
     if closure is not None:
-      raise NotImplementedError('FlatAdamW.step does not take a closure')
+      raise NotImplementedError(f'{type(self).__name__}.step does not take a closure')
     self.clip_and_step(None)
 
   def zero_grad(self, set_to_none=True):
@@ -151,13 +200,148 @@ class FlatAdamW(torch.optim.AdamW):
   def load_state_dict(self, state_dict):
     super().load_state_dict(state_dict)
     steps = []
-    for g in self.param_groups:
-      for p in g['params']:
-        st = self.state.get(p)
-        if st:
-          m, v = self._views[id(p)]
-          m.copy_(st['exp_avg'])
-          v.copy_(st['exp_avg_sq'])
+    for gi, g in enumerate(self.param_groups):
+      states = [self.state.get(p) or {} for p in g['params']]
+      for p, st in zip(g['params'], states):
+        for name, view in zip(self._state_names, self._views[id(p)]):
+          if name in st:
+            view.copy_(st[name])
+        if 'step' in st:
           steps.append(int(float(st['step'])))
+      self._restore_host_state(gi, states)
     self._step_count = max(steps) if steps else 0
     self._publish_state()
+
+  def _restore_host_state(self, gi, states):
+    pass
+
+
+class FlatAdamW(_FlatTail, torch.optim.AdamW):
+  _state_names = ('exp_avg', 'exp_avg_sq')
+
+  def __init__(self, model, param_groups, lr, betas, eps, weight_decay):
+    torch.optim.AdamW.__init__(self, param_groups, lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, fused=False, foreach=False)
+    self._lay_out(model)
+    self.flat_m, self.flat_v = self._state_bufs
+    self._publish_state()
+
+  def _publish_state(self):
+    """torch-layout per-parameter state backed by views of the flat moment buffers."""
+    for g in self.param_groups:
+      for p in g['params']:
+        m, v = self._views[id(p)]
+        self.state[p] = {'step': torch.tensor(float(self._step_count)), 'exp_avg': m, 'exp_avg_sq': v}
+
+  def _group_hparams(self, gi, g):
+    return None
+
+  def _update_multi(self, g, hp, items, clip, table):
+    b1, b2 = g['betas']
+    return ops.adamw_cast_multi_(items, float(g['lr']), b1, b2, g['eps'], g['weight_decay'], self._step_count, clip, table)
+
+  def _update_flat(self, g, hp, a, b, clip):
+    b1, b2 = g['betas']
+    ops.adamw_(self.flat_p[a:b], self.flat_g[a:b], self.flat_m[a:b], self.flat_v[a:b], float(g['lr']), b1, b2,
+               g['eps'], g['weight_decay'], self._step_count, clip)
+
+  def _after_step(self):
+    for st in self.state.values():
+      st['step'].fill_(float(self._step_count))
+
+
+class FlatNAdamW(_FlatTail, torch.optim.NAdam):
+  """torch.optim.NAdam(decoupled_weight_decay=True) on the flat buffers.  The product of the momentum cache (``mu_product``) is kept per
+  group on the host in fp64 (torch: an fp32 tensor per parameter, so the two agree to rounding) and published per parameter."""
+  _state_names = ('exp_avg', 'exp_avg_sq')
+
+  def __init__(self, model, param_groups, lr, betas, eps, weight_decay, momentum_decay=4e-3):
+    torch.optim.NAdam.__init__(self, param_groups, lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay,
+                               momentum_decay=momentum_decay, decoupled_weight_decay=True, foreach=False)
+    self._lay_out(model)
+    self.flat_m, self.flat_v = self._state_bufs
+    self._mu_product = [1.0] * len(self.param_groups)
+    self._publish_state()
+
+  def _publish_state(self):
+    for gi, g in enumerate(self.param_groups):
+      for p in g['params']:
+        m, v = self._views[id(p)]
+        self.state[p] = {'step': torch.tensor(float(self._step_count)), 'mu_product': torch.tensor(self._mu_product[gi]),
+                         'exp_avg': m, 'exp_avg_sq': v}
+
+  def _group_hparams(self, gi, g):
+    if not g.get('decoupled_weight_decay', True) or g.get('maximize', False):
+      raise NotImplementedError('FlatNAdamW implements decoupled weight decay and maximize=False only')
+    b1, b2 = g['betas']
+    lr = float(g['lr'])
+    bc2, cg, cm, self._mu_product[gi] = ops.nadam_scalars(lr, b1, b2, g['momentum_decay'], self._step_count, self._mu_product[gi])
+    return ops.optim_hparams('nadamw', lr, g['weight_decay'], beta1=b1, beta2=b2, eps=g['eps'], bc2=bc2, coef_grad=cg, coef_avg=cm)
+
+  def _restore_host_state(self, gi, states):
+    st = next((s for s in states if 'mu_product' in s), None)
+    self._mu_product[gi] = float(st['mu_product']) if st else 1.0
+
+
+class _FlatMomentum(_FlatTail):
+  """SGD / signSGD: one state buffer per parameter that torch creates at a parameter's first step (no ``step`` key), so the state dict
+  holds it only for groups that have stepped; ``_primed[gi]`` is the kernels' ``first`` flag, negated."""
+  _kind = None
+
+  def _init_flat(self, model):
+    self._lay_out(model)
+    self.flat_m, self.flat_v = self._state_bufs
+    self._primed = [False] * len(self.param_groups)
+    self._publish_state()
+
+  def _has_buffer(self, g):
+    return True
+
+  def _publish_state(self):
+    (name,) = self._state_names
+    for gi, g in enumerate(self.param_groups):
+      for p in g['params']:
+        if self._primed[gi]:
+          self.state[p] = {name: self._views[id(p)][0]}
+        else:
+          self.state.pop(p, None)
+
+  def _group_hparams(self, gi, g):
+    lr = float(g['lr'])
+    hp = ops.optim_hparams(self._kind, lr, g['weight_decay'], first=not self._primed[gi], momentum=g['momentum'], dampening=g['dampening'])
+    self._primed[gi] = self._primed[gi] or self._has_buffer(g)
+    return hp
+
+  def _restore_host_state(self, gi, states):
+    (name,) = self._state_names
+    have = [name in s for s in states]
+    if any(have) and not all(have):
+      raise ValueError(f'{type(self).__name__}: the state dict holds {name} for some parameters of group {gi} but not all')
+    self._primed[gi] = bool(have) and all(have)
+
+
+class FlatSGD(_FlatMomentum, torch.optim.SGD):
+  """torch.optim.SGD (coupled L2 decay, momentum with dampening, nesterov off) on the flat buffers."""
+  _state_names = ('momentum_buffer',)
+  _kind = 'sgd'
+
+  def __init__(self, model, param_groups, lr, momentum, dampening, weight_decay):
+    torch.optim.SGD.__init__(self, param_groups, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, foreach=False)
+    self._init_flat(model)
+
+  def _has_buffer(self, g):
+    return g['momentum'] != 0  # torch keeps no momentum_buffer without momentum
+
+  def _group_hparams(self, gi, g):
+    if g.get('nesterov', False) or g.get('maximize', False):
+      raise NotImplementedError('FlatSGD implements nesterov=False, maximize=False only')
+    return super()._group_hparams(gi, g)
+
+
+class FlatSignSGD(_FlatMomentum, SignSGD):
+  """SignSGD on the flat buffers."""
+  _state_names = ('m',)
+  _kind = 'signSGD'
+
+  def __init__(self, model, param_groups, lr, momentum, dampening, weight_decay):
+    SignSGD.__init__(self, param_groups, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay)
+    self._init_flat(model)

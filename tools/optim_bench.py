@@ -1,10 +1,18 @@
-"""Optimizer tail on its own: FlatAdamW.clip_and_step (||g||^2 sweep + AdamW, with and without the bf16 shadows written by the AdamW launch)
-and the stand-alone weight cast it replaces, 160M model.  Usage (GPU box): python tools/optim_bench.py"""
-import os, sys, torch
+"""Optimizer tail on its own: the flat optimizer's clip_and_step (||g||^2 sweep + the update, with and without the bf16 shadows written by the
+update launch) and the stand-alone weight cast it replaces, 160M model.
+Usage (GPU box): python tools/optim_bench.py [--optim adamw|nadamw|sgd|signSGD ...]   (default: adamw)"""
+import argparse, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 import plainlm_amd as P
-from plainlm_amd.optim import FlatAdamW
+from plainlm_amd import optim as O
+
+OPTIMS = {
+  'adamw': lambda m, g: O.FlatAdamW(m, g, lr=1e-4, betas=[0.9, 0.95], eps=1e-8, weight_decay=0.1),
+  'nadamw': lambda m, g: O.FlatNAdamW(m, g, lr=1e-4, betas=[0.9, 0.95], eps=1e-8, weight_decay=0.1),
+  'sgd': lambda m, g: O.FlatSGD(m, g, lr=1e-4, momentum=0.9, dampening=0.0, weight_decay=0.1),
+  'signSGD': lambda m, g: O.FlatSignSGD(m, g, lr=1e-4, momentum=0.9, dampening=0.0, weight_decay=0.1),
+}
 
 
 def t(fn, it=20):
@@ -17,15 +25,19 @@ def t(fn, it=20):
   return s.elapsed_time(e) / it
 
 
-for shadows in ('1', '0'):
-  os.environ['PLM_ADAMW_SHADOWS'] = shadows
-  model = bench.build_model(bench.CONFIGS['160m'], torch.device('cuda'))
-  model.enable_main_grad()
-  opt = FlatAdamW(model, P.get_param_groups(model, 0.1), lr=1e-4, betas=[0.9, 0.95], eps=1e-8, weight_decay=0.1)
-  opt.flat_g.normal_()
-  step = t(lambda: opt.clip_and_step(1.0))
-  def cast():
-    model.invalidate_shadows()
-    model.refresh_shadows()
-  print(f'PLM_ADAMW_SHADOWS={shadows}: clip_and_step {step:.3f} ms, stand-alone cast of all weights {t(cast):.3f} ms', flush=True)
-  del model, opt
+ap = argparse.ArgumentParser()
+ap.add_argument('--optim', nargs='+', choices=list(OPTIMS), default=['adamw'])
+args = ap.parse_args()
+for name in args.optim:
+  for shadows in ('1', '0'):
+    os.environ['PLM_ADAMW_SHADOWS'] = shadows
+    model = bench.build_model(bench.CONFIGS['160m'], torch.device('cuda'))
+    model.enable_main_grad()
+    opt = OPTIMS[name](model, P.get_param_groups(model, 0.1))
+    opt.flat_g.normal_()
+    step = t(lambda: opt.clip_and_step(1.0))
+    def cast():
+      model.invalidate_shadows()
+      model.refresh_shadows()
+    print(f'{name} PLM_ADAMW_SHADOWS={shadows}: clip_and_step {step:.3f} ms, stand-alone cast of all weights {t(cast):.3f} ms', flush=True)
+    del model, opt
