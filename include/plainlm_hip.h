@@ -264,7 +264,13 @@ int plm_adamw_cast_multi(const plm_adamw_item* items, int count, float lr, float
  *     momentum == 0: p -= lr d (m is neither read nor written and may be NULL); v must be NULL
  *   PLM_OPTIM_SIGNSGD  the reference's optim/signSGD.py:
  *     p *= decay ; m = momentum (first ? g : m) + (1-dampening) g ; p -= lr sign(m)  (sign(0) = 0); v must be NULL
- * `first` = 1 initialises the momentum buffer (SGD: torch's missing momentum_buffer; signSGD: the missing 'm').
+ *   PLM_OPTIM_SFO_ADAMW  schedule-free AdamW (Defazio et al. 2024, the schedulefree package's AdamWScheduleFree), p = y,
+ *     m = z, v = exp_avg_sq:
+ *     v = b2 v + (1-b2) g^2 ; gn = g / (sqrt(v / bc2) + eps) + weight_decay y ;
+ *     y = lerp(y, z, ckp1) + coef_y gn ; z -= lr gn   (the lerp reads the old z; lerp as torch.lerp spells it)
+ *     (lr = the warmed-up scheduled_lr, ckp1 = weight / weight_sum, coef_y = lr (b1 (1 - ckp1) - 1); needs m and v)
+ * `first` = 1 initialises the momentum buffer (SGD: torch's missing momentum_buffer; signSGD: the missing 'm'; schedule-free
+ * AdamW: z = a copy of p and v = 0, neither read).
  * decay = 1 - lr * weight_decay, rounded once from the host's double, as torch passes it to p.mul_().  The multi-tensor form
  * takes plm_adamw_item lists (v = NULL for SGD / signSGD) and writes the bf16 shadows like plm_adamw_cast_multi.  An unknown
  * kind, a missing or superfluous state buffer, or a shape / alignment plm_adamw_cast_multi would refuse gives PLM_E_INVALID
@@ -272,16 +278,22 @@ int plm_adamw_cast_multi(const plm_adamw_item* items, int count, float lr, float
 #define PLM_OPTIM_NADAMW 1
 #define PLM_OPTIM_SGD 2
 #define PLM_OPTIM_SIGNSGD 3
+#define PLM_OPTIM_SFO_ADAMW 4
 typedef struct plm_optim_hparams {
   int kind;   /* PLM_OPTIM_* */
-  int first;  /* 1: initialise the momentum buffer this step (SGD / signSGD) */
+  int first;  /* 1: initialise the state buffers this step (SGD / signSGD / schedule-free AdamW) */
   float lr, weight_decay, decay, beta1, beta2, eps, momentum, dampening;
-  float bc2, coef_grad, coef_avg; /* NAdamW */
+  float bc2, coef_grad, coef_avg; /* NAdamW (bc2 also schedule-free AdamW) */
+  float ckp1, coef_y;             /* schedule-free AdamW */
 } plm_optim_hparams;
 int plm_optim_f32(const plm_optim_hparams* h, float* p, const float* g, float* m, float* v, int64_t n,
                   const float* clip_coef_dev, void* stream);
 int plm_optim_cast_multi(const plm_optim_hparams* h, const plm_adamw_item* items, int count, const float* clip_coef_dev,
                          void* stream);
+/* Schedule-free train / eval swap on a flat fp32 span: p[i] = lerp(p[i], z[i], w), as torch.lerp
+ * (|w| < 0.5: p + w (z - p), else z - (z - p)(1 - w)).  eval(): w = 1 - 1/beta1 (p = x); train(): w = 1 - beta1 (p = y).
+ * A NULL p or z or n <= 0 gives PLM_E_INVALID. */
+int plm_lerp_f32(float* p, const float* z, int64_t n, float w, void* stream);
 
 /* Leave `n` CUs free when sizing the persistent GEMM grids (one workgroup per CU, static tile schedule), so that
  * concurrently running RCCL collectives do not push GEMM workgroups into a second round.  Process-wide; 0 = whole chip. */

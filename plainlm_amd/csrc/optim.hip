@@ -1,6 +1,13 @@
-// The reference's other optimizer tails (optim/init_optim.py:7-70): NAdamW, SGD and signSGD on the flat fp32 spans and on
-// the shadow-emitting Linear-weight lists, the two launch shapes of the AdamW tail in elementwise.hip.
+// The reference's other optimizer tails (optim/init_optim.py:7-70): NAdamW, SGD, signSGD and schedule-free AdamW on the flat fp32
+// spans and on the shadow-emitting Linear-weight lists, the two launch shapes of the AdamW tail in elementwise.hip; and the lerp that
+// swaps schedule-free parameters between their training (y) and evaluation (x) points.
 #include "plm_device.h"
+
+// torch.lerp's two-sided form (ATen/native/Lerp.h), exact at both ends: a + w (b - a) for |w| < 0.5, else b - (b - a)(1 - w)
+__device__ __forceinline__ float lerp_elem(float a, float b, float w) {
+  const float d = __fsub_rn(b, a);
+  return fabsf(w) < 0.5f ? __fmaf_rn(w, d, a) : __fmaf_rn(-d, __fsub_rn(1.f, w), b);
+}
 
 // One element of each update, every rounding spelled out (as adamw_elem does) so that the flat kernel and the multi-tensor
 // one give the same bits.  __fmul_rn / __fadd_rn are plain operators here and hipcc contracts a product that feeds an addition,
@@ -25,6 +32,16 @@ __device__ __forceinline__ float optim_elem(float p, float g, float& m, float& v
     const float mi = h.first ? d : __fmaf_rn(1.f - h.dampening, d, __fmul_rn(h.momentum, m));
     m = mi;
     return __fmaf_rn(-h.lr, mi, p);
+  } else if constexpr (KIND == PLM_OPTIM_SFO_ADAMW) {
+    // schedule-free AdamW (p = y, m = z, v = exp_avg_sq; `first` creates z as a copy of p and v as zeros), decay at y:
+    // gn = g / (sqrt(v / bc2) + eps) + wd y ; y = lerp(y, z, ckp1) + coef_y gn ; z -= lr gn  (the old z in the lerp)
+    const float z = h.first ? p : m;
+    const float vi = __fmaf_rn(h.beta2, h.first ? 0.f : v, __fmul_rn(__fmul_rn(1.f - h.beta2, gi), gi));
+    v = vi;
+    const float d = __fadd_rn(__fsqrt_rn(__fdiv_rn(vi, h.bc2)), h.eps);
+    const float gn = __fmaf_rn(h.weight_decay, p, __fdiv_rn(gi, d));
+    m = __fmaf_rn(-h.lr, gn, z);
+    return __fmaf_rn(h.coef_y, gn, lerp_elem(p, z, h.ckp1));
   } else {
     // signSGD: the momentum update runs on the first step too (its first m is (momentum + 1 - dampening) g)
     const float pd = __fmul_rn(p, h.decay);
@@ -36,12 +53,18 @@ __device__ __forceinline__ float optim_elem(float p, float g, float& m, float& v
   }
 }
 
-// which state the update reads / writes (block-uniform): the first step of SGD / signSGD does not read the buffer it creates,
-// SGD without momentum has none
+// which state the update reads / writes (block-uniform): the first step of SGD / signSGD / schedule-free AdamW does not read the
+// buffers it creates, SGD without momentum has none, only NAdamW and schedule-free AdamW have v
 template <int KIND>
 __device__ __forceinline__ bool optim_reads_m(const plm_optim_hparams& h) {
   return KIND == PLM_OPTIM_NADAMW || (!h.first && (KIND != PLM_OPTIM_SGD || h.momentum != 0.f));
 }
+template <int KIND>
+__device__ __forceinline__ bool optim_reads_v(const plm_optim_hparams& h) {
+  return KIND == PLM_OPTIM_NADAMW || (KIND == PLM_OPTIM_SFO_ADAMW && !h.first);
+}
+template <int KIND>
+constexpr bool optim_has_v() { return KIND == PLM_OPTIM_NADAMW || KIND == PLM_OPTIM_SFO_ADAMW; }
 template <int KIND>
 __device__ __forceinline__ bool optim_writes_m(const plm_optim_hparams& h) {
   return KIND != PLM_OPTIM_SGD || h.momentum != 0.f;
@@ -53,19 +76,20 @@ __global__ __launch_bounds__(256) void optim_kernel(plm_optim_hparams h, float* 
                                                     float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                     const float* __restrict__ clip) {
   const float cs = clip ? *clip : 1.f;
-  const bool rm = optim_reads_m<KIND>(h), wm = optim_writes_m<KIND>(h);
+  const bool rm = optim_reads_m<KIND>(h), wm = optim_writes_m<KIND>(h), rv = optim_reads_v<KIND>(h);
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     float mi = rm ? m[i] : 0.f;
-    float vi = KIND == PLM_OPTIM_NADAMW ? v[i] : 0.f;
+    float vi = rv ? v[i] : 0.f;
     p[i] = optim_elem<KIND>(p[i], g[i], mi, vi, cs, h);
     if (wm) m[i] = mi;
-    if (KIND == PLM_OPTIM_NADAMW) v[i] = vi;
+    if (optim_has_v<KIND>()) v[i] = vi;
   }
 }
 
 // The shadow-emitting form: the 64 x 64 tile walk, LDS transposition and block_base search of adamw_cast_multi_kernel, with
-// optim_elem per element.  SGD / signSGD move 24 B per parameter (p, g, m read; p, m written; 4 B of shadows), NAdamW 32 B.
+// optim_elem per element.  SGD / signSGD move 24 B per parameter (p, g, m read; p, m written; 4 B of shadows), NAdamW and
+// schedule-free AdamW 32 B.
 #define PLM_OPTIM_MULTI_MAX 56
 struct OptimGroup {
   float* p[PLM_OPTIM_MULTI_MAX];
@@ -96,7 +120,7 @@ __global__ __launch_bounds__(256) void optim_cast_multi_kernel(OptimGroup g, plm
   uint16_t* __restrict__ dst_t = g.dst_t[it];
   const int64_t r0 = (int64_t)(local / tiles_x) * 64, c0 = (int64_t)(local % tiles_x) * 64;
   const float cs = clip ? *clip : 1.f;
-  const bool rm = optim_reads_m<KIND>(h), wm = optim_writes_m<KIND>(h);
+  const bool rm = optim_reads_m<KIND>(h), wm = optim_writes_m<KIND>(h), rv = optim_reads_v<KIND>(h);
   const int t = threadIdx.x;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -109,7 +133,7 @@ __global__ __launch_bounds__(256) void optim_cast_multi_kernel(OptimGroup g, plm
       const f32x4_t pv = *reinterpret_cast<const f32x4_t*>(P + o), gv = *reinterpret_cast<const f32x4_t*>(G + o);
       f32x4_t mv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
       if (rm) mv = *reinterpret_cast<const f32x4_t*>(Mm + o);
-      if (KIND == PLM_OPTIM_NADAMW) vv = *reinterpret_cast<const f32x4_t*>(V + o);
+      if (rv) vv = *reinterpret_cast<const f32x4_t*>(V + o);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float me = mv[e], ve = vv[e];
@@ -118,7 +142,7 @@ __global__ __launch_bounds__(256) void optim_cast_multi_kernel(OptimGroup g, plm
         vv[e] = ve;
       }
       if (wm) *reinterpret_cast<f32x4_t*>(Mm + o) = mv;
-      if (KIND == PLM_OPTIM_NADAMW) *reinterpret_cast<f32x4_t*>(V + o) = vv;
+      if (optim_has_v<KIND>()) *reinterpret_cast<f32x4_t*>(V + o) = vv;
       *reinterpret_cast<f32x4_t*>(P + o) = pn;
     }
     bf16x4_t o4;
@@ -139,8 +163,10 @@ __global__ __launch_bounds__(256) void optim_cast_multi_kernel(OptimGroup g, plm
 }
 
 static const char* optim_name(int kind) {
-  return kind == PLM_OPTIM_NADAMW ? "nadamw" : kind == PLM_OPTIM_SGD ? "sgd" : kind == PLM_OPTIM_SIGNSGD ? "signSGD" : nullptr;
+  return kind == PLM_OPTIM_NADAMW ? "nadamw" : kind == PLM_OPTIM_SGD ? "sgd" : kind == PLM_OPTIM_SIGNSGD ? "signSGD"
+       : kind == PLM_OPTIM_SFO_ADAMW ? "sfo_adamw" : nullptr;
 }
+static bool optim_needs_v(const plm_optim_hparams* h) { return h->kind == PLM_OPTIM_NADAMW || h->kind == PLM_OPTIM_SFO_ADAMW; }
 static bool optim_needs_m(const plm_optim_hparams* h) { return h->kind != PLM_OPTIM_SGD || h->momentum != 0.f; }
 
 extern "C" int plm_optim_f32(const plm_optim_hparams* h, float* p, const float* g, float* m, float* v, int64_t n,
@@ -149,12 +175,14 @@ extern "C" int plm_optim_f32(const plm_optim_hparams* h, float* p, const float* 
   PLM_REQUIRE(optim_name(h->kind), "plm_optim_f32: unknown optimizer kind %d", h->kind);
   PLM_REQUIRE(p && g && n > 0, "plm_optim_f32: bad arguments");
   PLM_REQUIRE(!optim_needs_m(h) || m, "plm_optim_f32: %s needs the momentum buffer m", optim_name(h->kind));
-  PLM_REQUIRE((h->kind == PLM_OPTIM_NADAMW) == (v != nullptr), "plm_optim_f32: %s %s", optim_name(h->kind),
-              h->kind == PLM_OPTIM_NADAMW ? "needs v" : "takes no v (pass NULL)");
+  PLM_REQUIRE(optim_needs_v(h) == (v != nullptr), "plm_optim_f32: %s %s", optim_name(h->kind),
+              optim_needs_v(h) ? "needs v" : "takes no v (pass NULL)");
   const int64_t b = plm_cdiv(n, 256), cap = (int64_t)1 << 20;
   const dim3 grid((unsigned)(b > cap ? cap : b));
   if (h->kind == PLM_OPTIM_NADAMW)
     hipLaunchKernelGGL(optim_kernel<PLM_OPTIM_NADAMW>, grid, dim3(256), 0, (hipStream_t)stream, *h, p, g, m, v, n, clip_coef_dev);
+  else if (h->kind == PLM_OPTIM_SFO_ADAMW)
+    hipLaunchKernelGGL(optim_kernel<PLM_OPTIM_SFO_ADAMW>, grid, dim3(256), 0, (hipStream_t)stream, *h, p, g, m, v, n, clip_coef_dev);
   else if (h->kind == PLM_OPTIM_SGD)
     hipLaunchKernelGGL(optim_kernel<PLM_OPTIM_SGD>, grid, dim3(256), 0, (hipStream_t)stream, *h, p, g, m, v, n, clip_coef_dev);
   else
@@ -169,7 +197,7 @@ extern "C" int plm_optim_cast_multi(const plm_optim_hparams* h, const plm_adamw_
   const char* name = optim_name(h->kind);
   PLM_REQUIRE(name, "plm_optim_cast_multi: unknown optimizer kind %d", h->kind);
   PLM_REQUIRE(items && count >= 1, "plm_optim_cast_multi: null pointer or empty list");
-  const bool need_m = optim_needs_m(h), need_v = h->kind == PLM_OPTIM_NADAMW;
+  const bool need_m = optim_needs_m(h), need_v = optim_needs_v(h);
   int64_t tiles = 0;
   // validate every item before the first launch: a refused list leaves all parameters as they were
   for (int i = 0; i < count; ++i) {
@@ -202,11 +230,28 @@ extern "C" int plm_optim_cast_multi(const plm_optim_hparams* h, const plm_adamw_
     g.count = n;
     if (h->kind == PLM_OPTIM_NADAMW)
       hipLaunchKernelGGL(optim_cast_multi_kernel<PLM_OPTIM_NADAMW>, dim3((unsigned)base), dim3(256), 0, (hipStream_t)stream, g, *h, clip_coef_dev);
+    else if (h->kind == PLM_OPTIM_SFO_ADAMW)
+      hipLaunchKernelGGL(optim_cast_multi_kernel<PLM_OPTIM_SFO_ADAMW>, dim3((unsigned)base), dim3(256), 0, (hipStream_t)stream, g, *h, clip_coef_dev);
     else if (h->kind == PLM_OPTIM_SGD)
       hipLaunchKernelGGL(optim_cast_multi_kernel<PLM_OPTIM_SGD>, dim3((unsigned)base), dim3(256), 0, (hipStream_t)stream, g, *h, clip_coef_dev);
     else
       hipLaunchKernelGGL(optim_cast_multi_kernel<PLM_OPTIM_SIGNSGD>, dim3((unsigned)base), dim3(256), 0, (hipStream_t)stream, g, *h, clip_coef_dev);
     PLM_CHECK_LAUNCH("plm_optim_cast_multi");
   }
+  return PLM_OK;
+}
+
+// schedule-free train / eval swap: p = lerp(p, z, w) on a flat span (eval: w = 1 - 1/beta1, p = x; train: w = 1 - beta1, p = y)
+__global__ __launch_bounds__(256) void lerp_kernel(float* __restrict__ p, const float* __restrict__ z, int64_t n, float w) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) p[i] = lerp_elem(p[i], z[i], w);
+}
+
+extern "C" int plm_lerp_f32(float* p, const float* z, int64_t n, float w, void* stream) {
+  PLM_REQUIRE(p && z, "plm_lerp_f32: null p or z");
+  PLM_REQUIRE(n > 0, "plm_lerp_f32: n=%ld must be positive", (long)n);
+  const int64_t b = plm_cdiv(n, 256), cap = (int64_t)1 << 20;
+  hipLaunchKernelGGL(lerp_kernel, dim3((unsigned)(b > cap ? cap : b)), dim3(256), 0, (hipStream_t)stream, p, z, n, w);
+  PLM_CHECK_LAUNCH("plm_lerp_f32");
   return PLM_OK;
 }

@@ -11,7 +11,10 @@ Differences that stay inside the contract:
   * document masks travel as ``doc_start[B,T]`` (prefix sums of ``docs_lengths``) instead of a
     [B,T,T] boolean tensor;
   * ``eval`` implements the evident intent (sum of losses / number of batches across ranks);
-    the reference's version raises AttributeError at engine.py:175.
+    the reference's version raises AttributeError at engine.py:175;
+  * with an optimizer that has ``train()`` / ``eval()`` (schedule-free AdamW, ``optim: sfo_adamw``) ``eval`` first moves the
+    parameters to the optimizer's evaluation point x and ``step`` moves them back to y before its forward.  The reference engine
+    never calls these methods, so it trains correctly but evaluates schedule-free runs at y; schedulefree requires the calls.
 """
 
 import math
@@ -138,18 +141,27 @@ def initialize_scheduler(optimizer, cfg):
   raise NotImplementedError(f'Not implemented scheduler: {name}.')
 
 
+class MissingOptimKey(ValueError, NotImplementedError):
+  """A config that selects an optimizer but lacks a key the optimizer is built from.  A ValueError naming the key; for sfo_adamw
+  also the NotImplementedError that callers have always received for an sfo_adamw config without it."""
+
+
 def intialize_optimizer(param_groups, cfg, model=None):
-  """(sic) optim/init_optim.py:7-70: adamw, nadamw, sgd and signSGD.
+  """(sic) optim/init_optim.py:7-70: adamw, nadamw, sgd, signSGD and sfo_adamw.
   ``fused_optim: True`` (the shipped configs) with a model selects the flat optimizers of plainlm_amd.optim (clip + update on flat
   buffers with our kernels); ``False`` keeps the torch optimizers on the per-parameter views (for signSGD: optim.SignSGD, the
-  reference's arithmetic).  The reference also passes ``fused=cfg.fused_optim`` to torch.optim.NAdam, which torch 2.10 does not
-  accept; for NAdam ``fused_optim`` here selects only our flat path against torch's.  sfo_adamw needs the schedulefree package
-  and is not implemented."""
+  reference's arithmetic; for sfo_adamw: optim.AdamWScheduleFree, schedulefree.AdamWScheduleFree restated).  The reference also
+  passes ``fused=cfg.fused_optim`` to torch.optim.NAdam, which torch 2.10 does not accept; for NAdam ``fused_optim`` here selects
+  only our flat path against torch's.  sfo_adamw takes the optimizer's own warm-up from ``warmup_steps`` (an int, or a fraction of
+  ``steps_budget``) and, like the reference, not ``cfg.eps`` (the package's default 1e-8); the scheduler still sets ``lr`` on top."""
   name = cfg.optim
-  if name not in ('adamw', 'nadamw', 'sgd', 'signSGD'):
+  if name not in ('adamw', 'nadamw', 'sgd', 'signSGD', 'sfo_adamw'):
     raise NotImplementedError(f'Not implemented optim: {name}.')
   if name in ('sgd', 'signSGD') and not hasattr(cfg, 'dampening'):
     raise ValueError(f"optim '{name}' needs the config key 'dampening' (the reference reads cfg.dampening)")
+  if name == 'sfo_adamw' and not hasattr(cfg, 'warmup_steps'):
+    raise MissingOptimKey("optim 'sfo_adamw' is not available without the config key 'warmup_steps' "
+                          "(the reference reads cfg.warmup_steps for the optimizer's own warm-up)")
   eps = getattr(cfg, 'eps', 1e-8)
   flat = bool(getattr(cfg, 'fused_optim', True)) and model is not None
   from . import optim as O
@@ -162,6 +174,10 @@ def intialize_optimizer(param_groups, cfg, model=None):
       return O.FlatNAdamW(model, param_groups, lr=cfg.lr, betas=[cfg.beta1, cfg.beta2], eps=eps, weight_decay=cfg.weight_decay)
     return torch.optim.NAdam(param_groups, lr=cfg.lr, betas=[cfg.beta1, cfg.beta2], weight_decay=cfg.weight_decay,
                              decoupled_weight_decay=True, eps=eps)
+  if name == 'sfo_adamw':
+    kw = dict(lr=cfg.lr, betas=[cfg.beta1, cfg.beta2], weight_decay=cfg.weight_decay,
+              warmup_steps=_steps(cfg.warmup_steps, cfg.steps_budget))
+    return O.FlatAdamWScheduleFree(model, param_groups, **kw) if flat else O.AdamWScheduleFree(param_groups, **kw)
   kw = dict(lr=cfg.lr, momentum=cfg.beta1, dampening=cfg.dampening, weight_decay=cfg.weight_decay)
   if name == 'sgd':
     return O.FlatSGD(model, param_groups, **kw) if flat else torch.optim.SGD(param_groups, **kw)
@@ -293,6 +309,8 @@ class HipEngine(torch.nn.Module):
 
   def step(self, batch):
     self.model.train()
+    if hasattr(self.optimizer, 'train'):
+      self.optimizer.train()  # schedule-free: back to y after an eval() (a no-op otherwise)
     self.micro_steps += 1
     self.accumulated_samples += 1
     inputs, targets, doc_start = _move_to_device(batch, self.seq_len, self.device, self.intra_doc_masking, self._stager)
@@ -362,6 +380,8 @@ class HipEngine(torch.nn.Module):
   def eval(self, dataloader):
     self.check_losses()
     self.model.eval()
+    if hasattr(self.optimizer, 'eval'):
+      self.optimizer.eval()  # schedule-free: validation loss at the averaged iterate x; step() returns to y
     total_loss, num_batches = 0.0, 0
     for batch in dataloader:
       inputs, targets, doc_start = _move_to_device(batch, self.seq_len, self.device, self.intra_doc_masking, self._stager)

@@ -628,16 +628,35 @@ def adamw_cast_multi_(items, lr, beta1, beta2, eps, weight_decay, step, clip_coe
   return table
 
 
-_OPTIM_KINDS = {'nadamw': _lib.OPTIM_NADAMW, 'sgd': _lib.OPTIM_SGD, 'signSGD': _lib.OPTIM_SIGNSGD}
+_OPTIM_KINDS = {'nadamw': _lib.OPTIM_NADAMW, 'sgd': _lib.OPTIM_SGD, 'signSGD': _lib.OPTIM_SIGNSGD, 'sfo_adamw': _lib.OPTIM_SFO_ADAMW}
 
 
 def optim_hparams(kind, lr, weight_decay=0.0, first=False, beta1=0.0, beta2=0.0, eps=0.0, momentum=0.0, dampening=0.0, bc2=1.0,
-                  coef_grad=0.0, coef_avg=0.0):
-  """struct plm_optim_hparams for optim_ / optim_cast_multi_.  kind: 'nadamw' | 'sgd' | 'signSGD' (an int is passed through as is).
-  decay = 1 - lr * weight_decay is formed here in double and rounded once, the value torch hands to p.mul_()."""
+                  coef_grad=0.0, coef_avg=0.0, ckp1=0.0):
+  """struct plm_optim_hparams for optim_ / optim_cast_multi_.  kind: 'nadamw' | 'sgd' | 'signSGD' | 'sfo_adamw' (an int is passed
+  through as is).  decay = 1 - lr * weight_decay is formed here in double and rounded once, the value torch hands to p.mul_(); for
+  'sfo_adamw' (lr = the group's warmed-up scheduled_lr, ckp1 = weight / weight_sum) so is the y coefficient lr (beta1 (1 - ckp1) - 1),
+  the alpha of the package's y.add_()."""
   k = _OPTIM_KINDS[kind] if isinstance(kind, str) else int(kind)
   return _lib.OptimHparams(k, int(bool(first)), lr, weight_decay, 1.0 - lr * weight_decay, beta1, beta2, eps, momentum, dampening, bc2,
-                           coef_grad, coef_avg)
+                           coef_grad, coef_avg, ckp1, lr * (beta1 * (1.0 - ckp1) - 1.0))
+
+
+def sfo_scalars(group):
+  """Schedule-free AdamW's per-step host scalars for one parameter group (a dict with the package's keys: lr, betas, k,
+  warmup_steps, r, weight_lr_power, lr_max, weight_sum), in Python floats as the schedulefree package forms them.  Advances the
+  group's k / lr_max / weight_sum / scheduled_lr and returns (scheduled lr, ckp1, bc2)."""
+  k, warmup = group['k'], group['warmup_steps']
+  sched = (k + 1) / warmup if k < warmup else 1.0
+  lr = group['lr'] * sched
+  group['scheduled_lr'] = lr
+  lr_max = group['lr_max'] = max(lr, group['lr_max'])
+  weight = (k + 1) ** group['r'] * lr_max ** group['weight_lr_power']
+  weight_sum = group['weight_sum'] = group['weight_sum'] + weight
+  ckp1 = weight / weight_sum if weight_sum != 0 else 0.0
+  bc2 = 1.0 - group['betas'][1] ** (k + 1)
+  group['k'] = k + 1
+  return lr, ckp1, bc2
 
 
 def nadam_scalars(lr, beta1, beta2, momentum_decay, step, mu_product):
@@ -650,7 +669,7 @@ def nadam_scalars(lr, beta1, beta2, momentum_decay, step, mu_product):
 
 
 def optim_(hp, p, g, m, v, clip_coef=None):
-  """One NAdamW / SGD / signSGD step on a flat fp32 span (hp from optim_hparams).  m / v: None where the kind has no such buffer."""
+  """One NAdamW / SGD / signSGD / schedule-free AdamW step on a flat fp32 span (hp from optim_hparams).  m / v: None where the kind has no such buffer."""
   for t, n in ((p, 'p'), (g, 'g'), (m, 'm'), (v, 'v')):
     if t is not None:
       _need(t, F32, 'optim.' + n)
@@ -679,6 +698,16 @@ def optim_cast_multi_(hp, items, clip_coef=None, table=None):
       table[i] = _lib.AdamwItem(p.data_ptr(), g.data_ptr(), ptr(m), ptr(v), dst.data_ptr(), dst_t.data_ptr(), R, Cc, dst_t.stride(0))
   _lib.check(_lib.load().plm_optim_cast_multi(C.byref(hp), table, len(table), _p(clip_coef), _stream()), 'plm_optim_cast_multi')
   return table
+
+
+def lerp_(p, z, w):
+  """p <- torch.lerp(p, z, w) in place on a flat fp32 span: the schedule-free train / eval swap."""
+  _need(p, F32, 'lerp.p')
+  _need(z, F32, 'lerp.z')
+  if z.numel() != p.numel():
+    raise ValueError(f'lerp.z: {z.numel()} elements, p has {p.numel()}')
+  _lib.check(_lib.load().plm_lerp_f32(_p(p), _p(z), p.numel(), float(w), _stream()), 'plm_lerp_f32')
+  return p
 
 
 # ---- probes -------------------------------------------------------------------------------

@@ -16,6 +16,12 @@ The reference's other optimizers get the same treatment (same layout, clip and s
 ``FlatNAdamW`` (``torch.optim.NAdam(decoupled_weight_decay=True)``: ``step`` / ``mu_product`` / ``exp_avg`` / ``exp_avg_sq``),
 ``FlatSGD`` (``torch.optim.SGD``, nesterov off: ``momentum_buffer``) and ``FlatSignSGD`` (``SignSGD`` below, the arithmetic of the
 reference's optim/signSGD.py: ``m``).
+
+Schedule-free AdamW (the reference's ``sfo_adamw``: ``schedulefree.AdamWScheduleFree``, Defazio et al. 2024) is restated here without the
+package: ``AdamWScheduleFree`` in plain torch for ``fused_optim: False``, ``FlatAdamWScheduleFree`` on the flat buffers.  Both keep the
+package's state layout (group keys ``k`` / ``weight_sum`` / ``lr_max`` / ``scheduled_lr`` / ``train_mode`` / ...; per parameter ``z`` /
+``exp_avg_sq``, created at a parameter's first step) and its ``train()`` / ``eval()`` swaps of the parameters between y (where gradients
+are taken) and the averaged iterate x (what is evaluated).
 """
 
 import os
@@ -56,6 +62,75 @@ class SignSGD(torch.optim.Optimizer):
         m = st['m']
         m.mul_(mom).add_(p.grad, alpha=1.0 - damp)
         p.add_(m.sign(), alpha=-lr)
+    return loss
+
+
+def _sfo_defaults(lr, betas, eps, weight_decay, warmup_steps, r, weight_lr_power):
+  if not lr >= 0.0 or not eps >= 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+    raise ValueError(f'AdamWScheduleFree: invalid lr={lr} / eps={eps} / betas={betas}')
+  if betas[0] == 0.0:
+    raise ValueError('AdamWScheduleFree: beta1 = 0 has no averaged iterate to evaluate (eval() divides by beta1)')
+  return dict(lr=lr, betas=tuple(betas), eps=eps, r=r, k=0, warmup_steps=warmup_steps, train_mode=True, weight_sum=0.0, lr_max=-1.0,
+              scheduled_lr=0.0, weight_lr_power=weight_lr_power, weight_decay=weight_decay)
+
+
+class AdamWScheduleFree(torch.optim.Optimizer):
+  """Schedule-free AdamW with the arithmetic and state layout of ``schedulefree.AdamWScheduleFree`` (its defaults: eps 1e-8, r 0,
+  weight_lr_power 2), in the y-only form: the parameters hold y, ``z`` and ``exp_avg_sq`` are per-parameter state, x is never stored.
+  Per group and step the host forms (ops.sfo_scalars) the warmed-up lr, ckp1 = weight / weight_sum and bc2; per parameter
+  ``v = b2 v + (1-b2) g^2``, ``gn = g / (sqrt(v / bc2) + eps) + wd y``, ``y = lerp(y, z, ckp1) + lr (b1 (1 - ckp1) - 1) gn``,
+  ``z -= lr gn``.  ``eval()`` moves the parameters to x (``p.lerp_(z, 1 - 1/b1)``), ``train()`` back to y (``p.lerp_(z, 1 - b1)``);
+  ``step()`` refuses to run in eval mode.  Unlike the package, ``p.grad`` is left as it was."""
+
+  def __init__(self, params, lr=0.0025, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, warmup_steps=0, r=0.0, weight_lr_power=2.0):
+    super().__init__(params, _sfo_defaults(lr, betas, eps, weight_decay, warmup_steps, r, weight_lr_power))
+
+  @torch.no_grad()
+  def _swap(self, to_train):
+    for group in self.param_groups:
+      if group['train_mode'] == to_train:
+        continue
+      b1 = group['betas'][0]
+      w = 1.0 - b1 if to_train else 1.0 - 1.0 / b1
+      for p in group['params']:
+        st = self.state.get(p)
+        if st and 'z' in st:
+          p.lerp_(st['z'], w)
+      group['train_mode'] = to_train
+
+  def eval(self):
+    self._swap(False)
+
+  def train(self):
+    self._swap(True)
+
+  @torch.no_grad()
+  def step(self, closure=None):
+    if not all(g['train_mode'] for g in self.param_groups):
+      raise RuntimeError('AdamWScheduleFree: step() called in eval mode; call optimizer.train() first')
+    loss = None
+    if closure is not None:
+      with torch.enable_grad():
+        loss = closure()
+    for group in self.param_groups:
+      lr, ckp1, bc2 = ops.sfo_scalars(group)
+      b1, b2 = group['betas']
+      eps, wd = group['eps'], group['weight_decay']
+      for p in group['params']:
+        if p.grad is None:
+          continue
+        st = self.state[p]
+        if 'z' not in st:
+          st['z'] = p.detach().clone()
+          st['exp_avg_sq'] = torch.zeros_like(p)
+        z, v = st['z'], st['exp_avg_sq']
+        v.mul_(b2).addcmul_(p.grad, p.grad, value=1.0 - b2)
+        gn = p.grad / v.div(bc2).sqrt_().add_(eps)
+        if wd != 0:
+          gn.add_(p, alpha=wd)
+        p.lerp_(z, ckp1)
+        p.add_(gn, alpha=lr * (b1 * (1.0 - ckp1) - 1.0))
+        z.sub_(gn, alpha=lr)
     return loss
 
 
@@ -153,8 +228,12 @@ class _FlatTail:
   def _after_step(self):
     self._publish_state()
 
+  def _check_step(self):
+    pass
+
   @torch.no_grad()
   def clip_and_step(self, max_norm=None):
+    self._check_step()
     if getattr(self.model, 'sink', None) is not None:
       self.model.sink.flush_dw()  # queued weight-gradient GEMMs (functional.GradSink) must have been issued
     self._step_count += 1
@@ -345,3 +424,69 @@ class FlatSignSGD(_FlatMomentum, SignSGD):
   def __init__(self, model, param_groups, lr, momentum, dampening, weight_decay):
     SignSGD.__init__(self, param_groups, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay)
     self._init_flat(model)
+
+
+class FlatAdamWScheduleFree(_FlatTail, AdamWScheduleFree):
+  """AdamWScheduleFree on the flat buffers: the flat parameters hold y, the kernels' m / v slots carry z / exp_avg_sq.  The per-group
+  host scalars (k, weight_sum, lr_max: Python floats, i.e. fp64, as the package keeps them) live in param_groups and travel with
+  state_dict(); z / exp_avg_sq are published as views of the flat buffers once a group has stepped (``_primed``; its first step makes z a
+  copy of y inside the update launch).  ``train()`` / ``eval()`` lerp each stepped group's span toward z (ops.lerp_) and invalidate the
+  bf16 shadows, which the next forward re-casts."""
+  _state_names = ('z', 'exp_avg_sq')
+
+  def __init__(self, model, param_groups, lr, betas, weight_decay, warmup_steps=0, eps=1e-8, r=0.0, weight_lr_power=2.0):
+    AdamWScheduleFree.__init__(self, param_groups, lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay,
+                               warmup_steps=warmup_steps, r=r, weight_lr_power=weight_lr_power)
+    self._lay_out(model)
+    self.flat_z, self.flat_v = self._state_bufs
+    self._primed = [False] * len(self.param_groups)
+    self._publish_state()
+
+  def _publish_state(self):
+    for gi, g in enumerate(self.param_groups):
+      for p in g['params']:
+        if self._primed[gi]:
+          z, v = self._views[id(p)]
+          self.state[p] = {'z': z, 'exp_avg_sq': v}
+        else:
+          self.state.pop(p, None)
+
+  def _check_step(self):
+    if not all(g['train_mode'] for g in self.param_groups):
+      raise RuntimeError('FlatAdamWScheduleFree: step() called in eval mode; call optimizer.train() first')
+
+  def _group_hparams(self, gi, g):
+    lr, ckp1, bc2 = ops.sfo_scalars(g)
+    b1, b2 = g['betas']
+    hp = ops.optim_hparams('sfo_adamw', lr, g['weight_decay'], first=not self._primed[gi], beta1=b1, beta2=b2, eps=g['eps'], bc2=bc2,
+                           ckp1=ckp1)
+    self._primed[gi] = True
+    return hp
+
+  @torch.no_grad()
+  def _swap(self, to_train):
+    moved = False
+    for gi, (g, (lo, hi)) in enumerate(zip(self.param_groups, self.group_spans)):
+      if g['train_mode'] == to_train:
+        continue
+      if self._primed[gi] and hi > lo:
+        b1 = g['betas'][0]
+        ops.lerp_(self.flat_p[lo:hi], self.flat_z[lo:hi], 1.0 - b1 if to_train else 1.0 - 1.0 / b1)
+        moved = True
+      g['train_mode'] = to_train
+    if moved:
+      self.model.invalidate_shadows()  # raw-pointer update; the next forward re-casts them
+
+  def load_state_dict(self, state_dict):
+    super().load_state_dict(state_dict)
+    for g in self.param_groups:
+      g['k'] = int(g['k'])
+      g['weight_sum'], g['lr_max'], g['scheduled_lr'] = float(g['weight_sum']), float(g['lr_max']), float(g['scheduled_lr'])
+      g['train_mode'] = bool(g['train_mode'])
+    self._step_count = max(g['k'] for g in self.param_groups)
+
+  def _restore_host_state(self, gi, states):
+    have = ['z' in s and 'exp_avg_sq' in s for s in states]
+    if any(have) and not all(have):
+      raise ValueError(f'FlatAdamWScheduleFree: the state dict holds z / exp_avg_sq for some parameters of group {gi} but not all')
+    self._primed[gi] = bool(have) and all(have)
