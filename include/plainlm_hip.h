@@ -212,6 +212,28 @@ int plm_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout,
                  const float* rope_cos, const float* rope_sin, const int32_t* doc_start, const int32_t* doc_plan,
                  uint16_t* dqkv, float* delta, int64_t B, int64_t T, int64_t nh, int64_t hd, void* stream);
 
+/* Dense boolean masks (models/transformer.py:52-61 hands ANY bool [B,T,T] mask to SDPA: sliding windows, prefix-LM, padding, random
+ * patterns; keys after the query included).  A third mask mode with its own kernels (csrc/attn_masked.hip, head dims 32, 64, 128, T % 4 == 0).
+ * plm_attn_mask_pack: mask bool [M, T, T] (one byte per element, nonzero = may attend; the reference's layout) -> bits uint64 [M, T, ceil(T/64)]
+ *   (bit j % 64 of word (m, i, j / 64) = mask[m, i, j]; bits past T are 0) and tile_class uint8 [M, ceil(T/128), ceil(T/64)] of the 128-query x
+ *   64-key tiles the kernels walk (0: no bit set - skipped; 1: every in-range bit set - the unmasked path; 2: mixed).  batch_stride 1: M = B,
+ *   mask m is sequence m's; batch_stride 0: M = 1, one [T, T] mask shared by every sequence (packed once).  One launch, deterministic.
+ *   plm_attn_mask_bytes(M, T): bytes of bits followed by tile_class (the bits take M*T*ceil(T/64)*8 bytes, a multiple of 16; tile_class starts
+ *   there); the caller owns the storage.
+ * plm_attn_fwd_masked / plm_attn_bwd_masked: the plm_attn_fwd / plm_attn_bwd contract (rotated qkv, base-2 lse, dqkv w.r.t. the UN-rotated
+ *   q, k) under the packed mask, with the same batch_stride as the pack.  delta is stored with the plain sign (+rowsum(dO * O)) for every head dim.
+ *   A query row with no allowed key follows torch's SDPA: out = 0, lse = +INFINITY (the backward's exp2(s c - lse) is then exactly 0), and the
+ *   row's dQ and its contributions to dK / dV are 0.  Deterministic (no atomics).
+ * NULL pointers, hd not in {32, 64, 128}, a bad shape or batch_stride, and qkv / out / dout / dqkv / RoPE tables / bits / tile_class that are not
+ * 16-byte aligned are refused with PLM_E_INVALID before anything is launched. */
+int64_t plm_attn_mask_bytes(int64_t B, int64_t T);
+int plm_attn_mask_pack(const uint8_t* mask, int64_t batch_stride, uint64_t* bits, uint8_t* tile_class, int64_t B, int64_t T, void* stream);
+int plm_attn_fwd_masked(const uint16_t* qkv, const uint64_t* bits, const uint8_t* tile_class, int64_t batch_stride, uint16_t* out, float* lse,
+                        int64_t B, int64_t T, int64_t nh, int64_t hd, void* stream);
+int plm_attn_bwd_masked(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, const float* rope_cos,
+                        const float* rope_sin, const uint64_t* bits, const uint8_t* tile_class, int64_t batch_stride, uint16_t* dqkv,
+                        float* delta, int64_t B, int64_t T, int64_t nh, int64_t hd, void* stream);
+
 /* ---- fused cross-entropy forward+backward (engine/engine.py:81,111) -----
  * logits bf16[M, ld] (row stride ld >= V) are OVERWRITTEN with dlogits = (softmax - onehot) * grad_scale
  * (grad_scale = g/M); pad columns V..ld are set to zero so the buffer can feed a GEMM with K = ld.

@@ -3,15 +3,17 @@
 
 from fractions import Fraction
 
-from .transformer import ModelConfig, Transformer
+from .transformer import ModelConfig, Transformer, check_attn_mask_mode
 
 
 def construct_model(cfg):
   """cfg: any object with the reference's YAML keys (model, vocab_size, d_model, expand,
-  n_layers, n_heads, mlp_class, seq_len, tie_embeddings).  Returns (model, model_cfg)."""
+  n_layers, n_heads, mlp_class, seq_len, tie_embeddings), plus the optional ``attn_mask_mode`` ('doc', the default, or 'dense': see
+  ModelConfig).  Returns (model, model_cfg)."""
   if cfg.model != 'transformer':
     raise NotImplementedError(
       f"model '{cfg.model}' is outside the accelerated hot path (only 'transformer'; the Pythia/HF branch is not built)")
+  attn_mask_mode = check_attn_mask_mode(getattr(cfg, 'attn_mask_mode', 'doc'))
   model_cfg = ModelConfig(
     vocab_size=cfg.vocab_size,
     dim=cfg.d_model,
@@ -22,6 +24,7 @@ def construct_model(cfg):
     mlp=cfg.mlp_class,
     seq_len=cfg.seq_len,
     tie_embeddings=cfg.tie_embeddings,
+    attn_mask_mode=attn_mask_mode,
   )
   model = Transformer(model_cfg)
   print(f'Number of parameters: {model.count_params(non_embedding=False):_}')

@@ -76,6 +76,11 @@ static void rope_qk_launch(uint16_t* qkv, const float* rope_cos, const float* ro
   hipLaunchKernelGGL(rope_qk_kernel, dim3((unsigned)blocks), dim3(256), 0, s, qkv, rope_cos, rope_sin, B * T, (int)T, (int)nh, (int)hd, sgn);
 }
 
+// the inverse rotation in place (the masked family's backward, attn_masked.hip)
+void plm_rope_qk_inverse(uint16_t* qkv, const float* rope_cos, const float* rope_sin, int64_t B, int64_t T, int64_t nh, int64_t hd, hipStream_t s) {
+  rope_qk_launch(qkv, rope_cos, rope_sin, B, T, nh, hd, -1.f, s);
+}
+
 extern "C" int plm_rope_qk(uint16_t* qkv, const float* rope_cos, const float* rope_sin, int64_t B, int64_t T, int64_t nh, int64_t hd,
                            void* stream) {
   PLM_REQUIRE(qkv && rope_cos && rope_sin, "plm_rope_qk: null pointer");

@@ -369,13 +369,44 @@ class DocMask:
     self.plan = ops.attn_doc_plan(doc_start, n_heads) if plan is None else plan
 
 
+class DenseMask:
+  """Any boolean attention mask as the masked kernels take it (models/transformer.py:52-61 hands any bool mask to SDPA): bool [B,T,T], or
+  [T,T] / [1,T,T] shared by every sequence, True = may attend, keys after the query allowed.  Packed ONCE (ops.attn_mask_pack: bits + the
+  class of every 128 x 64 tile, B*T*T/8 bytes) and shared by every layer's forward and backward.  A query row with no allowed key gives 0,
+  as torch's SDPA does, and no gradient."""
+  __slots__ = ('bits', 'tile_class', 'n_heads', 'batch', 'seq_len')
+
+  def __init__(self, mask, n_heads):
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool:
+      raise TypeError(f'DenseMask: need a bool tensor (True = may attend), got {getattr(mask, "dtype", type(mask))}')
+    if mask.dim() not in (2, 3) or mask.shape[-1] != mask.shape[-2] or mask.shape[-1] == 0:
+      raise ValueError(f'DenseMask: need a bool [B, T, T] or [T, T] mask, got shape {tuple(mask.shape)}')
+    if mask.shape[-1] % 4:
+      raise ValueError(f'DenseMask: T={mask.shape[-1]} must be a multiple of 4 (as for every attention path here)')
+    self.n_heads = n_heads
+    self.seq_len = mask.shape[-1]
+    self.batch = mask.shape[0] if mask.dim() == 3 else 1  # 1: one mask for every sequence
+    self.bits, self.tile_class = ops.attn_mask_pack(mask)
+
+  def check(self, B, T):
+    if self.seq_len != T or self.batch not in (1, B):
+      raise ValueError(f'DenseMask of {self.batch} x [{self.seq_len}, {self.seq_len}] does not fit a batch of {B} x {T} tokens')
+
+
 class AttnFn(torch.autograd.Function):
-  """RoPE + causal/doc-masked SDPA on the raw w_qkv output (transformer.py:43-65).  ``doc``: None (causal), a DocMask, or a bare
-  int32 doc_start [B,T] (its plan is then built per call)."""
+  """RoPE + causal/doc-masked SDPA on the raw w_qkv output (transformer.py:43-65).  ``doc``: None (causal), a DocMask, a bare
+  int32 doc_start [B,T] (its plan is then built per call), or a DenseMask (any boolean mask: the masked kernel family)."""
 
   @staticmethod
   def forward(ctx, qkv, cos, sin, doc, B, T, nh):
     # qkv arrives with q, k already rotated (QKVRopeFn); attn_bwd returns the gradient w.r.t. the UN-rotated projection.
+    if isinstance(doc, DenseMask):
+      doc.check(B, T)
+      out, lse = ops.attn_fwd_masked(qkv, doc.bits, doc.tile_class, B, T, nh)
+      ctx.save_for_backward(qkv, out, lse, cos, sin)
+      ctx.doc = doc
+      ctx.dims = (B, T, nh)
+      return out
     if doc is not None and (not isinstance(doc, DocMask) or doc.n_heads != nh):
       doc = DocMask(doc.doc_start if isinstance(doc, DocMask) else doc, nh)
     ds, plan = (doc.doc_start, doc.plan) if doc is not None else (None, None)
@@ -389,6 +420,9 @@ class AttnFn(torch.autograd.Function):
   def backward(ctx, dout):
     qkv, out, lse, cos, sin = ctx.saved_tensors
     B, T, nh = ctx.dims
+    if isinstance(ctx.doc, DenseMask):
+      dqkv = ops.attn_bwd_masked(qkv, out, dout.contiguous(), lse, cos, sin, ctx.doc.bits, ctx.doc.tile_class, B, T, nh)
+      return dqkv, None, None, None, None, None, None
     ds, plan = (ctx.doc.doc_start, ctx.doc.plan) if ctx.doc is not None else (None, None)
     dqkv = ops.attn_bwd(qkv, out, dout.contiguous(), lse, cos, sin, B, T, nh, ds, plan)
     return dqkv, None, None, None, None, None, None

@@ -547,6 +547,71 @@ def attn_bwd(qkv, out, dout, lse, rope_cos, rope_sin, B, T, nh, doc_start=None, 
   return dqkv
 
 
+def attn_mask_pack(mask):
+  """Dense mask mode: bool [B, T, T] (True = may attend, the reference's layout) or [T, T] (one mask for every sequence) on the GPU ->
+  (bits int64 [M, T, ceil(T/64)] - the kernels' uint64 words: bit j % 64 of word (m, i, j // 64) is mask[m, i, j] -, tile_class uint8
+  [M, ceil(T/128), ceil(T/64)]: 0 = no bit set, 1 = every in-range bit set, 2 = mixed), M = B, or 1 for a [T, T] / [1, T, T] mask.  One launch,
+  both results views of one allocation; pack once per batch and pass the pair to every layer's attn_fwd_masked / attn_bwd_masked."""
+  if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool:
+    raise TypeError('attn_mask_pack: need a bool mask')
+  if mask.dim() not in (2, 3) or mask.shape[-1] != mask.shape[-2] or mask.shape[-1] == 0:
+    raise ValueError(f'attn_mask_pack: need a bool [B, T, T] or [T, T] mask, got shape {tuple(mask.shape)}')
+  if not mask.is_cuda:
+    raise RuntimeError('attn_mask_pack: mask must live on the GPU (plainlm_amd has no CPU path)')
+  mask = mask.contiguous()
+  T = mask.shape[-1]
+  M = mask.shape[0] if mask.dim() == 3 else 1
+  if T % 4:
+    raise ValueError(f'attn_mask_pack: T={T} must be a multiple of 4')
+  W, NQT = (T + 63) // 64, (T + 127) // 128
+  lib = _lib.load()
+  buf = torch.empty((lib.plm_attn_mask_bytes(M, T),), dtype=torch.uint8, device=mask.device)
+  nb = M * T * W * 8
+  bits = buf[:nb].view(torch.int64).view(M, T, W)
+  tile_class = buf[nb:nb + M * NQT * W].view(M, NQT, W)
+  _lib.check(lib.plm_attn_mask_pack(_p(mask), 1 if M > 1 else 0, _p(bits), _p(tile_class), M, T, _stream()), 'plm_attn_mask_pack')
+  return bits, tile_class
+
+
+def _mask_stride(bits, tile_class, B, T, what):
+  W = (T + 63) // 64
+  if bits.dtype != torch.int64 or tile_class.dtype != torch.uint8 or not bits.is_cuda or not tile_class.is_cuda:
+    raise TypeError(f'{what}: bits / tile_class must be the int64 / uint8 GPU tensors of attn_mask_pack')
+  if bits.dim() != 3 or bits.shape[0] not in (1, B) or tuple(bits.shape[1:]) != (T, W) or \
+     tuple(tile_class.shape) != (bits.shape[0], (T + 127) // 128, W):
+    raise ValueError(f'{what}: packed mask of shape {tuple(bits.shape)} / {tuple(tile_class.shape)} does not fit B={B}, T={T}')
+  return 1 if bits.shape[0] == B and B > 1 else 0
+
+
+def attn_fwd_masked(qkv_rot, bits, tile_class, B, T, nh):
+  """attn_fwd under a packed dense mask (attn_mask_pack).  A query row with no allowed key gives out = 0 and lse = +inf (torch's SDPA
+  returns 0 for such a row)."""
+  _need(qkv_rot, BF16, 'attn_fwd_masked.qkv', 2)
+  hd = qkv_rot.shape[1] // (3 * nh)
+  bs = _mask_stride(bits, tile_class, B, T, 'attn_fwd_masked')
+  out = torch.empty((B * T, nh * hd), dtype=BF16, device=qkv_rot.device)
+  lse = torch.empty((B, nh, T), dtype=F32, device=qkv_rot.device)
+  _hook('attn_fwd', attn_flops(B, T, nh, hd))
+  _lib.check(_lib.load().plm_attn_fwd_masked(_p(qkv_rot), _p(bits), _p(tile_class), bs, _p(out), _p(lse), B, T, nh, hd, _stream()),
+             'plm_attn_fwd_masked')
+  return out, lse
+
+
+def attn_bwd_masked(qkv, out, dout, lse, rope_cos, rope_sin, bits, tile_class, B, T, nh, return_delta=False):
+  """attn_bwd under a packed dense mask: dqkv w.r.t. the UN-rotated projection; return_delta: also delta = rowsum(dO * O), fp32 [B, nh, T]."""
+  _need(dout, BF16, 'attn_bwd_masked.dout', 2)
+  hd = qkv.shape[1] // (3 * nh)
+  bs = _mask_stride(bits, tile_class, B, T, 'attn_bwd_masked')
+  dqkv = torch.empty_like(qkv)
+  delta = torch.empty((B, nh, T), dtype=F32, device=qkv.device)
+  _hook('attn_bwd', 2.0 * attn_flops(B, T, nh, hd))
+  _lib.check(_lib.load().plm_attn_bwd_masked(_p(qkv), _p(out), _p(dout), _p(lse), _p(rope_cos), _p(rope_sin), _p(bits), _p(tile_class), bs,
+                                             _p(dqkv), _p(delta), B, T, nh, hd, _stream()), 'plm_attn_bwd_masked')
+  if return_delta:
+    return dqkv, delta
+  return dqkv
+
+
 # ---- cross entropy --------------------------------------------------------------------
 def ce_fwd_bwd_(logits, targets, grad_scale, V=None):
   """In place: logits[:, :V] <- (softmax - onehot) * grad_scale, logits[:, V:] <- 0 (logits is bf16 [M, ld], ld >= V).

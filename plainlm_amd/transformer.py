@@ -34,6 +34,18 @@ class ModelConfig:
   mlp: str = 'mlp'
   rmsnorm_eps: float = 1e-6
   tie_embeddings: bool = False
+  # not in the reference: how a bool attn_mask is read.  'doc': as a block-diagonal causal mask (doc_start + the tuned kernels; anything
+  # else is refused); 'dense': as any mask at all (functional.DenseMask + the masked kernels)
+  attn_mask_mode: str = 'doc'
+
+
+ATTN_MASK_MODES = ('doc', 'dense')
+
+
+def check_attn_mask_mode(mode):
+  if mode not in ATTN_MASK_MODES:
+    raise ValueError(f'attn_mask_mode: {mode!r} is not one of {ATTN_MASK_MODES}')
+  return mode
 
 
 def rope_tables(head_dim, seq_len, theta=500000.0):
@@ -215,6 +227,7 @@ class Transformer(nn.Module):
     super().__init__()
     self.cfg = cfg
     self.n_layers = cfg.n_layers
+    check_attn_mask_mode(cfg.attn_mask_mode)
     if cfg.dim % cfg.n_heads != 0:
       raise ValueError('dim must be divisible by n_heads')
     self.head_dim = cfg.dim // cfg.n_heads
@@ -364,7 +377,7 @@ class Transformer(nn.Module):
       cls.check_mask_status()
       ds, cls._mask_status = ops.doc_start_from_mask(attn_mask)
       return ds
-    raise TypeError('attn_mask must be None, a bool [B,T,T] mask or an int32 doc_start [B,T]')
+    raise TypeError('attn_mask must be None, a bool [B,T,T] mask, an int32 doc_start [B,T], a functional.DocMask or a functional.DenseMask')
 
   @classmethod
   def check_mask_status(cls):
@@ -373,7 +386,7 @@ class Transformer(nn.Module):
     st, cls._mask_status = cls._mask_status, None
     if st is not None and int(st.item()) != 0:
       raise ValueError('attn_mask: a row of the previous bool mask was not exactly True on [first allowed key, query]: only block-diagonal causal '
-                       'masks (data_prep_utils.py:7-23) are supported')
+                       'masks (data_prep_utils.py:7-23) are supported (any other mask: attn_mask_mode: dense, or pass a functional.DenseMask)')
 
   def _trunk(self, x, attn_mask):
     if x.dim() != 2 or x.dtype != torch.int64:
@@ -384,8 +397,14 @@ class Transformer(nn.Module):
     if T > self.cfg.seq_len:
       raise ValueError(f'sequence length {T} exceeds cfg.seq_len {self.cfg.seq_len}')
     rope = self._rope(x.device)
-    doc_start = self._doc_start(attn_mask, B, T)
-    if doc_start is not None and not isinstance(doc_start, Fn.DocMask):
+    if self.cfg.attn_mask_mode == 'dense' and isinstance(attn_mask, torch.Tensor) and attn_mask.dtype == torch.bool:
+      attn_mask = Fn.DenseMask(attn_mask.to(x.device), self.cfg.n_heads)  # packed once per batch, shared by every layer
+    if isinstance(attn_mask, Fn.DenseMask):
+      attn_mask.check(B, T)
+      doc_start = attn_mask
+    else:
+      doc_start = self._doc_start(attn_mask, B, T)
+    if doc_start is not None and not isinstance(doc_start, (Fn.DocMask, Fn.DenseMask)):
       doc_start = Fn.DocMask(doc_start, self.cfg.n_heads)  # + the plan: one small launch per batch, shared by every layer's attention launches
     self.refresh_shadows()
     h = self.embed_tokens(x).view(B * T, self.cfg.dim)
