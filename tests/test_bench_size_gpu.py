@@ -24,6 +24,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import cpu_ref as O  # noqa: E402
 from oracle import parity as PB  # noqa: E402
+from oracle import parity_ops as PO  # noqa: E402
 
 LOSS_RTOL = 1e-4
 
@@ -168,6 +169,8 @@ def test_fc1_swiglu_bench_shape_vs_oracle(ops):
   assert relerr(act.float(), O.swiglu(u.float().cpu(), H160)) <= 1.6e-2
   u2 = ops.gemm_nt(x.cuda(), w.cuda())
   assert torch.equal(u, u2) and torch.equal(act, ops.swiglu_fwd(u2))
+  rows = slice(0, 2048)  # oracle/parity_ops.py's budget on one block of rows (fp64 of all 32768 would cost seconds)
+  PO.check(PO.elementwise(act[rows], PO.swiglu_fwd_reference(u[rows].cpu())), 'fc1_swiglu bench shape')
 
 
 def test_fc2_dx_swiglu_bwd_bench_shape_vs_oracle(ops):
@@ -182,7 +185,11 @@ def test_fc2_dx_swiglu_bwd_bench_shape_vs_oracle(ops):
   leaf = u.float().requires_grad_(True)
   O.swiglu(leaf, H160).backward(dact)
   assert relerr(du.float(), leaf.grad) <= 1.6e-2
-  assert torch.equal(du, ops.swiglu_bwd(ops.gemm_nt(dy.cuda(), w2t.cuda()), u.cuda()))
+  dact_gpu = ops.gemm_nt(dy.cuda(), w2t.cuda())
+  assert torch.equal(du, ops.swiglu_bwd(dact_gpu, u.cuda()))
+  rows = slice(M160 - 2048, M160)
+  ref, allow = PO.swiglu_bwd_reference(dact_gpu[rows].cpu(), u[rows])
+  PO.check(PO.elementwise(du[rows], ref, allow), 'fc2_dx_swiglu_bwd bench shape')
 
 
 def test_qkv_rope_bench_shape_vs_oracle(ops):
@@ -199,8 +206,11 @@ def test_qkv_rope_bench_shape_vs_oracle(ops):
   got = ops.qkv_rope(x.cuda(), w.cuda(), cos.cuda(), sin.cuda(), B, T, nh)
   assert relerr(got.float(), ref) <= 8e-3
   two = ops.gemm_nt(x.cuda(), w.cuda())
+  pre = two[:T].cpu()
   ops.rope_qk_(two, cos.cuda(), sin.cuda(), B, T, nh)
   assert torch.equal(got, two)
+  ref, allow = PO.rope_reference(pre, cos, sin, 1, T, nh)
+  PO.check(PO.elementwise(got[:T, :2 * d], ref, allow), 'qkv rope bench shape')
 
 
 def test_cross_entropy_bench_shape_vs_oracle(ops):
@@ -227,6 +237,8 @@ def test_cross_entropy_bench_shape_vs_oracle(ops):
   print(f'cross-entropy 32768 x 50280: loss gpu {loss:.6f} oracle {tot:.6f}, dlogits worst rel-to-max {worst:.2e}')
   assert abs(loss - tot) <= 2e-6 * abs(tot) + 1e-6
   assert worst <= 8e-3
+  pick = torch.arange(0, M, 512)  # the budget on 64 rows spread over the batch (pad columns included)
+  PO.check(PO.ce(buf[pick.cuda()], rows[pick.cuda()], PO.ce_reference(logits[pick], tc[pick], 1.0 / M, V)), 'ce bench shape')
 
 
 def test_add_rmsnorm_bench_shape_vs_oracle(ops):
@@ -247,6 +259,10 @@ def test_add_rmsnorm_bench_shape_vs_oracle(ops):
   dx, dxb, dw = ops.rmsnorm_bwd(dy.cuda(), xout, w.cuda(), rstd, gin=gin.cuda(), want_bf16=True)
   assert relerr(dx, rr.grad + gin) <= 2e-5 and torch.equal(dxb, dx.bfloat16())
   assert relerr(dw, ww.grad) <= 1e-4  # 32768-term fp32 column sums in a different order
+  r = rr.detach()  # x + bf16 branch in fp32: the operands the forward read, not its own xout
+  ref_y, ref_rstd = PO.rmsnorm_fwd_reference(r, w, 1e-6)
+  ref_dx, ref_dw, dw_scale = PO.rmsnorm_bwd_reference(dy, r, w, rstd)
+  PO.check(PO.merge(PO.rmsnorm_fwd(y, rstd, ref_y, ref_rstd), PO.rmsnorm_bwd(dx, dw, ref_dx, ref_dw, dw_scale, gin)), 'add_rmsnorm bench shape')
 
 
 # --------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import cpu_ref as O  # noqa: E402
 from oracle import parity as PB  # noqa: E402
+from oracle import parity_ops as PO  # noqa: E402
 
 
 @pytest.fixture(scope='module')
@@ -163,6 +164,10 @@ def test_rmsnorm_fwd_bwd(ops, M, d, with_branch):
   acc = torch.ones(d, device='cuda')
   ops.rmsnorm_bwd(dy.cuda(), xout, w.cuda(), rstd, dw_out=acc, dw_accumulate=True)
   close(acc, ww.grad + 1, 2e-5, 'rmsnorm dw accumulate')
+  # oracle/parity_ops.py's budget: y and rstd from the fp32 r, dx / dw from the operands the backward read
+  ref_y, ref_rstd = PO.rmsnorm_fwd_reference(r, w, 1e-6)
+  ref_dx, ref_dw, dw_scale = PO.rmsnorm_bwd_reference(dy, r, w, rstd)
+  PO.check(PO.merge(PO.rmsnorm_fwd(y, rstd, ref_y, ref_rstd), PO.rmsnorm_bwd(dx, dw, ref_dx, ref_dw, dw_scale, gin)), f'rmsnorm {M}x{d} branch={with_branch}')
 
 
 def test_rmsnorm_golden(ops, golden_dir):
@@ -213,6 +218,8 @@ def test_swiglu_fwd_bwd(ops, M, h):
   yb.backward(dout.cuda())
   assert (out.float() - yb.float()).abs().max() <= 2 ** -7 * yb.float().abs().max()
   assert (du.float() - ub.grad.float()).abs().max() <= 2 ** -6 * ub.grad.float().abs().max()
+  ref_bwd, allow = PO.swiglu_bwd_reference(dout, u)
+  PO.check(PO.merge(PO.elementwise(out, PO.swiglu_fwd_reference(u)), PO.elementwise(du, ref_bwd, allow)), f'swiglu {M}x{h}')
 
 
 # --------------------------------------------------------------------------------------
@@ -852,11 +859,14 @@ def test_rope_qk_golden(ops, golden_dir):
   qkv = bf(torch.cat([z['rope_q'].reshape(B * T, d), z['rope_k'].reshape(B * T, d), torch.ones(B * T, d)], dim=1)).cuda()
   cos, sin = (t.cuda() for t in O.rope_table(hd, T))
   ref_q = O.rope_apply(qkv[:, :d].float().cpu().reshape(B, T, nh, hd), cos.cpu(), sin.cpu()).reshape(B * T, d)
+  pre = qkv.cpu()
   ops.rope_qk_(qkv, cos, sin, B, T, nh)
   close(qkv[:, :d].float(), z['rope_qr'].reshape(B * T, d), 8e-3, 'rope q vs reference')
   close(qkv[:, d:2 * d].float(), z['rope_kr'].reshape(B * T, d), 8e-3, 'rope k vs reference')
   assert (qkv[:, :d].float().cpu() - ref_q).abs().max() <= 2 ** -7 * ref_q.abs().max()
   assert (qkv[:, 2 * d:] == 1).all()  # v untouched
+  ref, allow = PO.rope_reference(pre, cos.cpu(), sin.cpu(), B, T, nh)
+  PO.check(PO.elementwise(qkv[:, :2 * d], ref, allow), 'rope golden')
 
 
 @pytest.mark.parametrize('B,T,nh,K', [(4, 256, 2, 128), (8, 1024, 12, 768), (3, 100, 1, 64), (5, 200, 2, 128), (3, 344, 5, 64), (8, 2048, 16, 1024)])  # last: 420M at full size
@@ -874,8 +884,11 @@ def test_qkv_projection_with_rope(ops, B, T, nh, K):
   close(got.float(), ref, 8e-3, 'qkv projection + rope')
   # the rotation in the GEMM epilogue (big shapes) and the stand-alone pass (small ones / fallback) give the same bits
   two = ops.gemm_nt(x.cuda(), w.cuda())
+  pre = two[:T].cpu()
   ops.rope_qk_(two, cos.cuda(), sin.cuda(), B, T, nh)
   assert torch.equal(got, two)
+  ref, allow = PO.rope_reference(pre, cos, sin, 1, T, nh)  # the first sequence, from the GEMM's own bf16 output
+  PO.check(PO.elementwise(got[:T, :2 * d], ref, allow), f'qkv rope {B}x{T}x{nh}')
 
 
 def test_attention_softmax_rescale_branch(ops):
@@ -991,6 +1004,7 @@ def test_cross_entropy(ops, M, V):
   lm = ops.mean(rows)
   assert abs(lm.item() - loss.item()) <= 2e-6 * abs(loss.item()) + 1e-6
   close(buf.float(), leaf.grad, 8e-3, 'dlogits (bf16)')
+  PO.check(PO.ce(buf, rows, PO.ce_reference(logits, tgt, 1.0 / M, V)), f'ce {M}x{V}')
 
 
 def test_cross_entropy_padded_rows(ops):
@@ -1008,6 +1022,7 @@ def test_cross_entropy_padded_rows(ops):
   assert abs(ops.mean(rows).item() - loss.item()) <= 2e-6 * abs(loss.item()) + 1e-6
   close(buf[:, :V].float(), leaf.grad, 8e-3, 'dlogits (padded rows)')
   assert (buf[:, V:] == 0).all()
+  PO.check(PO.ce(buf, rows, PO.ce_reference(logits, tgt, 1.0 / M, V)), 'ce padded rows')
 
 
 def test_cast_transpose_padded(ops):
