@@ -317,6 +317,35 @@ int plm_optim_cast_multi(const plm_optim_hparams* h, const plm_adamw_item* items
  * A NULL p or z or n <= 0 gives PLM_E_INVALID. */
 int plm_lerp_f32(float* p, const float* z, int64_t n, float w, void* stream);
 
+/* ---- MXFP8 (OCP MX: e4m3fn elements, one E8M0 scale byte per 32 elements)
+ * Layout of a quantized operand blocked along its K: data uint8 [rows, Kp] and scales uint8 [rows, Kp/32], both row-major, Kp = roundup(K, 128);
+ * padding elements are zero with scale byte 0.  Scale rule: amax = max |x| of the block, E = floor(log2 amax), e = E - 8 if amax <= 448 * 2^(E-8)
+ * else E - 7, clamped to [-127, 127]; scale byte e + 127, element RNE_e4m3fn(x * 2^-e) (subnormals kept).  amax = 0: scale byte 0, zero
+ * elements; a block holding NaN / Inf: scale byte 0xFF, every element 0x7F (NaN), so it reaches the GEMM output as NaN.
+ * plm_mx_quant: bf16 x [rows, cols] (leading dimension ld) -> the row-blocked copy q [rows, roundup(cols,128)] + s, and/or the transposed
+ * copy qt [cols, roundup(rows,128)] + st blocked along rows, from one read of x.  Either pair may be NULL, not both.  Needs cols % 8 == 0,
+ * ld % 8 == 0, x / q / qt 16-byte aligned.  plm_mx_quant_multi: the same for `count` items in one launch (per 64 items). */
+typedef struct plm_mx_quant_item {
+  const uint16_t* x; /* bf16 [rows, ld] */
+  int64_t ld;
+  int64_t rows;
+  int64_t cols;
+  uint8_t* q;  /* [rows, roundup(cols,128)] or NULL */
+  uint8_t* s;  /* [rows, roundup(cols,128)/32] or NULL */
+  uint8_t* qt; /* [cols, roundup(rows,128)] or NULL */
+  uint8_t* st; /* [cols, roundup(rows,128)/32] or NULL */
+} plm_mx_quant_item;
+int plm_mx_quant(const uint16_t* x, int64_t ld, int64_t rows, int64_t cols, uint8_t* q, uint8_t* s, uint8_t* qt, uint8_t* st, void* stream);
+int plm_mx_quant_multi(const plm_mx_quant_item* items, int count, void* stream);
+/* C[M,N] = deq(A)[M,Kp] . deq(B)[N,Kp]^T (A, B quantized along Kp as above) on v_mfma_scale_f32_32x32x64_f8f6f4, fp32 accumulation.
+ * mode PLM_MX_OUT_BF16: C bf16, PLM_MX_OUT_F32: C fp32 stored, PLM_MX_OUT_F32_ACC: C fp32 += the product (main_grad).  Row stride ldc >= N.
+ * Needs Kp % 128 == 0, A / B 16-byte aligned, scales 4-byte aligned. */
+#define PLM_MX_OUT_BF16 0
+#define PLM_MX_OUT_F32 1
+#define PLM_MX_OUT_F32_ACC 2
+int plm_gemm_mx_nt(const uint8_t* A, const uint8_t* As, const uint8_t* B, const uint8_t* Bs, void* C, int64_t ldc, int64_t M, int64_t N, int64_t Kp,
+                   int mode, void* stream);
+
 /* Leave `n` CUs free when sizing the persistent GEMM grids (one workgroup per CU, static tile schedule), so that
  * concurrently running RCCL collectives do not push GEMM workgroups into a second round.  Process-wide; 0 = whole chip. */
 int plm_set_cu_reserve(int n);

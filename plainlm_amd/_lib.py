@@ -17,7 +17,7 @@ _lib = None
 
 # ABI the signatures below were written for (plm_version() of the library must match: a stale .so that still exports every
 # symbol but with other argument lists / struct layouts would corrupt memory instead of raising)
-EXPECTED_ABI = 110
+EXPECTED_ABI = 111
 
 _P = C.c_void_p
 _I64 = C.c_int64
@@ -54,6 +54,14 @@ class TnProblem(C.Structure):
   """struct plm_tn_problem (include/plainlm_hip.h)."""
   _fields_ = [('A', _P), ('lda', _I64), ('B', _P), ('ldb', _I64), ('C', _P), ('ldc', _I64), ('M', _I64), ('N', _I64),
               ('accumulate', _I), ('alpha_dev', _P)]
+
+
+class MxQuantItem(C.Structure):
+  """struct plm_mx_quant_item (include/plainlm_hip.h)."""
+  _fields_ = [('x', _P), ('ld', _I64), ('rows', _I64), ('cols', _I64), ('q', _P), ('s', _P), ('qt', _P), ('st', _P)]
+
+
+MX_OUT_BF16, MX_OUT_F32, MX_OUT_F32_ACC = 0, 1, 2  # PLM_MX_OUT_*
 
 
 # name -> (restype, argtypes); must cover every function in include/plainlm_hip.h
@@ -117,6 +125,9 @@ SIGNATURES = {
   'plm_comm_allreduce_avg_f32': (_I, [_P, _P, _I64, _P]),
   'plm_comm_rsag_avg_f32': (_I, [_P, _P, _I64, _P]),
   'plm_comm_broadcast_f32': (_I, [_P, _P, _I64, _I, _P]),
+  'plm_mx_quant': (_I, [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
+  'plm_mx_quant_multi': (_I, [C.POINTER(MxQuantItem), _I, _P]),
+  'plm_gemm_mx_nt': (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P]),
   'plm_probe_ds_read_tr16': (_I, [_P, _P]),
   'plm_probe_mfma32': (_I, [_P, _P, _P, _P]),
 }

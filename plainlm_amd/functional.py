@@ -52,10 +52,11 @@ class GradSink:
 
   def defer_dw(self, dy, x, p):
     """Queue dW(p) (+)= dy^T x; runs when the group is full or at flush_dw()."""
-    if isinstance(dy, torch.Tensor) and isinstance(x, torch.Tensor):
-      nbytes = dy.numel() * dy.element_size() + x.numel() * x.element_size()
+    mx = isinstance(dy, ops.MxTensor) and isinstance(x, ops.MxTensor)  # linear_precision 'mxfp8': both blocked along the tokens
+    if mx or (isinstance(dy, torch.Tensor) and isinstance(x, torch.Tensor)):
+      nbytes = dy.nbytes() + x.nbytes() if mx else dy.numel() * dy.element_size() + x.numel() * x.element_size()
       if self.dw_queue_bytes_max is None:
-        self.resolve_queue_budget(dy.device)
+        self.resolve_queue_budget(dy.data.device if mx else dy.device)
       if self.dw_queue and self.dw_queue_bytes + nbytes > self.dw_queue_bytes_max:
         self._flush_linear_dw()  # BEFORE the append: the queue never pins more than the budget
       self.dw_queue_bytes += nbytes
@@ -105,8 +106,12 @@ class GradSink:
     self.dw_queue_bytes = 0
     if not q:
       return
-    if len(q) == 1 or not ops.gemm_tn_grouped([(dy, x, p.main_grad, acc, None) for dy, x, p, acc in q]):
-      for dy, x, p, acc in q:
+    for dy, x, p, acc in q:  # MX operands: one MX GEMM each, fp32 store or accumulate into main_grad
+      if isinstance(dy, ops.MxTensor):
+        ops.gemm_mx_nt(dy, x, out=p.main_grad, accumulate=acc)
+    bf = [it for it in q if not isinstance(it[0], ops.MxTensor)]
+    if len(bf) == 1 or (bf and not ops.gemm_tn_grouped([(dy, x, p.main_grad, acc, None) for dy, x, p, acc in bf])):
+      for dy, x, p, acc in bf:
         ops.gemm_tn(dy, x, out=p.main_grad, accumulate=acc)
     for _, _, p, _ in q:
       self.ready(p)
@@ -247,6 +252,107 @@ class QKVRopeFn(torch.autograd.Function):
   def backward(ctx, dy):
     dx, dw, _ = LinearFn.backward(ctx, dy)
     return dx, dw, None, None, None, None, None, None
+
+
+# ---- linear_precision 'mxfp8': the block linears on MX GEMMs ------------------------------------------------------
+# Separate Functions; the bf16 ones above are untouched.  Every bf16 input of a linear is quantized once into both orientations: the
+# row-blocked copy feeds the forward / dX GEMM, the column-blocked copy (blocked along the tokens) is what is kept for dW.  The fused RoPE
+# and SwiGLU epilogues are not used: the stand-alone kernels run between the GEMMs.
+def _mx_dw(lin, dyt, xt):
+  """dW = dY^T X from the copies of dY and X blocked along the tokens: queued in the sink, else returned fp32 to autograd."""
+  sink, p = lin.sink, lin.weight
+  if sink is not None and sink.active_for(p):
+    sink.defer_dw(dyt, xt, p)
+    return None
+  return ops.gemm_mx_nt(dyt, xt, out_dtype=torch.float32)
+
+
+def _mx_linear_bwd(ctx, lin, dy, xt):
+  """(dx, dW) of y = x W^T: dY quantized once into both orientations."""
+  dyr, dyt = ops.mx_quant(dy.contiguous())
+  dx = ops.gemm_mx_nt(dyr, lin.mx_weights()[1]) if ctx.needs_input_grad[0] else None
+  dw = _mx_dw(lin, dyt, xt) if ctx.needs_input_grad[1] else None
+  return dx, dw
+
+
+class MxLinearFn(torch.autograd.Function):
+  """LinearFn on MX GEMMs."""
+
+  @staticmethod
+  def forward(ctx, x, weight, lin):
+    xr, xt = ops.mx_quant(x)
+    ctx.xt, ctx.lin = xt, lin
+    return ops.gemm_mx_nt(xr, lin.mx_weights()[0])
+
+  @staticmethod
+  def backward(ctx, dy):
+    dx, dw = _mx_linear_bwd(ctx, ctx.lin, dy, ctx.xt)
+    return dx, dw, None
+
+
+class MxQKVRopeFn(torch.autograd.Function):
+  """QKVRopeFn on an MX GEMM followed by the stand-alone RoPE kernel (same contract with AttnFn: the backward is the Linear's)."""
+
+  @staticmethod
+  def forward(ctx, x, weight, lin, cos, sin, B, T, nh):
+    xr, xt = ops.mx_quant(x)
+    ctx.xt, ctx.lin = xt, lin
+    y = ops.gemm_mx_nt(xr, lin.mx_weights()[0])
+    ops.rope_qk_(y, cos, sin, B, T, nh)
+    return y
+
+  @staticmethod
+  def backward(ctx, dy):
+    dx, dw = _mx_linear_bwd(ctx, ctx.lin, dy, ctx.xt)
+    return dx, dw, None, None, None, None, None, None
+
+
+def _mx_mlp_bwd(ctx, dy, act_bwd):
+  fc1, fc2 = ctx.fc1, ctx.fc2
+  (u,) = ctx.saved_tensors
+  dyr, dyt = ops.mx_quant(dy.contiguous())
+  du = act_bwd(ops.gemm_mx_nt(dyr, fc2.mx_weights()[1]), u)
+  dw2 = _mx_dw(fc2, dyt, ctx.actt) if ctx.needs_input_grad[2] else None
+  dur, dut = ops.mx_quant(du)
+  dx = ops.gemm_mx_nt(dur, fc1.mx_weights()[1]) if ctx.needs_input_grad[0] else None
+  dw1 = _mx_dw(fc1, dut, ctx.xt) if ctx.needs_input_grad[1] else None
+  return dx, dw1, dw2
+
+
+class MxSwiGLUMLPFn(torch.autograd.Function):
+  """SwiGLUMLPFn on MX GEMMs: fc1 -> plm_swiglu_fwd -> fc2; backward fc2 dX -> plm_swiglu_bwd -> fc1."""
+
+  @staticmethod
+  def forward(ctx, x, w1, w2, fc1, fc2):
+    xr, xt = ops.mx_quant(x)
+    u = ops.gemm_mx_nt(xr, fc1.mx_weights()[0])
+    actr, actt = ops.mx_quant(ops.swiglu_fwd(u))
+    ctx.save_for_backward(u)
+    ctx.xt, ctx.actt, ctx.fc1, ctx.fc2 = xt, actt, fc1, fc2
+    return ops.gemm_mx_nt(actr, fc2.mx_weights()[0])
+
+  @staticmethod
+  def backward(ctx, dy):
+    dx, dw1, dw2 = _mx_mlp_bwd(ctx, dy, ops.swiglu_bwd)
+    return dx, dw1, dw2, None, None
+
+
+class MxPlainMLPFn(torch.autograd.Function):
+  """PlainMLPFn on MX GEMMs: fc1 -> plm_act_fwd -> fc2; backward fc2 dX -> plm_act_bwd -> fc1."""
+
+  @staticmethod
+  def forward(ctx, x, w1, w2, fc1, fc2, kind):
+    xr, xt = ops.mx_quant(x)
+    u = ops.gemm_mx_nt(xr, fc1.mx_weights()[0])
+    actr, actt = ops.mx_quant(ops.act_fwd(u, kind))
+    ctx.save_for_backward(u)
+    ctx.xt, ctx.actt, ctx.fc1, ctx.fc2, ctx.kind = xt, actt, fc1, fc2, kind
+    return ops.gemm_mx_nt(actr, fc2.mx_weights()[0])
+
+  @staticmethod
+  def backward(ctx, dy):
+    dx, dw1, dw2 = _mx_mlp_bwd(ctx, dy, lambda d, u: ops.act_bwd(d, u, ctx.kind))
+    return dx, dw1, dw2, None, None, None
 
 
 class EmbedFn(torch.autograd.Function):

@@ -110,6 +110,98 @@ def cast_bf16_t_multi(items):
     _lib.check(_lib.load().plm_cast_f32_bf16_t_multi(arr, len(items), _stream()), 'plm_cast_f32_bf16_t_multi')
 
 
+# ---- MXFP8 operands and GEMM --------------------------------------------------------------------------------
+def mx_pad(k):
+  """Padded reduction length of an MX operand: roundup(k, 128)."""
+  return (int(k) + 127) // 128 * 128
+
+
+class MxTensor:
+  """One MX-quantized GEMM operand blocked along its reduction dimension: ``data`` uint8 [rows, Kp] (OCP e4m3fn bits), ``scales`` uint8
+  [rows, Kp/32] (E8M0 bytes: 2^(byte - 127)), ``shape`` the logical (rows, K) with Kp = roundup(K, 128); the padding is zero."""
+  __slots__ = ('data', 'scales', 'shape')
+
+  def __init__(self, data, scales, shape):
+    self.data, self.scales, self.shape = data, scales, tuple(shape)
+
+  def nbytes(self):
+    return self.data.numel() + self.scales.numel()
+
+  @staticmethod
+  def empty(rows, k, device):
+    kp = mx_pad(k)
+    return MxTensor(torch.empty((rows, kp), dtype=torch.uint8, device=device), torch.empty((rows, kp // 32), dtype=torch.uint8, device=device),
+                    (rows, k))
+
+
+def _mx_item(x, rows, cols, device):
+  if not x.is_cuda or x.dtype != BF16 or x.dim() != 2 or x.stride(1) != 1:
+    raise ValueError('mx_quant.x: need a 2-D bf16 GPU tensor with unit inner stride')
+  R, Cc = x.shape
+  r = MxTensor.empty(R, Cc, x.device) if rows else None
+  c = MxTensor.empty(Cc, R, x.device) if cols else None
+  item = _lib.MxQuantItem(x.data_ptr(), x.stride(0), R, Cc, r.data.data_ptr() if r else 0, r.scales.data_ptr() if r else 0,
+                          c.data.data_ptr() if c else 0, c.scales.data_ptr() if c else 0)
+  return item, r, c
+
+
+def mx_quant(x, rows=True, cols=True):
+  """bf16 x [R, C] -> (row-blocked MxTensor of shape (R, C) blocked along C, or None; column-blocked MxTensor of x^T, shape (C, R) blocked
+  along R, or None), from one read of x.  The row-blocked copy is the operand of a GEMM reducing over C, the other of one reducing over R."""
+  if not (rows or cols):
+    raise ValueError('mx_quant: ask for at least one orientation')
+  item, r, c = _mx_item(x, rows, cols, x.device)
+  with _Timed('hbm:mx_quant', 2.0 * x.numel() + (1.03125 * x.numel() if rows else 0) + (1.03125 * x.numel() if cols else 0)):
+    _lib.check(_lib.load().plm_mx_quant(item.x, item.ld, item.rows, item.cols, item.q, item.s, item.qt, item.st, _stream()), 'plm_mx_quant')
+  return r, c
+
+
+def mx_quant_multi(xs, rows=True, cols=True):
+  """mx_quant over a list of bf16 tensors in one launch (per 64): a list of (row-blocked, column-blocked) pairs."""
+  if not xs:
+    return []
+  arr = (_lib.MxQuantItem * len(xs))()
+  out = []
+  for i, x in enumerate(xs):
+    arr[i], r, c = _mx_item(x, rows, cols, x.device)
+    out.append((r, c))
+  n = sum(x.numel() for x in xs)
+  with _Timed('hbm:mx_quant_multi', 2.0 * n + 1.03125 * n * (int(rows) + int(cols))):
+    _lib.check(_lib.load().plm_mx_quant_multi(arr, len(xs), _stream()), 'plm_mx_quant_multi')
+  return out
+
+
+def gemm_mx_nt(a, b, out=None, accumulate=False, out_dtype=BF16):
+  """C[M,N] (+)= deq(a)[M,K] @ deq(b)[N,K]^T for MxTensors a, b blocked along the same K; fp32 accumulation.  out_dtype bf16 (store) or fp32
+  (store, or += into ``out`` with accumulate=True)."""
+  if not isinstance(a, MxTensor) or not isinstance(b, MxTensor):
+    raise TypeError('gemm_mx_nt: a and b must be MxTensors (ops.mx_quant)')
+  M, K = a.shape
+  N = b.shape[0]
+  if b.shape[1] != K or a.data.shape[1] != b.data.shape[1]:
+    raise ValueError(f'gemm_mx_nt: reduction lengths differ ({K} vs {b.shape[1]})')
+  if out is None:
+    if accumulate:
+      raise ValueError('gemm_mx_nt: accumulate needs out')
+    out = torch.empty((M, N), dtype=out_dtype, device=a.data.device)
+  if out.dim() != 2 or out.shape != (M, N) or out.stride(1) != 1 or not out.is_cuda:
+    raise ValueError('gemm_mx_nt.out: bad shape/stride')
+  if out.dtype == BF16:
+    if accumulate:
+      raise ValueError('gemm_mx_nt: accumulate needs an fp32 out')
+    mode = _lib.MX_OUT_BF16
+  elif out.dtype == F32:
+    mode = _lib.MX_OUT_F32_ACC if accumulate else _lib.MX_OUT_F32
+  else:
+    raise TypeError(f'gemm_mx_nt.out: bf16 or fp32, got {out.dtype}')
+  lib = _lib.load()
+  _hook('gemm_mx_nt', 2.0 * M * N * K)
+  with _Timed('gemm_mx_nt', 2.0 * M * N * K):
+    _lib.check(lib.plm_gemm_mx_nt(_p(a.data), _p(a.scales), _p(b.data), _p(b.scales), _p(out), out.stride(0), M, N, a.data.shape[1], mode,
+                                  _stream()), 'plm_gemm_mx_nt')
+  return out
+
+
 # ---- embedding ----------------------------------------------------------------
 def embed_fwd(ids, W):
   _need(ids, torch.int64, 'embed_fwd.ids')

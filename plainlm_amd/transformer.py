@@ -37,9 +37,19 @@ class ModelConfig:
   # not in the reference: how a bool attn_mask is read.  'doc': as a block-diagonal causal mask (doc_start + the tuned kernels; anything
   # else is refused); 'dense': as any mask at all (functional.DenseMask + the masked kernels)
   attn_mask_mode: str = 'doc'
+  # not in the reference: 'bf16' (default) | 'mxfp8': the four linears of every block run their forward, dX and dW GEMMs on MX (e4m3fn,
+  # one E8M0 scale per 32 elements) operands; lm_head, attention, norms, loss and optimizer are unchanged
+  linear_precision: str = 'bf16'
 
 
 ATTN_MASK_MODES = ('doc', 'dense')
+LINEAR_PRECISIONS = ('bf16', 'mxfp8')
+
+
+def check_linear_precision(prec):
+  if prec not in LINEAR_PRECISIONS:
+    raise ValueError(f'linear_precision: {prec!r} is not one of {LINEAR_PRECISIONS}')
+  return prec
 
 
 def check_attn_mask_mode(mode):
@@ -70,6 +80,13 @@ class HipLinear(nn.Module):
     self.sink = None
     self._shadow = None
     self._shadow_key = None
+    # linear_precision 'mxfp8' (set by Transformer on the block linears): MX copies of the bf16 shadow - W blocked along in (forward) and
+    # W^T blocked along out (dX) - re-derived whenever the shadows were rewritten (every rewrite ends in mark_fresh: _shadow_gen counts
+    # them, including the optimizer's raw-pointer updates that leave the key unchanged).  Plain attributes: state_dict is unchanged.
+    self.mx = False
+    self._mx = None
+    self._mx_gen = -1
+    self._shadow_gen = 0
 
   def _key(self):
     w = self.weight
@@ -88,6 +105,7 @@ class HipLinear(nn.Module):
 
   def mark_fresh(self):
     self._shadow_key = self._key()
+    self._shadow_gen += 1
 
   def shadow(self):
     """(bf16 W [out, in], bf16 W^T [in, out_pad] with zero pad columns), re-cast when the master weight changed."""
@@ -100,9 +118,25 @@ class HipLinear(nn.Module):
   def invalidate(self):
     self._shadow_key = None
 
+  def mx_stale(self):
+    """The bf16 shadow [out, in] whose MX copies are out of date (shadow refreshed first), else None."""
+    wb = self.shadow()[0]
+    return wb if self._mx_gen != self._shadow_gen else None
+
+  def set_mx(self, pair):
+    self._mx, self._mx_gen = pair, self._shadow_gen
+
+  def mx_weights(self):
+    """(MxTensor W [out, in] blocked along in, MxTensor W^T [in, out] blocked along out), re-quantized when the bf16 shadow changed."""
+    wb = self.mx_stale()
+    if wb is not None:
+      self.set_mx(ops.mx_quant(wb))
+    return self._mx
+
   def forward(self, x):
     lead = x.shape[:-1]
-    y = Fn.LinearFn.apply(x.reshape(-1, self.in_features), self.weight, self)
+    fn = Fn.MxLinearFn if self.mx else Fn.LinearFn
+    y = fn.apply(x.reshape(-1, self.in_features), self.weight, self)
     return y.view(*lead, self.out_features)
 
   def extra_repr(self):
@@ -149,7 +183,7 @@ class GLU(nn.Module):
     self.fc2 = HipLinear(hidden_dim, dim)
 
   def apply_fn(self, x2d):
-    return Fn.SwiGLUMLPFn.apply(x2d, self.fc1.weight, self.fc2.weight, self.fc1, self.fc2)
+    return (Fn.MxSwiGLUMLPFn if self.fc1.mx else Fn.SwiGLUMLPFn).apply(x2d, self.fc1.weight, self.fc2.weight, self.fc1, self.fc2)
 
   def forward(self, x):
     lead = x.shape[:-1]
@@ -168,7 +202,7 @@ class MLP(nn.Module):
     self.fc2 = HipLinear(hidden_dim, dim)
 
   def apply_fn(self, x2d):
-    return Fn.PlainMLPFn.apply(x2d, self.fc1.weight, self.fc2.weight, self.fc1, self.fc2, self.kind)
+    return (Fn.MxPlainMLPFn if self.fc1.mx else Fn.PlainMLPFn).apply(x2d, self.fc1.weight, self.fc2.weight, self.fc1, self.fc2, self.kind)
 
   def forward(self, x):
     lead = x.shape[:-1]
@@ -194,7 +228,7 @@ class Attention(nn.Module):
     self.w_out = HipLinear(cfg.dim, cfg.dim)
 
   def forward(self, x2d, rope, doc_start, B, T):
-    qkv = Fn.QKVRopeFn.apply(x2d, self.w_qkv.weight, self.w_qkv, rope[0], rope[1], B, T, self.n_heads)
+    qkv = (Fn.MxQKVRopeFn if self.w_qkv.mx else Fn.QKVRopeFn).apply(x2d, self.w_qkv.weight, self.w_qkv, rope[0], rope[1], B, T, self.n_heads)
     a = Fn.AttnFn.apply(qkv, rope[0], rope[1], doc_start, B, T, self.n_heads)
     return self.w_out(a)
 
@@ -228,6 +262,7 @@ class Transformer(nn.Module):
     self.cfg = cfg
     self.n_layers = cfg.n_layers
     check_attn_mask_mode(cfg.attn_mask_mode)
+    check_linear_precision(cfg.linear_precision)
     if cfg.dim % cfg.n_heads != 0:
       raise ValueError('dim must be divisible by n_heads')
     self.head_dim = cfg.dim // cfg.n_heads
@@ -256,6 +291,11 @@ class Transformer(nn.Module):
     if cfg.tie_embeddings:
       self.tie_weights()
     self._wire_sink()
+    if cfg.linear_precision == 'mxfp8':
+      for layer in self.layers:
+        for m in layer.modules():
+          if isinstance(m, HipLinear):
+            m.mx = True
 
   # ---- init (models/transformer.py:116-129) ---------------------------------
   def _init_weights(self, module):
@@ -345,11 +385,21 @@ class Transformer(nn.Module):
     """Re-cast every stale bf16 weight shadow in ONE launch (the per-Linear casts are launch-latency bound: 49 launches of
     1 - 6 MB at the 160M size).  Called at the top of every forward; HipLinear.shadow() stays as the lazy fallback."""
     stale = [(m, it) for m in self.linear_modules() for it in (m.stale_item(),) if it is not None]
-    if not stale or not stale[0][1][0].is_cuda:
+    if stale and stale[0][1][0].is_cuda:
+      ops.cast_bf16_t_multi([it for _, it in stale])
+      for m, _ in stale:
+        m.mark_fresh()
+    self.refresh_mx()
+
+  def refresh_mx(self):
+    """linear_precision 'mxfp8': re-quantize every stale MX weight copy in ONE launch (ops.mx_quant_multi).  The fused optimizer tails
+    rewrite the bf16 shadows themselves, so this runs whether or not the cast above had work."""
+    if self.cfg.linear_precision != 'mxfp8' or not self.lm_head.weight.is_cuda:
       return
-    ops.cast_bf16_t_multi([it for _, it in stale])
-    for m, _ in stale:
-      m.mark_fresh()
+    stale = [(m, wb) for m in self.linear_modules() if m.mx for wb in (m.mx_stale(),) if wb is not None]
+    if stale:
+      for (m, _), pair in zip(stale, ops.mx_quant_multi([wb for _, wb in stale])):
+        m.set_mx(pair)
 
   # ---- forward ---------------------------------------------------------------------
   def _rope(self, device):

@@ -2,7 +2,8 @@
 samples the GPU's hwmon files (socket power, shader clock) and prints TFLOP/s next to average watts / MHz.  The same GEMM is run
 on random operands, on zeros and on a constant: equal instruction streams, different switching activity - if the zero run is
 much faster at a higher clock, the random run is clock-limited by power, not by what the kernel issues.
-Usage: python tools/power_probe.py [--seconds 2.5]   (ordinary user; reads /sys/class/drm/card*/device/hwmon and rocm-smi)"""
+--mx: only the MX GEMM (ops.gemm_mx_nt, quantization outside the loop) beside the bf16 NT kernel on the qkv / fc1 forward shapes.
+Usage: python tools/power_probe.py [--seconds 2.5] [--mx]   (ordinary user; reads /sys/class/drm/card*/device/hwmon and rocm-smi)"""
 
 import argparse
 import glob
@@ -151,6 +152,7 @@ def operands(kind, m, k, dev):
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--seconds', type=float, default=2.5)
+  ap.add_argument('--mx', action='store_true', help='the MX GEMM beside the bf16 NT kernel (qkv / fc1 forward shapes)')
   a = ap.parse_args()
   dev = 'cuda'
   torch.cuda.init()
@@ -165,6 +167,17 @@ def main():
   idle.stop_flag = True
   idle.join()
   print(json.dumps({'case': 'idle', **idle.summary(0.0)}), flush=True)
+  if a.mx:
+    for shape_name, (m, n, k) in {'qkv fwd': (M, 3 * d, d), 'fc1 fwd': (M, 2 * h, d)}.items():
+      out = torch.empty(m, n, device=dev, dtype=BF)
+      for kind in ('randn', 'zeros'):
+        A, Bm = operands(kind, m, k, dev), operands(kind, n, k, dev)
+        run_case(f'{shape_name} [{kind}] bf16 gemm_nt', lambda: ops.gemm_nt(A, Bm, out=out), 2.0 * m * n * k, a.seconds, files)
+        qa, _ = ops.mx_quant(A, cols=False)
+        qb, _ = ops.mx_quant(Bm, cols=False)
+        run_case(f'{shape_name} [{kind}] mx gemm_mx_nt', lambda: ops.gemm_mx_nt(qa, qb, out=out), 2.0 * m * n * k, a.seconds, files)
+        del A, Bm, qa, qb
+    return
   for shape_name, (m, n, k) in {'nt dX head': (M, d, V), 'nt fc1 fwd': (M, 2 * h, d), 'nt 8192^3': (8192, 8192, 8192)}.items():
     out = torch.empty(m, n, device=dev, dtype=BF)
     for kind in ('randn', 'small', 'pm1', 'ones', 'zeros'):
