@@ -242,6 +242,20 @@ int plm_ce_fwd_bwd(uint16_t* logits, const int64_t* targets, float* loss_rows, i
                    float grad_scale, void* stream);
 int plm_mean_f32(const float* x, float* out, int64_t n, void* stream);
 
+/* ---- forward-only scoring head -----
+ * nll fp32[M] = logsumexp(l) - l[target] and lse fp32[M] = logsumexp(l) of the rows l = bf16(Y[M,K] W[V,K]^T) - the logits the
+ * training head computes (plm_gemm_bf16_nt + plm_ce_fwd_bwd: same tile shape and K order, so the same bf16 values) - WITHOUT ever
+ * storing them: the persistent NT kernel reduces every output tile to one (max, sum-exp) pair per row and a second launch combines
+ * a row's pairs.  A target outside [0, V) is ignored: nll = 0 for that row, lse is written all the same.  lse may be NULL.
+ * No gradient is produced.  workspace: plm_head_score_workspace_bytes(M, V, K) bytes (about M * ceil(V / 128) * 8), 16-byte
+ * aligned, caller-owned.  NULL pointers, K % 64 != 0, row strides that are not multiples of 8, Y / W that are not 16-byte aligned
+ * give PLM_E_INVALID and a short workspace PLM_E_WORKSPACE before anything is launched.  Shapes that plm_gemm_bf16_nt serves with
+ * a 128x128 kernel (M < 512, V % 8 != 0) go through that kernel, 256 rows of logits at a time inside the workspace.
+ * Deterministic (no atomics). */
+size_t plm_head_score_workspace_bytes(int64_t M, int64_t V, int64_t K);
+int plm_head_score_bf16(const uint16_t* Y, int64_t ldy, const uint16_t* W, int64_t ldw, const int64_t* targets, float* nll,
+                        float* lse, int64_t M, int64_t V, int64_t K, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- device-scalar scaling (chunked lm_head + cross-entropy, models/transformer.py:114 + engine/engine.py:111,118)
  * The chunked head runs its dX / dW GEMMs inside forward, before autograd hands over the upstream gradient g
  * (engine.py:118 `(loss / accum).backward()`); backward applies g with

@@ -108,6 +108,8 @@ SIGNATURES = {
   'plm_attn_bwd_masked': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _P]),
   'plm_ce_fwd_bwd': (_I, [_P, _P, _P, _I64, _I64, _I64, _F, _P]),
   'plm_mean_f32': (_I, [_P, _P, _I64, _P]),
+  'plm_head_score_workspace_bytes': (_SZ, [_I64, _I64, _I64]),
+  'plm_head_score_bf16': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
   'plm_scale_bf16': (_I, [_P, _I64, _P, _P]),
   'plm_axpy_f32': (_I, [_P, _P, _I64, _P, _I, _P]),
   'plm_sumsq_f32': (_I, [_P, _I64, _P, _P, _P]),

@@ -149,6 +149,10 @@ struct EpiArgs {
   const float* rcos;    // ROPE: fp32 [T, 32] tables
   const float* rsin;
   int T, rope_cols;
+  // SCORE: forward-only scoring head (see the SCORE epilogue in the kernel).  C is not written.
+  const int64_t* targets;  // [M]
+  float* part;             // [tiles_n][M] (max, sum-exp) pairs, one per row and tile column
+  float* xt;               // [M] the bf16-rounded target logit of every row whose target is a valid column
 };
 
 template <class F, int... U>
@@ -212,7 +216,15 @@ static_assert(NtOvlPlan<4, 2, 1>::slot(0) == 3 && NtOvlPlan<4, 2, 1>::slot(1) ==
               "256x256: the two pieces of A half 0 leave in phases 3 and 4");
 static_assert(NtOvlPlan<1, 3, 2>::slot(1) == 4 && NtOvlPlan<1, 3, 2>::slot(0) == 5, "128x192: the B1 pass leaves in phase 4");
 
-template <int BM, int BN, int WM, int WN, bool HYB = false, bool GLU = false, bool GLUB = false, bool ROPE = false>
+// SCORE (forward-only scoring, plm_head_score_bf16): the tile never reaches memory.  The accumulators are rounded to bf16 as the
+// store path rounds them (the training head's logits are bf16, cross-entropy is fp32 on top of those), and every row of the tile is
+// reduced to one (max, sum-exp) pair: a lane holds, per 16-row block f and 16-column block j, row f * 16 + l15 and columns
+// j * 16 + 4 q .. + 3 of its wave tile, so a row's TN columns sit in the 2 * NBF * 4 registers of the four lanes l15 + 16 q - two
+// xor-shuffles (16, 32) finish a wave's share, the WN waves that share rows meet in the per-wave epilogue scratch (8 bytes per row,
+// two buffers alternating by tile, ONE workgroup barrier per tile), and thread r of the workgroup combines row r's WN pairs and
+// writes part[tile column][row].  Columns >= N (the clamped duplicates of the ragged edge) are set to -inf first (a rounded -inf
+// is -inf and exp2 of it 0); rows >= M write nothing.  The lane that holds column targets[row] also writes that rounded logit to xt[row]: one writer per row, no atomics.
+template <int BM, int BN, int WM, int WN, bool HYB = false, bool GLU = false, bool GLUB = false, bool ROPE = false, bool SCORE = false>
 __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(const uint16_t* __restrict__ A, int64_t lda,
                                                              const uint16_t* __restrict__ B, int64_t ldb,
                                                              uint16_t* __restrict__ C, int64_t ldc, int M, int N, int K,
@@ -222,6 +234,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(const uint16_t* __r
   const int64_t ldact = ea.ldact;
   static_assert(!(GLU || GLUB) || (BM == 256 && BN == 256 && WN == 4 && !HYB), "GLU epilogues: 256x256 tiles, whole-K items");
   static_assert(!(GLU && GLUB), "one epilogue at a time");
+  static_assert(!SCORE || !(HYB || GLU || GLUB || ROPE), "SCORE: whole-K items, no other epilogue");
   constexpr int TM = BM / WM, TN = BN / WN;  // wave tile
   static_assert(WM * WN == 8 && (TN == 64 || TN == 96) && (TM == 128 || TM == 64 || TM == 32), "unsupported geometry");
   constexpr int AH = TM / 2;                        // rows of one wave's A half
@@ -261,7 +274,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(const uint16_t* __r
 #ifndef PLM_NT_OVL
 #define PLM_NT_OVL 1
 #endif
-  constexpr bool OVL = PLM_NT_OVL && !HYB && !GLU && !GLUB && !ROPE;
+  constexpr bool OVL = PLM_NT_OVL && !HYB && !GLU && !GLUB && !ROPE && !SCORE;
   using OP = NtOvlPlan<NA, NBF, BF0>;  // unit u = mf * NPASS + pass
   constexpr int NPASS = OP::NPASS, NUNIT = OP::NUNIT;
   constexpr int OVS_2 = OVL ? OP::stores_in_slot(2) : 0, OVS_3 = OVL ? OP::stores_in_slot(3) : 0, OVS_4 = OVL ? OP::stores_in_slot(4) : 0;
@@ -433,6 +446,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(const uint16_t* __r
   phase_barrier();
 
   int st = 0;
+  int score_buf = 0;    // SCORE: which half of the wave scratch this tile's row pairs go to
   bool credit = false;  // NS stores of the previous tile's epilogue are still counted by vmcnt
   int credit_i = 0;     // the same flag as a scalar register operand of wait_vm_sel
   Cur cc;
@@ -630,6 +644,69 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(const uint16_t* __r
         }
       }
       continue;
+    }
+    if constexpr (SCORE) {
+      constexpr float LOG2E = 1.4426950408889634f;
+      const int cbase = n0 + wn * TN;  // first column of the wave tile
+      const int nvalid = N - cbase;    // its columns below N (<= 0: none, >= TN: all)
+      float* const wsc = reinterpret_cast<float*>(epi + score_buf * 2048);
+      if (nvalid < TN) {  // the ragged edge only (wave-uniform): one compare per column, applied to every row block
+        const int lim = nvalid - 4 * q;
+#pragma unroll
+        for (int j = 0; j < 2 * NBF; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const bool keep = j * 16 + e < lim;
+#pragma unroll
+            for (int f = 0; f < 2 * NA; ++f) acc4[f][j][e] = keep ? acc4[f][j][e] : -INFINITY;
+          }
+      }
+#pragma unroll
+      for (int f = 0; f < 2 * NA; ++f) {
+        const int gm = m0 + wm * TM + f * 16 + l15;
+        const int64_t tg = ea.targets[min(gm, M - 1)];
+        // this lane's first column of 16-column block 0, relative to the target: column j * 16 + e of the lane is the target when it equals tq
+        const int tq = (tg >= (int64_t)cbase && tg < (int64_t)N) ? (int)(tg - cbase) - 4 * q : -1;
+        float x[2 * NBF][4];
+        float mx = -INFINITY, xsel = 0.f;
+#pragma unroll
+        for (int j = 0; j < 2 * NBF; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float v = bf2f(f2bf(acc4[f][j][e]));  // the logit as the GEMM would have stored it
+            xsel = (j * 16 + e == tq) ? v : xsel;
+            x[j][e] = v;
+            mx = fmaxf(mx, v);
+          }
+        if (tq >= 0 && tq < TN && (tq & 15) < 4 && gm < M) ea.xt[gm] = xsel;
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float mxl = mx == -INFINITY ? 0.f : mx * LOG2E;  // a wave tile entirely beyond N: exp2(-inf) = 0, the pair stays (-inf, 0)
+        float sum = 0.f;
+#pragma unroll
+        for (int j = 0; j < 2 * NBF; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) sum += __builtin_amdgcn_exp2f(x[j][e] * LOG2E - mxl);
+        sum += __shfl_xor(sum, 16, 64);
+        sum += __shfl_xor(sum, 32, 64);
+        if (q == 0) *reinterpret_cast<float2*>(wsc + 2 * (f * 16 + l15)) = make_float2(mx, sum);
+      }
+      phase_barrier();  // every wave takes it once per tile; the other scratch half is next tile's, so no second barrier is needed
+      if (t < BM) {
+        const char* src = smem + 2 * STAGE + (t / TM) * WN * 4096 + score_buf * 2048 + (t % TM) * 8;
+        float2 a = *reinterpret_cast<const float2*>(src);
+#pragma unroll
+        for (int w = 1; w < WN; ++w) {
+          const float2 b = *reinterpret_cast<const float2*>(src + w * 4096);
+          const float m = fmaxf(a.x, b.x);  // ms_combine of ce.hip
+          const float sa = (a.x == -INFINITY) ? 0.f : a.y * __expf(a.x - m);
+          const float sb = (b.x == -INFINITY) ? 0.f : b.y * __expf(b.x - m);
+          a = make_float2(m, sa + sb);
+        }
+        if (m0 + t < M) *reinterpret_cast<float2*>(ea.part + 2 * ((int64_t)(n0 / BN) * M + m0 + t)) = a;
+      }
+      score_buf ^= 1;
+      continue;  // credit stays 0: the waits of the next K-tile count no stores (a wait that is too strict is safe)
     }
     // ---- epilogue: 32-row x 64-col pieces through this wave's private 4 KiB scratch ----
     // alpha is 1 for every launch of the step but lm_head's dX: the 4 * AF * 2 * NBF * 4 multiplies are taken only when a device scalar
@@ -1593,4 +1670,153 @@ bool plm_launch_gemm_nt_big(int variant, const uint16_t* A, int64_t lda, const u
   else
     hipLaunchKernelGGL((gemm_nt_big_kernel<128, 192, 4, 2>), g, block, 0, s, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, alpha_dev, tm, tn_, hyb, EpiArgs{});
   return true;
+}
+
+// =============================================================================================
+// Forward-only scoring head:  nll[M], lse[M] of  softmax(bf16(Y W^T))  without the [M, V] logits
+// =============================================================================================
+// Workspace: xt fp32[M] | then EITHER the row partials [ceil(V / BN)][M] (max, sum-exp) of the persistent kernel OR the logits of
+// PLM_HS_CHUNK rows (shapes the automatic policy of plm_gemm_bf16_nt gives to a 128x128 kernel: M < 512, V % 8 != 0, badly quantised
+// grids).  The query does not know the device, so it sizes the partials for the narrowest tile (BN = 128).
+#define PLM_HS_CHUNK 256
+static size_t hs_align(size_t n) { return (n + 255) & ~(size_t)255; }
+static size_t hs_xt_bytes(int64_t M) { return hs_align((size_t)M * sizeof(float)); }
+
+extern "C" size_t plm_head_score_workspace_bytes(int64_t M, int64_t V, int64_t K) {
+  if (M <= 0 || V <= 0 || K <= 0) return 0;
+  const size_t part = (size_t)M * (size_t)plm_cdiv(V, 128) * 2 * sizeof(float);
+  const size_t chunk = (size_t)PLM_HS_CHUNK * (size_t)(plm_cdiv(V, 8) * 8) * sizeof(uint16_t);
+  return hs_xt_bytes(M) + hs_align(part > chunk ? part : chunk);
+}
+
+// lse / nll of 32 rows per workgroup from their tile-column partials: thread (r = t & 31, slice = t >> 5) walks every 8th partial of
+// row r (a wave reads 2 x 256 contiguous bytes per step), the 8 slices of a row meet in LDS.  Fixed order: deterministic.
+__global__ __launch_bounds__(256) void head_score_combine_kernel(const float* __restrict__ part, const float* __restrict__ xt,
+                                                                 const int64_t* __restrict__ targets, float* __restrict__ nll,
+                                                                 float* __restrict__ lse_out, int M, int V, int ntc) {
+  __shared__ float2 sh[8][32];
+  const int r = threadIdx.x & 31, sl = threadIdx.x >> 5;
+  const int row = blockIdx.x * 32 + r;
+  float m = -INFINITY, s = 0.f;
+  if (row < M) {
+    for (int tc = sl; tc < ntc; tc += 8) {
+      const float2 b = *reinterpret_cast<const float2*>(part + 2 * ((int64_t)tc * M + row));
+      const float mm = fmaxf(m, b.x);  // ms_combine of ce.hip
+      const float sa = (m == -INFINITY) ? 0.f : s * __expf(m - mm);
+      const float sb = (b.x == -INFINITY) ? 0.f : b.y * __expf(b.x - mm);
+      m = mm;
+      s = sa + sb;
+    }
+  }
+  sh[sl][r] = make_float2(m, s);
+  __syncthreads();
+  if (sl != 0 || row >= M) return;
+#pragma unroll
+  for (int k = 1; k < 8; ++k) {
+    const float2 b = sh[k][r];
+    const float mm = fmaxf(m, b.x);
+    const float sa = (m == -INFINITY) ? 0.f : s * __expf(m - mm);
+    const float sb = (b.x == -INFINITY) ? 0.f : b.y * __expf(b.x - mm);
+    m = mm;
+    s = sa + sb;
+  }
+  const float lse = m + __logf(s);
+  const int64_t tg = targets[row];
+  nll[row] = (tg >= 0 && tg < V) ? lse - xt[row] : 0.f;
+  if (lse_out) lse_out[row] = lse;
+}
+
+// the same two numbers from materialised bf16 logits of a few rows (the 128x128-kernel shapes): one workgroup per row
+__global__ __launch_bounds__(256) void head_score_rows_kernel(const uint16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ targets,
+                                                              float* __restrict__ nll, float* __restrict__ lse_out, int V) {
+  __shared__ float2 sh[4];
+  const bf16_t* lr = reinterpret_cast<const bf16_t*>(logits) + (int64_t)blockIdx.x * ld;
+  float m = -INFINITY, s = 0.f;
+  auto add = [&](float bm, float bs) {
+    const float mm = fmaxf(m, bm);
+    const float sa = (m == -INFINITY) ? 0.f : s * __expf(m - mm);
+    const float sb = (bm == -INFINITY) ? 0.f : bs * __expf(bm - mm);
+    m = mm;
+    s = sa + sb;
+  };
+  for (int c = threadIdx.x; c < V; c += 256) add(bf2f(lr[c]), 1.f);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) add(__shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = make_float2(m, s);
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  m = sh[0].x;
+  s = sh[0].y;
+  for (int k = 1; k < 4; ++k) add(sh[k].x, sh[k].y);
+  const float lse = m + __logf(s);
+  const int64_t tg = targets[blockIdx.x];
+  nll[blockIdx.x] = (tg >= 0 && tg < V) ? lse - bf2f(lr[tg]) : 0.f;
+  if (lse_out) lse_out[blockIdx.x] = lse;
+}
+
+extern "C" int plm_gemm_bf16_nt_ws(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, void* C, int64_t ldc, int64_t M,
+                                   int64_t N, int64_t K, int c_dtype, int accumulate, const float* alpha_dev, int variant,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+
+extern "C" int plm_head_score_bf16(const uint16_t* Y, int64_t ldy, const uint16_t* W, int64_t ldw, const int64_t* targets, float* nll,
+                                   float* lse, int64_t M, int64_t V, int64_t K, void* workspace, size_t workspace_bytes, void* stream) {
+  PLM_REQUIRE(Y && W && targets && nll && workspace, "plm_head_score_bf16: null pointer");
+  PLM_REQUIRE(M > 0 && V > 0 && K > 0 && M < (1 << 30) && V < (1 << 30) && K < (1 << 30), "plm_head_score_bf16: bad shape M=%ld V=%ld K=%ld",
+              (long)M, (long)V, (long)K);
+  PLM_REQUIRE(K % 64 == 0, "plm_head_score_bf16: K %% 64 == 0 required (K=%ld)", (long)K);
+  PLM_REQUIRE(ldy % 8 == 0 && ldw % 8 == 0 && ldy >= K && ldw >= K, "plm_head_score_bf16: row strides must be multiples of 8 and >= K (ldy=%ld ldw=%ld)",
+              (long)ldy, (long)ldw);
+  PLM_REQUIRE(aligned16({Y, W, workspace}) && ((reinterpret_cast<uintptr_t>(nll) | reinterpret_cast<uintptr_t>(lse)) & 3) == 0 &&
+                  (reinterpret_cast<uintptr_t>(targets) & 7) == 0,
+              "plm_head_score_bf16: Y, W and the workspace must be 16-byte aligned, targets 8-byte, nll / lse 4-byte");
+  const size_t need = plm_head_score_workspace_bytes(M, V, K);
+  if (workspace_bytes < need) {
+    plm_set_error("plm_head_score_bf16: workspace of %zu bytes required, %zu given", need, workspace_bytes);
+    return PLM_E_WORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  float* xt = (float*)workspace;
+  char* rest = (char*)workspace + hs_xt_bytes(M);
+  // the tile shape plm_gemm_bf16_nt picks for this shape (no workspace: its stream-K hybrid is for K >= 8192), so that the accumulators
+  // are the ones the training head rounds to bf16
+  int which = -1;
+  if (!plm_env().gemm_v1 && V % 8 == 0 && M >= 512 && V >= 128 && ensure_num_cus()) {
+    const int slots = persistent_slots();
+    double eff;
+    const int w = nt_pick_tile(M, V, slots, &eff);
+    if (eff >= nt_dma128_eff(M, V, slots)) which = w;
+  }
+  if (which >= 0) {
+    const int slots = persistent_slots();
+    const int tm = (int)plm_cdiv(M, kNtTiles[which].bm), tn_ = (int)plm_cdiv(V, kNtTiles[which].bn);
+    const int nt_ = tm * tn_;
+    const dim3 g(nt_ < slots ? nt_ : slots), block(512);
+    const HybridArgs hyb{tm, 0, 1, nullptr};
+    const EpiArgs ea{nullptr, 0, nullptr, nullptr, 0, 0, targets, (float*)rest, xt};
+#define PLM_HS_LAUNCH(BM_, BN_, WM_, WN_)                                                                                                  \
+  hipLaunchKernelGGL((gemm_nt_big_kernel<BM_, BN_, WM_, WN_, false, false, false, false, true>), g, block, 0, s, Y, ldy, W, ldw, nullptr, 0, \
+                     (int)M, (int)V, (int)K, nullptr, tm, tn_, hyb, ea)
+    if (which == 0) PLM_HS_LAUNCH(256, 256, 2, 4);
+    else if (which == 1) PLM_HS_LAUNCH(256, 128, 4, 2);
+    else if (which == 2) PLM_HS_LAUNCH(256, 192, 4, 2);
+    else PLM_HS_LAUNCH(128, 192, 4, 2);
+#undef PLM_HS_LAUNCH
+    hipLaunchKernelGGL(head_score_combine_kernel, dim3((unsigned)plm_cdiv(M, 32)), dim3(256), 0, s, (const float*)rest, (const float*)xt, targets,
+                       nll, lse, (int)M, (int)V, tn_);
+    PLM_CHECK_LAUNCH("plm_head_score_bf16");
+    return PLM_OK;
+  }
+  // shapes plm_gemm_bf16_nt serves with a 128x128 kernel: that kernel (named explicitly, so that a chunk of rows gets the accumulators the
+  // whole matrix would) into PLM_HS_CHUNK rows of logits, then the row kernel
+  const int64_t ld = plm_cdiv(V, 8) * 8;
+  const int variant = (!plm_env().gemm_v1 && V % 8 == 0) ? 2 : 1;
+  for (int64_t r0 = 0; r0 < M; r0 += PLM_HS_CHUNK) {
+    const int64_t rows = M - r0 < PLM_HS_CHUNK ? M - r0 : PLM_HS_CHUNK;
+    const int rc = plm_gemm_bf16_nt_ws(Y + r0 * ldy, ldy, W, ldw, rest, ld, rows, V, K, 0, 0, nullptr, variant, nullptr, 0, stream);
+    if (rc != PLM_OK) return rc;
+    hipLaunchKernelGGL(head_score_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, (const uint16_t*)rest, ld, targets + r0, nll + r0,
+                       lse ? lse + r0 : nullptr, (int)V);
+  }
+  PLM_CHECK_LAUNCH("plm_head_score_bf16");
+  return PLM_OK;
 }

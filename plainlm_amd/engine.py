@@ -238,6 +238,15 @@ def _move_to_device(batch, seq_len, device, intra_doc_masking, stager=None):
   return inputs, targets, doc_start
 
 
+EVAL_HEADS = ('logits', 'fused')
+
+
+def check_eval_head(head):
+  if head not in EVAL_HEADS:
+    raise ValueError(f'eval_head: {head!r} is not one of {EVAL_HEADS}')
+  return head
+
+
 class HipEngine(torch.nn.Module):
   def __init__(self, model, cfg, device, local_rank=None, ckpt=None, comm_backend=None, bucket_cap_mb=64):
     super().__init__()
@@ -248,6 +257,9 @@ class HipEngine(torch.nn.Module):
     self.grad_clip = cfg.grad_clip
     self.dtype = cfg.dtype
     self.intra_doc_masking = getattr(cfg, 'intra_doc_masking', False)
+    # eval(): 'logits' = model.loss (the training head: [M, V] logits + the fused CE launch, whose gradient nobody reads); 'fused' =
+    # model.score (forward-only head, no logits buffer; the mean is over the non-ignored targets, as torch.nn.CrossEntropyLoss)
+    self.eval_head = check_eval_head(getattr(cfg, 'eval_head', 'logits'))
     self.device = device
     self._stager = _Stager()
     # 'Train loss is nan' (engine.py:116-117).  The reference reads the loss on the host before it enqueues backward: a wait for
@@ -385,7 +397,10 @@ class HipEngine(torch.nn.Module):
     total_loss, num_batches = 0.0, 0
     for batch in dataloader:
       inputs, targets, doc_start = _move_to_device(batch, self.seq_len, self.device, self.intra_doc_masking, self._stager)
-      loss = self.model.loss(inputs, targets, doc_start)
+      if self.eval_head == 'fused':
+        loss = self.model.score(inputs, targets, doc_start, reduction='mean')
+      else:
+        loss = self.model.loss(inputs, targets, doc_start)
       if torch.isnan(loss):
         raise ValueError('Validation loss is nan')
       total_loss += loss.item()

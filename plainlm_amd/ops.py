@@ -719,6 +719,39 @@ def ce_fwd_bwd_(logits, targets, grad_scale, V=None):
   return rows
 
 
+_score_ws = {}
+
+
+def head_score(y, w, targets, want_lse=False):
+  """Forward-only scoring head: nll fp32[M] = logsumexp(l) - l[target] of the rows l = bf16(y[M,K] @ w[V,K]^T) - the training head's
+  logits, bit for bit - without the [M, V] buffer (the NT GEMM reduces every tile to per-row (max, sum-exp) pairs).
+  A target outside [0, V) is ignored (nll = 0).  want_lse: also return lse fp32[M].  No gradient."""
+  for t, n in ((y, 'y'), (w, 'w')):
+    if not t.is_cuda:
+      raise RuntimeError(f'head_score.{n}: tensor must live on the GPU (plainlm_amd has no CPU path)')
+    if t.dtype != BF16 or t.dim() != 2 or t.stride(1) != 1:
+      raise ValueError(f'head_score.{n}: need a 2-D bf16 GPU tensor with unit inner stride')
+  _need(targets, torch.int64, 'head_score.targets', 1)
+  M, K = y.shape
+  V = w.shape[0]
+  if w.shape[1] != K or targets.shape[0] != M:
+    raise ValueError(f'head_score: y {tuple(y.shape)}, w {tuple(w.shape)}, targets {tuple(targets.shape)} do not fit')
+  lib = _lib.load()
+  _hook('gemm_nt', 2.0 * M * V * K)
+  key = (M, V, K, y.device)
+  ent = _score_ws.get(key)
+  if ent is None:
+    nbytes = int(lib.plm_head_score_workspace_bytes(M, V, K))
+    ent = _score_ws[key] = (torch.empty(max(nbytes, 16), dtype=torch.uint8, device=y.device), nbytes)
+  ws, nbytes = ent
+  nll = torch.empty((M,), dtype=F32, device=y.device)
+  lse = torch.empty((M,), dtype=F32, device=y.device) if want_lse else None
+  with _Timed('gemm_nt', 2.0 * M * V * K):
+    _lib.check(lib.plm_head_score_bf16(_p(y), y.stride(0), _p(w), w.stride(0), _p(targets), _p(nll), _p(lse), M, V, K, _p(ws), nbytes,
+                                       _stream()), 'plm_head_score_bf16')
+  return (nll, lse) if want_lse else nll
+
+
 def mean(x):
   _need(x, F32, 'mean.x')
   out = torch.empty((), dtype=F32, device=x.device)

@@ -476,3 +476,30 @@ class Transformer(nn.Module):
     y, B, T = self._trunk(x, attn_mask)
     tg = targets.reshape(-1).contiguous()
     return Fn.HeadLossFn.apply(y, self.lm_head.weight, self.lm_head, tg, self.head_chunk_rows)
+
+  @torch.compiler.disable
+  def score(self, x, targets, attn_mask=None, reduction='none'):
+    """Forward-only token losses: fp32 [B, T] cross-entropy of every target (0 where the target is outside [0, V), e.g. -100), from
+    the same bf16 logits as ``loss`` but without materialising them (ops.head_score).  reduction: 'none' | 'sum' (scalar) | 'mean'
+    (the sum over the NON-ignored targets' count - torch.nn.CrossEntropyLoss's rule; NaN when every target is ignored).
+    There is no backward: use ``loss`` to train."""
+    if reduction not in ('none', 'sum', 'mean'):
+      raise ValueError(f"score: reduction must be 'none', 'sum' or 'mean' (got {reduction!r})")
+    if isinstance(x, torch.Tensor) and not x.is_cuda:
+      raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (inputs are on CPU; there is no CPU fallback)')
+    if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+      raise RuntimeError('Transformer.score is forward-only (no backward): call it under torch.no_grad(), or use loss() to train')
+    y, B, T = self._trunk(x, attn_mask)
+    tg = targets.reshape(-1).contiguous()
+    wb, _ = self.lm_head.shadow()
+    nll = ops.head_score(y, wb, tg)
+    if reduction == 'none':
+      return nll.view(B, T)
+    total = nll.sum()
+    if reduction == 'sum':
+      return total
+    return total / ((tg >= 0) & (tg < self.cfg.vocab_size)).sum()
+
+  def token_logprobs(self, x, targets, attn_mask=None):
+    """log p(target) per token, fp32 [B, T] (0 where the target is ignored): ``-score(x, targets, attn_mask, 'none')``."""
+    return -self.score(x, targets, attn_mask, reduction='none')

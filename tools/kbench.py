@@ -92,6 +92,9 @@ def main():
       Bm = torch.randn(n, k, device=dev).to(BF)
       out = torch.empty(m, n, device=dev, dtype=BF)
       rec(name, timeit(lambda: ops.gemm_nt(A, Bm, out=out), a.iters), flops=2.0 * m * n * k)
+      if name == 'nt head fwd':  # the forward-only scoring head on the same operands: GEMM + log-sum-exp epilogue, no logits, no CE launch
+        tgs = torch.randint(0, n, (m,), device=dev)
+        rec('head score', timeit(lambda: ops.head_score(A, Bm, tgs), a.iters), flops=2.0 * m * n * k)
       if _lib.load().plm_gemm_nt_workspace_bytes(m, n, k) > 0:
         os.environ['PLM_NT_NO_HYBRID'] = '1'
         ops.reload_env()
