@@ -43,7 +43,8 @@ void plm_reload_env(void);
  * copy dst_t[cols, ld_t] (ld_t >= rows; columns rows..ld_t are left untouched) used by the dX GEMMs. */
 int plm_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, void* stream);
 int plm_cast_f32_bf16_t(const float* src, uint16_t* dst, uint16_t* dst_t, int64_t rows, int64_t cols, int64_t ld_t, void* stream);
-/* the `_t` cast for a whole list of weights in one launch (every Linear of the model at the top of a step) */
+/* the `_t` cast for a whole list of weights in one launch per 56 items (every Linear of the model at the top of a step); every item
+ * is validated before the first launch */
 typedef struct plm_cast_item {
   const float* src; /* fp32 [rows, cols] */
   uint16_t* dst;    /* bf16 [rows, cols] */
@@ -264,33 +265,19 @@ int plm_head_score_bf16(const uint16_t* Y, int64_t ldy, const uint16_t* W, int64
 int plm_scale_bf16(uint16_t* x, int64_t n, const float* alpha_dev, void* stream);
 int plm_axpy_f32(float* out, const float* x, int64_t n, const float* alpha_dev, int accumulate, void* stream);
 
-/* ---- optimizer tail (engine/engine.py:126-135, optim/init_optim.py:14-21)
- * sumsq: out[0] = sum(x^2) (single-launch deterministic two-stage reduce; scratch >= 4096 floats)
- * adamw: decoupled-weight-decay Adam on a flat fp32 span, matching torch.optim.AdamW:
- *   p *= 1 - lr*wd ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ;
- *   p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps), with g pre-multiplied by *clip_coef_dev (NULL = 1). */
+/* ---- optimizer tail (engine/engine.py:126-135, optim/init_optim.py:7-70)
+ * sumsq: out[0] = sum(x^2) (single-launch deterministic two-stage reduce; scratch >= 4096 floats) */
 int plm_sumsq_f32(const float* x, int64_t n, float* scratch, float* out, void* stream);
-int plm_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
-                  float eps, float weight_decay, float bc1, float bc2, const float* clip_coef_dev, void* stream);
-/* The same update for a list of Linear weights [rows, cols] that ALSO writes the bf16 shadows the next step's GEMMs read
- * (dst = bf16(W) [rows, cols], dst_t = bf16(W)^T [cols, ld_t], columns 0..rows-1), i.e. plm_adamw_f32 followed by
+/* The reference's optimizers, selected by h->kind, on two launch shapes: plm_optim_f32 on a flat fp32 span, and
+ * plm_optim_cast_multi on a list of Linear weights [rows, cols] that ALSO writes the bf16 shadows the next step's GEMMs read
+ * (dst = bf16(W) [rows, cols], dst_t = bf16(W)^T [cols, ld_t], columns 0..rows-1), i.e. plm_optim_f32 followed by
  * plm_cast_f32_bf16_t_multi in one pass over the parameters ("bf16 weight shadow copy emitted by the
- * optimizer"; replaces the per-call fp32 -> bf16 weight casts of autocast, engine/engine.py:75).  Same bits as the two calls. */
-typedef struct plm_adamw_item {
-  float* p;         /* fp32 [rows, cols], updated in place */
-  const float* g;   /* fp32 gradient */
-  float* m;         /* exp_avg */
-  float* v;         /* exp_avg_sq */
-  uint16_t* dst;    /* bf16 [rows, cols] */
-  uint16_t* dst_t;  /* bf16 [cols, ld_t] */
-  int64_t rows, cols, ld_t;
-} plm_adamw_item;
-int plm_adamw_cast_multi(const plm_adamw_item* items, int count, float lr, float beta1, float beta2, float eps,
-                         float weight_decay, float bc1, float bc2, const float* clip_coef_dev, void* stream);
-
-/* The reference's other optimizers (optim/init_optim.py:7-70) on the same two launch shapes, selected by h->kind.  g is
- * pre-multiplied by *clip_coef_dev (NULL = 1) as in plm_adamw_f32; the flat and the multi-tensor form give the same bits
- * per element.  Scalars are host-computed per group and step:
+ * optimizer"; replaces the per-call fp32 -> bf16 weight casts of autocast, engine/engine.py:75).  g is pre-multiplied by
+ * *clip_coef_dev (NULL = 1); the two forms give the same bits per element.  Scalars are host-computed per group and step:
+ *   PLM_OPTIM_ADAMW    torch.optim.AdamW (decoupled decay; bc1 = 1 - b1^t, bc2 = 1 - b2^t):
+ *     p *= 1 - lr*wd ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
+ *     (the entry points form 1 - lr*wd as fmaf(-lr, wd, 1), lr / bc1 and sqrt(bc2) in fp32 from the struct's lr, weight_decay,
+ *     bc1, bc2; decay, coef_grad and coef_avg are ignored; needs m and v)
  *   PLM_OPTIM_NADAMW   torch.optim.NAdam(decoupled_weight_decay=True):
  *     p *= decay ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; d = sqrt(v / bc2) + eps ;
  *     p -= coef_grad * g / d + coef_avg * m / d
@@ -307,24 +294,36 @@ int plm_adamw_cast_multi(const plm_adamw_item* items, int count, float lr, float
  *     (lr = the warmed-up scheduled_lr, ckp1 = weight / weight_sum, coef_y = lr (b1 (1 - ckp1) - 1); needs m and v)
  * `first` = 1 initialises the momentum buffer (SGD: torch's missing momentum_buffer; signSGD: the missing 'm'; schedule-free
  * AdamW: z = a copy of p and v = 0, neither read).
- * decay = 1 - lr * weight_decay, rounded once from the host's double, as torch passes it to p.mul_().  The multi-tensor form
- * takes plm_adamw_item lists (v = NULL for SGD / signSGD) and writes the bf16 shadows like plm_adamw_cast_multi.  An unknown
- * kind, a missing or superfluous state buffer, or a shape / alignment plm_adamw_cast_multi would refuse gives PLM_E_INVALID
- * before anything is launched. */
+ * decay (all kinds but AdamW) = 1 - lr * weight_decay, rounded once from the host's double, as torch passes it to p.mul_().
+ * rows, cols and ld_t are positive multiples of 8 below 2^31, ld_t >= rows, every pointer is 16-byte aligned.  An unknown kind
+ * (0, what a zeroed struct carries, included), a missing or superfluous state buffer, or a bad shape / alignment gives
+ * PLM_E_INVALID.  The multi-tensor entry points (this one and plm_cast_f32_bf16_t_multi) validate EVERY item before their first
+ * launch, whatever the length of the list: a refused list leaves all parameters as they were. */
 #define PLM_OPTIM_NADAMW 1
 #define PLM_OPTIM_SGD 2
 #define PLM_OPTIM_SIGNSGD 3
 #define PLM_OPTIM_SFO_ADAMW 4
+#define PLM_OPTIM_ADAMW 5
 typedef struct plm_optim_hparams {
   int kind;   /* PLM_OPTIM_* */
   int first;  /* 1: initialise the state buffers this step (SGD / signSGD / schedule-free AdamW) */
   float lr, weight_decay, decay, beta1, beta2, eps, momentum, dampening;
-  float bc2, coef_grad, coef_avg; /* NAdamW (bc2 also schedule-free AdamW) */
+  float bc2, coef_grad, coef_avg; /* NAdamW (bc2 also AdamW and schedule-free AdamW) */
   float ckp1, coef_y;             /* schedule-free AdamW */
+  float bc1;                      /* AdamW */
 } plm_optim_hparams;
+typedef struct plm_optim_item {
+  float* p;         /* fp32 [rows, cols], updated in place */
+  const float* g;   /* fp32 gradient */
+  float* m;         /* exp_avg / momentum buffer / z (NULL for SGD without momentum) */
+  float* v;         /* exp_avg_sq (NULL for SGD / signSGD) */
+  uint16_t* dst;    /* bf16 [rows, cols] */
+  uint16_t* dst_t;  /* bf16 [cols, ld_t] */
+  int64_t rows, cols, ld_t;
+} plm_optim_item;
 int plm_optim_f32(const plm_optim_hparams* h, float* p, const float* g, float* m, float* v, int64_t n,
                   const float* clip_coef_dev, void* stream);
-int plm_optim_cast_multi(const plm_optim_hparams* h, const plm_adamw_item* items, int count, const float* clip_coef_dev,
+int plm_optim_cast_multi(const plm_optim_hparams* h, const plm_optim_item* items, int count, const float* clip_coef_dev,
                          void* stream);
 /* Schedule-free train / eval swap on a flat fp32 span: p[i] = lerp(p[i], z[i], w), as torch.lerp
  * (|w| < 0.5: p + w (z - p), else z - (z - p)(1 - w)).  eval(): w = 1 - 1/beta1 (p = x); train(): w = 1 - beta1 (p = y).

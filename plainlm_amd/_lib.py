@@ -17,7 +17,7 @@ _lib = None
 
 # ABI the signatures below were written for (plm_version() of the library must match: a stale .so that still exports every
 # symbol but with other argument lists / struct layouts would corrupt memory instead of raising)
-EXPECTED_ABI = 111
+EXPECTED_ABI = 112
 
 _P = C.c_void_p
 _I64 = C.c_int64
@@ -30,8 +30,8 @@ class CastItem(C.Structure):
   _fields_ = [('src', _P), ('dst', _P), ('dst_t', _P), ('rows', _I64), ('cols', _I64), ('ld_t', _I64)]
 
 
-class AdamwItem(C.Structure):
-  """struct plm_adamw_item (include/plainlm_hip.h)."""
+class OptimItem(C.Structure):
+  """struct plm_optim_item (include/plainlm_hip.h)."""
   _fields_ = [('p', _P), ('g', _P), ('m', _P), ('v', _P), ('dst', _P), ('dst_t', _P), ('rows', _I64), ('cols', _I64), ('ld_t', _I64)]
 
 
@@ -39,10 +39,10 @@ class OptimHparams(C.Structure):
   """struct plm_optim_hparams (include/plainlm_hip.h)."""
   _fields_ = [('kind', _I), ('first', _I), ('lr', _F), ('weight_decay', _F), ('decay', _F), ('beta1', _F), ('beta2', _F), ('eps', _F),
               ('momentum', _F), ('dampening', _F), ('bc2', _F), ('coef_grad', _F), ('coef_avg', _F),
-              ('ckp1', _F), ('coef_y', _F)]
+              ('ckp1', _F), ('coef_y', _F), ('bc1', _F)]
 
 
-OPTIM_NADAMW, OPTIM_SGD, OPTIM_SIGNSGD, OPTIM_SFO_ADAMW = 1, 2, 3, 4  # PLM_OPTIM_*
+OPTIM_NADAMW, OPTIM_SGD, OPTIM_SIGNSGD, OPTIM_SFO_ADAMW, OPTIM_ADAMW = 1, 2, 3, 4, 5  # PLM_OPTIM_*
 
 
 class ColsumItem(C.Structure):
@@ -113,10 +113,8 @@ SIGNATURES = {
   'plm_scale_bf16': (_I, [_P, _I64, _P, _P]),
   'plm_axpy_f32': (_I, [_P, _P, _I64, _P, _I, _P]),
   'plm_sumsq_f32': (_I, [_P, _I64, _P, _P, _P]),
-  'plm_adamw_f32': (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _P, _P]),
-  'plm_adamw_cast_multi': (_I, [C.POINTER(AdamwItem), _I, _F, _F, _F, _F, _F, _F, _F, _P, _P]),
   'plm_optim_f32': (_I, [C.POINTER(OptimHparams), _P, _P, _P, _P, _I64, _P, _P]),
-  'plm_optim_cast_multi': (_I, [C.POINTER(OptimHparams), C.POINTER(AdamwItem), _I, _P, _P]),
+  'plm_optim_cast_multi': (_I, [C.POINTER(OptimHparams), C.POINTER(OptimItem), _I, _P, _P]),
   'plm_lerp_f32': (_I, [_P, _P, _I64, _F, _P]),
   'plm_set_cu_reserve': (_I, [_I]),
   'plm_comm_unique_id': (_I, [_P]),

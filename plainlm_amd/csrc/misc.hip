@@ -15,7 +15,7 @@ void plm_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* plm_last_error_string(void) { return g_err; }
-extern "C" int plm_version(void) { return 111; }  // 111: + plm_mx_quant / plm_mx_quant_multi / plm_gemm_mx_nt (MXFP8 block linears); 110: + plm_attn_mask_bytes / plm_attn_mask_pack / plm_attn_fwd_masked / plm_attn_bwd_masked (dense bit-packed masks); 109: + PLM_OPTIM_SFO_ADAMW (plm_optim_hparams gains ckp1 / coef_y), + plm_lerp_f32; 108: + plm_optim_f32 / plm_optim_cast_multi (NAdamW, SGD, signSGD tails); 107: round 6 (document-mask plan: plm_attn_doc_plan, plm_attn_fwd / plm_attn_bwd take doc_plan); 106: round 5 (NT variant 7 re-purposed: the 128 x 192 tile; the PLM_NT_DUO / PLM_DUO_* switches removed); 105: round 4 (+ plm_adamw_cast_multi); 104: round 3 (+ plm_reload_env); 103 / 102: round 2 (see include/plainlm_hip.h); 101: round 1
+extern "C" int plm_version(void) { return 112; }  // 112: + PLM_OPTIM_ADAMW (plm_optim_hparams.bc1), plm_adamw_item -> plm_optim_item, - plm_adamw_f32 / plm_adamw_cast_multi; 111: + plm_mx_quant / plm_mx_quant_multi / plm_gemm_mx_nt (MXFP8 block linears); 110: + plm_attn_mask_bytes / plm_attn_mask_pack / plm_attn_fwd_masked / plm_attn_bwd_masked (dense bit-packed masks); 109: + PLM_OPTIM_SFO_ADAMW (plm_optim_hparams gains ckp1 / coef_y), + plm_lerp_f32; 108: + plm_optim_f32 / plm_optim_cast_multi (NAdamW, SGD, signSGD tails); 107: round 6 (document-mask plan: plm_attn_doc_plan, plm_attn_fwd / plm_attn_bwd take doc_plan); 106: round 5 (NT variant 7 re-purposed: the 128 x 192 tile; the PLM_NT_DUO / PLM_DUO_* switches removed); 105: round 4 (+ plm_adamw_cast_multi); 104: round 3 (+ plm_reload_env); 103 / 102: round 2 (see include/plainlm_hip.h); 101: round 1
 
 static PlmEnv g_env;
 static void load_env() {

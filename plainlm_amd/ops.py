@@ -788,48 +788,19 @@ def sumsq(x, scratch=None):
   return out
 
 
-def adamw_(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, clip_coef=None):
-  for t, n in ((p, 'p'), (g, 'g'), (m, 'm'), (v, 'v')):
-    _need(t, F32, 'adamw.' + n)
-  bc1 = 1.0 - beta1 ** step
-  bc2 = 1.0 - beta2 ** step
-  _lib.check(_lib.load().plm_adamw_f32(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, weight_decay, bc1, bc2,
-                                       _p(clip_coef), _stream()), 'plm_adamw_f32')
-
-
-def adamw_cast_multi_(items, lr, beta1, beta2, eps, weight_decay, step, clip_coef=None, table=None):
-  """AdamW on a list of Linear weights that also writes their bf16 shadows: items = [(p, g, m, v fp32 [rows, cols], dst bf16 [rows, cols],
-  dst_t bf16 [cols, >= rows])].  Returns the ctypes item table; pass it back as `table` on later steps (the pointers do not move)."""
-  if table is None:
-    table = (_lib.AdamwItem * len(items))()
-    for i, (p, g, m, v, dst, dst_t) in enumerate(items):
-      for t, n in ((p, 'p'), (g, 'g'), (m, 'm'), (v, 'v')):
-        _need(t, F32, 'adamw_cast_multi.' + n, 2)
-      R, Cc = p.shape
-      if dst.dtype != BF16 or tuple(dst.shape) != (R, Cc) or not dst.is_contiguous() or not dst.is_cuda:
-        raise ValueError('adamw_cast_multi.dst: need contiguous bf16 [rows, cols] on the GPU')
-      if dst_t.dtype != BF16 or dst_t.dim() != 2 or dst_t.shape[0] != Cc or dst_t.shape[1] < R or dst_t.stride(1) != 1 or not dst_t.is_cuda:
-        raise ValueError('adamw_cast_multi.dst_t: need bf16 [cols, >= rows] on the GPU')
-      table[i] = _lib.AdamwItem(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), dst.data_ptr(), dst_t.data_ptr(), R, Cc, dst_t.stride(0))
-  bc1 = 1.0 - beta1 ** step
-  bc2 = 1.0 - beta2 ** step
-  _lib.check(_lib.load().plm_adamw_cast_multi(table, len(table), lr, beta1, beta2, eps, weight_decay, bc1, bc2, _p(clip_coef), _stream()),
-             'plm_adamw_cast_multi')
-  return table
-
-
-_OPTIM_KINDS = {'nadamw': _lib.OPTIM_NADAMW, 'sgd': _lib.OPTIM_SGD, 'signSGD': _lib.OPTIM_SIGNSGD, 'sfo_adamw': _lib.OPTIM_SFO_ADAMW}
+_OPTIM_KINDS = {'adamw': _lib.OPTIM_ADAMW, 'nadamw': _lib.OPTIM_NADAMW, 'sgd': _lib.OPTIM_SGD, 'signSGD': _lib.OPTIM_SIGNSGD, 'sfo_adamw': _lib.OPTIM_SFO_ADAMW}
 
 
 def optim_hparams(kind, lr, weight_decay=0.0, first=False, beta1=0.0, beta2=0.0, eps=0.0, momentum=0.0, dampening=0.0, bc2=1.0,
-                  coef_grad=0.0, coef_avg=0.0, ckp1=0.0):
-  """struct plm_optim_hparams for optim_ / optim_cast_multi_.  kind: 'nadamw' | 'sgd' | 'signSGD' | 'sfo_adamw' (an int is passed
-  through as is).  decay = 1 - lr * weight_decay is formed here in double and rounded once, the value torch hands to p.mul_(); for
+                  coef_grad=0.0, coef_avg=0.0, ckp1=0.0, bc1=1.0):
+  """struct plm_optim_hparams for optim_ / optim_cast_multi_.  kind: 'adamw' | 'nadamw' | 'sgd' | 'signSGD' | 'sfo_adamw' (an int is
+  passed through as is).  decay = 1 - lr * weight_decay is formed here in double and rounded once, the value torch hands to p.mul_(); for
   'sfo_adamw' (lr = the group's warmed-up scheduled_lr, ckp1 = weight / weight_sum) so is the y coefficient lr (beta1 (1 - ckp1) - 1),
-  the alpha of the package's y.add_()."""
+  the alpha of the package's y.add_().  'adamw' takes bc1 = 1 - beta1^t and bc2 = 1 - beta2^t; the library forms its decay and step
+  size itself, in fp32."""
   k = _OPTIM_KINDS[kind] if isinstance(kind, str) else int(kind)
   return _lib.OptimHparams(k, int(bool(first)), lr, weight_decay, 1.0 - lr * weight_decay, beta1, beta2, eps, momentum, dampening, bc2,
-                           coef_grad, coef_avg, ckp1, lr * (beta1 * (1.0 - ckp1) - 1.0))
+                           coef_grad, coef_avg, ckp1, lr * (beta1 * (1.0 - ckp1) - 1.0), bc1)
 
 
 def sfo_scalars(group):
@@ -859,7 +830,7 @@ def nadam_scalars(lr, beta1, beta2, momentum_decay, step, mu_product):
 
 
 def optim_(hp, p, g, m, v, clip_coef=None):
-  """One NAdamW / SGD / signSGD / schedule-free AdamW step on a flat fp32 span (hp from optim_hparams).  m / v: None where the kind has no such buffer."""
+  """One optimizer step (any kind) on a flat fp32 span (hp from optim_hparams).  m / v: None where the kind has no such buffer."""
   for t, n in ((p, 'p'), (g, 'g'), (m, 'm'), (v, 'v')):
     if t is not None:
       _need(t, F32, 'optim.' + n)
@@ -869,10 +840,10 @@ def optim_(hp, p, g, m, v, clip_coef=None):
 
 
 def optim_cast_multi_(hp, items, clip_coef=None, table=None):
-  """optim_ on a list of Linear weights that also writes their bf16 shadows: items = [(p, g, m, v, dst, dst_t)] as for adamw_cast_multi_,
-  with v (and m for SGD without momentum) None.  Returns the ctypes item table; pass it back as `table` on later steps."""
+  """optim_ on a list of Linear weights that also writes their bf16 shadows: items = [(p, g, m, v fp32 [rows, cols], dst bf16
+  [rows, cols], dst_t bf16 [cols, >= rows])], with v (and m for SGD without momentum) None where the kind has no such buffer.  Returns the ctypes item table; pass it back as `table` on later steps."""
   if table is None:
-    table = (_lib.AdamwItem * len(items))()
+    table = (_lib.OptimItem * len(items))()
     for i, (p, g, m, v, dst, dst_t) in enumerate(items):
       for t, n in ((p, 'p'), (g, 'g'), (m, 'm'), (v, 'v')):
         if t is not None:
@@ -885,7 +856,7 @@ def optim_cast_multi_(hp, items, clip_coef=None, table=None):
       if dst_t.dtype != BF16 or dst_t.dim() != 2 or dst_t.shape[0] != Cc or dst_t.shape[1] < R or dst_t.stride(1) != 1 or not dst_t.is_cuda:
         raise ValueError('optim_cast_multi.dst_t: need bf16 [cols, >= rows] on the GPU')
       ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-      table[i] = _lib.AdamwItem(p.data_ptr(), g.data_ptr(), ptr(m), ptr(v), dst.data_ptr(), dst_t.data_ptr(), R, Cc, dst_t.stride(0))
+      table[i] = _lib.OptimItem(p.data_ptr(), g.data_ptr(), ptr(m), ptr(v), dst.data_ptr(), dst_t.data_ptr(), R, Cc, dst_t.stride(0))
   _lib.check(_lib.load().plm_optim_cast_multi(C.byref(hp), table, len(table), _p(clip_coef), _stream()), 'plm_optim_cast_multi')
   return table
 

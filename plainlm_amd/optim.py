@@ -138,7 +138,7 @@ class _FlatTail:
   """What every flat optimizer shares, mixed in front of its torch class: the flat re-layout of parameters, gradients and state
   buffers (one span per parameter group), the model's gradient span table, the shadow-emitting launch plan, ``clip_and_step``,
   ``step`` and ``zero_grad``.  Subclasses name their per-parameter state buffers (``_state_names``, torch's keys) and implement
-  ``_group_hparams`` / ``_publish_state`` / ``_restore_host_state``; ``_update_multi`` / ``_update_flat`` launch the update."""
+  ``_group_hparams`` / ``_publish_state`` / ``_restore_host_state``."""
 
   _state_names = ()
 
@@ -218,13 +218,6 @@ class _FlatTail:
   def _item(self, lin):
     return (lin.weight.data, lin.weight.main_grad) + self._views[id(lin.weight)] + (lin._shadow[0], lin._shadow[1])
 
-  def _update_multi(self, group, hp, items, clip, table):
-    return ops.optim_cast_multi_(hp, items, clip, table)
-
-  def _update_flat(self, group, hp, a, b, clip):
-    m, v = (t[a:b] if t is not None else None for t in self._state_bufs)
-    ops.optim_(hp, self.flat_p[a:b], self.flat_g[a:b], m, v, clip)
-
   def _after_step(self):
     self._publish_state()
 
@@ -254,11 +247,12 @@ class _FlatTail:
           # a shadow buffer or a weight was re-allocated behind our back (model moved, weights re-laid): rebuild the cached table
           items = [self._item(lin) for lin in lins]
           table = None
-        table = self._update_multi(g, hp, items, clip, table)
+        table = ops.optim_cast_multi_(hp, items, clip, table)
         self._fused[gi] = (lins, items, table, spans)
         fresh.extend(lins)
       for a, b in spans:
-        self._update_flat(g, hp, a, b, clip)
+        m, v = (t[a:b] if t is not None else None for t in self._state_bufs)
+        ops.optim_(hp, self.flat_p[a:b], self.flat_g[a:b], m, v, clip)
     self._after_step()
     self.model.invalidate_shadows()  # raw-pointer update: torch's version counters did not move
     for lin in fresh:                # ... except where this step has just written the shadows itself
@@ -312,16 +306,9 @@ class FlatAdamW(_FlatTail, torch.optim.AdamW):
         self.state[p] = {'step': torch.tensor(float(self._step_count)), 'exp_avg': m, 'exp_avg_sq': v}
 
   def _group_hparams(self, gi, g):
-    return None
-
-  def _update_multi(self, g, hp, items, clip, table):
     b1, b2 = g['betas']
-    return ops.adamw_cast_multi_(items, float(g['lr']), b1, b2, g['eps'], g['weight_decay'], self._step_count, clip, table)
-
-  def _update_flat(self, g, hp, a, b, clip):
-    b1, b2 = g['betas']
-    ops.adamw_(self.flat_p[a:b], self.flat_g[a:b], self.flat_m[a:b], self.flat_v[a:b], float(g['lr']), b1, b2,
-               g['eps'], g['weight_decay'], self._step_count, clip)
+    return ops.optim_hparams('adamw', float(g['lr']), g['weight_decay'], beta1=b1, beta2=b2, eps=g['eps'],
+                             bc1=1.0 - b1 ** self._step_count, bc2=1.0 - b2 ** self._step_count)
 
   def _after_step(self):
     for st in self.state.values():

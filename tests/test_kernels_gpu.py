@@ -1093,5 +1093,6 @@ def test_sumsq_and_adamw(ops):
   clip = torch.tensor(0.5, device='cuda')
   for step in (1, 2, 3):
     opt.step()
-    ops.adamw_(p, gr, m, v, 1e-2, 0.9, 0.95, 1e-8, 0.1, step, clip)
+    hp = ops.optim_hparams('adamw', 1e-2, 0.1, beta1=0.9, beta2=0.95, eps=1e-8, bc1=1.0 - 0.9 ** step, bc2=1.0 - 0.95 ** step)
+    ops.optim_(hp, p, gr, m, v, clip)
   close(p, ref.detach(), 1e-5, 'adamw vs torch.optim.AdamW')

@@ -94,7 +94,7 @@ def test_mx_entry_points_refuse_bad_shapes_without_a_gpu():
   assert 'ld=' in refused('plm_mx_quant', p(), 8, 4, 16, p(), p(), None, None, None)
   items = (_lib.MxQuantItem * 2)(_lib.MxQuantItem(0x100000, 16, 4, 16, 0x100000, 0x100000, 0, 0), _lib.MxQuantItem(0x100000, 16, 4, 16, 0, 0, 0, 0))
   assert 'item 1' in refused('plm_mx_quant_multi', items, 2, None)
-  assert lib.plm_version() == 111
+  assert lib.plm_version() == 112
 
 
 @pytest.mark.timeout(600)

@@ -1,9 +1,11 @@
-"""The NAdamW / SGD / signSGD tails on MI355X (plainlm_amd/csrc/optim.hip): the flat kernel against the torch optimizers, the
-shadow-emitting multi-tensor form against the flat kernel bit for bit, the argument checks, the flat optimizers on the small model
+"""The AdamW / NAdamW / SGD / signSGD tails on MI355X (plainlm_amd/csrc/optim.hip): the flat kernel against the torch optimizers, the
+shadow-emitting multi-tensor form against the flat kernel bit for bit, AdamW's bits against those of its former kernels, the argument
+checks (all items of a list before its first launch), the flat optimizers on the small model
 (clip, shadows, torch-layout state both ways) and the engine with each optimizer against its torch-side twin (fused_optim False),
 checkpoints included."""
 
 import copy
+import importlib.util
 import os
 from collections import namedtuple
 
@@ -15,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 from plainlm_amd.optim import SignSGD  # noqa: E402
 
-KINDS = ['nadamw', 'sgd', 'sgd0', 'signSGD']  # sgd0: SGD without momentum (no buffer)
+KINDS = ['adamw', 'nadamw', 'sgd', 'sgd0', 'signSGD']  # sgd0: SGD without momentum (no buffer)
 HP = dict(lr=1e-2, wd=0.1, b1=0.9, b2=0.95, eps=1e-8, damp=0.1)
 
 
@@ -33,6 +35,8 @@ def relmax(a, ref):
 
 
 def _torch_opt(kind, params, lr=HP['lr'], wd=HP['wd']):
+  if kind == 'adamw':
+    return torch.optim.AdamW(params, lr=lr, betas=(HP['b1'], HP['b2']), eps=HP['eps'], weight_decay=wd)
   if kind == 'nadamw':
     return torch.optim.NAdam(params, lr=lr, betas=(HP['b1'], HP['b2']), eps=HP['eps'], weight_decay=wd, decoupled_weight_decay=True)
   if kind in ('sgd', 'sgd0'):
@@ -48,6 +52,9 @@ class _Kernel:
 
   def hparams(self, lr, wd=HP['wd']):
     self.step += 1
+    if self.kind == 'adamw':
+      return self.ops.optim_hparams('adamw', lr, wd, beta1=HP['b1'], beta2=HP['b2'], eps=HP['eps'], bc1=1.0 - HP['b1'] ** self.step,
+                                    bc2=1.0 - HP['b2'] ** self.step)
     if self.kind == 'nadamw':
       bc2, cg, cm, self.mu_product = self.ops.nadam_scalars(lr, HP['b1'], HP['b2'], 4e-3, self.step, self.mu_product)
       return self.ops.optim_hparams('nadamw', lr, wd, beta1=HP['b1'], beta2=HP['b2'], eps=HP['eps'], bc2=bc2, coef_grad=cg, coef_avg=cm)
@@ -56,7 +63,7 @@ class _Kernel:
 
   def buffers(self, like):
     m = None if self.kind == 'sgd0' else torch.zeros_like(like)
-    v = torch.zeros_like(like) if self.kind == 'nadamw' else None
+    v = torch.zeros_like(like) if self.kind in ('adamw', 'nadamw') else None
     return m, v
 
 
@@ -100,7 +107,7 @@ def test_flat_kernel_matches_torch_optimizer(P, kind):
       m.copy_(st['m'])
     else:
       assert relmax(p, ref.detach()) < 1e-5, s
-      if kind == 'nadamw':
+      if kind in ('adamw', 'nadamw'):
         assert relmax(m, st['exp_avg']) < 1e-5 and relmax(v, st['exp_avg_sq']) < 1e-5, s
       elif kind == 'sgd':
         assert relmax(m, st['momentum_buffer']) < 1e-5, s
@@ -115,7 +122,7 @@ def _items(shapes, kind, gen):
     p = torch.randn(rows, cols, device='cuda', generator=gen)
     g = torch.randn(rows, cols, device='cuda', generator=gen)
     m = None if kind == 'sgd0' else torch.randn(rows, cols, device='cuda', generator=gen) * 0.1
-    v = torch.rand(rows, cols, device='cuda', generator=gen) * 0.01 if kind == 'nadamw' else None
+    v = torch.rand(rows, cols, device='cuda', generator=gen) * 0.01 if kind in ('adamw', 'nadamw') else None
     dst = torch.empty(rows, cols, dtype=torch.bfloat16, device='cuda')
     dst_t = torch.full((cols, ld_t), 7.0, dtype=torch.bfloat16, device='cuda')
     out.append((p, g, m, v, dst, dst_t))
@@ -173,6 +180,15 @@ def test_bad_arguments_are_refused_before_any_launch(P):
   mis = buf[1:].view(64, 64)  # 4 bytes off 16-byte alignment
   with pytest.raises(RuntimeError, match='item 1: pointers must be 16-byte aligned'):
     ops.optim_cast_multi_(hn, [good, (mis,) + good[1:]])
+  ha = ops.optim_hparams('adamw', 1e-3, 0.1, beta1=0.9, beta2=0.95, eps=1e-8, bc1=0.1, bc2=0.05)
+  with pytest.raises(RuntimeError, match='item 1: adamw needs v'):
+    ops.optim_cast_multi_(ha, [good, bad_v])
+  with pytest.raises(RuntimeError, match='item 1: adamw needs the momentum buffer m'):
+    ops.optim_cast_multi_(ha, [good, good[:2] + (None,) + good[3:]])
+  with pytest.raises(RuntimeError, match='adamw needs v'):
+    ops.optim_(ha, good[0].view(-1), good[1].view(-1), good[2].view(-1), None)
+  with pytest.raises(RuntimeError, match='adamw needs the momentum buffer m'):
+    ops.optim_(ha, good[0].view(-1), good[1].view(-1), None, good[3].view(-1))
   with pytest.raises(RuntimeError, match='unknown optimizer kind 9'):
     ops.optim_cast_multi_(ops.optim_hparams(9, 1e-3), [good])
   with pytest.raises(RuntimeError, match='unknown optimizer kind 0'):
@@ -181,6 +197,67 @@ def test_bad_arguments_are_refused_before_any_launch(P):
     ops.optim_(hn, good[0].view(-1), good[1].view(-1), good[2].view(-1), None)
   torch.cuda.synchronize()
   assert torch.equal(good[0], before)  # the valid first item of each refused list was not updated
+
+
+def test_bad_item_beyond_the_56th_leaves_the_first_56_untouched(P):
+  """The C side launches once per 56 items; it validates the WHOLE list first.  Item 57 has 12 rows (not a multiple of 8): the call is
+  refused on the host and the 56 valid items in front of it - a full first launch - keep their parameters, state and shadows, for
+  plm_optim_cast_multi (AdamW) and for plm_cast_f32_bf16_t_multi."""
+  from plainlm_amd import ops
+  gen = torch.Generator(device='cuda').manual_seed(4)
+  items = _items([(64, 64, 64)] * 56 + [(12, 8, 16)] + [(8, 8, 8)], 'adamw', gen)
+  before = [tuple(t.clone() for t in it[:4]) for it in items]
+  for it in items:
+    it[4].fill_(3.0)
+  ha = ops.optim_hparams('adamw', 1e-2, 0.1, beta1=0.9, beta2=0.95, eps=1e-8, bc1=0.1, bc2=0.05)
+  with pytest.raises(RuntimeError, match='plm_optim_cast_multi: item 56: rows=12 cols=8 must be positive multiples of 8'):
+    ops.optim_cast_multi_(ha, items)
+  with pytest.raises(RuntimeError, match='plm_cast_f32_bf16_t_multi: item 56: rows=12 cols=8 must be positive multiples of 8'):
+    ops.cast_bf16_t_multi([(it[0], it[4], it[5]) for it in items])
+  torch.cuda.synchronize()
+  for i, (it, old) in enumerate(zip(items, before)):
+    for t, o in zip(it[:4], old):
+      assert torch.equal(t, o), i
+    assert (it[4] == 3.0).all() and (it[5] == 7.0).all(), i
+
+
+def test_adamw_bits_are_those_of_the_separate_adamw_kernels(P, golden_dir):
+  """AdamW as a kind of the plm_optim_* family against tests/golden/adamw_bits.npz, what plm_adamw_f32 / plm_adamw_cast_multi of the
+  tree before (ABI 111) left on an MI355X (make_adamw_bits.py, whose seeded CPU inputs are rebuilt here): p, m, v and the shadows
+  bit for bit - the flat form on 4099 elements over 3 steps, the multi-tensor form on three matrices with partial tiles and
+  ld_t > rows over 2, with a device clip coefficient and a changing lr, at an ordinary hyper-parameter set and at lr = 0.826,
+  wd = 0.71, where decay = fma(-lr, wd, 1) and lr / bc1 formed in fp32 differ from their double-then-round values."""
+  from plainlm_amd import ops
+  spec = importlib.util.spec_from_file_location('make_adamw_bits', os.path.join(golden_dir, 'make_adamw_bits.py'))
+  G = importlib.util.module_from_spec(spec)
+  spec.loader.exec_module(G)
+  z = np.load(os.path.join(golden_dir, 'adamw_bits.npz'))
+  want = lambda key: torch.from_numpy(z[key])  # noqa: E731
+  bits = lambda t: t.view(torch.int16).cpu()  # noqa: E731
+
+  def hparams(hp, t):
+    return ops.optim_hparams('adamw', G.step_lr(hp, t), hp['wd'], beta1=hp['b1'], beta2=hp['b2'], eps=hp['eps'], bc1=1.0 - hp['b1'] ** t,
+                             bc2=1.0 - hp['b2'] ** t)
+
+  for name, hp in G.SETS.items():
+    p0, gs = G.flat_inputs()
+    p, m, v = p0.cuda(), torch.zeros(G.FLAT_N, device='cuda'), torch.zeros(G.FLAT_N, device='cuda')
+    clip = torch.tensor([G.FLAT_CLIP], device='cuda')
+    for t in range(1, G.FLAT_STEPS + 1):
+      ops.optim_(hparams(hp, t), p, gs[t - 1].cuda(), m, v, clip)
+    for k, x in (('p', p), ('m', m), ('v', v)):
+      assert torch.equal(x.cpu(), want(f'{name}/flat/{k}')), (name, 'flat', k)
+    mats = [(p.cuda(), [g.cuda() for g in gs], m.cuda(), v.cuda(), torch.empty(p.shape, dtype=torch.bfloat16, device='cuda'),
+             torch.full((p.shape[1], ld_t), 7.0, dtype=torch.bfloat16, device='cuda'))
+            for (p, gs, m, v), (_, _, ld_t) in zip(G.multi_inputs(), G.MULTI_SHAPES)]
+    clip = torch.tensor([G.MULTI_CLIP], device='cuda')
+    for t in range(1, G.MULTI_STEPS + 1):
+      ops.optim_cast_multi_(hparams(hp, t), [(p, gs[t - 1], m, v, dst, dst_t) for p, gs, m, v, dst, dst_t in mats], clip)
+    for i, (p, _, m, v, dst, dst_t) in enumerate(mats):
+      for k, x in (('p', p), ('m', m), ('v', v)):
+        assert torch.equal(x.cpu(), want(f'{name}/multi/{i}/{k}')), (name, 'multi', i, k)
+      assert torch.equal(bits(dst), want(f'{name}/multi/{i}/dst').view(torch.int16)), (name, i, 'dst')
+      assert torch.equal(bits(dst_t), want(f'{name}/multi/{i}/dst_t').view(torch.int16)), (name, i, 'dst_t')
 
 
 # ---- the flat optimizers on the small model ------------------------------------------------------------------------------------------

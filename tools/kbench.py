@@ -230,7 +230,8 @@ def main():
     flat = torch.randn(n_params, device=dev)
     rec(f'sumsq {n_params / 1e6:.0f}M', timeit(lambda: ops.sumsq(flat), a.iters), bytes_=4.0 * flat.numel())
     m_, v_, g_ = torch.zeros_like(flat), torch.zeros_like(flat), torch.randn_like(flat)
-    rec(f'adamw {n_params / 1e6:.0f}M', timeit(lambda: ops.adamw_(flat, g_, m_, v_, 1e-3, 0.9, 0.95, 1e-8, 0.1, 1), a.iters), bytes_=28.0 * flat.numel())
+    hp = ops.optim_hparams('adamw', 1e-3, 0.1, beta1=0.9, beta2=0.95, eps=1e-8, bc1=1.0 - 0.9, bc2=1.0 - 0.95)
+    rec(f'adamw {n_params / 1e6:.0f}M', timeit(lambda: ops.optim_(hp, flat, g_, m_, v_), a.iters), bytes_=28.0 * flat.numel())
 
   if a.json:
     with open(a.json, 'w') as f:
