@@ -61,7 +61,8 @@ BOUNDS = {
 # bf16 arithmetic in fp64
 # --------------------------------------------------------------------------------------
 def _exp2i(e: Tensor) -> Tensor:
-  return torch.ldexp(torch.ones_like(e, dtype=F64), e)
+  """2^e as fp64, assembled from its bits (|e| < 1023): exact on every device (a device's pow need not return exact powers of two)."""
+  return ((e.to(torch.int64) + 1023) << 52).view(F64)
 
 
 def ulp_of(v: Tensor) -> Tensor:
@@ -101,8 +102,9 @@ def elementwise(got: Tensor, ref: Tensor, allow: Optional[Tensor] = None) -> Dic
   far.  ``neq`` divides by at least NEQ_MIN elements, so a tensor smaller than that may have up to
   BOUNDS['neq'] * NEQ_MIN = 2.56, i.e. 2 mismatches (an honest kernel flips ~1e-3 of its elements; one flip among 96 is no 1 % rate).
   The budget's own cases all have at least 4096 elements; only the smallest shapes of the older tests (RMSNorm 5 x 64)
-  fall under this floor."""
-  g = got.detach().cpu().double()
+  fall under this floor.  Evaluated on ``ref``'s device (the CPU for every reference of this file; parity_gemm.py keeps its
+  full-size GEMM references on the GPU)."""
+  g = got.detach().to(ref.device).double()
   r = ref.double()
   slack = FLOOR if allow is None else allow.double() + FLOOR
   err = torch.where(torch.isfinite(g), (g - r).abs(), torch.full_like(g, float('inf')))
