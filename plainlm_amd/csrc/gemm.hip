@@ -19,7 +19,7 @@
 // rasterisation (GROUP_M row-panels x all column tiles) so A panels and B tiles are reused from L2.
 #include <stdlib.h>
 
-#include "plm_device.h"
+#include "gemm_launch.h"
 
 #define GBM 128
 #define GBN 128
@@ -300,42 +300,11 @@ __global__ __launch_bounds__(256) void gemm_nt_dma_kernel(const uint16_t* __rest
   }
 }
 
-bool plm_launch_gemm_nt_big(int variant, const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, uint16_t* C, int64_t ldc,
-                            int64_t M, int64_t N, int64_t K, const float* alpha_dev, void* workspace, size_t workspace_bytes,
-                            hipStream_t s);  // gemm_big.hip
-extern "C" int plm_rope_qk(uint16_t* qkv, const float* rope_cos, const float* rope_sin, int64_t B, int64_t T, int64_t nh, int64_t hd,
-                           void* stream);
-
-extern "C" int plm_gemm_bf16_nt_ws(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, void* C, int64_t ldc, int64_t M,
-                                   int64_t N, int64_t K, int c_dtype, int accumulate, const float* alpha_dev, int variant,
-                                   void* workspace, size_t workspace_bytes, void* stream) {
-  PLM_REQUIRE(A && B && C, "plm_gemm_bf16_nt: null pointer");
-  PLM_REQUIRE(variant >= 0 && variant <= 7, "plm_gemm_bf16_nt_ex: variant must be 0..7");
-  PLM_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "plm_gemm_bf16_nt: bad shape M=%ld N=%ld K=%ld",
-              (long)M, (long)N, (long)K);
-  PLM_REQUIRE(K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0, "plm_gemm_bf16_nt: K, lda, ldb must be multiples of 8 and ldc of 4 (K=%ld lda=%ld ldb=%ld ldc=%ld)",
-              (long)K, (long)lda, (long)ldb, (long)ldc);
-  PLM_REQUIRE(((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(C)) & 15) == 0,
-              "plm_gemm_bf16_nt: base pointers must be 16-byte aligned");
-  PLM_REQUIRE(c_dtype == 0 || c_dtype == 1, "plm_gemm_bf16_nt: c_dtype must be 0 (bf16) or 1 (fp32)");
-  PLM_REQUIRE(!(accumulate && c_dtype == 0), "plm_gemm_bf16_nt: accumulate needs an fp32 C");
-  const int tiles_m = (int)plm_cdiv(M, GBM), tiles_n = (int)plm_cdiv(N, GBN);
-  const dim3 grid((unsigned)(tiles_m * tiles_n)), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  const bool force_v1 = plm_env().gemm_v1;
-  const bool dma_shape = (K % GBK == 0) && (N % 8 == 0) && (ldc % 8 == 0);
-  PLM_REQUIRE(variant <= 1 || dma_shape, "plm_gemm_bf16_nt_ex: variant %d needs K %% 64 == 0, N %% 8 == 0, ldc %% 8 == 0", variant);
-  PLM_REQUIRE(variant <= 2 || c_dtype == 0, "plm_gemm_bf16_nt_ex: the big-tile variants write bf16 C only");
-  const bool dma_ok = variant >= 2 || (variant == 0 && !force_v1 && dma_shape);
-  if ((variant == 0 && dma_ok && c_dtype == 0) || variant >= 3) {
-    if (plm_launch_gemm_nt_big(variant, A, lda, B, ldb, (uint16_t*)C, ldc, M, N, K, alpha_dev, workspace, workspace_bytes, s)) {
-      PLM_CHECK_LAUNCH("plm_gemm_bf16_nt (big tile)");
-      return PLM_OK;
-    }
-  }
-#define PLM_NT_LAUNCH(KERN)                                                                                              \
-  hipLaunchKernelGGL(KERN, grid, block, 0, s, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, alpha_dev, tiles_m, tiles_n)
-  if (dma_ok) {
+void plm_launch_gemm_nt_128(const NtPlan& p, const GemmOperands& o, int c_dtype, int accumulate, hipStream_t s) {
+  const dim3 grid((unsigned)p.grid), block(256);
+#define PLM_NT_LAUNCH(KERN)                                                                                                    \
+  hipLaunchKernelGGL(KERN, grid, block, 0, s, o.A, o.lda, o.B, o.ldb, o.C, o.ldc, (int)o.M, (int)o.N, (int)o.K, o.alpha_dev, p.tm, p.tn)
+  if (p.kernel == NT_DMA128) {
     if (c_dtype == 0) PLM_NT_LAUNCH((gemm_nt_dma_kernel<false, false>));
     else if (accumulate) PLM_NT_LAUNCH((gemm_nt_dma_kernel<true, true>));
     else PLM_NT_LAUNCH((gemm_nt_dma_kernel<true, false>));
@@ -345,82 +314,6 @@ extern "C" int plm_gemm_bf16_nt_ws(const uint16_t* A, int64_t lda, const uint16_
     else PLM_NT_LAUNCH((gemm_nt_kernel<true, false>));
   }
 #undef PLM_NT_LAUNCH
-  PLM_CHECK_LAUNCH("plm_gemm_bf16_nt");
-  return PLM_OK;
-}
-
-extern "C" int plm_gemm_bf16_nt_ex(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, void* C, int64_t ldc, int64_t M,
-                                   int64_t N, int64_t K, int c_dtype, int accumulate, const float* alpha_dev, int variant,
-                                   void* stream) {
-  return plm_gemm_bf16_nt_ws(A, lda, B, ldb, C, ldc, M, N, K, c_dtype, accumulate, alpha_dev, variant, nullptr, 0, stream);
-}
-
-extern "C" int plm_gemm_bf16_nt(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, void* C, int64_t ldc, int64_t M,
-                                int64_t N, int64_t K, int c_dtype, int accumulate, const float* alpha_dev, void* stream) {
-  return plm_gemm_bf16_nt_ws(A, lda, B, ldb, C, ldc, M, N, K, c_dtype, accumulate, alpha_dev, 0, nullptr, 0, stream);
-}
-
-// w_qkv projection with RoPE: qkv[M, 3*nh*hd] = x W^T with the q | k column blocks rotated (row m = position m % T) in the GEMM
-// epilogue: the 16-byte chunks are rotated on their way from the transposition scratch to memory, one 16-byte table read per
-// table and chunk (round 1 rotated accumulator fragments - per-lane table gathers, 58 us per call - and lost to the 31 us
-// stand-alone pass, which remains the fallback: same bits).
-bool plm_launch_gemm_nt_rope(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, uint16_t* C, int64_t ldc, int64_t M, int64_t N,
-                             int64_t K, const float* rcos, const float* rsin, int64_t T, int64_t rope_cols, hipStream_t s);
-extern "C" int plm_qkv_rope_bf16(const uint16_t* X, int64_t ldx, const uint16_t* W, int64_t ldw, uint16_t* QKV, int64_t ldq, int64_t M,
-                                 int64_t K, const float* rope_cos, const float* rope_sin, int64_t B, int64_t T, int64_t nh, int64_t hd,
-                                 void* stream) {
-  PLM_REQUIRE(X && W && QKV && rope_cos && rope_sin, "plm_qkv_rope_bf16: null pointer");
-  PLM_REQUIRE((hd == 64 || hd == 32 || hd == 128) && B > 0 && T > 0 && nh > 0 && M == B * T, "plm_qkv_rope_bf16: bad shape (hd 32 / 64 / 128, M == B*T)");
-  const int64_t N = 3 * nh * hd;
-  PLM_REQUIRE(ldq == N, "plm_qkv_rope_bf16: needs a dense output (ldq == 3*nh*hd)");
-  if (hd == 64 && !plm_env().gemm_v1 &&  // the store-side rotation is built for 64-wide heads; other head dims take GEMM + the stand-alone pass
-      plm_launch_gemm_nt_rope(X, ldx, W, ldw, QKV, ldq, M, N, K, rope_cos, rope_sin, T, 2 * nh * hd, (hipStream_t)stream)) {
-    PLM_CHECK_LAUNCH("plm_qkv_rope_bf16");
-    return PLM_OK;
-  }
-  if (int rc = plm_gemm_bf16_nt_ex(X, ldx, W, ldw, QKV, ldq, M, N, K, 0, 0, nullptr, 0, stream)) return rc;
-  return plm_rope_qk(QKV, rope_cos, rope_sin, B, T, nh, hd, stream);
-}
-
-// fc1 of the SwiGLU MLP with the activation in the GEMM epilogue (models/components.py:50-56):
-//   U[M, 2h] = X[M, K] W[2h, K]^T  (gate | up, kept for backward)  and  ACT[M, h] = bf16(bf16(silu(gate)) * up).
-// One launch on the persistent 256x256 kernel when the shape qualifies (2h % 256 == 0, K % 64 == 0, M >= 512); otherwise the GEMM
-// followed by plm_swiglu_fwd - the two paths produce the same bits.
-bool plm_launch_gemm_nt_glu(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, uint16_t* C, int64_t ldc, uint16_t* act,
-                            int64_t ldact, int64_t M, int64_t N, int64_t K, hipStream_t s);
-extern "C" int plm_fc1_swiglu_bf16(const uint16_t* X, int64_t ldx, const uint16_t* W, int64_t ldw, uint16_t* U, uint16_t* ACT, int64_t M,
-                                   int64_t h, int64_t K, void* stream) {
-  PLM_REQUIRE(X && W && U && ACT, "plm_fc1_swiglu_bf16: null pointer");
-  PLM_REQUIRE(M > 0 && h > 0 && K > 0 && h % 8 == 0, "plm_fc1_swiglu_bf16: bad shape (h %% 8 == 0)");
-  const int64_t N = 2 * h;
-  if (!plm_env().gemm_v1 && plm_launch_gemm_nt_glu(X, ldx, W, ldw, U, N, ACT, h, M, N, K, (hipStream_t)stream)) {
-    PLM_CHECK_LAUNCH("plm_fc1_swiglu_bf16");
-    return PLM_OK;
-  }
-  if (int rc = plm_gemm_bf16_nt_ex(X, ldx, W, ldw, U, N, M, N, K, 0, 0, nullptr, 0, stream)) return rc;
-  return plm_swiglu_fwd(U, ACT, M, h, stream);
-}
-
-// Backward of the SwiGLU MLP's second half (models/components.py:55-57): d(act)[M, h] = dY[M, K] W2T[h, K]^T never reaches memory -
-// the epilogue of that GEMM applies the SwiGLU backward with the saved fc1 output U[M, 2h] and writes DU[M, 2h] (d(gate) | d(up)).
-// One launch when h % 256 == 0, K % 64 == 0, M >= 512; otherwise the GEMM followed by plm_swiglu_bwd (same bits; `scratch` must then
-// hold M*h bf16 values for d(act), it is not touched by the fused path and may be NULL when the shape qualifies).
-bool plm_launch_gemm_nt_glub(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const uint16_t* U, int64_t ldu, uint16_t* DU,
-                             int64_t lddu, int64_t M, int64_t h, int64_t K, hipStream_t s);
-extern "C" int plm_fc2_dx_swiglu_bwd_bf16(const uint16_t* dY, int64_t lddy, const uint16_t* W2T, int64_t ldw, const uint16_t* U, uint16_t* DU,
-                                          uint16_t* scratch, int64_t M, int64_t h, int64_t K, void* stream) {
-  PLM_REQUIRE(dY && W2T && U && DU, "plm_fc2_dx_swiglu_bwd_bf16: null pointer");
-  PLM_REQUIRE(M > 0 && h > 0 && K > 0 && h % 8 == 0, "plm_fc2_dx_swiglu_bwd_bf16: bad shape (h %% 8 == 0)");
-  if (!plm_env().gemm_v1 && plm_launch_gemm_nt_glub(dY, lddy, W2T, ldw, U, 2 * h, DU, 2 * h, M, h, K, (hipStream_t)stream)) {
-    PLM_CHECK_LAUNCH("plm_fc2_dx_swiglu_bwd_bf16");
-    return PLM_OK;
-  }
-  if (!scratch) {  // not an error of the shape: the caller retries with the buffer
-    plm_set_error("plm_fc2_dx_swiglu_bwd_bf16: this shape (or PLM_GEMM_V1) takes the two-launch path and needs the M*h bf16 d(act) scratch");
-    return PLM_E_WORKSPACE;
-  }
-  if (int rc = plm_gemm_bf16_nt_ex(dY, lddy, W2T, ldw, scratch, h, M, h, K, 0, 0, nullptr, 0, stream)) return rc;
-  return plm_swiglu_bwd(scratch, U, DU, M, h, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -668,122 +561,27 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   }
 }
 
-static int tn_splits(int64_t M, int64_t N, int64_t K) {
-  // The DMA kernels run 2 workgroups per CU (512 slots on 256 CUs): aim for just under 2 full rounds.
-  const int64_t tiles = plm_cdiv(M, GBM) * plm_cdiv(N, GBN);
-  if (tiles >= 512) return 1;
-  int64_t s = 1024 / tiles;
-  const int64_t max_by_k = K / 512 > 0 ? K / 512 : 1;  // keep >= 512 contraction rows per slab
-  if (s > max_by_k) s = max_by_k;
-  if (s > 32) s = 32;
-  return (int)(s < 1 ? 1 : s);
+// splits == 1: C (+)= alpha*acc directly (MODE 0 / 1); otherwise raw partials into the slabs (MODE 2), summed by plm_launch_splitk_reduce
+void plm_launch_gemm_tn_128(const TnPlan& p, const GemmOperands& o, int accumulate, float* slabs, hipStream_t s) {
+  const dim3 grid((unsigned)p.grid, (unsigned)p.splits), block(256);
+#define PLM_TN_LAUNCH(KERN, C_, LDC_, ALPHA_)                                                                                      \
+  hipLaunchKernelGGL(KERN, grid, block, 0, s, o.A, o.lda, o.B, o.ldb, C_, LDC_, (int)o.M, (int)o.N, (int)o.K, p.kchunk, ALPHA_, p.tm, p.tn)
+  if (p.kernel == TN_DMA128) {
+    if (p.splits > 1) PLM_TN_LAUNCH(gemm_tn_dma_kernel<2>, slabs, o.N, (const float*)nullptr);
+    else if (accumulate) PLM_TN_LAUNCH(gemm_tn_dma_kernel<1>, (float*)o.C, o.ldc, o.alpha_dev);
+    else PLM_TN_LAUNCH(gemm_tn_dma_kernel<0>, (float*)o.C, o.ldc, o.alpha_dev);
+  } else {
+    if (p.splits > 1) PLM_TN_LAUNCH(gemm_tn_kernel<2>, slabs, o.N, (const float*)nullptr);
+    else if (accumulate) PLM_TN_LAUNCH(gemm_tn_kernel<1>, (float*)o.C, o.ldc, o.alpha_dev);
+    else PLM_TN_LAUNCH(gemm_tn_kernel<0>, (float*)o.C, o.ldc, o.alpha_dev);
+  }
+#undef PLM_TN_LAUNCH
 }
 
-bool plm_tn_big_plan(int64_t M, int64_t N, int64_t K, int* splits, int* rfull);  // gemm_big.hip
-void plm_launch_gemm_tn_big(int splits, int rfull, int accumulate, const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb,
-                            float* C, int64_t ldc, float* slabs, int64_t M, int64_t N, int64_t K, const float* alpha_dev,
-                            hipStream_t s);
-
-// one place decides kernel + split layout, so the workspace query and the launch always agree.
-// rfull: tile rows (of 256) that the big kernel computes without split (0 for the 128x128 kernels).
-static int tn_plan(int64_t M, int64_t N, int64_t K, bool& big, int& rfull) {
-  big = false;
-  rfull = 0;
-  if (!plm_env().tn_no_big && !plm_env().gemm_v1) {
-    int sb = 1;
-    if (plm_tn_big_plan(M, N, K, &sb, &rfull)) {
-      big = true;
-      return sb;
-    }
-  }
-  rfull = 0;
-  return tn_splits(M, N, K);
-}
-
-extern "C" size_t plm_gemm_tn_workspace_bytes(int64_t M, int64_t N, int64_t K) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  bool big;
-  int rfull;
-  const int s = tn_plan(M, N, K, big, rfull);
-  const int64_t rows = M - (int64_t)rfull * 256;
-  return (s > 1 && rows > 0) ? (size_t)s * (size_t)rows * (size_t)N * sizeof(float) : 0;
-}
-
-extern "C" int plm_gemm_bf16_tn(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
-                                int64_t N, int64_t K, int accumulate, const float* alpha_dev, void* workspace,
-                                size_t workspace_bytes, void* stream) {
-  PLM_REQUIRE(A && B && C, "plm_gemm_bf16_tn: null pointer");
-  PLM_REQUIRE(M > 0 && N > 0 && K > 0 && M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "plm_gemm_bf16_tn: bad shape M=%ld N=%ld K=%ld",
-              (long)M, (long)N, (long)K);
-  PLM_REQUIRE(M % 8 == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0,
-              "plm_gemm_bf16_tn: M, N, lda, ldb must be multiples of 8 and ldc of 4 (M=%ld N=%ld lda=%ld ldb=%ld ldc=%ld)", (long)M, (long)N,
-              (long)lda, (long)ldb, (long)ldc);
-  PLM_REQUIRE(((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(C)) & 15) == 0,
-              "plm_gemm_bf16_tn: base pointers must be 16-byte aligned");
-  const int tiles_m = (int)plm_cdiv(M, GBM), tiles_n = (int)plm_cdiv(N, GBN);
-  bool big;
-  int rfull;
-  const int splits = tn_plan(M, N, K, big, rfull);
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 block(256);
-  if (big) {
-    const int64_t rem_rows = M - (int64_t)rfull * 256;  // rows whose tiles are split over K
-    const bool split_part = splits > 1 && rem_rows > 0;
-    if (split_part) {
-      const size_t need = (size_t)splits * (size_t)rem_rows * (size_t)N * sizeof(float);
-      if (!workspace || workspace_bytes < need) {
-        plm_set_error("plm_gemm_bf16_tn: workspace of %zu bytes required, %zu given", need, workspace_bytes);
-        return PLM_E_WORKSPACE;
-      }
-      PLM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "plm_gemm_bf16_tn: workspace must be 16-byte aligned");
-    }
-    plm_launch_gemm_tn_big(split_part ? splits : 1, split_part ? rfull : (int)plm_cdiv(M, 256), accumulate, A, lda, B, ldb, C, ldc,
-                           (float*)workspace, M, N, K, alpha_dev, s);
-    if (split_part) {
-      const int64_t nv = rem_rows * (N / 4);
-      int64_t rb = plm_cdiv(nv, 256);
-      if (rb > 4096) rb = 4096;
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)rb), block, 0, s, (const float*)workspace, C + (int64_t)rfull * 256 * ldc, ldc,
-                         (int)rem_rows, (int)N, splits, accumulate, alpha_dev);
-    }
-    PLM_CHECK_LAUNCH("plm_gemm_bf16_tn (big tile)");
-    return PLM_OK;
-  }
-  const bool force_v1 = plm_env().gemm_v1;
-  const bool dma_ok = !force_v1 && (K % GBK == 0);
-  if (splits == 1) {
-    const dim3 grid((unsigned)(tiles_m * tiles_n), 1);
-    if (dma_ok) {
-      if (accumulate)
-        hipLaunchKernelGGL(gemm_tn_dma_kernel<1>, grid, block, 0, s, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, (int)K, alpha_dev, tiles_m, tiles_n);
-      else
-        hipLaunchKernelGGL(gemm_tn_dma_kernel<0>, grid, block, 0, s, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, (int)K, alpha_dev, tiles_m, tiles_n);
-    } else if (accumulate)
-      hipLaunchKernelGGL(gemm_tn_kernel<1>, grid, block, 0, s, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, (int)K, alpha_dev, tiles_m, tiles_n);
-    else
-      hipLaunchKernelGGL(gemm_tn_kernel<0>, grid, block, 0, s, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, (int)K, alpha_dev, tiles_m, tiles_n);
-    PLM_CHECK_LAUNCH("plm_gemm_bf16_tn");
-    return PLM_OK;
-  }
-  const size_t need = (size_t)splits * (size_t)M * (size_t)N * sizeof(float);
-  if (!workspace || workspace_bytes < need) {
-    plm_set_error("plm_gemm_bf16_tn: workspace of %zu bytes required, %zu given", need, workspace_bytes);
-    return PLM_E_WORKSPACE;
-  }
-  PLM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "plm_gemm_bf16_tn: workspace must be 16-byte aligned");
-  const int kchunk = (int)(plm_cdiv(plm_cdiv(K, splits), GBK) * GBK);
-  const dim3 grid((unsigned)(tiles_m * tiles_n), (unsigned)splits);
-  if (dma_ok)
-    hipLaunchKernelGGL(gemm_tn_dma_kernel<2>, grid, block, 0, s, A, lda, B, ldb, (float*)workspace, (int64_t)N, (int)M, (int)N, (int)K, kchunk,
-                       (const float*)nullptr, tiles_m, tiles_n);
-  else
-    hipLaunchKernelGGL(gemm_tn_kernel<2>, grid, block, 0, s, A, lda, B, ldb, (float*)workspace, (int64_t)N, (int)M, (int)N, (int)K, kchunk,
-                       (const float*)nullptr, tiles_m, tiles_n);
-  const int64_t nv = M * (N / 4);
+void plm_launch_splitk_reduce(const TnPlan& p, const GemmOperands& o, int accumulate, float* slabs, hipStream_t s) {
+  const int64_t nv = p.split_rows * (o.N / 4);
   int64_t rb = plm_cdiv(nv, 256);
   if (rb > 4096) rb = 4096;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)rb), block, 0, s, (const float*)workspace, C, ldc, (int)M, (int)N, splits, accumulate,
-                     alpha_dev);
-  PLM_CHECK_LAUNCH("plm_gemm_bf16_tn");
-  return PLM_OK;
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, s, (const float*)slabs, (float*)o.C + (int64_t)p.rfull * 256 * o.ldc, o.ldc,
+                     (int)p.split_rows, (int)o.N, p.splits, accumulate, o.alpha_dev);
 }

@@ -17,16 +17,14 @@
 //   * LDS: 2 stages x 4 half-tiles (128-byte rows, XOR swizzle applied on the DMA source address, as in
 //     gemm.hip) + a 4 KiB per-wave epilogue scratch: C leaves as full 128-byte row segments.
 //
-// Requirements (checked by the dispatcher in gemm.hip): bf16 C, no accumulate, K % 64 == 0, N % 8 == 0,
+// Requirements (checked by nt_plan in gemm_plan.h): bf16 C, no accumulate, K % 64 == 0, N % 8 == 0,
 // 16-byte aligned C rows.
 #include <stdlib.h>
 
 #include <type_traits>
 #include <utility>
 
-#include "plm_device.h"
-
-#include <initializer_list>
+#include "gemm_launch.h"
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void gbl_void_t;
@@ -71,42 +69,6 @@ __device__ __forceinline__ void phase_barrier() { asm volatile("s_waitcnt lgkmcn
 
 #define BIG_GROUP_M 4
 
-static int g_num_cus = 0;
-static int g_cu_reserve = 0;  // CUs left free for concurrent kernels (RCCL collectives during backward)
-
-// number of persistent workgroups to launch: one per CU minus the reserve
-static int persistent_slots() {
-  const int n = g_num_cus - g_cu_reserve;
-  return n < 8 ? 8 : n;
-}
-
-// The persistent GEMMs launch one workgroup per CU with a static tile schedule.  A concurrent kernel that occupies
-// some CUs (RCCL's all-reduce on the side stream) would push the displaced workgroups into a second round; leaving
-// `n` CUs free avoids that.  Process-wide setting; 0 restores the full chip.
-extern "C" int plm_set_cu_reserve(int n) {
-  if (n < 0 || n > 128) {
-    plm_set_error("plm_set_cu_reserve: n=%d out of range 0..128", n);
-    return PLM_E_INVALID;
-  }
-  g_cu_reserve = n;
-  return PLM_OK;
-}
-
-static bool ensure_num_cus() {
-  if (g_num_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
-    g_num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return true;
-}
-
-static double round_efficiency(int64_t tiles, int slots) {
-  const int64_t rounds = (tiles + slots - 1) / slots;
-  return (double)tiles / (double)(rounds * slots);
-}
-
 // Hybrid work items (HYB): the tiles of the first `rfull` tile rows take the whole contraction and write bf16 C (whole
 // rounds of the persistent grid); the K-tiles of the remaining tile rows form ONE stream (tile-major, then k) that is
 // cut into `nchunks` equal runs of `L` K-tiles, one run per workgroup ("stream-K" for the last, partial round).  A run
@@ -143,17 +105,7 @@ struct HybridArgs {
 // ROPE: C is the w_qkv projection [M, 3*nh*64] of M = B*T token rows; the 16-byte chunks of its q | k column blocks (columns
 // < rope_cols) are rotated on their way from the transposition scratch to memory - the same rope8() on the same bf16 values as
 // rope_qk_kernel, i.e. the same bits, without the extra pass over 2/3 of the projection (31 us, 200 MB per layer).
-struct EpiArgs {
-  uint16_t* act;        // GLU: activation output [M, N/2];  GLUB: the saved fc1 output [M, 2N] (read-only)
-  int64_t ldact;
-  const float* rcos;    // ROPE: fp32 [T, 32] tables
-  const float* rsin;
-  int T, rope_cols;
-  // SCORE: forward-only scoring head (see the SCORE epilogue in the kernel).  C is not written.
-  const int64_t* targets;  // [M]
-  float* part;             // [tiles_n][M] (max, sum-exp) pairs, one per row and tile column
-  float* xt;               // [M] the bf16-rounded target logit of every row whose target is a valid column
-};
+// (the epilogue operands: EpiArgs in gemm_launch.h)
 
 template <class F, int... U>
 __device__ __forceinline__ void nt_for_units(F& f, std::integer_sequence<int, U...>) {
@@ -870,25 +822,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(const uint16_t* __r
 // write (C = / += alpha*acc) themselves, the remaining tiles are split over K into dense fp32 blocks
 // ws[split * n_rem + r][256][256] that tn_grouped_reduce_kernel sums into C.  The more problems a launch carries, the smaller the
 // split remainder: one block (108 tiles) is all remainder (7 pieces per tile), twelve blocks (1296 tiles) leave 16 tiles to split.
-#define PLM_TN_GROUP_MAX 48
-// (kernel arguments: 48 problems x (operands + outputs) = 3.2 KB of the 4 KB kernarg segment)
-struct TnGroup {
-  const uint16_t* A[PLM_TN_GROUP_MAX];
-  const uint16_t* B[PLM_TN_GROUP_MAX];
-  int lda[PLM_TN_GROUP_MAX], ldb[PLM_TN_GROUP_MAX];
-  int M[PLM_TN_GROUP_MAX], N[PLM_TN_GROUP_MAX], tiles_n[PLM_TN_GROUP_MAX];
-  int tile_base[PLM_TN_GROUP_MAX + 1];  // first global tile of each problem; [count] = number of tiles
-  int count;
-  int n_full;  // tiles 0 .. n_full-1 take the whole contraction and write C directly (whole rounds of the persistent grid)
-  int splits;  // the remaining tiles are cut `splits` ways over K (L K-tiles each): items n_full + split * n_rem + r, split-major so
-  int L;       // that the workgroups of an XCD share a split's A / B panels in L2; pieces go to ws[split * n_rem + r][256][256]
-};
-struct TnGroupOut {
-  float* C[PLM_TN_GROUP_MAX];
-  const float* alpha[PLM_TN_GROUP_MAX];
-  int ldc[PLM_TN_GROUP_MAX];
-  int accumulate[PLM_TN_GROUP_MAX];
-};
+// (PLM_TN_GROUP_MAX and the kernel arguments TnGroup / TnGroupOut: gemm_plan.h, beside the plan that fills them)
 
 // v_mfma_f32_16x16x32_bf16 (see gemm_nt_big_kernel): a lane group of 16 reads K-chunk q = lane >> 4 of a 16-column block, so the
 // four groups of one transpose read touch k-rows 8 apart - the pair rotation takes bit 3 of the k-row as well as its low two bits.
@@ -1237,45 +1171,11 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_big_kernel(const uint16_t* __r
   }
 }
 
-// Plan for the big TN kernel: returns false when it should not be used.  rfull = tile rows done without split.
-bool plm_tn_big_plan(int64_t M, int64_t N, int64_t K, int* splits, int* rfull) {
-  if (g_num_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
-    g_num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  if (K % 64 != 0 || M < 256 || N < 256) return false;
-  const int64_t R = plm_cdiv(M, 256), Cn = plm_cdiv(N, 256), tiles = R * Cn;
-  const int64_t max_by_k = K / 512 > 0 ? K / 512 : 1;  // >= 8 K-tiles per item
-  const int64_t slots = persistent_slots();
-  int64_t rf = 0, s = 1;
-  if (tiles < slots) {
-    s = slots / tiles;
-  } else {
-    rf = ((tiles / slots) * slots) / Cn;
-    const int64_t rem = (R - rf) * Cn;
-    s = rem > 0 ? slots / rem : 1;
-  }
-  if (s > max_by_k) s = max_by_k;
-  if (s < 1) s = 1;
-  *splits = (int)s;
-  *rfull = (int)rf;
-  return true;
-}
-
-void plm_launch_gemm_tn_big(int splits, int rfull, int accumulate, const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb,
-                            float* C, int64_t ldc, float* slabs, int64_t M, int64_t N, int64_t K, const float* alpha_dev,
-                            hipStream_t s) {
-  const int tm = (int)plm_cdiv(M, 256), tn = (int)plm_cdiv(N, 256);
-  const int kchunk = (int)(plm_cdiv(plm_cdiv(K, splits), 64) * 64);
-  const int nitems = rfull * tn + (tm - rfull) * tn * splits;
-  const int slots = persistent_slots();
-  const dim3 grid(nitems < slots ? nitems : slots), block(512);
+void plm_launch_gemm_tn_persistent(const TnPlan& p, const GemmOperands& o, int accumulate, float* slabs, hipStream_t s) {
   // deep-prefetch ring + offset wave groups (see gemm_nt_big_kernel): each alone measured equal to the plain ring in the step, together
   // +0.8 % end to end (round 1, run 34)
-  hipLaunchKernelGGL((gemm_tn_big_kernel<false>), grid, block, 0, s, A, lda, B, ldb, C, ldc, slabs, (int)M, (int)N, (int)K, kchunk, splits,
-                     rfull, accumulate, alpha_dev, tm, tn, TnGroup{}, TnGroupOut{});
+  hipLaunchKernelGGL((gemm_tn_big_kernel<false>), dim3((unsigned)p.grid), dim3(512), 0, s, o.A, o.lda, o.B, o.ldb, (float*)o.C, o.ldc, slabs, (int)o.M, (int)o.N,
+                     (int)o.K, p.kchunk, p.splits, p.rfull, accumulate, o.alpha_dev, p.tm, p.tn, TnGroup{}, TnGroupOut{});
 }
 
 // ---- grouped TN (dW of one transformer block in one stream-K launch) ----------------------------------------------
@@ -1313,100 +1213,12 @@ __global__ __launch_bounds__(256) void tn_grouped_reduce_kernel(const float* __r
   }
 }
 
-static bool tn_group_plan(const int64_t* Ms, const int64_t* Ns, int count, int64_t K, TnGroup* g, int* nslabs) {
-  if (g_num_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
-    g_num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  if (count < 1 || count > PLM_TN_GROUP_MAX || K % 64 != 0 || K < 64) return false;
-  int base = 0;
-  for (int p = 0; p < count; ++p) {
-    if (Ms[p] < 8 || Ns[p] < 8 || Ms[p] % 8 != 0 || Ns[p] % 8 != 0) return false;
-    g->M[p] = (int)Ms[p];
-    g->N[p] = (int)Ns[p];
-    g->tiles_n[p] = (int)plm_cdiv(Ns[p], 256);
-    g->tile_base[p] = base;
-    base += (int)(plm_cdiv(Ms[p], 256) * plm_cdiv(Ns[p], 256));
-  }
-  g->tile_base[count] = base;
-  g->count = count;
-  const int64_t nkt = K / 64;
-  const int slots = persistent_slots();
-  // whole-K tiles for the full rounds; the remainder is split over K with the count that fills its rounds best (>= 8 K-tiles per
-  // piece, mild bias against slab traffic).  Fewer than `slots` tiles: everything is remainder (plain split-K).
-  const int nfull = (base / slots) * slots, nrem = base - nfull;
-  int best = 1;
-  if (nrem > 0) {
-    double best_cost = 1e30;
-    for (int sp = 1; sp <= 32 && (sp == 1 || nkt / sp >= 8); ++sp) {
-      const int64_t L = plm_cdiv(nkt, sp);
-      const int64_t rounds = plm_cdiv((int64_t)sp * nrem, slots);
-      const double cost = (double)(rounds * L) * (1.0 + 0.01 * (sp - 1));  // K-tiles of wall time for the remainder
-      if (cost < best_cost - 1e-9) {
-        best_cost = cost;
-        best = sp;
-      }
-    }
-  }
-  g->n_full = nfull;
-  g->splits = nrem > 0 ? best : 0;
-  g->L = (int)plm_cdiv(nkt, best);
-  *nslabs = nrem > 0 ? best * nrem : 0;  // dense 256x256 fp32 blocks
-  return (int64_t)base * nkt < (1ll << 30);
-}
-
-extern "C" size_t plm_gemm_tn_grouped_workspace_bytes(const int64_t* Ms, const int64_t* Ns, int count, int64_t K) {
-  TnGroup g{};
-  int ns = 0;
-  if (!Ms || !Ns || !tn_group_plan(Ms, Ns, count, K, &g, &ns)) return 0;
-  return (size_t)ns * 65536 * sizeof(float) + 16;  // never zero: 0 means "unsupported shapes"
-}
-
-extern "C" int plm_gemm_bf16_tn_grouped(const plm_tn_problem* probs, int count, int64_t K, void* workspace, size_t workspace_bytes,
-                                        void* stream) {
-  PLM_REQUIRE(probs && workspace, "plm_gemm_bf16_tn_grouped: null pointer");
-  PLM_REQUIRE(count >= 1 && count <= PLM_TN_GROUP_MAX, "plm_gemm_bf16_tn_grouped: count=%d must be 1..%d", count, PLM_TN_GROUP_MAX);
-  int64_t Ms[PLM_TN_GROUP_MAX], Ns[PLM_TN_GROUP_MAX];
-  TnGroup g{};
-  TnGroupOut o{};
-  for (int p = 0; p < count; ++p) {
-    const plm_tn_problem& q = probs[p];
-    PLM_REQUIRE(q.A && q.B && q.C, "plm_gemm_bf16_tn_grouped: null pointer in problem %d", p);
-    PLM_REQUIRE(q.M % 8 == 0 && q.N % 8 == 0 && q.lda % 8 == 0 && q.ldb % 8 == 0 && q.ldc % 4 == 0 && q.lda >= q.M && q.ldb >= q.N && q.ldc >= q.N,
-                "plm_gemm_bf16_tn_grouped: problem %d: M, N, lda, ldb must be multiples of 8, ldc of 4", p);
-    PLM_REQUIRE(q.lda < (1ll << 31) && q.ldb < (1ll << 31) && q.ldc < (1ll << 31), "plm_gemm_bf16_tn_grouped: problem %d: row strides must fit 31 bits", p);
-    PLM_REQUIRE(((reinterpret_cast<uintptr_t>(q.A) | reinterpret_cast<uintptr_t>(q.B) | reinterpret_cast<uintptr_t>(q.C)) & 15) == 0,
-                "plm_gemm_bf16_tn_grouped: problem %d: base pointers must be 16-byte aligned", p);
-    Ms[p] = q.M;
-    Ns[p] = q.N;
-    g.A[p] = q.A;
-    g.B[p] = q.B;
-    g.lda[p] = (int)q.lda;
-    g.ldb[p] = (int)q.ldb;
-    o.C[p] = q.C;
-    o.ldc[p] = (int)q.ldc;
-    o.alpha[p] = q.alpha_dev;
-    o.accumulate[p] = q.accumulate;
-  }
-  int ns = 0;
-  PLM_REQUIRE(tn_group_plan(Ms, Ns, count, K, &g, &ns), "plm_gemm_bf16_tn_grouped: unsupported shapes (K %% 64 == 0, M, N multiples of 8)");
-  const size_t need = (size_t)ns * 65536 * sizeof(float);
-  if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
-    plm_set_error("plm_gemm_bf16_tn_grouped: workspace of %zu bytes (16-byte aligned) required, %zu given", need, workspace_bytes);
-    return PLM_E_WORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const int nrem = g.tile_base[count] - g.n_full;
+void plm_launch_gemm_tn_grouped(const TnGroup& g, const TnGroupOut& out, int64_t K, float* ws, int slots, hipStream_t s) {
+  const int nrem = g.tile_base[g.count] - g.n_full;
   const int64_t nitems = g.n_full + (int64_t)nrem * g.splits;
-  const int slots = persistent_slots();
   hipLaunchKernelGGL((gemm_tn_big_kernel<true>), dim3((unsigned)(nitems < slots ? nitems : slots)), dim3(512), 0, s, nullptr, 0, nullptr, 0,
-                     nullptr, 0, (float*)workspace, 0, 0, (int)K, 0, 1, 0, 0, nullptr, 0, 0, g, o);
-  if (nrem > 0)
-    hipLaunchKernelGGL(tn_grouped_reduce_kernel, dim3((unsigned)(nrem * 16)), dim3(256), 0, s, (const float*)workspace, g, o);
-  PLM_CHECK_LAUNCH("plm_gemm_bf16_tn_grouped");
-  return PLM_OK;
+                     nullptr, 0, ws, 0, 0, (int)K, 0, 1, 0, 0, nullptr, 0, 0, g, out);
+  if (nrem > 0) hipLaunchKernelGGL(tn_grouped_reduce_kernel, dim3((unsigned)(nrem * 16)), dim3(256), 0, s, (const float*)ws, g, out);
 }
 
 // C[row0 + r][c] = bf16(alpha * sum of the pieces of (r, c)'s tile) for the stream-K rows of a hybrid NT GEMM.
@@ -1436,259 +1248,51 @@ __global__ __launch_bounds__(256) void nt_streamk_reduce_kernel(const float* __r
   }
 }
 
-// Tile shapes of the persistent NT kernel and the automatic policy that picks one per launch: round efficiency of the tile count on the
-// persistent grid x the useful fraction of the (ragged) edge tiles x a measured per-tile rate relative to 256x256.  256x192 has 22 % fewer
-// LDS-DMA bytes and 17 % fewer LDS reads per MFMA than 256x128, and N = 768 is four 192-column tiles = exactly two rounds at M = 32768;
-// 256x256 at 0.90 round efficiency beats 256x128 at 1.0 on the qkv shape.  128x192 (round 5; 8 waves of 32x96) is the shape of the
-// short batches: M = 8192 (the reference's document-mask config, config_doc_mask.yaml:35) makes N = 768 exactly ONE round of 256 tiles
-// and N = 2304 exactly three, where every 256-row tile leaves 25-62 % of the chip idle.
-// Rates fitted on gpurun_out/r05b kbench --variants tables at M = 8192 / 16384 / 32768 (profiles/r05_kbench_variants.txt).
-// Order = preference on ties (the first strictly greater wins).
-struct NtTileShape {
-  int bm, bn;
-  double rate;
-};
-static const NtTileShape kNtTiles[4] = {{256, 256, 1.0}, {256, 128, 0.88}, {256, 192, 0.94}, {128, 192, 0.72}};
-static const int kNtTileVariant[4] = {4, 6, 5, 7};  // the explicit variant number of each (plm_gemm_bf16_nt_ex)
-static double nt_tile_eff(int i, int64_t M, int64_t N, int slots) {
-  const NtTileShape& t = kNtTiles[i];
-  const int64_t tm = plm_cdiv(M, t.bm), tn = plm_cdiv(N, t.bn);
-  return round_efficiency(tm * tn, slots) * ((double)N / (double)(tn * t.bn)) * ((double)M / (double)(tm * t.bm)) * t.rate;
+// One dispatcher from a persistent NtPlan to a kernel instantiation: the tile switch exists here and nowhere else.  GLU / GLUB exist for
+// the 256x256 tile only (nt_plan gives them no other), the stream-K schedule (HYB) for the plain epilogue on that tile.
+template <NtEpilogue EPI, bool HYB, int BM, int BN, int WM, int WN>
+static void nt_launch_tile(const NtPlan& p, const GemmOperands& o, float* slabs, const EpiArgs& ea, hipStream_t s) {
+  hipLaunchKernelGGL((gemm_nt_big_kernel<BM, BN, WM, WN, HYB, EPI == NT_EPI_GLU, EPI == NT_EPI_GLUB, EPI == NT_EPI_ROPE, EPI == NT_EPI_SCORE>),
+                     dim3((unsigned)p.grid), dim3(512), 0, s, o.A, o.lda, o.B, o.ldb, (uint16_t*)o.C, o.ldc, (int)o.M, (int)o.N, (int)o.K, o.alpha_dev, p.tm,
+                     p.tn, HybridArgs{p.rfull, p.nchunks, p.L, slabs}, ea);
 }
-// index into kNtTiles of the best shape, its efficiency in *eff
-static int nt_pick_tile(int64_t M, int64_t N, int slots, double* eff) {
-  int best = 0;
-  double be = -1.0;
-  for (int i = 0; i < 4; ++i) {
-    const double e = nt_tile_eff(i, M, N, slots);
-    if (e > be) {
-      be = e;
-      best = i;
+
+template <NtEpilogue EPI>
+static void nt_launch(const NtPlan& p, const GemmOperands& o, float* slabs, const EpiArgs& ea, hipStream_t s) {
+  if constexpr (EPI == NT_EPI_NONE) {
+    if (p.kernel == NT_HYBRID) {
+      nt_launch_tile<EPI, true, 256, 256, 2, 4>(p, o, slabs, ea, s);
+      const int64_t rem_rows = o.M - (int64_t)p.rfull * 256;
+      const int64_t nv = rem_rows * (o.N / 8);
+      int64_t rb = plm_cdiv(nv, 256);
+      if (rb > 4096) rb = 4096;
+      hipLaunchKernelGGL(nt_streamk_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, s, (const float*)slabs,
+                         (uint16_t*)o.C + (int64_t)p.rfull * 256 * o.ldc, o.ldc, (int)rem_rows, (int)o.N, p.tn, (int)(o.K / 64), p.L, p.nchunks, o.alpha_dev);
+      return;
     }
   }
-  *eff = be;
-  return best;
-}
-// the hardware-scheduled 128x128 LDS-DMA kernel of gemm.hip (two 4-wave workgroups per CU, ~0.8 of the persistent 256x256 per-tile rate)
-// on the same scale: what the persistent kernels have to beat
-static double nt_dma128_eff(int64_t M, int64_t N, int slots) {
-  const int64_t tm = plm_cdiv(M, 128), tn = plm_cdiv(N, 128);
-  return round_efficiency(tm * tn, 2 * slots) * ((double)N / (double)(tn * 128)) * ((double)M / (double)(tm * 128)) * 0.80;
-}
-
-// Hybrid plan for the 256x256 NT kernel: whole-K tiles for the full rounds, stream-K over the remaining tile rows.
-// Returns false when the plain schedules are at least as good (or the shape does not qualify).
-struct NtHybridPlan {
-  int rfull, nchunks, L, nslabs;
-};
-bool plm_nt_hybrid_plan(int64_t M, int64_t N, int64_t K, NtHybridPlan* p) {
-  if (g_num_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
-    g_num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  if (p.tile == 0) nt_launch_tile<EPI, false, 256, 256, 2, 4>(p, o, nullptr, ea, s);
+  if constexpr (EPI != NT_EPI_GLU && EPI != NT_EPI_GLUB) {
+    if (p.tile == 1) nt_launch_tile<EPI, false, 256, 128, 4, 2>(p, o, nullptr, ea, s);
+    else if (p.tile == 2) nt_launch_tile<EPI, false, 256, 192, 4, 2>(p, o, nullptr, ea, s);
+    else if (p.tile == 3) nt_launch_tile<EPI, false, 128, 192, 4, 2>(p, o, nullptr, ea, s);
   }
-  if (plm_env().nt_no_hybrid) return false;
-  const bool mk = plm_env().nt_hybrid_min_k >= 0;  // tests / A-B runs lower the thresholds
-  // measured (profiles/r01_kbench_run18*): the fp32 slab traffic (~40 us) only pays off for long K.  Round 3 lowered the threshold to 2048
-  // while CUs are reserved for RCCL because the plain alternative was then the 128x128 kernel (the 0.85 cliff); with the shared tile policy
-  // the alternative is the persistent 256x256 kernel on two ragged rounds, which beats the hybrid at K = 2048 ... 4096 under an 8- and a
-  // 16-CU reserve (profiles/r05_kbench_variants.txt: fc2 fwd 97 vs 115 us, dX qkv 108 vs 134, dX fc1 187 vs 197) - only lm_head's dX
-  // (K = 50304) still gains (2004 vs 2089 us under 16 reserved CUs)
-  const int64_t min_k = mk ? plm_env().nt_hybrid_min_k : 8192, min_l = mk ? 2 : 8;
-  if (K % 64 != 0 || N % 8 != 0 || M < 2048 || N < 256 || K < min_k) return false;
-  const int slots = persistent_slots();
-  const int64_t R = plm_cdiv(M, 256), Cn = plm_cdiv(N, 256), tiles = R * Cn, nkt = K / 64;
-  if (tiles <= slots) return false;                          // single partial round: nothing to balance
-  if (round_efficiency(tiles, slots) >= 0.9) return false;  // plain 256x256 is already well packed
-  // ... or a narrower plain tile is (lm_head dX on the whole chip: 4 x 192 columns = exactly two rounds; in the step that beats the
-  // hybrid's slab traffic by 0.5 % end to end, round 2).  The same per-tile rates as the automatic policy below.
-  double e_plain;
-  nt_pick_tile(M, N, slots, &e_plain);
-  if (!mk && e_plain >= 0.9) return false;
-  const int64_t rf = ((tiles / slots) * slots) / Cn;        // whole tile rows inside the full rounds
-  const int64_t rem = (R - rf) * Cn;
-  if (rem <= 0 || rf <= 0) return false;
-  const int64_t total = rem * nkt;
-  const int64_t L = plm_cdiv(total, slots);
-  if (L < min_l || L * 10 > nkt * 9) return false;  // too short to amortise a prologue / no round saved
-  p->rfull = (int)rf;
-  p->L = (int)L;
-  p->nchunks = (int)plm_cdiv(total, L);
-  p->nslabs = (int)((nkt - 1) / L + 2);
-  return true;
 }
 
-extern "C" size_t plm_gemm_nt_workspace_bytes(int64_t M, int64_t N, int64_t K) {
-  NtHybridPlan p;
-  if (M <= 0 || N <= 0 || K <= 0 || !plm_nt_hybrid_plan(M, N, K, &p)) return 0;
-  return (size_t)p.nslabs * (size_t)(M - (int64_t)p.rfull * 256) * (size_t)N * sizeof(float);
-}
-
-// 16-byte alignment of every pointer a fused launch touches with 16-byte vector accesses (LDS-DMA sources, row stores, the saved fc1 output,
-// the RoPE tables): a caller of the C ABI with a misaligned view gets the two-launch fallback (whose GEMM checks its own operands), not a
-// misaligned global_load_lds_dwordx4
-static bool aligned16(std::initializer_list<const void*> ptrs) {
-  uintptr_t v = 0;
-  for (const void* p : ptrs) v |= reinterpret_cast<uintptr_t>(p);
-  return (v & 15) == 0;
-}
-
-// fc1 + SwiGLU in one launch (see GLU above).  Returns false when the shape does not qualify (the caller then runs the GEMM and
-// plm_swiglu_fwd separately - same bits).
-bool plm_launch_gemm_nt_glu(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, uint16_t* C, int64_t ldc, uint16_t* act,
-                            int64_t ldact, int64_t M, int64_t N, int64_t K, hipStream_t s) {
-  if (g_num_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
-    g_num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+void plm_launch_gemm_nt_persistent(const NtPlan& p, NtEpilogue epilogue, const GemmOperands& o, float* slabs, const EpiArgs& ea, hipStream_t s) {
+  switch (epilogue) {
+    case NT_EPI_NONE: return nt_launch<NT_EPI_NONE>(p, o, slabs, ea, s);
+    case NT_EPI_ROPE: return nt_launch<NT_EPI_ROPE>(p, o, slabs, ea, s);
+    case NT_EPI_GLU: return nt_launch<NT_EPI_GLU>(p, o, slabs, ea, s);
+    case NT_EPI_GLUB: return nt_launch<NT_EPI_GLUB>(p, o, slabs, ea, s);
+    case NT_EPI_SCORE: return nt_launch<NT_EPI_SCORE>(p, o, slabs, ea, s);
   }
-  if (K % 64 != 0 || N % 256 != 0 || M < 512 || lda % 8 != 0 || ldb % 8 != 0 || ldc % 8 != 0 || ldact % 8 != 0) return false;
-  if (!aligned16({A, B, C, act})) return false;
-  const int tm = (int)plm_cdiv(M, 256), tn = (int)(N / 256);
-  const int slots = persistent_slots();
-  const int nt_ = tm * tn;
-  const HybridArgs hyb{tm, 0, 1, nullptr};
-  hipLaunchKernelGGL((gemm_nt_big_kernel<256, 256, 2, 4, false, true>), dim3(nt_ < slots ? nt_ : slots), dim3(512), 0, s, A, lda, B, ldb, C, ldc,
-                     (int)M, (int)N, (int)K, nullptr, tm, tn, hyb, EpiArgs{act, ldact, nullptr, nullptr, 0, 0});
-  return true;
-}
-
-// dX of fc2 + SwiGLU backward in one launch (see GLUB above): DU[M, 2h] from dY[M, K] , W2^T[h, K] and the saved fc1 output U[M, 2h].
-bool plm_launch_gemm_nt_glub(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, const uint16_t* U, int64_t ldu, uint16_t* DU,
-                             int64_t lddu, int64_t M, int64_t h, int64_t K, hipStream_t s) {
-  if (g_num_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
-    g_num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  if (K % 64 != 0 || h % 256 != 0 || M < 512 || lda % 8 != 0 || ldb % 8 != 0 || ldu % 4 != 0 || lddu % 8 != 0) return false;
-  if (!aligned16({A, B, DU}) || (reinterpret_cast<uintptr_t>(U) & 7) != 0) return false;  // U is read in 8-byte pieces
-  const int tm = (int)plm_cdiv(M, 256), tn = (int)(h / 256);
-  const int slots = persistent_slots();
-  const int nt_ = tm * tn;
-  const HybridArgs hyb{tm, 0, 1, nullptr};
-  hipLaunchKernelGGL((gemm_nt_big_kernel<256, 256, 2, 4, false, false, true>), dim3(nt_ < slots ? nt_ : slots), dim3(512), 0, s, A, lda, B, ldb, DU,
-                     lddu, (int)M, (int)h, (int)K, nullptr, tm, tn, hyb, EpiArgs{const_cast<uint16_t*>(U), ldu, nullptr, nullptr, 0, 0});
-  return true;
-}
-
-// w_qkv projection with RoPE in the epilogue (see ROPE above): the automatic tile policy of plm_launch_gemm_nt_big, no hybrid.
-bool plm_launch_gemm_nt_rope(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, uint16_t* C, int64_t ldc, int64_t M, int64_t N,
-                             int64_t K, const float* rcos, const float* rsin, int64_t T, int64_t rope_cols, hipStream_t s) {
-  if (g_num_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
-    g_num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  if (K % 64 != 0 || N % 8 != 0 || M < 512 || N < 128 || lda % 8 != 0 || ldb % 8 != 0 || ldc % 8 != 0) return false;
-  if (!aligned16({A, B, C, rcos, rsin})) return false;
-  const int slots = persistent_slots();
-  double eff;
-  const int which = nt_pick_tile(M, N, slots, &eff);
-  // badly quantised on every tile shape (odd CU reserves): the caller takes the plain GEMM (which may prefer the 128x128 kernel) + the rope pass
-  if (eff < nt_dma128_eff(M, N, slots)) return false;
-  const int tm = (int)plm_cdiv(M, kNtTiles[which].bm), tn_ = (int)plm_cdiv(N, kNtTiles[which].bn);
-  const int nt_ = tm * tn_;
-  const dim3 g(nt_ < slots ? nt_ : slots), block(512);
-  const HybridArgs hyb{tm, 0, 1, nullptr};
-  const EpiArgs ea{nullptr, 0, rcos, rsin, (int)T, (int)rope_cols};
-  if (which == 0)
-    hipLaunchKernelGGL((gemm_nt_big_kernel<256, 256, 2, 4, false, false, false, true>), g, block, 0, s, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K,
-                       nullptr, tm, tn_, hyb, ea);
-  else if (which == 1)
-    hipLaunchKernelGGL((gemm_nt_big_kernel<256, 128, 4, 2, false, false, false, true>), g, block, 0, s, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K,
-                       nullptr, tm, tn_, hyb, ea);
-  else if (which == 2)
-    hipLaunchKernelGGL((gemm_nt_big_kernel<256, 192, 4, 2, false, false, false, true>), g, block, 0, s, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K,
-                       nullptr, tm, tn_, hyb, ea);
-  else
-    hipLaunchKernelGGL((gemm_nt_big_kernel<128, 192, 4, 2, false, false, false, true>), g, block, 0, s, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K,
-                       nullptr, tm, tn_, hyb, ea);
-  return true;
-}
-
-// Host-side launcher used by plm_gemm_bf16_nt (gemm.hip). Returns false when no big-tile variant fits.
-
-// variant: 0 automatic | 4 / 5 / 6 / 7 the persistent kernel on 256x256 / 256x192 / 256x128 / 128x192 tiles (what the automatic policy picks
-// from; explicit numbers exist for the tests and tools/kbench.py) | 3 = 4.
-// Returns false when the shape is better served by the 128x128 kernels of gemm.hip.
-bool plm_launch_gemm_nt_big(int variant, const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, uint16_t* C, int64_t ldc,
-                            int64_t M, int64_t N, int64_t K, const float* alpha_dev, void* workspace, size_t workspace_bytes,
-                            hipStream_t s) {
-  if (!ensure_num_cus()) return false;
-  const int slots = persistent_slots();
-  const dim3 block(512);
-  // long K with a badly quantised tile count (lm_head dX: 384 tiles on 256 CUs): whole-K tiles for the full rounds + stream-K
-  // over the remaining tile rows, on the staggered schedule (needs the caller's fp32 workspace)
-  if (variant == 0 && workspace) {
-    NtHybridPlan p;
-    if (plm_nt_hybrid_plan(M, N, K, &p)) {
-      const int tm = (int)plm_cdiv(M, 256), tn256 = (int)plm_cdiv(N, 256);
-      const int64_t rem_rows = M - (int64_t)p.rfull * 256;
-      const size_t need = (size_t)p.nslabs * (size_t)rem_rows * (size_t)N * sizeof(float);
-      if (workspace_bytes >= need) {
-        const HybridArgs h{p.rfull, p.nchunks, p.L, (float*)workspace};
-        const int nitems = p.rfull * tn256 + p.nchunks;
-        const dim3 g2(nitems < slots ? nitems : slots);
-        hipLaunchKernelGGL((gemm_nt_big_kernel<256, 256, 2, 4, true>), g2, block, 0, s, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, alpha_dev,
-                           tm, tn256, h, EpiArgs{});
-        const int64_t nv = rem_rows * (N / 8);
-        int64_t rb = plm_cdiv(nv, 256);
-        if (rb > 4096) rb = 4096;
-        hipLaunchKernelGGL(nt_streamk_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, s, (const float*)workspace,
-                           C + (int64_t)p.rfull * 256 * ldc, ldc, (int)rem_rows, (int)N, tn256, (int)(K / 64), p.L, p.nchunks, alpha_dev);
-        return true;
-      }
-    }
-  }
-  // one schedule (deep-prefetch 4-phase ring with offset wave groups), four tile shapes; variant 3 is kept as an alias of 4
-  int which = 0;
-  if (variant == 0) {
-    double eff;
-    which = nt_pick_tile(M, N, slots, &eff);
-    // when every persistent shape quantises badly (e.g. odd slot counts while CUs are reserved for RCCL) the hardware-scheduled 128x128
-    // LDS-DMA kernel is the better choice
-    if (M < 512 || N < 128 || eff < nt_dma128_eff(M, N, slots)) return false;
-  } else {
-    for (int i = 0; i < 4; ++i)
-      if (kNtTileVariant[i] == (variant == 3 ? 4 : variant)) which = i;
-  }
-  const int tm = (int)plm_cdiv(M, kNtTiles[which].bm), tn_ = (int)plm_cdiv(N, kNtTiles[which].bn);
-  const int nt_ = tm * tn_;
-  const dim3 g(nt_ < slots ? nt_ : slots);
-  const HybridArgs hyb{tm, 0, 1, nullptr};  // plain schedule
-  if (which == 0)
-    hipLaunchKernelGGL((gemm_nt_big_kernel<256, 256, 2, 4>), g, block, 0, s, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, alpha_dev, tm, tn_, hyb, EpiArgs{});
-  else if (which == 1)
-    hipLaunchKernelGGL((gemm_nt_big_kernel<256, 128, 4, 2>), g, block, 0, s, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, alpha_dev, tm, tn_, hyb, EpiArgs{});
-  else if (which == 2)
-    hipLaunchKernelGGL((gemm_nt_big_kernel<256, 192, 4, 2>), g, block, 0, s, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, alpha_dev, tm, tn_, hyb, EpiArgs{});
-  else
-    hipLaunchKernelGGL((gemm_nt_big_kernel<128, 192, 4, 2>), g, block, 0, s, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, alpha_dev, tm, tn_, hyb, EpiArgs{});
-  return true;
 }
 
 // =============================================================================================
 // Forward-only scoring head:  nll[M], lse[M] of  softmax(bf16(Y W^T))  without the [M, V] logits
 // =============================================================================================
-// Workspace: xt fp32[M] | then EITHER the row partials [ceil(V / BN)][M] (max, sum-exp) of the persistent kernel OR the logits of
-// PLM_HS_CHUNK rows (shapes the automatic policy of plm_gemm_bf16_nt gives to a 128x128 kernel: M < 512, V % 8 != 0, badly quantised
-// grids).  The query does not know the device, so it sizes the partials for the narrowest tile (BN = 128).
-#define PLM_HS_CHUNK 256
-static size_t hs_align(size_t n) { return (n + 255) & ~(size_t)255; }
-static size_t hs_xt_bytes(int64_t M) { return hs_align((size_t)M * sizeof(float)); }
-
-extern "C" size_t plm_head_score_workspace_bytes(int64_t M, int64_t V, int64_t K) {
-  if (M <= 0 || V <= 0 || K <= 0) return 0;
-  const size_t part = (size_t)M * (size_t)plm_cdiv(V, 128) * 2 * sizeof(float);
-  const size_t chunk = (size_t)PLM_HS_CHUNK * (size_t)(plm_cdiv(V, 8) * 8) * sizeof(uint16_t);
-  return hs_xt_bytes(M) + hs_align(part > chunk ? part : chunk);
-}
-
+// (entry point, workspace layout and the choice between the two kernels below: plm_head_score_bf16 in gemm_api.hip)
 // lse / nll of 32 rows per workgroup from their tile-column partials: thread (r = t & 31, slice = t >> 5) walks every 8th partial of
 // row r (a wave reads 2 x 256 contiguous bytes per step), the 8 slices of a row meet in LDS.  Fixed order: deterministic.
 __global__ __launch_bounds__(256) void head_score_combine_kernel(const float* __restrict__ part, const float* __restrict__ xt,
@@ -1753,70 +1357,12 @@ __global__ __launch_bounds__(256) void head_score_rows_kernel(const uint16_t* __
   nll[blockIdx.x] = (tg >= 0 && tg < V) ? lse - bf2f(lr[tg]) : 0.f;
   if (lse_out) lse_out[blockIdx.x] = lse;
 }
+void plm_launch_head_score_combine(const float* part, const float* xt, const int64_t* targets, float* nll, float* lse, int64_t M, int64_t V, int ntc,
+                                   hipStream_t s) {
+  hipLaunchKernelGGL(head_score_combine_kernel, dim3((unsigned)plm_cdiv(M, 32)), dim3(256), 0, s, part, xt, targets, nll, lse, (int)M, (int)V, ntc);
+}
 
-extern "C" int plm_gemm_bf16_nt_ws(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, void* C, int64_t ldc, int64_t M,
-                                   int64_t N, int64_t K, int c_dtype, int accumulate, const float* alpha_dev, int variant,
-                                   void* workspace, size_t workspace_bytes, void* stream);
-
-extern "C" int plm_head_score_bf16(const uint16_t* Y, int64_t ldy, const uint16_t* W, int64_t ldw, const int64_t* targets, float* nll,
-                                   float* lse, int64_t M, int64_t V, int64_t K, void* workspace, size_t workspace_bytes, void* stream) {
-  PLM_REQUIRE(Y && W && targets && nll && workspace, "plm_head_score_bf16: null pointer");
-  PLM_REQUIRE(M > 0 && V > 0 && K > 0 && M < (1 << 30) && V < (1 << 30) && K < (1 << 30), "plm_head_score_bf16: bad shape M=%ld V=%ld K=%ld",
-              (long)M, (long)V, (long)K);
-  PLM_REQUIRE(K % 64 == 0, "plm_head_score_bf16: K %% 64 == 0 required (K=%ld)", (long)K);
-  PLM_REQUIRE(ldy % 8 == 0 && ldw % 8 == 0 && ldy >= K && ldw >= K, "plm_head_score_bf16: row strides must be multiples of 8 and >= K (ldy=%ld ldw=%ld)",
-              (long)ldy, (long)ldw);
-  PLM_REQUIRE(aligned16({Y, W, workspace}) && ((reinterpret_cast<uintptr_t>(nll) | reinterpret_cast<uintptr_t>(lse)) & 3) == 0 &&
-                  (reinterpret_cast<uintptr_t>(targets) & 7) == 0,
-              "plm_head_score_bf16: Y, W and the workspace must be 16-byte aligned, targets 8-byte, nll / lse 4-byte");
-  const size_t need = plm_head_score_workspace_bytes(M, V, K);
-  if (workspace_bytes < need) {
-    plm_set_error("plm_head_score_bf16: workspace of %zu bytes required, %zu given", need, workspace_bytes);
-    return PLM_E_WORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  float* xt = (float*)workspace;
-  char* rest = (char*)workspace + hs_xt_bytes(M);
-  // the tile shape plm_gemm_bf16_nt picks for this shape (no workspace: its stream-K hybrid is for K >= 8192), so that the accumulators
-  // are the ones the training head rounds to bf16
-  int which = -1;
-  if (!plm_env().gemm_v1 && V % 8 == 0 && M >= 512 && V >= 128 && ensure_num_cus()) {
-    const int slots = persistent_slots();
-    double eff;
-    const int w = nt_pick_tile(M, V, slots, &eff);
-    if (eff >= nt_dma128_eff(M, V, slots)) which = w;
-  }
-  if (which >= 0) {
-    const int slots = persistent_slots();
-    const int tm = (int)plm_cdiv(M, kNtTiles[which].bm), tn_ = (int)plm_cdiv(V, kNtTiles[which].bn);
-    const int nt_ = tm * tn_;
-    const dim3 g(nt_ < slots ? nt_ : slots), block(512);
-    const HybridArgs hyb{tm, 0, 1, nullptr};
-    const EpiArgs ea{nullptr, 0, nullptr, nullptr, 0, 0, targets, (float*)rest, xt};
-#define PLM_HS_LAUNCH(BM_, BN_, WM_, WN_)                                                                                                  \
-  hipLaunchKernelGGL((gemm_nt_big_kernel<BM_, BN_, WM_, WN_, false, false, false, false, true>), g, block, 0, s, Y, ldy, W, ldw, nullptr, 0, \
-                     (int)M, (int)V, (int)K, nullptr, tm, tn_, hyb, ea)
-    if (which == 0) PLM_HS_LAUNCH(256, 256, 2, 4);
-    else if (which == 1) PLM_HS_LAUNCH(256, 128, 4, 2);
-    else if (which == 2) PLM_HS_LAUNCH(256, 192, 4, 2);
-    else PLM_HS_LAUNCH(128, 192, 4, 2);
-#undef PLM_HS_LAUNCH
-    hipLaunchKernelGGL(head_score_combine_kernel, dim3((unsigned)plm_cdiv(M, 32)), dim3(256), 0, s, (const float*)rest, (const float*)xt, targets,
-                       nll, lse, (int)M, (int)V, tn_);
-    PLM_CHECK_LAUNCH("plm_head_score_bf16");
-    return PLM_OK;
-  }
-  // shapes plm_gemm_bf16_nt serves with a 128x128 kernel: that kernel (named explicitly, so that a chunk of rows gets the accumulators the
-  // whole matrix would) into PLM_HS_CHUNK rows of logits, then the row kernel
-  const int64_t ld = plm_cdiv(V, 8) * 8;
-  const int variant = (!plm_env().gemm_v1 && V % 8 == 0) ? 2 : 1;
-  for (int64_t r0 = 0; r0 < M; r0 += PLM_HS_CHUNK) {
-    const int64_t rows = M - r0 < PLM_HS_CHUNK ? M - r0 : PLM_HS_CHUNK;
-    const int rc = plm_gemm_bf16_nt_ws(Y + r0 * ldy, ldy, W, ldw, rest, ld, rows, V, K, 0, 0, nullptr, variant, nullptr, 0, stream);
-    if (rc != PLM_OK) return rc;
-    hipLaunchKernelGGL(head_score_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, (const uint16_t*)rest, ld, targets + r0, nll + r0,
-                       lse ? lse + r0 : nullptr, (int)V);
-  }
-  PLM_CHECK_LAUNCH("plm_head_score_bf16");
-  return PLM_OK;
+void plm_launch_head_score_rows(const uint16_t* logits, int64_t ld, const int64_t* targets, float* nll, float* lse, int64_t rows, int64_t V,
+                                hipStream_t s) {
+  hipLaunchKernelGGL(head_score_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, logits, ld, targets, nll, lse, (int)V);
 }

@@ -454,7 +454,7 @@ def gemm_tn(A, B, out=None, accumulate=False, alpha=None):
   return out
 
 
-TN_GROUP_MAX = 48  # PLM_TN_GROUP_MAX of csrc/gemm_big.hip
+TN_GROUP_MAX = 48  # PLM_TN_GROUP_MAX of csrc/gemm_plan.h
 
 
 def gemm_tn_grouped(problems):

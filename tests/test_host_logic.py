@@ -412,6 +412,16 @@ def test_register_budget_of_the_attention_and_128x128_gemm_kernels():
   assert seen >= 22, seen
 
 
+def test_the_gemm_plan_header_is_host_only():
+  """csrc/gemm_plan.h is arithmetic on shapes: it compiles alone as plain C++17 - the project's compiler in C++ mode, which has no ROCm
+  include path - so nothing of HIP (and no kernel file's state) can leak into the launch plans."""
+  import subprocess
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  r = subprocess.run(['/opt/rocm/bin/hipcc', '-x', 'c++', '-std=c++17', '-fsyntax-only', os.path.join(root, 'plainlm_amd', 'csrc', 'gemm_plan.h')],
+                     capture_output=True, text=True, timeout=120)
+  assert r.returncode == 0, r.stderr[-2000:]
+
+
 
 def test_every_entry_point_refuses_null_pointers_without_a_gpu():
   """Error behaviour of the boundary (include/plainlm_hip.h): argument checks come before any HIP call, so they can be exercised here - every

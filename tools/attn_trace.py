@@ -28,7 +28,7 @@ def build():
   out = os.path.join(ROOT, 'tools', '_trace_build')
   os.makedirs(out, exist_ok=True)
   procs = []
-  for f in ('misc.hip', 'elementwise.hip', 'ce.hip', 'gemm.hip', 'gemm_big.hip', 'attn.hip', 'attn_causal.hip', 'attn_doc.hip'):
+  for f in ('misc.hip', 'elementwise.hip', 'ce.hip', 'gemm.hip', 'gemm_big.hip', 'gemm_api.hip', 'attn.hip', 'attn_causal.hip', 'attn_doc.hip'):
     o = os.path.join(out, f.replace('.hip', '.o'))
     objs.append(o)
     src = os.path.join(csrc, f)
