@@ -12,6 +12,7 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libplainlm_hip.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'plainlm_hip.h')
+EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'plainlm_hip_ext.h')
 
 _lib = None
 
@@ -133,11 +134,27 @@ SIGNATURES = {
 }
 
 
-def header_functions():
-  """Names of all functions declared in include/plainlm_hip.h."""
-  with open(HEADER_PATH) as f:
+# the same for include/plainlm_hip_ext.h (additions that do not move plm_version(); see that header for why it is a file of its own)
+EXT_SIGNATURES = {
+  'plm_head_predict_workspace_bytes': (_SZ, [_I64, _I64, _I64]),
+  'plm_head_predict_bf16': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
+}
+
+
+def _declared(path):
+  with open(path) as f:
     src = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
   return sorted(set(re.findall(r'\b(plm_[a-z0-9_]+)\s*\(', src)))
+
+
+def header_functions():
+  """Names of all functions declared in include/plainlm_hip.h."""
+  return _declared(HEADER_PATH)
+
+
+def ext_header_functions():
+  """Names of all functions declared in include/plainlm_hip_ext.h."""
+  return _declared(EXT_HEADER_PATH)
 
 
 def load():
@@ -152,6 +169,12 @@ def load():
   lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
   for name, (res, args) in SIGNATURES.items():
     fn = getattr(lib, name)  # AttributeError -> symbol missing, loud by construction
+    fn.restype = res
+    fn.argtypes = args
+  for name, (res, args) in EXT_SIGNATURES.items():
+    fn = getattr(lib, name, None)
+    if fn is None:  # the ABI number does not move for the ext header: a library from before it would pass the version check below
+      raise RuntimeError(f'{LIB_PATH} lacks {name} (include/plainlm_hip_ext.h): rebuild it (make -C plainlm_amd/csrc)')
     fn.restype = res
     fn.argtypes = args
   got = lib.plm_version()

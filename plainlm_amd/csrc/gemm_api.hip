@@ -3,6 +3,7 @@
 // file (gemm_launch.h): no kernel lives here, and no kernel file decides anything.
 #include <initializer_list>
 
+#include "../../include/plainlm_hip_ext.h"
 #include "gemm_launch.h"
 
 static int g_num_cus = 0;
@@ -327,5 +328,65 @@ extern "C" int plm_head_score_bf16(const uint16_t* Y, int64_t ldy, const uint16_
     plm_launch_head_score_rows((const uint16_t*)rest, ld, targets + r0, nll + r0, lse ? lse + r0 : nullptr, rows, V, s);
   }
   PLM_CHECK_LAUNCH("plm_head_score_bf16");
+  return PLM_OK;
+}
+
+// =============================================================================================
+// Prediction head (include/plainlm_hip_ext.h):  pred[M], logp[M], entropy[M] (and nll / lse as above) without the logits
+// =============================================================================================
+// Workspace: xt fp32[M] | then EITHER the 16-byte row records [ceil(V / BN)][M] of the persistent kernel's prediction mode OR the logits of
+// PLM_HS_CHUNK rows - plm_head_score_bf16's layout with records twice as large, sized for the narrowest tile (BN = 128) as well.
+extern "C" size_t plm_head_predict_workspace_bytes(int64_t M, int64_t V, int64_t K) {
+  if (M <= 0 || V <= 0 || K <= 0) return 0;
+  const size_t part = (size_t)M * (size_t)plm_cdiv(V, 128) * 4 * sizeof(float);
+  const size_t chunk = (size_t)PLM_HS_CHUNK * (size_t)(plm_cdiv(V, 8) * 8) * sizeof(uint16_t);
+  return hs_xt_bytes(M) + hs_align(part > chunk ? part : chunk);
+}
+
+extern "C" int plm_head_predict_bf16(const uint16_t* Y, int64_t ldy, const uint16_t* W, int64_t ldw, const int64_t* targets, int64_t* pred,
+                                     float* logp, float* entropy, float* nll, float* lse, int64_t M, int64_t V, int64_t K, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  PLM_REQUIRE(Y && W && pred && logp && workspace, "plm_head_predict_bf16: null pointer");
+  PLM_REQUIRE(targets || !nll, "plm_head_predict_bf16: null pointer (nll needs targets)");
+  PLM_REQUIRE(M > 0 && V > 0 && K > 0 && M < (1 << 30) && V < (1 << 30) && K < (1 << 30), "plm_head_predict_bf16: bad shape M=%ld V=%ld K=%ld",
+              (long)M, (long)V, (long)K);
+  PLM_REQUIRE(K % 64 == 0, "plm_head_predict_bf16: K %% 64 == 0 required (K=%ld)", (long)K);
+  PLM_REQUIRE(ldy % 8 == 0 && ldw % 8 == 0 && ldy >= K && ldw >= K, "plm_head_predict_bf16: row strides must be multiples of 8 and >= K (ldy=%ld ldw=%ld)",
+              (long)ldy, (long)ldw);
+  PLM_REQUIRE(aligned16({Y, W, workspace}) &&
+                  ((reinterpret_cast<uintptr_t>(logp) | reinterpret_cast<uintptr_t>(entropy) | reinterpret_cast<uintptr_t>(nll) |
+                    reinterpret_cast<uintptr_t>(lse)) & 3) == 0 &&
+                  ((reinterpret_cast<uintptr_t>(targets) | reinterpret_cast<uintptr_t>(pred)) & 7) == 0,
+              "plm_head_predict_bf16: Y, W and the workspace must be 16-byte aligned, targets / pred 8-byte, logp / entropy / nll / lse 4-byte");
+  const size_t need = plm_head_predict_workspace_bytes(M, V, K);
+  if (workspace_bytes < need) {
+    plm_set_error("plm_head_predict_bf16: workspace of %zu bytes required, %zu given", need, workspace_bytes);
+    return PLM_E_WORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  float* xt = (float*)workspace;
+  char* rest = (char*)workspace + hs_xt_bytes(M);
+  // the plan of plm_head_score_bf16 (= the one plm_gemm_bf16_nt makes for this shape): the same accumulators, hence the same bf16 logits
+  const int64_t ld = plm_cdiv(V, 8) * 8;
+  const int slots = persistent_slots();
+  if (slots == 0) return PLM_E_HIP;
+  const NtPlan p = nt_plan(M, V, K, ld, 0, 0, false, NT_EPI_SCORE, slots, plan_env());
+  const HeadPredictOut out{pred, logp, entropy, nll, lse};
+  if (p.ok) {
+    plm_launch_gemm_nt_persistent(p, NT_EPI_SCORE, GemmOperands{Y, ldy, W, ldw, nullptr, 0, M, V, K, nullptr}, nullptr,
+                                  EpiArgs{nullptr, 0, nullptr, nullptr, 0, 0, targets, nullptr, xt, (float*)rest}, s);
+    plm_launch_head_predict_combine((const float*)rest, xt, targets, out, M, V, p.tn, s);
+    PLM_CHECK_LAUNCH("plm_head_predict_bf16");
+    return PLM_OK;
+  }
+  const int variant = p.kernel == NT_DMA128 ? 2 : 1;
+  for (int64_t r0 = 0; r0 < M; r0 += PLM_HS_CHUNK) {
+    const int64_t rows = M - r0 < PLM_HS_CHUNK ? M - r0 : PLM_HS_CHUNK;
+    const int rc = plm_gemm_bf16_nt_ws(Y + r0 * ldy, ldy, W, ldw, rest, ld, rows, V, K, 0, 0, nullptr, variant, nullptr, 0, stream);
+    if (rc != PLM_OK) return rc;
+    const HeadPredictOut o{pred + r0, logp + r0, entropy ? entropy + r0 : nullptr, nll ? nll + r0 : nullptr, lse ? lse + r0 : nullptr};
+    plm_launch_head_predict_rows((const uint16_t*)rest, ld, targets ? targets + r0 : nullptr, o, rows, V, s);
+  }
+  PLM_CHECK_LAUNCH("plm_head_predict_bf16");
   return PLM_OK;
 }

@@ -176,6 +176,25 @@ static_assert(NtOvlPlan<1, 3, 2>::slot(1) == 4 && NtOvlPlan<1, 3, 2>::slot(0) ==
 // two buffers alternating by tile, ONE workgroup barrier per tile), and thread r of the workgroup combines row r's WN pairs and
 // writes part[tile column][row].  Columns >= N (the clamped duplicates of the ragged edge) are set to -inf first (a rounded -inf
 // is -inf and exp2 of it 0); rows >= M write nothing.  The lane that holds column targets[row] also writes that rounded logit to xt[row]: one writer per row, no atomics.
+// Prediction mode of SCORE (plm_head_predict_bf16; selected by a non-null ea.part4): next to (max, sum-exp) a row
+// carries u = sum e^(x - max) (x - max) and the column of its first maximum, 16 bytes per row in the wave scratch (a wave tile has at most
+// 128 rows: the 2048-byte half is exactly full) and in part4[tile column][row].  A lane finds the lowest of ITS columns that equals the
+// row's maximum after the two shuffles have made that maximum known (constants selected by compares: no per-column state), the four
+// lanes of a row take the minimum.  entropy = log s - u / s and log p(pred) = -log s come out of the combine kernel.
+// Two records meet as (m, s) always did; u is rescaled with them and the column follows the larger maximum, the lower one when equal.
+// An empty record (-inf, 0, 0, none) gives way to the other side: its differences are NaN or -inf and must not be multiplied.
+__device__ __forceinline__ float4 head_rec_combine(const float4 a, const float4 b) {
+  const float m = fmaxf(a.x, b.x);  // (m, s): ms_combine of ce.hip, the scoring mode's instructions
+  const float ea_ = __expf(a.x - m), eb_ = __expf(b.x - m);
+  const float sa = (a.x == -INFINITY) ? 0.f : a.y * ea_;
+  const float sb = (b.x == -INFINITY) ? 0.f : b.y * eb_;
+  const float ua = (a.x == -INFINITY) ? 0.f : ea_ * fmaf(a.y, a.x - m, a.z);
+  const float ub = (b.x == -INFINITY) ? 0.f : eb_ * fmaf(b.y, b.x - m, b.z);
+  const int ia = __float_as_int(a.w), ib = __float_as_int(b.w);
+  const int idx = b.x > a.x ? ib : (b.x == a.x ? min(ia, ib) : ia);  // a NaN maximum cannot occur (fmaxf drops NaN operands)
+  return make_float4(m, sa + sb, ua + ub, __int_as_float(idx));
+}
+
 template <int BM, int BN, int WM, int WN, bool HYB = false, bool GLU = false, bool GLUB = false, bool ROPE = false, bool SCORE = false>
 __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(const uint16_t* __restrict__ A, int64_t lda,
                                                              const uint16_t* __restrict__ B, int64_t ldb,
@@ -612,6 +631,67 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_big_kernel(const uint16_t* __r
 #pragma unroll
             for (int f = 0; f < 2 * NA; ++f) acc4[f][j][e] = keep ? acc4[f][j][e] : -INFINITY;
           }
+      }
+      if (ea.part4 != nullptr) {  // prediction mode (kernel argument: uniform), see above the kernel
+        constexpr int NOCOL = 0x7fffffff;
+        const bool has_tg = ea.targets != nullptr;
+#pragma unroll
+        for (int f = 0; f < 2 * NA; ++f) {
+          const int gm = m0 + wm * TM + f * 16 + l15;
+          const int64_t tg = has_tg ? ea.targets[min(gm, M - 1)] : (int64_t)-1;
+          const int tq = (tg >= (int64_t)cbase && tg < (int64_t)N) ? (int)(tg - cbase) - 4 * q : -1;
+          float x[2 * NBF][4];
+          float mx = -INFINITY, xsel = 0.f;
+#pragma unroll
+          for (int j = 0; j < 2 * NBF; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float v = bf2f(f2bf(acc4[f][j][e]));
+              xsel = (j * 16 + e == tq) ? v : xsel;
+              x[j][e] = v;
+              mx = fmaxf(mx, v);
+            }
+          if (tq >= 0 && tq < TN && (tq & 15) < 4 && gm < M) ea.xt[gm] = xsel;
+          mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+          mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+          const float mxl = mx == -INFINITY ? 0.f : mx * LOG2E;
+          // sum: the scoring mode's instructions in its order (lse keeps its bits).  u: a -inf logit (edge column) has p = 0 and
+          // x - mx = -inf, whose product is NaN: the difference is floored at a finite value first, so that it contributes p * d = -0
+          // (an all -inf wave tile: -inf - -inf = NaN, and fmaxf drops the NaN operand).  The first maximum: walked from the last
+          // column down, so the lowest column that equals the row's maximum stays; -inf is no maximum (NOCOL: the record is empty).
+          float sum = 0.f, u = 0.f;
+          int ix = NOCOL;
+#pragma unroll
+          for (int j = 0; j < 2 * NBF; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float pe = __builtin_amdgcn_exp2f(x[j][e] * LOG2E - mxl);
+              sum += pe;
+              u = fmaf(pe, fmaxf(x[j][e] - mx, -3.0e38f), u);
+            }
+#pragma unroll
+          for (int j = 2 * NBF - 1; j >= 0; --j)
+#pragma unroll
+            for (int e = 3; e >= 0; --e) ix = (x[j][e] == mx) ? j * 16 + e : ix;
+          ix = (ix == NOCOL || mx == -INFINITY) ? NOCOL : cbase + 4 * q + ix;  // absolute column; edge columns are -inf and never equal a finite mx
+          sum += __shfl_xor(sum, 16, 64);
+          sum += __shfl_xor(sum, 32, 64);
+          u += __shfl_xor(u, 16, 64);
+          u += __shfl_xor(u, 32, 64);
+          ix = min(ix, __shfl_xor(ix, 16, 64));
+          ix = min(ix, __shfl_xor(ix, 32, 64));
+          if (q == 0) *reinterpret_cast<float4*>(wsc + 4 * (f * 16 + l15)) = make_float4(mx, sum, u, __int_as_float(ix));
+        }
+        phase_barrier();
+        if (t < BM) {
+          const char* src = smem + 2 * STAGE + (t / TM) * WN * 4096 + score_buf * 2048 + (t % TM) * 16;
+          float4 a = *reinterpret_cast<const float4*>(src);
+#pragma unroll
+          for (int w = 1; w < WN; ++w) a = head_rec_combine(a, *reinterpret_cast<const float4*>(src + w * 4096));
+          if (m0 + t < M) *reinterpret_cast<float4*>(ea.part4 + 4 * ((int64_t)(n0 / BN) * M + m0 + t)) = a;
+        }
+        score_buf ^= 1;
+        continue;
       }
 #pragma unroll
       for (int f = 0; f < 2 * NA; ++f) {
@@ -1365,4 +1445,79 @@ void plm_launch_head_score_combine(const float* part, const float* xt, const int
 void plm_launch_head_score_rows(const uint16_t* logits, int64_t ld, const int64_t* targets, float* nll, float* lse, int64_t rows, int64_t V,
                                 hipStream_t s) {
   hipLaunchKernelGGL(head_score_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, logits, ld, targets, nll, lse, (int)V);
+}
+
+// =============================================================================================
+// Prediction head:  argmax, its log-probability and the entropy of  softmax(bf16(Y W^T))  without the [M, V] logits
+// =============================================================================================
+// (entry point and workspace layout: plm_head_predict_bf16 in gemm_api.hip; the record and its combine rule: head_rec_combine above)
+__device__ __forceinline__ void head_predict_store(const float4 rec, float xt, const int64_t* targets, const HeadPredictOut& out, int64_t row, int V) {
+  const float ls = __logf(rec.y);
+  const float lse = rec.x + ls;
+  const int idx = __float_as_int(rec.w);
+  out.pred[row] = (idx >= 0 && idx < V) ? idx : 0;  // a row without a maximum (all NaN or all -inf): still a valid token id
+  out.logp[row] = -ls;
+  if (out.entropy) out.entropy[row] = ls - rec.z / rec.y;
+  if (out.nll) {
+    const int64_t tg = targets[row];
+    out.nll[row] = (tg >= 0 && tg < V) ? lse - xt : 0.f;
+  }
+  if (out.lse) out.lse[row] = lse;
+}
+
+// head_score_combine_kernel's row / slice walk over 16-byte records: thread (r = t & 31, slice = t >> 5) walks every 8th record of row r,
+// the 8 slices of a row meet in LDS.  Fixed order (lower tile columns first): deterministic, and (m, s) see the scoring head's operations.
+__global__ __launch_bounds__(256) void head_predict_combine_kernel(const float* __restrict__ part4, const float* __restrict__ xt,
+                                                                   const int64_t* __restrict__ targets, HeadPredictOut out, int M, int V, int ntc) {
+  __shared__ float4 sh[8][32];
+  const int r = threadIdx.x & 31, sl = threadIdx.x >> 5;
+  const int row = blockIdx.x * 32 + r;
+  float4 a = make_float4(-INFINITY, 0.f, 0.f, __int_as_float(0x7fffffff));
+  if (row < M) {
+    for (int tc = sl; tc < ntc; tc += 8) a = head_rec_combine(a, *reinterpret_cast<const float4*>(part4 + 4 * ((int64_t)tc * M + row)));
+  }
+  sh[sl][r] = a;
+  __syncthreads();
+  if (sl != 0 || row >= M) return;
+#pragma unroll
+  for (int k = 1; k < 8; ++k) a = head_rec_combine(a, sh[k][r]);
+  const bool has_xt = out.nll != nullptr;
+  head_predict_store(a, has_xt ? xt[row] : 0.f, targets, out, row, V);
+}
+
+// the same outputs from materialised bf16 logits of a few rows (the 128x128-kernel shapes): one workgroup per row, thread t takes columns
+// t, t + 256, ...; equal maxima resolve to the lower column at every meeting, so the order of the meetings does not matter
+__global__ __launch_bounds__(256) void head_predict_rows_kernel(const uint16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ targets,
+                                                                HeadPredictOut out, int V) {
+  __shared__ float4 sh[4];
+  const bf16_t* lr = reinterpret_cast<const bf16_t*>(logits) + (int64_t)blockIdx.x * ld;
+  float4 a = make_float4(-INFINITY, 0.f, 0.f, __int_as_float(0x7fffffff));
+  for (int c = threadIdx.x; c < V; c += 256) {
+    const float x = bf2f(lr[c]);
+    a = head_rec_combine(a, make_float4(x, 1.f, 0.f, __int_as_float(x == -INFINITY ? 0x7fffffff : c)));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+    a = head_rec_combine(a, make_float4(__shfl_xor(a.x, o, 64), __shfl_xor(a.y, o, 64), __shfl_xor(a.z, o, 64), __shfl_xor(a.w, o, 64)));
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  a = sh[0];
+  for (int k = 1; k < 4; ++k) a = head_rec_combine(a, sh[k]);
+  float xt = 0.f;
+  if (out.nll) {
+    const int64_t tg = targets[blockIdx.x];
+    if (tg >= 0 && tg < V) xt = bf2f(lr[tg]);
+  }
+  head_predict_store(a, xt, targets, out, blockIdx.x, V);
+}
+
+void plm_launch_head_predict_combine(const float* part4, const float* xt, const int64_t* targets, const HeadPredictOut& out, int64_t M, int64_t V,
+                                     int ntc, hipStream_t s) {
+  hipLaunchKernelGGL(head_predict_combine_kernel, dim3((unsigned)plm_cdiv(M, 32)), dim3(256), 0, s, part4, xt, targets, out, (int)M, (int)V, ntc);
+}
+
+void plm_launch_head_predict_rows(const uint16_t* logits, int64_t ld, const int64_t* targets, const HeadPredictOut& out, int64_t rows, int64_t V,
+                                  hipStream_t s) {
+  hipLaunchKernelGGL(head_predict_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, logits, ld, targets, out, (int)V);
 }

@@ -16,6 +16,9 @@ struct EpiArgs {
   const int64_t* targets;  // [M]
   float* part;             // [tiles_n][M] (max, sum-exp) pairs, one per row and tile column
   float* xt;               // [M] the bf16-rounded target logit of every row whose target is a valid column
+  // SCORE, prediction mode (plm_head_predict_bf16): non-null selects it.  The per-row record grows to
+  // (max, sum-exp, u = sum e^(x-max) (x-max), column of the first maximum as int bits) and goes HERE instead of `part`; targets may be null.
+  float* part4;            // [tiles_n][M] 16-byte records
 };
 
 struct GemmOperands {
@@ -41,3 +44,12 @@ void plm_launch_head_score_combine(const float* part, const float* xt, const int
                                    hipStream_t s);
 void plm_launch_head_score_rows(const uint16_t* logits, int64_t ld, const int64_t* targets, float* nll, float* lse, int64_t rows, int64_t V,
                                 hipStream_t s);
+// outputs of the prediction head, one element per row; all but pred / logp may be null (nll needs targets)
+struct HeadPredictOut {
+  int64_t* pred;
+  float *logp, *entropy, *nll, *lse;
+};
+void plm_launch_head_predict_combine(const float* part4, const float* xt, const int64_t* targets, const HeadPredictOut& out, int64_t M, int64_t V,
+                                     int ntc, hipStream_t s);
+void plm_launch_head_predict_rows(const uint16_t* logits, int64_t ld, const int64_t* targets, const HeadPredictOut& out, int64_t rows, int64_t V,
+                                  hipStream_t s);

@@ -411,5 +411,33 @@ class HipEngine(torch.nn.Module):
       total_loss, num_batches = t[0].item(), t[1].item()
     return total_loss / num_batches
 
+  @torch.no_grad()
+  def eval_metrics(self, dataloader):
+    """{'loss', 'accuracy', 'entropy', 'tokens'} of a validation pass through model.predict (no logits buffer).  loss: eval() with
+    eval_head 'fused', to the bit (the mean of the batches' valid-token means).  accuracy: correct top-1 predictions over the non-ignored
+    targets of all batches; entropy: the mean predictive entropy (nats) over the same tokens; tokens: their number.  The sums stay on the
+    device and are read once, after the last batch (eval() reads every batch's loss); a NaN batch loss raises then."""
+    self.check_losses()
+    self.model.eval()
+    if hasattr(self.optimizer, 'eval'):
+      self.optimizer.eval()  # schedule-free: at the averaged iterate x, as eval(); step() returns to y
+    V = self.model.cfg.vocab_size
+    acc = torch.zeros(6, device=self.device, dtype=torch.float64)  # batch-loss sum, batches, correct, entropy sum, tokens, NaN batches
+    for batch in dataloader:
+      inputs, targets, doc_start = _move_to_device(batch, self.seq_len, self.device, self.intra_doc_masking, self._stager)
+      r = self.model.predict(inputs, doc_start, targets=targets)
+      valid = (targets >= 0) & (targets < V)
+      n = valid.sum()
+      loss = r.nll.reshape(-1).sum() / n  # score(..., reduction='mean'): the same reduction over the same bits
+      correct = ((r.tokens == targets) & valid).sum()
+      ent = torch.where(valid, r.entropy, torch.zeros_like(r.entropy)).sum(dtype=torch.float64)
+      acc += torch.stack([loss.double(), torch.ones_like(ent), correct.double(), ent, n.double(), torch.isnan(loss).double()])
+    if dist.is_initialized():
+      dist.all_reduce(acc, op=dist.ReduceOp.SUM)
+    loss_sum, batches, correct, ent_sum, tokens, bad = acc.tolist()
+    if bad or loss_sum != loss_sum:
+      raise ValueError('Validation loss is nan')
+    return {'loss': loss_sum / batches, 'accuracy': correct / tokens, 'entropy': ent_sum / tokens, 'tokens': int(tokens)}
+
 
 TorchEngine = HipEngine  # the name train.py imports (train.py:44)

@@ -4,6 +4,7 @@ allocator owns all memory), pass raw device pointers + the current HIP stream.
 Every function here launches hand-written gfx950 kernels; none has a torch fallback.
 """
 
+import collections
 import ctypes as C
 import os
 
@@ -750,6 +751,44 @@ def head_score(y, w, targets, want_lse=False):
     _lib.check(lib.plm_head_score_bf16(_p(y), y.stride(0), _p(w), w.stride(0), _p(targets), _p(nll), _p(lse), M, V, K, _p(ws), nbytes,
                                        _stream()), 'plm_head_score_bf16')
   return (nll, lse) if want_lse else nll
+
+
+HeadPredict = collections.namedtuple('HeadPredict', ['pred', 'logp', 'entropy', 'nll', 'lse'])
+_predict_ws = {}
+
+
+def head_predict(y, w, targets=None, want_entropy=True, want_lse=False):
+  """Prediction head: per row of l = bf16(y[M,K] @ w[V,K]^T) - the training head's logits, bit for bit, never stored -
+  pred int64[M] (first index of the maximum, always in [0, V)), logp fp32[M] = log softmax(l)[pred], entropy fp32[M] in nats, and with
+  ``targets`` nll fp32[M] as head_score gives it (0 where the target is outside [0, V)); want_lse: lse fp32[M].  Returns the named tuple
+  (pred, logp, entropy, nll, lse) with None for the parts not asked for.  No gradient."""
+  for t, n in ((y, 'y'), (w, 'w')):
+    if not t.is_cuda:
+      raise RuntimeError(f'head_predict.{n}: tensor must live on the GPU (plainlm_amd has no CPU path)')
+    if t.dtype != BF16 or t.dim() != 2 or t.stride(1) != 1:
+      raise ValueError(f'head_predict.{n}: need a 2-D bf16 GPU tensor with unit inner stride')
+  if targets is not None:
+    _need(targets, torch.int64, 'head_predict.targets', 1)
+  M, K = y.shape
+  V = w.shape[0]
+  if w.shape[1] != K or (targets is not None and targets.shape[0] != M):
+    raise ValueError(f'head_predict: y {tuple(y.shape)}, w {tuple(w.shape)}, targets '
+                     f'{None if targets is None else tuple(targets.shape)} do not fit')
+  lib = _lib.load()
+  _hook('gemm_nt', 2.0 * M * V * K)
+  key = (M, V, K, y.device)
+  ent = _predict_ws.get(key)
+  if ent is None:
+    nbytes = int(lib.plm_head_predict_workspace_bytes(M, V, K))
+    ent = _predict_ws[key] = (torch.empty(max(nbytes, 16), dtype=torch.uint8, device=y.device), nbytes)
+  ws, nbytes = ent
+  new = lambda want, dtype=F32: torch.empty((M,), dtype=dtype, device=y.device) if want else None  # noqa: E731
+  pred, logp = new(True, torch.int64), new(True)
+  entropy, nll, lse = new(want_entropy), new(targets is not None), new(want_lse)
+  with _Timed('gemm_nt', 2.0 * M * V * K):
+    _lib.check(lib.plm_head_predict_bf16(_p(y), y.stride(0), _p(w), w.stride(0), _p(targets), _p(pred), _p(logp), _p(entropy), _p(nll),
+                                         _p(lse), M, V, K, _p(ws), nbytes, _stream()), 'plm_head_predict_bf16')
+  return HeadPredict(pred, logp, entropy, nll, lse)
 
 
 def mean(x):

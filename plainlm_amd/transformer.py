@@ -13,6 +13,7 @@ avoids materialising the O(T^2) boolean mask of engine/engine.py:21-23.
 
 import math
 import os
+from collections import namedtuple
 from dataclasses import dataclass
 
 import torch
@@ -254,6 +255,9 @@ class Block(nn.Module):
     a = self.attn(n1, rope, doc_start, B, T)
     x, n2 = Fn.AddNormFn.apply(x, a, self.mlp_norm.weight, self.mlp_norm)
     return x, self.mlp.apply_fn(n2)
+
+
+HeadPrediction = namedtuple('HeadPrediction', ['tokens', 'logprob', 'entropy', 'nll'])  # Transformer.predict
 
 
 class Transformer(nn.Module):
@@ -499,6 +503,30 @@ class Transformer(nn.Module):
     if reduction == 'sum':
       return total
     return total / ((tg >= 0) & (tg < self.cfg.vocab_size)).sum()
+
+  @torch.compiler.disable
+  def predict(self, x, attn_mask=None, targets=None, last_only=False):
+    """Forward-only predictions without the logits buffer (ops.head_predict): HeadPrediction(tokens int64, logprob fp32 = log p(tokens),
+    entropy fp32 in nats, nll fp32 or None) of every position, [B, T] - or [B], the last position alone, with ``last_only`` (the
+    next-token call; the head then sees the B last rows of the trunk's output through a strided view, no copy).  tokens is the first
+    index of the largest logit of ``forward``; with ``targets`` [B, T] nll is what ``score`` returns.  There is no backward."""
+    if isinstance(x, torch.Tensor) and not x.is_cuda:
+      raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (inputs are on CPU; there is no CPU fallback)')
+    if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+      raise RuntimeError('Transformer.predict is forward-only (no backward): call it under torch.no_grad(), or use loss() to train')
+    if targets is not None and isinstance(x, torch.Tensor) and tuple(targets.shape) != tuple(x.shape):
+      raise ValueError(f'predict: targets {tuple(targets.shape)} do not match the inputs {tuple(x.shape)}')
+    y, B, T = self._trunk(x, attn_mask)
+    wb, _ = self.lm_head.shadow()
+    if last_only:
+      y = y.view(B, T, self.cfg.dim)[:, -1]  # row stride T * dim
+      tg = None if targets is None else targets[:, -1].contiguous()
+      shape = (B,)
+    else:
+      tg = None if targets is None else targets.reshape(-1).contiguous()
+      shape = (B, T)
+    r = ops.head_predict(y, wb, tg)
+    return HeadPrediction(r.pred.view(shape), r.logp.view(shape), r.entropy.view(shape), None if r.nll is None else r.nll.view(shape))
 
   def token_logprobs(self, x, targets, attn_mask=None):
     """log p(target) per token, fp32 [B, T] (0 where the target is ignored): ``-score(x, targets, attn_mask, 'none')``."""
