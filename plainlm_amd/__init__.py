@@ -14,5 +14,6 @@ os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
 from .construct import construct_model, get_param_groups  # noqa: F401
 from .transformer import HeadPrediction, ModelConfig, Transformer  # noqa: F401
 from .engine import HipEngine, TorchEngine  # noqa: F401
+from .generate import KVCache  # noqa: F401
 
-__all__ = ['construct_model', 'get_param_groups', 'ModelConfig', 'Transformer', 'HeadPrediction', 'HipEngine', 'TorchEngine']
+__all__ = ['construct_model', 'get_param_groups', 'ModelConfig', 'Transformer', 'HeadPrediction', 'HipEngine', 'TorchEngine', 'KVCache']

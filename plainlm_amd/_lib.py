@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libplainlm_hip.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'plainlm_hip.h')
 EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'plainlm_hip_ext.h')
+GEN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'plainlm_hip_gen.h')
 
 _lib = None
 
@@ -141,6 +142,14 @@ EXT_SIGNATURES = {
 }
 
 
+# the same for include/plainlm_hip_gen.h (KV-cached generation; a file of its own for the ext header's reason)
+GEN_SIGNATURES = {
+  'plm_kv_append_rope': (_I, [_P, _I64, _P, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
+  'plm_attn_decode_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I]),
+  'plm_attn_decode': (_I, [_P, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
+}
+
+
 def _declared(path):
   with open(path) as f:
     src = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
@@ -155,6 +164,11 @@ def header_functions():
 def ext_header_functions():
   """Names of all functions declared in include/plainlm_hip_ext.h."""
   return _declared(EXT_HEADER_PATH)
+
+
+def gen_header_functions():
+  """Names of all functions declared in include/plainlm_hip_gen.h."""
+  return _declared(GEN_HEADER_PATH)
 
 
 def load():
@@ -175,6 +189,12 @@ def load():
     fn = getattr(lib, name, None)
     if fn is None:  # the ABI number does not move for the ext header: a library from before it would pass the version check below
       raise RuntimeError(f'{LIB_PATH} lacks {name} (include/plainlm_hip_ext.h): rebuild it (make -C plainlm_amd/csrc)')
+    fn.restype = res
+    fn.argtypes = args
+  for name, (res, args) in GEN_SIGNATURES.items():
+    fn = getattr(lib, name, None)
+    if fn is None:  # as above: the ABI number does not move for the gen header either
+      raise RuntimeError(f'{LIB_PATH} lacks {name} (include/plainlm_hip_gen.h): rebuild it (make -C plainlm_amd/csrc)')
     fn.restype = res
     fn.argtypes = args
   got = lib.plm_version()

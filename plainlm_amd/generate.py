@@ -1,0 +1,122 @@
+"""KV-cached generation: the cache, and the host logic of ``Transformer.prefill / decode_step / generate``.
+
+Everything that can be stated without a GPU lives here as plain functions over tensors on any device - the length checks, the choice of
+the row a padded prompt is continued from, the token loop with its EOS freezing - so that tests/test_decode_host.py runs them on the CPU
+with a fake step function.  The kernels are reached through ops.kv_append_rope / ops.attn_decode from transformer.py.
+"""
+
+import torch
+
+from . import ops
+
+FINISH_CHECK_EVERY = 16  # generate: the one device-to-host read of the loop (have all sequences emitted eos_id?) at most this often
+
+
+class KVCache:
+  """Per-layer ``kv`` bf16 [B, Tmax, 2*dim] (row (b, j): the k | v columns of token j's rotated qkv row), ``lens`` int32 [B] on the
+  device, one decode workspace shared by all layers, and the status flag of the append kernel (checked by ``check``)."""
+
+  def __init__(self, n_layers, B, Tmax, n_heads, head_dim, device):
+    dim = n_heads * head_dim
+    self.B, self.Tmax, self.n_heads, self.head_dim = B, Tmax, n_heads, head_dim
+    self.kv = [torch.empty((B, Tmax, 2 * dim), dtype=torch.bfloat16, device=device) for _ in range(n_layers)]  # rows >= lens are never read
+    # [pos | lens] = [lens - 1 | lens] during a decode step: one in-place add per step moves both, every layer reads the same pair
+    self._pl = torch.zeros((2, B), dtype=torch.int32, device=device)
+    self._pl[0] -= 1
+    self.workspace = ops.attn_decode_workspace(B, n_heads, head_dim, Tmax, 0, device)  # automatic split count
+    self.status = torch.zeros((1,), dtype=torch.int32, device=device)
+
+  @property
+  def lens(self):
+    return self._pl[1]
+
+  @property
+  def pos(self):
+    """Position of the token appended by the current decode step (lens - 1)."""
+    return self._pl[0]
+
+  def set_lens(self, lens):
+    self._pl[1].copy_(lens)
+    self._pl[0].copy_(lens - 1)
+
+  def advance(self):
+    self._pl += 1
+
+  def check(self):
+    """Raises if a decode step tried to append past the cache (or past the RoPE table); reads the device flag, so it waits for the GPU."""
+    if int(self.status.item()) != 0:
+      raise RuntimeError(f'KVCache: a decode step appended at a position outside [0, {self.Tmax}): that token was not stored '
+                         '(prefill with a larger max_len)')
+
+
+def pad4(n):
+  return (int(n) + 3) // 4 * 4
+
+
+def prompt_lens_list(prompt_lens, B, T):
+  """prompt_lens (None | a sequence of ints | an integer tensor on the host) as a list of B ints in [1, T]."""
+  if prompt_lens is None:
+    return [int(T)] * B
+  if isinstance(prompt_lens, torch.Tensor):
+    if prompt_lens.is_cuda:
+      raise TypeError('prompt_lens: pass host integers (a list, a tuple or a CPU tensor): they size the cache before anything is launched')
+    prompt_lens = prompt_lens.tolist()
+  lens = [int(v) for v in prompt_lens]
+  if len(lens) != B:
+    raise ValueError(f'prompt_lens: {len(lens)} lengths for a batch of {B}')
+  if any(v < 1 or v > T for v in lens):
+    raise ValueError(f'prompt_lens: every length must be in [1, {T}] (the prompt tensor\'s width), got {lens}')
+  return lens
+
+
+def check_lengths(T, max_new_tokens, seq_len):
+  """The refusals of generate that need no GPU; returns the cache length (the padded prompt must fit it too)."""
+  if int(max_new_tokens) < 1:
+    raise ValueError(f'generate: max_new_tokens must be at least 1, got {max_new_tokens}')
+  if T < 1:
+    raise ValueError('generate: empty prompt')
+  if T + int(max_new_tokens) > seq_len:
+    raise ValueError(f'generate: prompt length {T} + max_new_tokens {max_new_tokens} exceeds cfg.seq_len {seq_len}')
+  return max(pad4(T), T + int(max_new_tokens))
+
+
+def last_rows(y, B, T, lens):
+  """Rows lens[b] - 1 of every sequence of y [B*T, d] -> [B, d]: what a right-padded prompt is continued from (NOT the padded last row)."""
+  idx = torch.arange(B, device=y.device) * T + (lens.to(device=y.device, dtype=torch.int64) - 1)
+  return y.index_select(0, idx)
+
+
+def generate_loop(first, step, max_new_tokens, eos_id=None, all_done=None, check_every=FINISH_CHECK_EVERY):
+  """The token loop.  ``first`` = (tokens int64 [B], logprob fp32 [B]) from the prefill; ``step(tokens) -> (tokens, logprob)`` is one
+  decode step.  Returns (tokens [B, N], logprobs [B, N]).  After a sequence has emitted eos_id its later tokens are eos_id with
+  log-probability 0 (its steps still run: the batch stays rectangular).  Nothing is read back per token; ``all_done(done)`` - the one
+  device-to-host read - runs at most once every ``check_every`` steps and ends the loop early."""
+  tok, lp = first
+  toks, lps = [tok], [lp]
+  done = (tok == eos_id) if eos_id is not None else None
+  if all_done is None:
+    all_done = lambda d: bool(d.all())  # noqa: E731
+  for i in range(1, int(max_new_tokens)):
+    if done is not None and i % check_every == 0 and all_done(done):
+      rest = int(max_new_tokens) - i
+      toks += [torch.full_like(tok, eos_id)] * rest
+      lps += [torch.zeros_like(lp)] * rest
+      break
+    tok, lp = step(tok)
+    if done is not None:
+      tok = torch.where(done, torch.full_like(tok, eos_id), tok)
+      lp = torch.where(done, torch.zeros_like(lp), lp)
+      done = done | (tok == eos_id)
+    toks.append(tok)
+    lps.append(lp)
+  return torch.stack(toks, dim=1), torch.stack(lps, dim=1)
+
+
+def sampled(sample, logits):
+  """(tokens int64 [B], log p(tokens) fp32 [B]) from the caller's sampler on fp32 logits [B, V]."""
+  lf = logits.float()
+  tok = sample(lf)
+  if not isinstance(tok, torch.Tensor) or tok.dtype != torch.int64 or tuple(tok.shape) != (lf.shape[0],):
+    raise TypeError('generate: sample(logits fp32 [B, V]) must return an int64 [B] tensor')
+  tok = tok.to(lf.device)
+  return tok, torch.log_softmax(lf, dim=-1).gather(1, tok[:, None])[:, 0]

@@ -705,6 +705,76 @@ def attn_bwd_masked(qkv, out, dout, lse, rope_cos, rope_sin, bits, tile_class, B
   return dqkv
 
 
+# ---- KV-cached generation ------------------------------------------
+def _need_kv(kv, nh, hd, name):
+  """kv bf16 [B, Tmax, >= 2*nh*hd]: rows may be padded (stride(1) a multiple of 8), sequences are Tmax rows apart."""
+  if not kv.is_cuda:
+    raise RuntimeError(f'{name}: tensor must live on the GPU (plainlm_amd has no CPU path)')
+  if kv.dtype != BF16 or kv.dim() != 3 or kv.shape[2] != 2 * nh * hd or kv.stride(2) != 1 or kv.stride(0) != kv.shape[1] * kv.stride(1):
+    raise ValueError(f'{name}: need a bf16 [B, Tmax, 2*nh*hd] cache with unit inner stride and batch stride Tmax * row stride')
+  return kv
+
+
+def kv_append_rope(qkv, pos, rope_cos, rope_sin, kv, nh, q_out=None, status=None):
+  """One decode token per sequence: qkv bf16 [B, 3*nh*hd] UN-rotated (row stride may exceed it), pos int32 [B].  Rotates q and k at
+  position pos[b] (rope_qk_'s bits), returns rotated q [B, nh*hd] and writes rotated k | untouched v into kv[b, pos[b]].  A pos[b] outside
+  [0, min(Tmax, rope rows)) writes nothing for that sequence and sets status[0] = 1 (int32 [1], zeroed by the caller; made here when
+  absent).  Returns (q_out, status): status is a device tensor, the caller decides when to look."""
+  if not qkv.is_cuda:
+    raise RuntimeError('kv_append_rope.qkv: tensor must live on the GPU (plainlm_amd has no CPU path)')
+  if qkv.dtype != BF16 or qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[1] % (3 * nh) != 0:
+    raise ValueError('kv_append_rope.qkv: need a 2-D bf16 GPU tensor [B, 3*nh*hd] with unit inner stride')
+  B = qkv.shape[0]
+  hd = qkv.shape[1] // (3 * nh)
+  _need(pos, torch.int32, 'kv_append_rope.pos', 1)
+  _need(rope_cos, F32, 'kv_append_rope.rope_cos', 2)
+  _need(rope_sin, F32, 'kv_append_rope.rope_sin', 2)
+  _need_kv(kv, nh, hd, 'kv_append_rope.kv')
+  if pos.shape[0] != B or kv.shape[0] != B or rope_cos.shape != rope_sin.shape or rope_cos.shape[1] != hd // 2:
+    raise ValueError('kv_append_rope: pos / kv do not fit the batch, or the RoPE tables the head_dim')
+  q_out = torch.empty((B, nh * hd), dtype=BF16, device=qkv.device) if q_out is None else _need(q_out, BF16, 'kv_append_rope.q_out', 2)
+  status = torch.zeros((1,), dtype=torch.int32, device=qkv.device) if status is None else _need(status, torch.int32, 'kv_append_rope.status')
+  _lib.check(_lib.load().plm_kv_append_rope(_p(qkv), qkv.stride(0), _p(pos), _p(rope_cos), _p(rope_sin), rope_cos.shape[0], _p(q_out), _p(kv),
+                                            kv.stride(1), _p(status), B, kv.shape[1], nh, hd, _stream()), 'plm_kv_append_rope')
+  return q_out, status
+
+
+_decode_ws = {}
+
+
+def attn_decode_workspace(B, nh, hd, Tmax, splits, device):
+  """(uint8 workspace, bytes) of attn_decode for this shape and splits argument, cached per shape."""
+  key = (B, nh, hd, Tmax, int(splits), device)
+  ent = _decode_ws.get(key)
+  if ent is None:
+    nbytes = int(_lib.load().plm_attn_decode_workspace_bytes(B, nh, hd, Tmax, int(splits)))
+    if nbytes == 0:
+      raise ValueError(f'attn_decode: unsupported shape B={B} nh={nh} hd={hd} Tmax={Tmax} or splits={splits} (0 = automatic, 1..64)')
+    ent = _decode_ws[key] = (torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes)
+  return ent
+
+
+def attn_decode(q, kv, lens, nh, splits=0, want_lse=False, workspace=None):
+  """Attention of one rotated query row per sequence over its cache: q bf16 [B, nh*hd], kv bf16 [B, Tmax, 2*nh*hd] (kv_append_rope's
+  layout), lens int32 [B] (clamped to [0, Tmax]; sequence b attends keys 0 .. lens[b]-1, lens[b] == 0 gives out = 0 and lse = +inf).
+  splits: 0 automatic (from the shape alone) | 1..64 forced.  Returns out bf16 [B, nh*hd], or (out, lse fp32 [B, nh], base 2 like
+  attn_fwd's) with want_lse.  workspace: (uint8 tensor, bytes) of attn_decode_workspace for the same splits, else a cached one per shape."""
+  _need(q, BF16, 'attn_decode.q', 2)
+  B = q.shape[0]
+  hd = q.shape[1] // nh
+  _need_kv(kv, nh, hd, 'attn_decode.kv')
+  _need(lens, torch.int32, 'attn_decode.lens', 1)
+  if q.shape[1] != nh * hd or kv.shape[0] != B or lens.shape[0] != B:
+    raise ValueError(f'attn_decode: q {tuple(q.shape)}, kv {tuple(kv.shape)}, lens {tuple(lens.shape)} do not fit nh={nh}')
+  Tmax = kv.shape[1]
+  ws, nbytes = attn_decode_workspace(B, nh, hd, Tmax, splits, q.device) if workspace is None else workspace
+  out = torch.empty((B, nh * hd), dtype=BF16, device=q.device)
+  lse = torch.empty((B, nh), dtype=F32, device=q.device) if want_lse else None
+  _lib.check(_lib.load().plm_attn_decode(_p(q), _p(kv), kv.stride(1), _p(lens), _p(out), _p(lse), B, Tmax, nh, hd, int(splits), _p(ws), nbytes,
+                                         _stream()), 'plm_attn_decode')
+  return (out, lse) if want_lse else out
+
+
 # ---- cross entropy --------------------------------------------------------------------
 def ce_fwd_bwd_(logits, targets, grad_scale, V=None):
   """In place: logits[:, :V] <- (softmax - onehot) * grad_scale, logits[:, V:] <- 0 (logits is bf16 [M, ld], ld >= V).

@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from . import functional as Fn
+from . import generate as G
 from . import ops
 
 
@@ -228,8 +229,11 @@ class Attention(nn.Module):
     self.w_qkv = HipLinear(cfg.dim, 3 * cfg.dim)
     self.w_out = HipLinear(cfg.dim, cfg.dim)
 
-  def forward(self, x2d, rope, doc_start, B, T):
+  def forward(self, x2d, rope, doc_start, B, T, cache=None):
     qkv = (Fn.MxQKVRopeFn if self.w_qkv.mx else Fn.QKVRopeFn).apply(x2d, self.w_qkv.weight, self.w_qkv, rope[0], rope[1], B, T, self.n_heads)
+    if cache is not None:  # prefill: this layer's kv [B, Tmax, 2*dim] takes the k | v columns of the rotated qkv, as they are
+      d = self.n_heads * self.head_dim
+      cache[:, :T].copy_(qkv.detach().view(B, T, 3 * d)[:, :, d:])
     a = Fn.AttnFn.apply(qkv, rope[0], rope[1], doc_start, B, T, self.n_heads)
     return self.w_out(a)
 
@@ -245,14 +249,14 @@ class Block(nn.Module):
     self.mlp_norm = RMSNorm(cfg.dim, cfg.rmsnorm_eps)
     self.layer_id = layer_id
 
-  def forward(self, x, branch, rope, doc_start, B, T):
+  def forward(self, x, branch, rope, doc_start, B, T, cache=None):
     """x fp32 [M,d] residual stream, branch bf16 [M,d] = previous block's MLP output (or None).
-    Returns (x_mid, mlp_out): the residual add of the MLP output is fused into the NEXT norm."""
+    Returns (x_mid, mlp_out): the residual add of the MLP output is fused into the NEXT norm.  cache: this layer's KV buffer (prefill)."""
     if branch is None:
       x, n1 = Fn.NormFn.apply(x, self.attn_norm.weight, self.attn_norm)
     else:
       x, n1 = Fn.AddNormFn.apply(x, branch, self.attn_norm.weight, self.attn_norm)
-    a = self.attn(n1, rope, doc_start, B, T)
+    a = self.attn(n1, rope, doc_start, B, T, cache)
     x, n2 = Fn.AddNormFn.apply(x, a, self.mlp_norm.weight, self.mlp_norm)
     return x, self.mlp.apply_fn(n2)
 
@@ -442,7 +446,7 @@ class Transformer(nn.Module):
       raise ValueError('attn_mask: a row of the previous bool mask was not exactly True on [first allowed key, query]: only block-diagonal causal '
                        'masks (data_prep_utils.py:7-23) are supported (any other mask: attn_mask_mode: dense, or pass a functional.DenseMask)')
 
-  def _trunk(self, x, attn_mask):
+  def _trunk(self, x, attn_mask, cache=None):
     if x.dim() != 2 or x.dtype != torch.int64:
       raise TypeError('inputs must be an int64 [B, T] tensor')
     if not x.is_cuda:
@@ -463,8 +467,8 @@ class Transformer(nn.Module):
     self.refresh_shadows()
     h = self.embed_tokens(x).view(B * T, self.cfg.dim)
     branch = None
-    for layer in self.layers:
-      h, branch = layer(h, branch, rope, doc_start, B, T)
+    for i, layer in enumerate(self.layers):
+      h, branch = layer(h, branch, rope, doc_start, B, T, None if cache is None else cache.kv[i])
     _, y = Fn.AddNormFn.apply(h, branch, self.out_norm.weight, self.out_norm)
     return y, B, T
 
@@ -531,3 +535,99 @@ class Transformer(nn.Module):
   def token_logprobs(self, x, targets, attn_mask=None):
     """log p(target) per token, fp32 [B, T] (0 where the target is ignored): ``-score(x, targets, attn_mask, 'none')``."""
     return -self.score(x, targets, attn_mask, reduction='none')
+
+  # ---- KV-cached generation (DESIGN.md section 12; host logic in generate.py) ---------------------------------------------------
+  def _check_decode(self, what, t):
+    if self.cfg.linear_precision == 'mxfp8':
+      raise NotImplementedError(f"Transformer.{what}: linear_precision: mxfp8 has no cached decode path (the decode step runs the bf16 shadows)")
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int64:
+      raise TypeError(f'Transformer.{what}: tokens must be an int64 tensor')
+    if not t.is_cuda:
+      raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (inputs are on CPU; there is no CPU fallback)')
+
+  @torch.compiler.disable
+  def prefill(self, x, prompt_lens=None, max_len=None, logits=False):
+    """Run the prompt x int64 [B, T] through the trunk once and keep every layer's rotated k | v: returns (KVCache, HeadPrediction [B]) -
+    the greedy next token of every sequence, its log-probability and the entropy, from row prompt_lens[b] - 1 (host integers; default T).
+    Prompts are right-padded to a multiple of 4 (the attention kernels' granularity), which under a causal mask changes no earlier row;
+    with prompt_lens shorter rows hold padding the cache never reads (lens = prompt_lens).  max_len: cache rows per sequence (default
+    cfg.seq_len).  logits=True returns the bf16 [B, V] logits of those rows in
+    place of the prediction.  Runs under no_grad."""
+    self._check_decode('prefill', x)
+    if x.dim() != 2:
+      raise TypeError('inputs must be an int64 [B, T] tensor')
+    B, T = x.shape
+    lens = G.prompt_lens_list(prompt_lens, B, T)
+    Tp = G.pad4(T)
+    Tmax = self.cfg.seq_len if max_len is None else int(max_len)
+    if Tp > Tmax or Tmax > self.cfg.seq_len:
+      raise ValueError(f'prefill: the padded prompt ({Tp} rows) must fit max_len {Tmax}, and max_len cfg.seq_len {self.cfg.seq_len}')
+    with torch.no_grad():
+      if Tp != T:
+        x = torch.nn.functional.pad(x, (0, Tp - T))
+      cache = G.KVCache(self.n_layers, B, Tmax, self.cfg.n_heads, self.head_dim, x.device)
+      lens_dev = torch.tensor(lens, dtype=torch.int32).to(x.device)
+      cache.set_lens(lens_dev)
+      y, _, _ = self._trunk(x.contiguous(), None, cache)
+      rows = G.last_rows(y, B, Tp, lens_dev)
+      wb, _ = self.lm_head.shadow()
+      if logits:
+        return cache, ops.gemm_nt(rows, wb)
+      r = ops.head_predict(rows, wb)
+    return cache, HeadPrediction(r.pred, r.logp, r.entropy, None)
+
+  @torch.compiler.disable
+  def decode_step(self, tokens, cache, logits=False):
+    """One token per sequence on top of ``cache``: tokens int64 [B] are appended at positions cache.lens (then lens += 1, on the device)
+    and the HeadPrediction [B] of the NEXT token is returned - or, with logits=True, its bf16 logits [B, V].  The Block structure as it
+    is, through ops calls on the bf16 shadows: about ten launches per layer, none of them sized by the context except decode attention."""
+    self._check_decode('decode_step', tokens)
+    B = cache.B
+    if tuple(tokens.shape) != (B,):
+      raise ValueError(f'decode_step: tokens {tuple(tokens.shape)} do not match the cache\'s batch of {B}')
+    nh = self.cfg.n_heads
+    with torch.no_grad():
+      self.refresh_shadows()
+      rope = self._rope(tokens.device)
+      cache.advance()  # pos = the appended token's position, lens = pos + 1: what this step's attention sees
+      x = ops.embed_fwd(tokens.contiguous(), self.embed_tokens.weight)
+      branch = None
+      for i, layer in enumerate(self.layers):
+        xo, n1, _ = ops.rmsnorm_fwd(x, layer.attn_norm.weight, layer.attn_norm.eps, branch=branch)
+        x = x if xo is None else xo
+        qkv = ops.gemm_nt(n1, layer.attn.w_qkv.shadow()[0])
+        q, _ = ops.kv_append_rope(qkv, cache.pos, rope[0], rope[1], cache.kv[i], nh, status=cache.status)
+        a = ops.attn_decode(q, cache.kv[i], cache.lens, nh, workspace=cache.workspace)
+        a = ops.gemm_nt(a, layer.attn.w_out.shadow()[0])
+        x, n2, _ = ops.rmsnorm_fwd(x, layer.mlp_norm.weight, layer.mlp_norm.eps, branch=a)
+        u = ops.gemm_nt(n2, layer.mlp.fc1.shadow()[0])
+        act = ops.swiglu_fwd(u) if isinstance(layer.mlp, GLU) else ops.act_fwd(u, layer.mlp.kind)
+        branch = ops.gemm_nt(act, layer.mlp.fc2.shadow()[0])
+      _, y, _ = ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps, branch=branch)
+      wb, _ = self.lm_head.shadow()
+      if logits:
+        return ops.gemm_nt(y, wb)
+      r = ops.head_predict(y, wb)
+    return HeadPrediction(r.pred, r.logp, r.entropy, None)
+
+  @torch.compiler.disable
+  def generate(self, prompt, max_new_tokens, prompt_lens=None, eos_id=None, sample=None, return_logprobs=False):
+    """Continue prompt int64 [B, T] by max_new_tokens tokens: returns the new tokens int64 [B, max_new_tokens], with return_logprobs
+    also their log-probabilities fp32 [B, max_new_tokens].  Greedy by default, through the fused prediction head (no logits are built);
+    ``sample`` is an optional callable fp32 logits [B, V] -> int64 [B] (temperature, top-k, nucleus: the caller's few lines of torch),
+    with which every step returns logits instead.  prompt_lens: host integers, the true length of every right-padded prompt.  After a
+    sequence emits eos_id its later tokens are eos_id and their log-probabilities 0.  No device-to-host copy happens per token."""
+    if isinstance(prompt, torch.Tensor) and not prompt.is_cuda:
+      raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (inputs are on CPU; there is no CPU fallback)')
+    if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+      raise RuntimeError('Transformer.generate is forward-only (no backward): call it under torch.no_grad(), or use loss() to train')
+    self._check_decode('generate', prompt)
+    if prompt.dim() != 2:
+      raise TypeError('inputs must be an int64 [B, T] tensor')
+    max_len = G.check_lengths(prompt.shape[1], max_new_tokens, self.cfg.seq_len)
+    want_logits = sample is not None
+    pick = (lambda r: G.sampled(sample, r)) if want_logits else (lambda r: (r.tokens, r.logprob))  # noqa: E731
+    cache, r = self.prefill(prompt, prompt_lens, max_len=max_len, logits=want_logits)
+    toks, lps = G.generate_loop(pick(r), lambda t: pick(self.decode_step(t, cache, logits=want_logits)), max_new_tokens, eos_id)
+    cache.check()
+    return (toks, lps) if return_logprobs else toks

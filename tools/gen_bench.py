@@ -1,0 +1,113 @@
+"""Cost of one new token at the 160M shape (12 layers, d = 768, 12 heads, V = 50280), B = 8, context 1024:
+  C  one cached decode step (Transformer.decode_step on a cache prefilled with the context)
+  R  predict(last_only=True) on the same full prefix: the recompute route, all there was before the cache
+Both alternate in one process, random weights (the model's own init) and random tokens, HIP events around each call, median of --runs
+after --warmup.  Also: the host time to enqueue C (its launches return before the kernels finish: a step that takes no longer than
+its enqueue is launch-bound), the two new kernels alone (append; decode attention per split count), and whether C and R pick the
+same tokens.
+Usage: python tools/gen_bench.py [--runs 20] [--out profiles/generate_bench.txt]"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from plainlm_amd import ModelConfig, Transformer, ops  # noqa: E402
+
+B, CTX, SEQ = 8, 1024, 1028  # the timed step appends token number CTX + 1; the recompute route sees CTX + 4 rows (rows are 4 at a time)
+
+
+def timed(fn):
+  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+  e0.record()
+  fn()
+  e1.record()
+  e1.synchronize()
+  return e0.elapsed_time(e1)
+
+
+def med(v):
+  return '%.3f [%.3f %.3f]' % (statistics.median(v), min(v), max(v))
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--runs', type=int, default=20)
+  ap.add_argument('--warmup', type=int, default=3)
+  ap.add_argument('--out', default=None)
+  a = ap.parse_args()
+  torch.manual_seed(0)
+  cfg = ModelConfig(vocab_size=50280, seq_len=SEQ, dim=768, expand=8 / 3, n_layers=12, n_heads=12, mlp='glu')
+  m = Transformer(cfg).cuda()
+  tok = torch.randint(0, cfg.vocab_size, (B, CTX + 4), device='cuda')
+  lens = torch.full((B,), CTX, dtype=torch.int32, device='cuda')
+  with torch.no_grad():
+    cache, first = m.prefill(tok[:, :CTX].contiguous())
+    nxt = tok[:, CTX].contiguous()
+
+    def step():  # the same step every time: the cache is wound back to the context before it (outside the timed region)
+      return m.decode_step(nxt, cache)
+
+    def recompute():  # the prefix + the new token, right-padded to the kernels' 4 rows: the prediction after token CTX + 1 is row CTX
+      return m.predict(tok)
+
+    def recompute_last():
+      return m.predict(tok, last_only=True)
+
+    r_c = step()
+    r_r = recompute()
+    same = (r_c.tokens == r_r.tokens[:, CTX]).float().mean().item()
+    dlp = (r_c.logprob - r_r.logprob[:, CTX]).abs().max().item()
+    tc, tr, th = [], [], []
+    for i in range(a.warmup + a.runs):
+      cache.set_lens(lens)
+      torch.cuda.synchronize()
+      e = timed(step)
+      # enqueue time: a second step, not waited for
+      cache.set_lens(lens)
+      torch.cuda.synchronize()
+      t0 = time.perf_counter()
+      step()
+      h = (time.perf_counter() - t0) * 1e3
+      torch.cuda.synchronize()
+      r = timed(recompute_last)
+      if i >= a.warmup:
+        tc.append(e), tr.append(r), th.append(h)
+    # the two new kernels alone, at this shape
+    nh, hd = cfg.n_heads, m.head_dim
+    rope = m._rope(tok.device)
+    qkv = torch.randn(B, 3 * cfg.dim, device='cuda').to(torch.bfloat16)
+    pos = lens.clone()
+    ta = [timed(lambda: ops.kv_append_rope(qkv, pos, rope[0], rope[1], cache.kv[0], nh, status=cache.status)) for _ in range(a.warmup + a.runs)][a.warmup:]
+    q = torch.randn(B, cfg.dim, device='cuda').to(torch.bfloat16)
+    full = torch.full((B,), CTX + 1, dtype=torch.int32, device='cuda')
+    ks = {}
+    for s in (0, 1, 2, 4, 8, 16, 32, 64):
+      ks[s] = [timed(lambda: ops.attn_decode(q, cache.kv[0], full, nh, splits=s)) for _ in range(a.warmup + a.runs)][a.warmup:]
+  launches = 2 + 10 * cfg.n_layers + 1 + 2  # lens += 1, embedding; per layer 2 norms, 4 GEMMs, append, 2 decode, activation; out norm; head (2)
+  mc, mr = statistics.median(tc), statistics.median(tr)
+  kv_bytes = B * (CTX + 1) * 2 * cfg.dim * 2
+  lines = [
+    '# tools/gen_bench.py: 160M (12 layers, d 768, 12 heads, V 50280), B = %d, context %d; one process, sides alternating; ms, median of %d [min max]' % (B, CTX, a.runs),
+    'cached decode step (C)                       %s' % med(tc),
+    'predict(last_only=True) on the prefix (R)    %s' % med(tr),
+    'R / C                                        %.2f' % (mr / mc),
+    'host time to enqueue C (%d launches)        %s' % (launches, med(th)),
+    'C and R choose the same token                %.3f of %d sequences (max |dlogp| %.2e; random weights: near-uniform logits)' % (same, B, dlp),
+    'plm_kv_append_rope alone                     %s' % med(ta),
+  ]
+  for s, v in ks.items():
+    lines.append('plm_attn_decode alone, splits = %-2s %s       %s   (%.0f GB/s of k | v)'
+                 % (s, '(auto)' if s == 0 else '      ', med(v), kv_bytes / statistics.median(v) / 1e6))
+  text = '\n'.join(lines) + '\n'
+  print(text, end='')
+  if a.out:
+    with open(a.out, 'w') as f:
+      f.write(text)
+
+
+if __name__ == '__main__':
+  main()
