@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, 'libplainlm_hip.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'plainlm_hip.h')
 EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'plainlm_hip_ext.h')
 GEN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'plainlm_hip_gen.h')
+SAMPLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'plainlm_hip_sample.h')
 
 _lib = None
 
@@ -149,6 +150,11 @@ GEN_SIGNATURES = {
   'plm_attn_decode': (_I, [_P, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
 }
 
+# the same for include/plainlm_hip_sample.h (on-device sampling; a file of its own for the ext header's reason)
+SAMPLE_SIGNATURES = {
+  'plm_sample_logits_bf16': (_I, [_P, _I64, _P, _F, _I64, _F, _P, _P, _P, _P, _I64, _I64, _P]),
+}
+
 
 def _declared(path):
   with open(path) as f:
@@ -169,6 +175,11 @@ def ext_header_functions():
 def gen_header_functions():
   """Names of all functions declared in include/plainlm_hip_gen.h."""
   return _declared(GEN_HEADER_PATH)
+
+
+def sample_header_functions():
+  """Names of all functions declared in include/plainlm_hip_sample.h."""
+  return _declared(SAMPLE_HEADER_PATH)
 
 
 def load():
@@ -195,6 +206,12 @@ def load():
     fn = getattr(lib, name, None)
     if fn is None:  # as above: the ABI number does not move for the gen header either
       raise RuntimeError(f'{LIB_PATH} lacks {name} (include/plainlm_hip_gen.h): rebuild it (make -C plainlm_amd/csrc)')
+    fn.restype = res
+    fn.argtypes = args
+  for name, (res, args) in SAMPLE_SIGNATURES.items():
+    fn = getattr(lib, name, None)
+    if fn is None:  # as above: the ABI number does not move for the sample header either
+      raise RuntimeError(f'{LIB_PATH} lacks {name} (include/plainlm_hip_sample.h): rebuild it (make -C plainlm_amd/csrc)')
     fn.restype = res
     fn.argtypes = args
   got = lib.plm_version()

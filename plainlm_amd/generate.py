@@ -2,8 +2,12 @@
 
 Everything that can be stated without a GPU lives here as plain functions over tensors on any device - the length checks, the choice of
 the row a padded prompt is continued from, the token loop with its EOS freezing - so that tests/test_decode_host.py runs them on the CPU
-with a fake step function.  The kernels are reached through ops.kv_append_rope / ops.attn_decode from transformer.py.
+with a fake step function.  The kernels are reached through ops.kv_append_rope / ops.attn_decode from transformer.py.  On-device
+sampling adds the argument rules (check_sampling), the one draw of uniforms per call (draw_uniforms) and the
+per-step pick (sampling_pick over ops.sample_logits).
 """
+
+import math
 
 import torch
 
@@ -120,3 +124,56 @@ def sampled(sample, logits):
     raise TypeError('generate: sample(logits fp32 [B, V]) must return an int64 [B] tensor')
   tok = tok.to(lf.device)
   return tok, torch.log_softmax(lf, dim=-1).gather(1, tok[:, None])[:, 0]
+
+
+def check_sampling(temperature=None, top_k=None, top_p=None, sample=None, seed=None):
+  """The sampling arguments of generate, normalised: None when the call is greedy or goes through the caller's ``sample``, else
+  (temperature, top_k, top_p) for ops.sample_logits.  top_k None is 0 (off), top_p None is 1 (off); temperature None or 0 with neither
+  filter is greedy, temperature None with a filter is 1.  Refused with ValueError: ``sample`` together with any of the other four, a
+  negative or non-finite temperature, temperature 0 together with a filter (that is greedy: say so by leaving the filters out), top_k < 0,
+  top_p outside (0, 1]."""
+  if sample is not None:
+    given = [n for n, v in (('temperature', temperature), ('top_k', top_k), ('top_p', top_p), ('seed', seed)) if v is not None]
+    if given:
+      raise ValueError(f'generate: sample= is the caller\'s own sampler; it cannot be combined with {", ".join(given)}')
+    return None
+  k = 0 if top_k is None else int(top_k)
+  p = 1.0 if top_p is None else float(top_p)
+  if k < 0:
+    raise ValueError(f'generate: top_k must be >= 0 (0 or None = off), got {top_k}')
+  if not (0.0 < p <= 1.0):
+    raise ValueError(f'generate: top_p must be in (0, 1] (1 or None = off), got {top_p}')
+  t = None if temperature is None else float(temperature)
+  if t is not None and (not math.isfinite(t) or t < 0.0):
+    raise ValueError(f'generate: temperature must be finite and >= 0, got {temperature}')
+  filtered = k > 0 or p < 1.0
+  if t is None or t == 0.0:
+    if not filtered:
+      return None  # greedy: the fused prediction head, no logits
+    if t is not None:
+      raise ValueError('generate: temperature 0 is greedy decoding, which top_k / top_p cannot change: leave them out, or give a positive temperature')
+    t = 1.0
+  return t, k, p
+
+
+def draw_uniforms(max_new_tokens, B, device, seed=None):
+  """u fp32 [max_new_tokens, B] on ``device``, drawn once per generate call: step n uses row n.  ``seed`` seeds a torch.Generator of
+  that device (the same seed gives the same bits); None draws from torch's default generator."""
+  gen = None
+  if seed is not None:
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(seed))
+  return torch.rand((int(max_new_tokens), int(B)), generator=gen, dtype=torch.float32, device=device)
+
+
+def sampling_pick(u, temperature, top_k, top_p, sampler=None):
+  """pick(logits bf16 [B, V]) -> (tokens, logprob) for generate_loop: its n-th call samples with row n of u, through ops.sample_logits
+  (``sampler`` stands in for it in the host tests)."""
+  sampler = ops.sample_logits if sampler is None else sampler
+  n = [0]
+
+  def pick(logits):
+    r = sampler(logits, u[n[0]], temperature, top_k, top_p)
+    n[0] += 1
+    return r[0], r[1]
+  return pick

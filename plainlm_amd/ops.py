@@ -775,6 +775,33 @@ def attn_decode(q, kv, lens, nh, splits=0, want_lse=False, workspace=None):
   return (out, lse) if want_lse else out
 
 
+SampleLogits = collections.namedtuple('SampleLogits', ['tokens', 'logprob', 'n_kept', 'cutoff'])
+
+
+def sample_logits(logits, u, temperature=1.0, top_k=0, top_p=1.0, want_stats=False):
+  """One token per row of logits bf16 [B, V] (unit inner stride, any row stride >= V and any 2-byte aligned base: a column slice of a
+  wider buffer is fine) by temperature, then top-k, then top-p, then the draw with u fp32 [B] (top-k keeps every
+  tie with the k-th value, top-p keeps or drops equal logits together; top_k = 0 and top_p = 1 are off).  One launch, bit-reproducible.
+  Returns the named tuple (tokens int64 [B], logprob fp32 [B] = log softmax(logits)[tokens] at temperature 1, n_kept int32 [B],
+  cutoff fp32 [B]): the size of the kept set and its lowest logit with want_stats, else None."""
+  if not logits.is_cuda:
+    raise RuntimeError('sample_logits.logits: tensor must live on the GPU (plainlm_amd has no CPU path)')
+  if logits.dtype != BF16 or logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or \
+     (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1]):
+    raise ValueError('sample_logits.logits: need a 2-D bf16 GPU tensor [B, V] with unit inner stride and row stride >= V')
+  B, V = logits.shape
+  _need(u, F32, 'sample_logits.u', 1)
+  if u.shape[0] != B:
+    raise ValueError(f'sample_logits: u {tuple(u.shape)} does not fit logits {tuple(logits.shape)}')
+  new = lambda want, dtype: torch.empty((B,), dtype=dtype, device=logits.device) if want else None  # noqa: E731
+  tok, logp = new(True, torch.int64), new(True, F32)
+  n_kept, cutoff = new(want_stats, torch.int32), new(want_stats, F32)
+  _lib.check(_lib.load().plm_sample_logits_bf16(_p(logits), logits.stride(0) if B > 1 else V, _p(u), float(temperature), int(top_k),
+                                                float(top_p), _p(tok), _p(logp), _p(n_kept), _p(cutoff), B, V, _stream()),
+             'plm_sample_logits_bf16')
+  return SampleLogits(tok, logp, n_kept, cutoff)
+
+
 # ---- cross entropy --------------------------------------------------------------------
 def ce_fwd_bwd_(logits, targets, grad_scale, V=None):
   """In place: logits[:, :V] <- (softmax - onehot) * grad_scale, logits[:, V:] <- 0 (logits is bf16 [M, ld], ld >= V).

@@ -611,12 +611,17 @@ class Transformer(nn.Module):
     return HeadPrediction(r.pred, r.logp, r.entropy, None)
 
   @torch.compiler.disable
-  def generate(self, prompt, max_new_tokens, prompt_lens=None, eos_id=None, sample=None, return_logprobs=False):
+  def generate(self, prompt, max_new_tokens, prompt_lens=None, eos_id=None, sample=None, return_logprobs=False, temperature=None,
+               top_k=None, top_p=None, seed=None):
     """Continue prompt int64 [B, T] by max_new_tokens tokens: returns the new tokens int64 [B, max_new_tokens], with return_logprobs
     also their log-probabilities fp32 [B, max_new_tokens].  Greedy by default, through the fused prediction head (no logits are built);
     ``sample`` is an optional callable fp32 logits [B, V] -> int64 [B] (temperature, top-k, nucleus: the caller's few lines of torch),
     with which every step returns logits instead.  prompt_lens: host integers, the true length of every right-padded prompt.  After a
-    sequence emits eos_id its later tokens are eos_id and their log-probabilities 0.  No device-to-host copy happens per token."""
+    sequence emits eos_id its later tokens are eos_id and their log-probabilities 0.  No device-to-host copy happens per token.
+    temperature / top_k / top_p sample on the device (one ops.sample_logits launch per token next to the logits
+    GEMM; top-k keeps ties with the k-th value, top-p keeps or drops equal logits together; the returned log-probabilities stay the
+    model's, at temperature 1).  The uniforms of the whole call are drawn once, from a generator seeded with ``seed`` (bit-reproducible)
+    or from torch's default generator.  temperature None or 0 without a filter is greedy; ``sample`` excludes all four."""
     if isinstance(prompt, torch.Tensor) and not prompt.is_cuda:
       raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (inputs are on CPU; there is no CPU fallback)')
     if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
@@ -625,8 +630,12 @@ class Transformer(nn.Module):
     if prompt.dim() != 2:
       raise TypeError('inputs must be an int64 [B, T] tensor')
     max_len = G.check_lengths(prompt.shape[1], max_new_tokens, self.cfg.seq_len)
-    want_logits = sample is not None
-    pick = (lambda r: G.sampled(sample, r)) if want_logits else (lambda r: (r.tokens, r.logprob))  # noqa: E731
+    on_device = G.check_sampling(temperature, top_k, top_p, sample, seed)
+    want_logits = sample is not None or on_device is not None
+    if on_device is not None:
+      pick = G.sampling_pick(G.draw_uniforms(max_new_tokens, prompt.shape[0], prompt.device, seed), *on_device)
+    else:
+      pick = (lambda r: G.sampled(sample, r)) if want_logits else (lambda r: (r.tokens, r.logprob))  # noqa: E731
     cache, r = self.prefill(prompt, prompt_lens, max_len=max_len, logits=want_logits)
     toks, lps = G.generate_loop(pick(r), lambda t: pick(self.decode_step(t, cache, logits=want_logits)), max_new_tokens, eos_id)
     cache.check()
