@@ -235,6 +235,60 @@ int plm_attn_bwd_masked(const uint16_t* qkv, const uint16_t* out, const uint16_t
                         const float* rope_sin, const uint64_t* bits, const uint8_t* tile_class, int64_t batch_stride, uint16_t* dqkv,
                         float* delta, int64_t B, int64_t T, int64_t nh, int64_t hd, void* stream);
 
+/* ---- KV-cached generation -----
+ * Every argument check of these entry points comes before any HIP call.
+ * Cache layout: one bf16 buffer per layer, kv[B, Tmax, ld_kv] (ld_kv >= 2*nh*hd, a multiple of 8; sequence b starts at b * Tmax * ld_kv).
+ * Row (b, j) holds the k | v column blocks of token j of sequence b: columns [nh*hd, 3*nh*hd) of that layer's ROTATED qkv row, the bits
+ * plm_qkv_rope_bf16 wrote.  head_dim is 32, 64 or 128.
+ *
+ * plm_kv_append_rope: one token per sequence.  qkv bf16 [B, ld_qkv] is the UN-rotated projection (q | k | v, 3*nh*hd columns); pos
+ * int32[B]; rope_cos / rope_sin fp32 [rope_T, hd/2].  For every sequence with 0 <= pos[b] < min(Tmax, rope_T): q and k are rotated at
+ * position pos[b] with the arithmetic of plm_rope_qk (same bits), rotated q goes to q_out bf16 [B, nh*hd], rotated k and the untouched v
+ * to kv[b, pos[b], 0 : 2*nh*hd].  Any other pos[b] writes nothing for that sequence and sets the caller-zeroed status[0] to 1 (the
+ * convention of plm_attn_doc_start_from_mask).  One launch.  qkv, q_out, kv and the tables must be 16-byte aligned. */
+int plm_kv_append_rope(const uint16_t* qkv, int64_t ld_qkv, const int32_t* pos, const float* rope_cos, const float* rope_sin,
+                       int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t Tmax, int64_t nh,
+                       int64_t hd, void* stream);
+
+/* plm_attn_decode: attention of one (rotated) query row per sequence over its cache.  q bf16 [B, nh*hd]; lens int32[B], clamped to
+ * [0, Tmax]: sequence b, head h attends keys 0 .. lens[b]-1, and cache rows at and beyond lens[b] are never read.  Writes out bf16
+ * [B, nh*hd] and, unless NULL, lse fp32 [B, nh]: the base-2 log-sum-exp of the scaled scores, plm_attn_fwd's convention, comparable with
+ * row lens[b]-1 of a full causal forward.  lens[b] == 0 gives out = 0 and lse = +INFINITY (the masked kernels' rule for a row with no key).
+ * Flash-decoding: a (B*nh) x S grid walks S contiguous key ranges per (sequence, head) and leaves fp32 partials (max, sum, acc[hd]) in the
+ * workspace; a second launch combines them in split order.  No atomics: bit-reproducible, and for a fixed S independent of the other
+ * sequences of the batch.  splits: 0 = automatic (a function of B, nh, Tmax and the CU count only - lens is never read back), 1..64
+ * forced.  workspace: plm_attn_decode_workspace_bytes(B, nh, hd, Tmax, splits) bytes for the same splits argument, 16-byte aligned,
+ * caller-owned (the query returns 0 for arguments the launch refuses).  NULL pointers (lse excepted), a head_dim other than 32 / 64 /
+ * 128, bases that are not 16-byte aligned, splits outside 0..64 give PLM_E_INVALID and a short workspace PLM_E_WORKSPACE before anything
+ * is launched. */
+size_t plm_attn_decode_workspace_bytes(int64_t B, int64_t nh, int64_t hd, int64_t Tmax, int splits);
+int plm_attn_decode(const uint16_t* q, const uint16_t* kv, int64_t ld_kv, const int32_t* lens, uint16_t* out, float* lse, int64_t B,
+                    int64_t Tmax, int64_t nh, int64_t hd, int splits, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- temperature / top-k / top-p sampling of one token per row -----
+ * Every argument check comes before any HIP call.
+ * logits bf16 [B, ld] (ld >= V; any 2-byte aligned base and any ld: columns >= V are never loaded); u fp32 [B], one uniform per row,
+ * clamped on the device (NaN or negative -> 0, >= 1 -> the largest float below 1).  One launch, one workgroup per row, no workspace;
+ * row b's outputs depend on row b and u[b] alone, and the same inputs give the same bits on every run (integer histograms and 64-bit
+ * fixed-point sums only: no result depends on the order in which anything arrives).
+ *
+ * The rule, in this order.  A NaN, -inf (or +inf: outside the contract) logit has weight 0, is never kept and never chosen.
+ *   temperature  w_i = exp((x_i - x_max) / temperature), fp32; x_max the largest finite logit of the row.
+ *   top-k        by VALUE: with v_k the top_k-th largest value, every i with x_i >= v_k stays - all ties with the k-th value included.
+ *                top_k = 0 or top_k >= V: off.
+ *   top-p        by VALUE CLASS: mass(t) = sum of w_i over the top-k survivors with x_i >= t, as a share of their total; t* is the
+ *                largest value present with mass(t*) >= top_p; every survivor with x_i >= t* stays.  Equal logits go in or out together;
+ *                the maximum's class always stays.  top_p = 1: off.
+ *   draw         over the kept columns in ascending index order, C_i the running sum of w, Z the last C: the lowest kept i with
+ *                C_i > u * Z.
+ * Outputs: tok int64 [B], always in [0, V); logp fp32 [B] = log softmax(x)[tok] over all V raw logits at temperature 1 (the model's
+ * log-probability); unless NULL, n_kept int32 [B] = the size of the kept set and cutoff fp32 [B] = its lowest raw logit.  A row without
+ * any finite logit gives tok = 0, n_kept = 0, logp = cutoff = NaN.
+ * PLM_E_INVALID before anything is launched for: a NULL pointer (n_kept and cutoff excepted), B < 1, V < 1 or V >= 2^31, ld < V, a
+ * logits base that is not 2-byte aligned, a temperature that is not finite or <= 0, top_k < 0, top_p outside (0, 1]. */
+int plm_sample_logits_bf16(const uint16_t* logits, int64_t ld, const float* u, float temperature, int64_t top_k, float top_p,
+                           int64_t* tok, float* logp, int32_t* n_kept, float* cutoff, int64_t B, int64_t V, void* stream);
+
 /* ---- fused cross-entropy forward+backward (engine/engine.py:81,111) -----
  * logits bf16[M, ld] (row stride ld >= V) are OVERWRITTEN with dlogits = (softmax - onehot) * grad_scale
  * (grad_scale = g/M); pad columns V..ld are set to zero so the buffer can feed a GEMM with K = ld.
@@ -256,6 +310,26 @@ int plm_mean_f32(const float* x, float* out, int64_t n, void* stream);
 size_t plm_head_score_workspace_bytes(int64_t M, int64_t V, int64_t K);
 int plm_head_score_bf16(const uint16_t* Y, int64_t ldy, const uint16_t* W, int64_t ldw, const int64_t* targets, float* nll,
                         float* lse, int64_t M, int64_t V, int64_t K, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- prediction head -----
+ * Per row of l = bf16(Y[M,K] W[V,K]^T) - the logits plm_gemm_bf16_nt would store and plm_head_score_bf16 reduces: same tile shape,
+ * same K order, same rounding - WITHOUT ever storing them:
+ *   pred    int64[M]  column of the largest logit, the lowest column among equal ones; always in [0, V), also for a row with NaN
+ *   logp    fp32[M]   log softmax(l)[pred] = max(l) - lse  (<= 0)
+ *   entropy fp32[M]   lse - sum_i softmax(l)_i l_i, in nats                                   (may be NULL)
+ *   nll     fp32[M]   lse - l[target], 0 for a target outside [0, V)                          (may be NULL; needs targets)
+ *   lse     fp32[M]   logsumexp(l)                                                            (may be NULL)
+ * nll and lse carry the bits plm_head_score_bf16 returns for the same operands.  targets int64[M] may be NULL (then nll must be).
+ * The persistent NT kernel reduces every output tile to one 16-byte record per row (max, sum-exp, sum e^(l-max) (l-max), column of
+ * the first maximum) and a second launch combines a row's records in a fixed order.  No gradient is produced.
+ * workspace: plm_head_predict_workspace_bytes(M, V, K) bytes (about M * ceil(V / 128) * 16), 16-byte aligned, caller-owned.
+ * NULL pointers, K % 64 != 0, row strides that are not multiples of 8, Y / W that are not 16-byte aligned give PLM_E_INVALID and a
+ * short workspace PLM_E_WORKSPACE before anything is launched.  Shapes that plm_gemm_bf16_nt serves with a 128x128 kernel (M < 512,
+ * V % 8 != 0) go through that kernel, 256 rows of logits at a time inside the workspace.  Deterministic (no atomics). */
+size_t plm_head_predict_workspace_bytes(int64_t M, int64_t V, int64_t K);
+int plm_head_predict_bf16(const uint16_t* Y, int64_t ldy, const uint16_t* W, int64_t ldw, const int64_t* targets, int64_t* pred,
+                          float* logp, float* entropy, float* nll, float* lse, int64_t M, int64_t V, int64_t K, void* workspace,
+                          size_t workspace_bytes, void* stream);
 
 /* ---- device-scalar scaling (chunked lm_head + cross-entropy, models/transformer.py:114 + engine/engine.py:111,118)
  * The chunked head runs its dX / dW GEMMs inside forward, before autograd hands over the upstream gradient g

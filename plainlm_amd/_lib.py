@@ -12,9 +12,6 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libplainlm_hip.so')
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'plainlm_hip.h')
-EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'plainlm_hip_ext.h')
-GEN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'plainlm_hip_gen.h')
-SAMPLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'plainlm_hip_sample.h')
 
 _lib = None
 
@@ -109,10 +106,16 @@ SIGNATURES = {
   'plm_attn_mask_pack': (_I, [_P, _I64, _P, _P, _I64, _I64, _P]),
   'plm_attn_fwd_masked': (_I, [_P, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _P]),
   'plm_attn_bwd_masked': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _P]),
+  'plm_kv_append_rope': (_I, [_P, _I64, _P, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
+  'plm_attn_decode_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I]),
+  'plm_attn_decode': (_I, [_P, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
+  'plm_sample_logits_bf16': (_I, [_P, _I64, _P, _F, _I64, _F, _P, _P, _P, _P, _I64, _I64, _P]),
   'plm_ce_fwd_bwd': (_I, [_P, _P, _P, _I64, _I64, _I64, _F, _P]),
   'plm_mean_f32': (_I, [_P, _P, _I64, _P]),
   'plm_head_score_workspace_bytes': (_SZ, [_I64, _I64, _I64]),
   'plm_head_score_bf16': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
+  'plm_head_predict_workspace_bytes': (_SZ, [_I64, _I64, _I64]),
+  'plm_head_predict_bf16': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
   'plm_scale_bf16': (_I, [_P, _I64, _P, _P]),
   'plm_axpy_f32': (_I, [_P, _P, _I64, _P, _I, _P]),
   'plm_sumsq_f32': (_I, [_P, _I64, _P, _P, _P]),
@@ -136,50 +139,11 @@ SIGNATURES = {
 }
 
 
-# the same for include/plainlm_hip_ext.h (additions that do not move plm_version(); see that header for why it is a file of its own)
-EXT_SIGNATURES = {
-  'plm_head_predict_workspace_bytes': (_SZ, [_I64, _I64, _I64]),
-  'plm_head_predict_bf16': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
-}
-
-
-# the same for include/plainlm_hip_gen.h (KV-cached generation; a file of its own for the ext header's reason)
-GEN_SIGNATURES = {
-  'plm_kv_append_rope': (_I, [_P, _I64, _P, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
-  'plm_attn_decode_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I]),
-  'plm_attn_decode': (_I, [_P, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
-}
-
-# the same for include/plainlm_hip_sample.h (on-device sampling; a file of its own for the ext header's reason)
-SAMPLE_SIGNATURES = {
-  'plm_sample_logits_bf16': (_I, [_P, _I64, _P, _F, _I64, _F, _P, _P, _P, _P, _I64, _I64, _P]),
-}
-
-
-def _declared(path):
-  with open(path) as f:
-    src = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
-  return sorted(set(re.findall(r'\b(plm_[a-z0-9_]+)\s*\(', src)))
-
-
 def header_functions():
   """Names of all functions declared in include/plainlm_hip.h."""
-  return _declared(HEADER_PATH)
-
-
-def ext_header_functions():
-  """Names of all functions declared in include/plainlm_hip_ext.h."""
-  return _declared(EXT_HEADER_PATH)
-
-
-def gen_header_functions():
-  """Names of all functions declared in include/plainlm_hip_gen.h."""
-  return _declared(GEN_HEADER_PATH)
-
-
-def sample_header_functions():
-  """Names of all functions declared in include/plainlm_hip_sample.h."""
-  return _declared(SAMPLE_HEADER_PATH)
+  with open(HEADER_PATH) as f:
+    src = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
+  return sorted(set(re.findall(r'\b(plm_[a-z0-9_]+)\s*\(', src)))
 
 
 def load():
@@ -193,25 +157,9 @@ def load():
       '(or __graft_entry__.build()). plainlm_amd has no CPU fallback.')
   lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
   for name, (res, args) in SIGNATURES.items():
-    fn = getattr(lib, name)  # AttributeError -> symbol missing, loud by construction
-    fn.restype = res
-    fn.argtypes = args
-  for name, (res, args) in EXT_SIGNATURES.items():
     fn = getattr(lib, name, None)
-    if fn is None:  # the ABI number does not move for the ext header: a library from before it would pass the version check below
-      raise RuntimeError(f'{LIB_PATH} lacks {name} (include/plainlm_hip_ext.h): rebuild it (make -C plainlm_amd/csrc)')
-    fn.restype = res
-    fn.argtypes = args
-  for name, (res, args) in GEN_SIGNATURES.items():
-    fn = getattr(lib, name, None)
-    if fn is None:  # as above: the ABI number does not move for the gen header either
-      raise RuntimeError(f'{LIB_PATH} lacks {name} (include/plainlm_hip_gen.h): rebuild it (make -C plainlm_amd/csrc)')
-    fn.restype = res
-    fn.argtypes = args
-  for name, (res, args) in SAMPLE_SIGNATURES.items():
-    fn = getattr(lib, name, None)
-    if fn is None:  # as above: the ABI number does not move for the sample header either
-      raise RuntimeError(f'{LIB_PATH} lacks {name} (include/plainlm_hip_sample.h): rebuild it (make -C plainlm_amd/csrc)')
+    if fn is None:  # the ABI number did not move for every addition: a library from before one would pass the version check below
+      raise RuntimeError(f'{LIB_PATH} lacks {name} (include/plainlm_hip.h): rebuild it (make -C plainlm_amd/csrc)')
     fn.restype = res
     fn.argtypes = args
   got = lib.plm_version()

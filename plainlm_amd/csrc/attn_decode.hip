@@ -11,7 +11,7 @@
 // of what the other sequences hold.
 #include "plm_device.h"
 
-#include "../../include/plainlm_hip_gen.h"
+#include "../../include/plainlm_hip.h"
 
 #define DEC_THREADS 256
 #define DEC_WAVES (DEC_THREADS / PLM_WAVE)

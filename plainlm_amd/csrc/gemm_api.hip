@@ -3,7 +3,7 @@
 // file (gemm_launch.h): no kernel lives here, and no kernel file decides anything.
 #include <initializer_list>
 
-#include "../../include/plainlm_hip_ext.h"
+#include "../../include/plainlm_hip.h"
 #include "gemm_launch.h"
 
 static int g_num_cus = 0;
@@ -332,7 +332,7 @@ extern "C" int plm_head_score_bf16(const uint16_t* Y, int64_t ldy, const uint16_
 }
 
 // =============================================================================================
-// Prediction head (include/plainlm_hip_ext.h):  pred[M], logp[M], entropy[M] (and nll / lse as above) without the logits
+// Prediction head (include/plainlm_hip.h):  pred[M], logp[M], entropy[M] (and nll / lse as above) without the logits
 // =============================================================================================
 // Workspace: xt fp32[M] | then EITHER the 16-byte row records [ceil(V / BN)][M] of the persistent kernel's prediction mode OR the logits of
 // PLM_HS_CHUNK rows - plm_head_score_bf16's layout with records twice as large, sized for the narrowest tile (BN = 128) as well.

@@ -13,7 +13,7 @@
 
 #include "plm_device.h"
 
-#include "../../include/plainlm_hip_sample.h"
+#include "../../include/plainlm_hip.h"
 
 #define SMP_THREADS 1024
 #define SMP_WAVES (SMP_THREADS / PLM_WAVE)

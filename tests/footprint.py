@@ -17,8 +17,15 @@ Index-valued inputs (ids, targets, doc_start, plan words) get margins of two dif
 Margins: at least GUARD_ROWS rows of the buffer and at least 4096 bytes on each side; a flat buffer counts 16 bytes (one vector
 access) as its row.  With ld > cols the pad columns are margin unless a ``written`` / ``untouched`` mask claims them.  Payload bases
 are 16-byte aligned; ``misalign=True`` puts a base at 16 bytes past a 128-byte line.  Works on any torch device: the calibration in
-tests/test_footprint_host.py runs it on the CPU over Python stand-ins of a kernel."""
+tests/test_footprint_host.py runs it on the CPU over Python stand-ins of a kernel.
 
+The tests/test_footprint_*gpu.py files hold the cases, one file per subject: each fills a module-level ``CASES`` dict (id -> (entry
+points covered, case function, ...)) and runs its rows through ``run_on_gpu``.  ``L`` / ``P`` / ``call`` reach the library without the
+ops wrappers, which allocate exact-size tensors - what these tests must not do."""
+
+import ctypes as C
+
+import pytest
 import torch
 
 GUARD_ROWS = 264      # as GUARD of tests/test_gemm_parity_gpu.py: more than one tile of rows
@@ -235,3 +242,43 @@ def run_case(entry, case, device, sync=None):
         uniq.append(f)
     raise FootprintError(entry, uniq)
   return arenas
+
+
+# ---- what the GPU case files share
+def L():
+  from plainlm_amd import _lib
+  return _lib.load()
+
+
+def P(b, offset=0):
+  """Device pointer of an arena buffer or of a tensor (plus a byte offset), NULL for None."""
+  if b is None:
+    return C.c_void_p(0)
+  return C.c_void_p((b.ptr if isinstance(b, Buf) else b.data_ptr()) + offset)
+
+
+def call(name, *args):
+  from plainlm_amd import _lib, ops
+  _lib.check(getattr(L(), name)(*args, ops._stream()), name)
+
+
+def run_on_gpu(cid, entries, fn, env=None):
+  """run_case on the GPU for one row of a CASES table, under the row's environment switches; returns the two arenas."""
+  if not torch.cuda.is_available():
+    pytest.skip('no GPU')
+  from plainlm_amd import ops
+  with pytest.MonkeyPatch.context() as mp:
+    for k, v in (env or {}).items():
+      mp.setenv(k, v)
+    if env:
+      ops.reload_env()
+    try:
+      return run_case(f'{entries[0]} [{cid}]', fn, 'cuda', sync=torch.cuda.synchronize)
+    except RuntimeError as e:
+      if 'rc=-1' in str(e) or 'rc=-4' in str(e):   # a refused argument: an ordinary failure of this case
+        raise
+      pytest.exit(f'{cid}: {e}: a launch failed on the device, nothing more is started on it', returncode=3)
+    finally:
+      if env:
+        mp.undo()
+        ops.reload_env()

@@ -1,4 +1,4 @@
-"""CPU reference of the prediction head (include/plainlm_hip_ext.h plm_head_predict_bf16): what the GPU tests
+"""CPU reference of the prediction head (include/plainlm_hip.h plm_head_predict_bf16): what the GPU tests
 compare against, and a plain fp32 restatement of the kernel's tile-wise arithmetic that shows how much of the tests' bound the
 arithmetic itself uses.
 

@@ -1,4 +1,4 @@
-"""The sampling rule of DESIGN.md section 13 (include/plainlm_hip_sample.h) restated in fp64 numpy, for whole batches at once.
+"""The sampling rule of DESIGN.md section 13 (include/plainlm_hip.h) restated in fp64 numpy, for whole batches at once.
 
   temperature  w_i = exp((x_i - x_max) / tau); a NaN or infinite logit has weight 0, is never kept and never chosen
   top-k        by value: every i with x_i >= v_k, v_k the k-th largest value (all ties with it stay); k = 0 or k >= V is off

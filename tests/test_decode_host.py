@@ -1,7 +1,7 @@
-"""CPU tests (no GPU) of KV-cached generation: the three entry points of include/plainlm_hip_gen.h refuse bad arguments before any HIP
-call; the gen header, the library and _lib.GEN_SIGNATURES name the same functions while the two older headers and the ABI number stay
-where they were; the workspace query is positive and monotone; tests/decode_ref.py's split-and-combine restatement equals the unsplit
-softmax, empty splits included; and the host logic of generate (plainlm_amd/generate.py) on a fake step function."""
+"""CPU tests (no GPU) of KV-cached generation: its three entry points refuse bad arguments before any HIP call (the header, the
+binding table and the library are compared in tests/test_host_logic.py); the workspace query is positive and monotone;
+tests/decode_ref.py's split-and-combine restatement equals the unsplit softmax, empty splits included; and the host logic of generate
+(plainlm_amd/generate.py) on a fake step function."""
 
 import ctypes as C
 import math
@@ -102,31 +102,6 @@ def test_kv_append_rope_refuses_bad_arguments_without_a_gpu():
     a = list(ok)
     a[i] = 0
     assert 'bad shape' in refused(*a)[1], i
-
-
-def test_gen_header_library_and_signature_table_agree_and_the_older_headers_did_not_move():
-  lib = _lib_loaded()
-  gen = _lib.gen_header_functions()
-  assert gen == ['plm_attn_decode', 'plm_attn_decode_workspace_bytes', 'plm_kv_append_rope']
-  assert set(gen) == set(_lib.GEN_SIGNATURES)
-  for name in gen:
-    assert hasattr(lib, name), name
-    assert getattr(lib, name).argtypes == _lib.GEN_SIGNATURES[name][1]
-  main, ext = _lib.header_functions(), _lib.ext_header_functions()
-  assert not set(gen) & (set(main) | set(ext))
-  assert len(main) == 64 and set(main) == set(_lib.SIGNATURES) and set(ext) == set(_lib.EXT_SIGNATURES) and len(ext) == 2
-  assert _lib.EXPECTED_ABI == 112 and lib.plm_version() == 112
-  with open(os.path.join(ROOT, 'plainlm_amd', 'csrc', 'Makefile')) as f:
-    mk = f.read()
-  assert 'plainlm_hip_gen.h' in mk and 'attn_decode.hip' in mk  # a changed declaration rebuilds the objects
-
-
-def test_load_names_a_library_without_the_gen_symbols(monkeypatch):
-  _lib_loaded()
-  monkeypatch.setattr(_lib, '_lib', None)
-  monkeypatch.setitem(_lib.GEN_SIGNATURES, 'plm_attn_decode_not_there', (C.c_int, []))
-  with pytest.raises(RuntimeError, match='plainlm_hip_gen.h.*rebuild'):
-    _lib.load()
 
 
 def test_decode_workspace_is_positive_and_monotone():

@@ -1,8 +1,7 @@
-"""Where the launches of include/plainlm_hip_gen.h read and write, on a real MI355X: the footprint guarantee of
-tests/test_footprint_gpu.py for the KV-cache entry points, which that file's table cannot list (its completeness test is tied to
-plainlm_hip.h).  Same machinery (tests/footprint.py: every buffer between margins, two runs that differ in one fill byte; W / I / C+R / U
-are bit equality), ragged shapes, padded row strides where the ABI takes one, and a completeness test of its own over the gen header."""
-import ctypes as C
+"""Where the launches of KV-cached generation read and write, on a real MI355X: the footprint cases of the KV-cache entry points.
+Same machinery as tests/test_footprint_gpu.py (tests/footprint.py: every buffer between margins, two runs that differ in one fill byte;
+W / I / C+R / U are bit equality), ragged shapes, padded row strides where the ABI takes one.  That file's completeness test counts
+these rows."""
 import os
 import sys
 
@@ -11,6 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import footprint as FP  # noqa: E402
+from footprint import L, P, call  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -18,29 +18,6 @@ BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 CASES = {}      # id -> (entry points covered, case function)
 B, NH, HD, TMAX = 5, 3, 64, 37
 D = NH * HD
-
-
-@pytest.fixture(scope='module')
-def ops():
-  if not torch.cuda.is_available():
-    pytest.skip('no GPU')
-  from plainlm_amd import ops as _ops
-  return _ops
-
-
-def L():
-  from plainlm_amd import _lib
-  return _lib.load()
-
-
-def P(b):
-  """Device pointer of an arena buffer, NULL for None."""
-  return C.c_void_p(0) if b is None else C.c_void_p(b.ptr)
-
-
-def call(name, *args):
-  from plainlm_amd import _lib, ops
-  _lib.check(getattr(L(), name)(*args, ops._stream()), name)
 
 
 def rnd(seed, *shape, dtype=F32):
@@ -99,20 +76,5 @@ _decode_cases()
 
 
 @pytest.mark.parametrize('cid', list(CASES))
-def test_footprint(ops, cid):
-  entries, fn = CASES[cid]
-  try:
-    FP.run_case(f'{entries[0]} [{cid}]', fn, 'cuda', sync=torch.cuda.synchronize)
-  except RuntimeError as e:
-    if 'rc=-1' in str(e) or 'rc=-4' in str(e):   # a refused argument: an ordinary failure of this case
-      raise
-    pytest.exit(f'{cid}: {e}: a launch failed on the device, nothing more is started on it', returncode=3)
-
-
-def test_every_gen_entry_point_is_in_the_table():
-  """Every function of include/plainlm_hip_gen.h has a row here (all of them launch, or size what a launch needs)."""
-  from plainlm_amd import _lib
-  covered = {e for entries, _ in CASES.values() for e in entries}
-  want = set(_lib.gen_header_functions())
-  assert want - covered == set(), sorted(want - covered)
-  assert covered - want == set(), sorted(covered - want)
+def test_footprint(cid):
+  FP.run_on_gpu(cid, *CASES[cid])

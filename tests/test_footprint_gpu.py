@@ -6,6 +6,8 @@ test_footprint_host.py shows on the CPU that each check fails for the defect it 
 per entry point.  Not here: plm_comm_* (several ranks), the two probes (already exact)."""
 import ctypes as C
 import functools
+import glob
+import importlib
 import os
 import sys
 
@@ -14,36 +16,12 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import footprint as FP  # noqa: E402
+from footprint import L, P, call  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 BF16, F32, I32, U8 = torch.bfloat16, torch.float32, torch.int32, torch.uint8
 CASES = {}      # id -> (entry points covered, case function, environment switches)
-
-
-@pytest.fixture(scope='module')
-def ops():
-  if not torch.cuda.is_available():
-    pytest.skip('no GPU')
-  from plainlm_amd import ops as _ops
-  return _ops
-
-
-def L():
-  from plainlm_amd import _lib
-  return _lib.load()
-
-
-def P(b):
-  """Device pointer of an arena buffer (or of a tensor), NULL for None."""
-  if b is None:
-    return C.c_void_p(0)
-  return C.c_void_p(b.ptr if isinstance(b, FP.Buf) else b.data_ptr())
-
-
-def call(name, *args):
-  from plainlm_amd import _lib, ops
-  _lib.check(getattr(L(), name)(*args, ops._stream()), name)
 
 
 def case(cid, entries, env=None):
@@ -810,32 +788,25 @@ _mx_cases()
 # the test
 # ======================================================================================================================================
 @pytest.mark.parametrize('cid', list(CASES))
-def test_footprint(ops, monkeypatch, cid):
-  entries, fn, env = CASES[cid]
-  for k, v in env.items():
-    monkeypatch.setenv(k, v)
-  if env:
-    ops.reload_env()
-  try:
-    FP.run_case(f'{entries[0]} [{cid}]', fn, 'cuda', sync=torch.cuda.synchronize)
-  except RuntimeError as e:
-    if 'rc=-1' in str(e) or 'rc=-4' in str(e):   # a refused argument: an ordinary failure of this case
-      raise
-    pytest.exit(f'{cid}: {e}: a launch failed on the device, nothing more is started on it', returncode=3)
-  finally:
-    if env:
-      monkeypatch.undo()
-      ops.reload_env()
+def test_footprint(cid):
+  FP.run_on_gpu(cid, *CASES[cid])
 
 
 NOT_HERE = ('plm_comm_', 'plm_probe_', 'plm_version', 'plm_last_error_string', 'plm_reload_env', 'plm_set_cu_reserve')
 
 
-def test_every_entry_point_is_in_the_table():
-  """Every function of include/plainlm_hip.h that launches something has a row (the comm entry points need several ranks, the probes are
-  exact already)."""
+def test_every_entry_point_has_a_footprint_case():
+  """Every function of include/plainlm_hip.h that launches something, or sizes what a launch needs, has a row in the CASES of some
+  tests/test_footprint_*gpu.py (the comm entry points need several ranks, the probes are exact already).  The files are found by
+  glob: a new entry point brings a case file of its own."""
   from plainlm_amd import _lib
-  covered = {e for entries, _, _ in CASES.values() for e in entries}
+  here = os.path.dirname(os.path.abspath(__file__))
+  files = sorted(glob.glob(os.path.join(here, 'test_footprint_*gpu.py')))
+  assert os.path.abspath(__file__) in files, files
+  covered = set()
+  for f in files:
+    mod = importlib.import_module(os.path.splitext(os.path.basename(f))[0])
+    covered |= {e for row in mod.CASES.values() for e in row[0]}
   want = {f for f in _lib.header_functions() if not f.startswith(NOT_HERE)}
   assert want - covered == set(), sorted(want - covered)
   assert covered - want == set(), sorted(covered - want)

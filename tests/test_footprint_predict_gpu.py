@@ -1,8 +1,7 @@
-"""Where the launches of include/plainlm_hip_ext.h read and write, on a real MI355X: the footprint guarantee of
-tests/test_footprint_gpu.py for the entry points that file's table cannot list (its completeness test is tied to plainlm_hip.h).
-Same machinery (tests/footprint.py: every buffer between margins, two runs that differ in one fill byte; W / I / C+R / U are bit
-equality), same shapes and strides as the scoring head's rows there, and a completeness test of its own over the ext header."""
-import ctypes as C
+"""Where the launches of the prediction head read and write, on a real MI355X: the footprint cases of plm_head_predict_bf16 and its
+workspace query.  Same machinery as tests/test_footprint_gpu.py (tests/footprint.py: every buffer between margins, two runs that differ
+in one fill byte; W / I / C+R / U are bit equality), same shapes and strides as the scoring head's rows there.  That file's completeness
+test counts these rows."""
 import os
 import sys
 
@@ -11,34 +10,12 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import footprint as FP  # noqa: E402
+from footprint import L, P, call  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 BF16, F32, I64 = torch.bfloat16, torch.float32, torch.int64
 CASES = {}      # id -> (entry points covered, case function)
-
-
-@pytest.fixture(scope='module')
-def ops():
-  if not torch.cuda.is_available():
-    pytest.skip('no GPU')
-  from plainlm_amd import ops as _ops
-  return _ops
-
-
-def L():
-  from plainlm_amd import _lib
-  return _lib.load()
-
-
-def P(b):
-  """Device pointer of an arena buffer, NULL for None."""
-  return C.c_void_p(0) if b is None else C.c_void_p(b.ptr)
-
-
-def call(name, *args):
-  from plainlm_amd import _lib, ops
-  _lib.check(getattr(L(), name)(*args, ops._stream()), name)
 
 
 def rnd(seed, *shape, dtype=F32):
@@ -74,20 +51,5 @@ _head_predict_cases()
 
 
 @pytest.mark.parametrize('cid', list(CASES))
-def test_footprint(ops, cid):
-  entries, fn = CASES[cid]
-  try:
-    FP.run_case(f'{entries[0]} [{cid}]', fn, 'cuda', sync=torch.cuda.synchronize)
-  except RuntimeError as e:
-    if 'rc=-1' in str(e) or 'rc=-4' in str(e):   # a refused argument: an ordinary failure of this case
-      raise
-    pytest.exit(f'{cid}: {e}: a launch failed on the device, nothing more is started on it', returncode=3)
-
-
-def test_every_ext_entry_point_is_in_the_table():
-  """Every function of include/plainlm_hip_ext.h has a row here (all of them launch, or size what a launch needs)."""
-  from plainlm_amd import _lib
-  covered = {e for entries, _ in CASES.values() for e in entries}
-  want = set(_lib.ext_header_functions())
-  assert want - covered == set(), sorted(want - covered)
-  assert covered - want == set(), sorted(covered - want)
+def test_footprint(cid):
+  FP.run_on_gpu(cid, *CASES[cid])

@@ -1,10 +1,8 @@
-"""Where the launch of include/plainlm_hip_sample.h reads and writes, on a real MI355X: the footprint guarantee of
-tests/test_footprint_gpu.py for plm_sample_logits_bf16, which that file's table cannot list (its completeness test is tied to
-plainlm_hip.h).  Same machinery (tests/footprint.py: every buffer between margins, two runs that differ in one fill byte; W / I / C+R / U
-are bit equality).  The logits are a column window of a wider buffer: the base is 3 columns (6 bytes) into a row, the row stride is odd,
-so every row starts at another 2-byte alignment; the columns before the window, the columns >= V and the pad hold the fill bytes - NaN in
-one run - and a result that took one in differs between the runs."""
-import ctypes as C
+"""Where the launch of plm_sample_logits_bf16 reads and writes, on a real MI355X.  Same machinery as tests/test_footprint_gpu.py
+(tests/footprint.py: every buffer between margins, two runs that differ in one fill byte; W / I / C+R / U are bit equality); that file's
+completeness test counts these rows.  The logits are a column window of a wider buffer: the base is 3 columns (6 bytes) into a row, the
+row stride is odd, so every row starts at another 2-byte alignment; the columns before the window, the columns >= V and the pad hold the
+fill bytes - NaN in one run - and a result that took one in differs between the runs."""
 import os
 import sys
 
@@ -13,30 +11,13 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import footprint as FP  # noqa: E402
+from footprint import P, call  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 BF16, F32, I32, I64 = torch.bfloat16, torch.float32, torch.int32, torch.int64
 CASES = {}      # id -> (entry points covered, case function)
 SKIP, TAIL, PAD = 3, 2, 8   # columns of the buffer before the window, after it, and the pad beyond the payload
-
-
-@pytest.fixture(scope='module')
-def ops():
-  if not torch.cuda.is_available():
-    pytest.skip('no GPU')
-  from plainlm_amd import ops as _ops
-  return _ops
-
-
-def P(b, offset=0):
-  """Device pointer of an arena buffer (plus a byte offset), NULL for None."""
-  return C.c_void_p(0) if b is None else C.c_void_p(b.ptr + offset)
-
-
-def call(name, *args):
-  from plainlm_amd import _lib, ops
-  _lib.check(getattr(_lib.load(), name)(*args, ops._stream()), name)
 
 
 def _cases():
@@ -67,14 +48,8 @@ _cases()
 
 
 @pytest.mark.parametrize('cid', list(CASES))
-def test_footprint(ops, cid):
-  entries, fn = CASES[cid]
-  try:
-    arenas = FP.run_case(f'{entries[0]} [{cid}]', fn, 'cuda', sync=torch.cuda.synchronize)
-  except RuntimeError as e:
-    if 'rc=-1' in str(e) or 'rc=-4' in str(e):   # a refused argument: an ordinary failure of this case
-      raise
-    pytest.exit(f'{cid}: {e}: a launch failed on the device, nothing more is started on it', returncode=3)
+def test_footprint(cid):
+  arenas = FP.run_on_gpu(cid, *CASES[cid])
   # the in-place role does not compare the payload with its pre-launch state: the window must still hold what was put there
   for ar in arenas:
     logits = next(b for b in ar.bufs if b.name == 'logits')
@@ -83,12 +58,3 @@ def test_footprint(ops, cid):
     assert ((tok.t >= 0) & (tok.t < V)).all()
   a, b = (next(x for x in ar.bufs if x.name == 'logits') for ar in arenas)
   assert torch.equal(a.body[:, SKIP:SKIP + V], b.body[:, SKIP:SKIP + V])
-
-
-def test_every_sample_entry_point_is_in_the_table():
-  """Every function of include/plainlm_hip_sample.h has a row here."""
-  from plainlm_amd import _lib
-  covered = {e for entries, _ in CASES.values() for e in entries}
-  want = set(_lib.sample_header_functions())
-  assert want - covered == set(), sorted(want - covered)
-  assert covered - want == set(), sorted(covered - want)

@@ -1,8 +1,7 @@
-"""CPU tests (no GPU) of the prediction head: the two entry points of include/plainlm_hip_ext.h refuse bad arguments before any HIP
-call, the ABI number and the main header did not move, the ext header, the library and _lib.EXT_SIGNATURES name the same functions,
-the workspace is a few per cent of the logits buffer, the kernels that carry the prediction mode meet the plain NT kernel's
-register / K-loop bar, the Python layers validate their options, and the reference arithmetic of tests/predict_ref.py is itself
-within a seventh of the GPU tests' bound."""
+"""CPU tests (no GPU) of the prediction head: its two entry points refuse bad arguments before any HIP call (the header, the binding
+table and the library are compared in tests/test_host_logic.py), the workspace is a few per cent of the logits buffer, the kernels that
+carry the prediction mode meet the plain NT kernel's register / K-loop bar, the Python layers validate their options, and the reference
+arithmetic of tests/predict_ref.py is itself within a seventh of the GPU tests' bound."""
 
 import ast
 import ctypes as C
@@ -33,7 +32,7 @@ def _lib_loaded():
 
 def test_head_predict_entry_point_refuses_bad_arguments_without_a_gpu():
   lib = _lib_loaded()
-  assert lib.plm_version() == 112  # the ext header's additions do not move it
+  assert lib.plm_version() == 112  # the prediction head's additions did not move it
   p = lambda: C.c_void_p(0x100000)  # plausible, never dereferenced
   def refused(*args):
     rc = lib.plm_head_predict_bf16(*args)
@@ -59,31 +58,6 @@ def test_head_predict_entry_point_refuses_bad_arguments_without_a_gpu():
   need = lib.plm_head_predict_workspace_bytes(512, 1024, 768)
   rc, msg = refused(p(), 768, p(), 768, p(), p(), p(), p(), p(), p(), 512, 1024, 768, p(), need - 1, None)
   assert rc == -4 and 'workspace' in msg  # PLM_E_WORKSPACE
-
-
-def test_ext_header_library_and_signature_table_agree_and_the_main_header_did_not_move():
-  lib = _lib_loaded()
-  ext = _lib.ext_header_functions()
-  assert ext == ['plm_head_predict_bf16', 'plm_head_predict_workspace_bytes']
-  assert set(ext) == set(_lib.EXT_SIGNATURES)
-  for name in ext:
-    assert hasattr(lib, name), name
-    assert getattr(lib, name).argtypes == _lib.EXT_SIGNATURES[name][1]
-  # additive: the main header declares what the main table binds, none of the new names, and plm_version() is where it was
-  main = _lib.header_functions()
-  assert set(main) == set(_lib.SIGNATURES) and not set(main) & set(ext)
-  assert len(main) == 64 and 'plm_head_score_bf16' in main
-  assert _lib.EXPECTED_ABI == 112 and lib.plm_version() == 112
-  with open(os.path.join(ROOT, 'plainlm_amd', 'csrc', 'Makefile')) as f:
-    assert 'plainlm_hip_ext.h' in f.read()  # a changed declaration rebuilds the objects
-
-
-def test_load_names_a_library_without_the_ext_symbols(monkeypatch):
-  _lib_loaded()
-  monkeypatch.setattr(_lib, '_lib', None)
-  monkeypatch.setitem(_lib.EXT_SIGNATURES, 'plm_head_predict_not_there', (C.c_int, []))
-  with pytest.raises(RuntimeError, match='rebuild'):
-    _lib.load()
 
 
 def test_head_predict_workspace_is_positive_monotone_and_small():

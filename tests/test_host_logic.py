@@ -2,8 +2,10 @@
 mirror of the reference's module API has the right names/shapes/init/param groups, the product
 path refuses to run without a GPU, schedules and doc_start match the oracle."""
 
+import ctypes as C
 import json
 import os
+import re
 from collections import namedtuple
 
 import numpy as np
@@ -26,6 +28,140 @@ def test_library_exports_every_header_symbol():
   for n in names:
     assert hasattr(lib, n), n
   assert lib.plm_version() >= 100
+
+
+def _lib_loaded():
+  if not os.path.exists(_lib.LIB_PATH):
+    import __graft_entry__
+    __graft_entry__.build()
+  return _lib.load()
+
+
+def test_header_signature_table_and_library_exports_name_the_same_functions():
+  """include/plainlm_hip.h is the whole surface: what it declares, what _lib.SIGNATURES binds and what the built library exports under
+  plm_* are one set.  No count is pinned: an entry point is added by declaring it, adding its row and building."""
+  import shutil
+  import subprocess
+  lib = _lib_loaded()
+  nm = shutil.which('nm') or '/opt/rocm/llvm/bin/llvm-nm'
+  out = subprocess.run([nm, '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+  exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith('plm_')}
+  declared = set(_lib.header_functions())
+  assert declared == set(_lib.SIGNATURES), sorted(declared ^ set(_lib.SIGNATURES))
+  assert declared == exported, sorted(declared ^ exported)
+  for name in ('plm_head_predict_bf16', 'plm_head_predict_workspace_bytes', 'plm_attn_decode', 'plm_attn_decode_workspace_bytes',
+               'plm_kv_append_rope', 'plm_sample_logits_bf16', 'plm_head_score_bf16'):
+    assert name in declared, name
+  for name, (res, args) in _lib.SIGNATURES.items():
+    assert getattr(lib, name).restype == res and getattr(lib, name).argtypes == args, name
+  assert _lib.EXPECTED_ABI == 112 and lib.plm_version() == 112
+
+
+_C_SCALARS = {'int': C.c_int, 'int64_t': C.c_int64, 'float': C.c_float, 'size_t': C.c_size_t}
+_C_RETURNS = dict(_C_SCALARS, **{'void': None, 'const char*': C.c_char_p})
+_C_STRUCTS = {'plm_cast_item': _lib.CastItem, 'plm_optim_item': _lib.OptimItem, 'plm_optim_hparams': _lib.OptimHparams,
+              'plm_colsum_item': _lib.ColsumItem, 'plm_tn_problem': _lib.TnProblem, 'plm_mx_quant_item': _lib.MxQuantItem}
+
+
+def _header_declarations():
+  """name -> (return type, [parameter text]) of every function declared in include/plainlm_hip.h."""
+  with open(_lib.HEADER_PATH) as f:
+    src = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
+  src = re.sub(r'^\s*#.*$', '', src, flags=re.M)
+  src = re.sub(r'typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;', '', src, flags=re.S)   # the item structs: fields, not parameters
+  decls = {}
+  for stmt in src.split(';'):
+    m = re.search(r'([\w\s\*]+?)\b(plm_[a-z0-9_]+)\s*\((.*)\)\s*$', stmt, flags=re.S)
+    if not m:
+      continue
+    ret = re.sub(r'\s*\*', '*', ' '.join(m.group(1).split()))
+    params = [' '.join(a.split()) for a in m.group(3).split(',')]
+    assert m.group(2) not in decls, m.group(2)
+    decls[m.group(2)] = (ret, [] if params == ['void'] else params)
+  return decls
+
+
+def _allowed_ctypes(param):
+  """The ctypes a parameter of the header may be bound with."""
+  m = re.fullmatch(r'(const )?(\w+) ?(\*{0,2}) ?(\w+)(\[\d+\])?', param)
+  assert m, param
+  const, base, stars, _, array = m.groups()
+  depth = len(stars) + (1 if array else 0)
+  if depth == 0:
+    return {_C_SCALARS[base]}
+  if depth == 2:
+    return {C.c_void_p, C.POINTER(C.c_void_p)}
+  ok = {C.c_void_p}
+  if base in _C_STRUCTS:
+    ok.add(C.POINTER(_C_STRUCTS[base]))
+  if const and base == 'int64_t':
+    ok.add(C.POINTER(C.c_int64))
+  return ok
+
+
+def _abi_mismatches(signatures):
+  bad = []
+  decls = _header_declarations()
+  for name in sorted(set(decls) | set(signatures)):
+    if name not in decls or name not in signatures:
+      bad.append(f'{name}: not in both the header and the table')
+      continue
+    (ret, params), (res, args) = decls[name], signatures[name]
+    if _C_RETURNS[ret] is not res:
+      bad.append(f'{name}: returns {ret}, bound as {res}')
+    if len(params) != len(args):
+      bad.append(f'{name}: {len(params)} parameters, {len(args)} argtypes')
+      continue
+    bad += [f'{name}: parameter {i} `{p}` bound as {a}' for i, (p, a) in enumerate(zip(params, args)) if a not in _allowed_ctypes(p)]
+  return bad
+
+
+def test_signature_table_matches_the_header_types(monkeypatch):
+  """A wrong argtypes list corrupts memory instead of raising, so every row of _lib.SIGNATURES is compared with the declaration it binds:
+  return type, parameter count, scalars exactly (int / int64_t / float / size_t), and a pointer as c_void_p - or POINTER of the ctypes
+  mirror for an item struct, POINTER(c_int64) for const int64_t*, POINTER(c_void_p) for a T**; an array parameter counts as a pointer."""
+  assert len(_header_declarations()) == len(_lib.header_functions())   # the parser sees every declaration
+  assert _abi_mismatches(_lib.SIGNATURES) == []
+  # and the comparison bites: one argument dropped, one int64_t bound as int, a wrong return type, a pointer to the wrong struct
+  def reported(name, res, args):
+    with monkeypatch.context() as mp:
+      mp.setitem(_lib.SIGNATURES, name, (res, args))
+      return _abi_mismatches(_lib.SIGNATURES)
+  res, args = _lib.SIGNATURES['plm_attn_decode']
+  assert args[2] is C.c_int64
+  bad = reported('plm_attn_decode', res, args[:-1])
+  assert len(bad) == 1 and 'plm_attn_decode: 14 parameters, 13 argtypes' in bad[0], bad
+  bad = reported('plm_attn_decode', res, args[:2] + [C.c_int] + args[3:])
+  assert len(bad) == 1 and 'plm_attn_decode: parameter 2 `int64_t ld_kv`' in bad[0], bad
+  bad = reported('plm_attn_decode_workspace_bytes', C.c_int, _lib.SIGNATURES['plm_attn_decode_workspace_bytes'][1])
+  assert len(bad) == 1 and 'returns size_t' in bad[0], bad
+  bad = reported('plm_mx_quant_multi', C.c_int, [C.POINTER(_lib.CastItem), C.c_int, C.c_void_p])
+  assert len(bad) == 1 and 'plm_mx_quant_multi: parameter 0' in bad[0], bad
+  monkeypatch.delitem(_lib.SIGNATURES, 'plm_sample_logits_bf16')
+  assert _abi_mismatches(_lib.SIGNATURES) == ['plm_sample_logits_bf16: not in both the header and the table']
+
+
+def test_load_names_a_symbol_the_library_lacks(monkeypatch):
+  """The ABI number does not move for a purely additive entry point, so a stale library passes the version check: load() names the symbol."""
+  _lib_loaded()
+  monkeypatch.setattr(_lib, '_lib', None)
+  monkeypatch.setitem(_lib.SIGNATURES, 'plm_attn_decode_not_there', (C.c_int, []))
+  with pytest.raises(RuntimeError, match=r'plm_attn_decode_not_there.*include/plainlm_hip\.h.*rebuild it \(make -C plainlm_amd/csrc\)'):
+    _lib.load()
+
+
+def test_makefile_builds_every_kernel_file_and_rebuilds_on_a_changed_declaration():
+  import glob
+  csrc = os.path.join(os.path.dirname(_lib.LIB_PATH), 'csrc')
+  with open(os.path.join(csrc, 'Makefile')) as f:
+    mk = f.read()
+  srcs = re.search(r'^SRCS := (.*)$', mk, flags=re.M).group(1).split()
+  assert sorted(srcs) == sorted(os.path.basename(p) for p in glob.glob(os.path.join(csrc, '*.hip')))
+  hdrs = re.search(r'^HDRS := (.*)$', mk, flags=re.M).group(1)
+  rules = re.findall(r'^(\S+\.o): (.*)$', mk.replace('$(HDRS)', hdrs), flags=re.M)
+  assert {t for t, _ in rules} >= {'%.o', 'attn_causal.o', 'attn_doc.o', 'comm.o'}
+  for target, prereqs in rules:
+    assert '../../include/plainlm_hip.h' in prereqs.split(), target
 
 
 def _cfg(**over):

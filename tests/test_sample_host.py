@@ -1,7 +1,7 @@
 """CPU tests (no GPU) of on-device sampling: tests/sample_ref.py against the customary sort-based top-k / top-p code where no tie sits
-on a boundary, and its own tie rule where one does; plm_sample_logits_bf16 refuses bad arguments before any HIP call; the sample header,
-the library and _lib.SAMPLE_SIGNATURES name the same single function while the three older headers and the ABI number stay where they
-were; and the host logic of generate's sampling arguments (plainlm_amd/generate.py) with a fake step and a fake sampler."""
+on a boundary, and its own tie rule where one does; plm_sample_logits_bf16 refuses bad arguments before any HIP call (the header, the
+binding table and the library are compared in tests/test_host_logic.py); and the host logic of generate's sampling arguments
+(plainlm_amd/generate.py) with a fake step and a fake sampler."""
 
 import ctypes as C
 import os
@@ -158,30 +158,6 @@ def test_sample_logits_refuses_bad_arguments_without_a_gpu():
     a = list(ok)
     a[5] = tp
     assert 'top_p' in refused(*a), tp
-
-
-def test_sample_header_library_and_signature_table_agree_and_the_older_headers_did_not_move():
-  lib = _lib_loaded()
-  smp = _lib.sample_header_functions()
-  assert smp == ['plm_sample_logits_bf16'] and set(smp) == set(_lib.SAMPLE_SIGNATURES)
-  assert hasattr(lib, smp[0]) and getattr(lib, smp[0]).argtypes == _lib.SAMPLE_SIGNATURES[smp[0]][1]
-  main, ext, gen = _lib.header_functions(), _lib.ext_header_functions(), _lib.gen_header_functions()
-  assert not set(smp) & (set(main) | set(ext) | set(gen))
-  assert len(main) == 64 and set(main) == set(_lib.SIGNATURES)
-  assert len(ext) == 2 and set(ext) == set(_lib.EXT_SIGNATURES)
-  assert len(gen) == 3 and set(gen) == set(_lib.GEN_SIGNATURES)
-  assert _lib.EXPECTED_ABI == 112 and lib.plm_version() == 112
-  with open(os.path.join(ROOT, 'plainlm_amd', 'csrc', 'Makefile')) as f:
-    mk = f.read()
-  assert 'plainlm_hip_sample.h' in mk and 'sample.hip' in mk  # a changed declaration rebuilds the objects
-
-
-def test_load_names_a_library_without_the_sample_symbol(monkeypatch):
-  _lib_loaded()
-  monkeypatch.setattr(_lib, '_lib', None)
-  monkeypatch.setitem(_lib.SAMPLE_SIGNATURES, 'plm_sample_not_there', (C.c_int, []))
-  with pytest.raises(RuntimeError, match='plainlm_hip_sample.h.*rebuild'):
-    _lib.load()
 
 
 # ---- generate's sampling arguments -----------------------------------------------------------------------------------------------------
