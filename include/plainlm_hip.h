@@ -265,6 +265,40 @@ size_t plm_attn_decode_workspace_bytes(int64_t B, int64_t nh, int64_t hd, int64_
 int plm_attn_decode(const uint16_t* q, const uint16_t* kv, int64_t ld_kv, const int32_t* lens, uint16_t* out, float* lse, int64_t B,
                     int64_t Tmax, int64_t nh, int64_t hd, int splits, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- cache extension: a chunk of up to n tokens per sequence on top of a live cache -----
+ * Every argument check of these entry points comes before any HIP call.  The cache is the one above.  A chunk is n rows per sequence,
+ * row b*n + r = chunk row r of sequence b; lens0 int32[B] is the cache length before the chunk; n_new int32[B] is the number of real rows
+ * of every sequence's chunk, c_b = n_new[b] clamped to [0, n] - or NULL: c_b = n for every sequence.
+ *
+ * plm_kv_append_rope_rows: qkv bf16 [B*n, ld_qkv] is the UN-rotated projection.  For rows r < c_b: q and k are rotated at position
+ * lens0[b] + r with the arithmetic of plm_rope_qk (same bits), rotated q goes to q_out bf16 [B*n, nh*hd] row b*n + r, rotated k and the
+ * untouched v to kv[b, lens0[b] + r, 0 : 2*nh*hd].  Rows r >= c_b write no cache row and a q_out row of zeros: every byte of q_out is
+ * defined.  A sequence with lens0[b] < 0 or lens0[b] + c_b > min(Tmax, rope_T) is refused on the device: none of its cache rows is
+ * written, its q_out rows are zeros and the caller-zeroed status[0] is set to 1; the other sequences are unaffected.  One launch.
+ * PLM_E_INVALID before anything is launched: NULL pointers (n_new excepted), a head_dim other than 32 / 64 / 128, n < 1 or B*n >= 2^31,
+ * a bad shape, row strides that are not multiples of 8 or shorter than a row, qkv / q_out / kv / tables not 16-byte aligned.
+ *
+ * plm_attn_extend: q bf16 [B*n, nh*hd], already rotated (q_out above).  lens0 is clamped to [0, Tmax].  Query (b, r) with r < c_b attends
+ * keys 0 .. min(lens0[b] + r, Tmax - 1) inclusive - its own key, just appended, included.  Writes out bf16 [B*n, nh*hd] and, unless NULL,
+ * lse fp32 [B, nh, n]: the base-2 log-sum-exp of the scaled scores (plm_attn_fwd's convention), comparable with row lens0[b] + r of a full
+ * causal forward.  Rows r >= c_b give out = 0 and lse = +INFINITY.  Cache rows at and beyond lens0[b] + c_b are never loaded (they may
+ * hold anything, NaN included); q rows r >= c_b are never loaded either.
+ * The keys 0 .. lens0[b] + c_b - 1 of sequence b are cut into S contiguous ranges as plm_attn_decode cuts them; a
+ * (B*nh*ceil(n/128)) x S grid of MFMA workgroups (128 query rows x 64-key tiles) leaves fp32 partials (max, sum, acc[hd]) per (query row,
+ * split) in the workspace, and a second launch combines them in split order, skipping empty ones.  S = 1 writes out directly: one launch.
+ * No atomics: bit-reproducible, and for a forced S independent of the other sequences of the batch.  splits: 0 = automatic (a function of
+ * B, n, nh, Tmax and the CU count only - nothing is read back), 1..64 forced.  workspace: plm_attn_extend_workspace_bytes(B, n, nh, hd,
+ * Tmax, splits) bytes for the same splits argument, 16-byte aligned, caller-owned (the query returns 0 for arguments the launch refuses).
+ * NULL pointers (lse and n_new excepted), a head_dim other than 32 / 64 / 128, n < 1, B*n >= 2^31, bases that are not 16-byte aligned,
+ * splits outside 0..64 give PLM_E_INVALID and a short workspace PLM_E_WORKSPACE before anything is launched. */
+int plm_kv_append_rope_rows(const uint16_t* qkv, int64_t ld_qkv, const int32_t* lens0, const int32_t* n_new, const float* rope_cos,
+                            const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B,
+                            int64_t n, int64_t Tmax, int64_t nh, int64_t hd, void* stream);
+size_t plm_attn_extend_workspace_bytes(int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t Tmax, int splits);
+int plm_attn_extend(const uint16_t* q, const uint16_t* kv, int64_t ld_kv, const int32_t* lens0, const int32_t* n_new, uint16_t* out,
+                    float* lse, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, int splits, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 /* ---- temperature / top-k / top-p sampling of one token per row -----
  * Every argument check comes before any HIP call.
  * logits bf16 [B, ld] (ld >= V; any 2-byte aligned base and any ld: columns >= V are never loaded); u fp32 [B], one uniform per row,

@@ -109,6 +109,9 @@ SIGNATURES = {
   'plm_kv_append_rope': (_I, [_P, _I64, _P, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
   'plm_attn_decode_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I]),
   'plm_attn_decode': (_I, [_P, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
+  'plm_kv_append_rope_rows': (_I, [_P, _I64, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P]),
+  'plm_attn_extend_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I]),
+  'plm_attn_extend': (_I, [_P, _P, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
   'plm_sample_logits_bf16': (_I, [_P, _I64, _P, _F, _I64, _F, _P, _P, _P, _P, _I64, _I64, _P]),
   'plm_ce_fwd_bwd': (_I, [_P, _P, _P, _I64, _I64, _I64, _F, _P]),
   'plm_mean_f32': (_I, [_P, _P, _I64, _P]),

@@ -1,4 +1,5 @@
-"""KV-cached generation: the cache, and the host logic of ``Transformer.prefill / decode_step / generate``.
+"""KV-cached generation: the cache, and the host logic of ``Transformer.prefill / decode_step / generate``
+(and of ``Transformer.extend``, DESIGN.md section 14: a chunk of tokens per sequence on top of a live cache).
 
 Everything that can be stated without a GPU lives here as plain functions over tensors on any device - the length checks, the choice of
 the row a padded prompt is continued from, the token loop with its EOS freezing - so that tests/test_decode_host.py runs them on the CPU
@@ -29,6 +30,7 @@ class KVCache:
     self._pl[0] -= 1
     self.workspace = ops.attn_decode_workspace(B, n_heads, head_dim, Tmax, 0, device)  # automatic split count
     self.status = torch.zeros((1,), dtype=torch.int32, device=device)
+    self._extend_ws = {}  # chunk width n -> (workspace, bytes) of ops.attn_extend, made at the first extend of that width
 
   @property
   def lens(self):
@@ -46,11 +48,45 @@ class KVCache:
   def advance(self):
     self._pl += 1
 
+  def advance_by(self, n_new):
+    """Move [pos | lens] by n_new - an int32 [B] device tensor, or an int - with one in-place add (Transformer.extend, after its chunk)."""
+    self._pl += n_new
+
+  def extend_workspace(self, n):
+    """The (workspace, bytes) pair of ops.attn_extend for chunks of n rows (automatic split count): allocated at the first chunk of that
+    width and kept, shared by all layers."""
+    ws = self._extend_ws.get(n)
+    if ws is None:
+      ws = self._extend_ws[n] = ops.attn_extend_workspace(self.B, n, self.n_heads, self.head_dim, self.Tmax, 0, self.status.device)
+    return ws
+
   def check(self):
     """Raises if a decode step tried to append past the cache (or past the RoPE table); reads the device flag, so it waits for the GPU."""
     if int(self.status.item()) != 0:
       raise RuntimeError(f'KVCache: a decode step appended at a position outside [0, {self.Tmax}): that token was not stored '
                          '(prefill with a larger max_len)')
+
+
+def chunk_lens(token_lens, B, n, device):
+  """token_lens of Transformer.extend as (what advance_by takes, the int32 [B] device tensor the kernels take or None for "n
+  everywhere").  None: every sequence appends all n tokens.  Host integers (a sequence of B ints in [0, n], or a CPU tensor) are checked
+  here and copied to the device; an int32 [B] device tensor is never read back: it is clamped to [0, n] on the device (as the kernels
+  clamp it), so that the lengths move by what was appended and the gather of the last rows stays inside the chunk."""
+  if token_lens is None:
+    return int(n), None
+  if isinstance(token_lens, torch.Tensor) and token_lens.device.type != 'cpu':
+    if token_lens.dtype != torch.int32 or tuple(token_lens.shape) != (B,):
+      raise TypeError(f'extend: a device token_lens must be an int32 [{B}] tensor, got {token_lens.dtype} {tuple(token_lens.shape)}')
+    t = token_lens.clamp(0, int(n))
+    return t, t
+  vals = token_lens.tolist() if isinstance(token_lens, torch.Tensor) else list(token_lens)
+  vals = [int(v) for v in vals]
+  if len(vals) != B:
+    raise ValueError(f'extend: {len(vals)} token_lens for a batch of {B}')
+  if any(v < 0 or v > n for v in vals):
+    raise ValueError(f'extend: every token_lens must be in [0, {n}] (the token tensor\'s width), got {vals}')
+  t = torch.tensor(vals, dtype=torch.int32).to(device)
+  return t, t
 
 
 def pad4(n):

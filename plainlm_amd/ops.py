@@ -775,6 +775,86 @@ def attn_decode(q, kv, lens, nh, splits=0, want_lse=False, workspace=None):
   return (out, lse) if want_lse else out
 
 
+# ---- cache extension: a chunk of tokens per sequence on top of a live cache ------------------------------
+def _chunk_counts(n_new, B, name):
+  if n_new is not None:
+    _need(n_new, torch.int32, f'{name}.n_new', 1)
+    if n_new.shape[0] != B:
+      raise ValueError(f'{name}: n_new {tuple(n_new.shape)} does not fit the batch of {B}')
+  return n_new
+
+
+def kv_append_rope_rows(qkv, lens0, rope_cos, rope_sin, kv, nh, n_new=None, q_out=None, status=None):
+  """A chunk of n tokens per sequence: qkv bf16 [B*n, 3*nh*hd] UN-rotated (row b*n + r = chunk row r of sequence b; the row stride may
+  exceed the width), lens0 int32 [B] the cache lengths before the chunk, n_new int32 [B] the real rows of every chunk (clamped to
+  [0, n]; None: n everywhere).  Rows r < n_new[b] are rotated at position lens0[b] + r (rope_qk_'s bits): rotated q goes to q_out
+  [B*n, nh*hd], rotated k | untouched v into kv[b, lens0[b] + r].  Rows past n_new[b] write no cache row and zeros to q_out.  A sequence
+  with lens0[b] < 0 or lens0[b] + n_new[b] > min(Tmax, rope rows) stores nothing, gets zero q_out rows and sets status[0] = 1 (int32 [1],
+  zeroed by the caller; made here when absent).  Returns (q_out, status): status is a device tensor, the caller decides when to look."""
+  if not qkv.is_cuda:
+    raise RuntimeError('kv_append_rope_rows.qkv: tensor must live on the GPU (plainlm_amd has no CPU path)')
+  if qkv.dtype != BF16 or qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[1] % (3 * nh) != 0:
+    raise ValueError('kv_append_rope_rows.qkv: need a 2-D bf16 GPU tensor [B*n, 3*nh*hd] with unit inner stride')
+  hd = qkv.shape[1] // (3 * nh)
+  _need(lens0, torch.int32, 'kv_append_rope_rows.lens0', 1)
+  _need(rope_cos, F32, 'kv_append_rope_rows.rope_cos', 2)
+  _need(rope_sin, F32, 'kv_append_rope_rows.rope_sin', 2)
+  _need_kv(kv, nh, hd, 'kv_append_rope_rows.kv')
+  B = kv.shape[0]
+  if B < 1 or qkv.shape[0] < B or qkv.shape[0] % B != 0 or lens0.shape[0] != B or rope_cos.shape != rope_sin.shape or rope_cos.shape[1] != hd // 2:
+    raise ValueError('kv_append_rope_rows: qkv rows are not a multiple of the cache\'s batch, lens0 does not fit it, or the RoPE tables the head_dim')
+  n = qkv.shape[0] // B
+  _chunk_counts(n_new, B, 'kv_append_rope_rows')
+  q_out = torch.empty((B * n, nh * hd), dtype=BF16, device=qkv.device) if q_out is None else _need(q_out, BF16, 'kv_append_rope_rows.q_out', 2)
+  if tuple(q_out.shape) != (B * n, nh * hd):
+    raise ValueError(f'kv_append_rope_rows.q_out: need [{B * n}, {nh * hd}], got {tuple(q_out.shape)}')
+  status = torch.zeros((1,), dtype=torch.int32, device=qkv.device) if status is None else _need(status, torch.int32, 'kv_append_rope_rows.status')
+  _lib.check(_lib.load().plm_kv_append_rope_rows(_p(qkv), qkv.stride(0), _p(lens0), _p(n_new), _p(rope_cos), _p(rope_sin), rope_cos.shape[0],
+                                                 _p(q_out), _p(kv), kv.stride(1), _p(status), B, n, kv.shape[1], nh, hd, _stream()),
+             'plm_kv_append_rope_rows')
+  return q_out, status
+
+
+_extend_ws = {}
+
+
+def attn_extend_workspace(B, n, nh, hd, Tmax, splits, device):
+  """(uint8 workspace, bytes) of attn_extend for this shape and splits argument, cached per shape (and so per chunk width n)."""
+  key = (B, n, nh, hd, Tmax, int(splits), device)
+  ent = _extend_ws.get(key)
+  if ent is None:
+    nbytes = int(_lib.load().plm_attn_extend_workspace_bytes(B, n, nh, hd, Tmax, int(splits)))
+    if nbytes == 0:
+      raise ValueError(f'attn_extend: unsupported shape B={B} n={n} nh={nh} hd={hd} Tmax={Tmax} or splits={splits} (0 = automatic, 1..64)')
+    ent = _extend_ws[key] = (torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes)
+  return ent
+
+
+def attn_extend(q, kv, lens0, nh, n_new=None, splits=0, want_lse=False, workspace=None):
+  """Attention of a chunk of n rotated query rows per sequence over its cache: q bf16 [B*n, nh*hd] (kv_append_rope_rows's q_out), kv bf16
+  [B, Tmax, 2*nh*hd] with the chunk already appended, lens0 int32 [B] the lengths BEFORE the chunk (clamped to [0, Tmax]), n_new int32 [B]
+  the real rows of every chunk (None: n).  Row r < n_new[b] of sequence b attends keys 0 .. lens0[b] + r; rows past n_new[b] give out = 0
+  and lse = +inf.  splits: 0 automatic (from the shape alone) | 1..64 forced.  Returns out bf16 [B*n, nh*hd], or (out, lse fp32
+  [B, nh, n], base 2 like attn_fwd's) with want_lse.  workspace: (uint8 tensor, bytes) of attn_extend_workspace for the same splits, else
+  a cached one per shape."""
+  _need(q, BF16, 'attn_extend.q', 2)
+  hd = q.shape[1] // nh
+  _need_kv(kv, nh, hd, 'attn_extend.kv')
+  _need(lens0, torch.int32, 'attn_extend.lens0', 1)
+  B = kv.shape[0]
+  if q.shape[1] != nh * hd or B < 1 or q.shape[0] < B or q.shape[0] % B != 0 or lens0.shape[0] != B:
+    raise ValueError(f'attn_extend: q {tuple(q.shape)}, kv {tuple(kv.shape)}, lens0 {tuple(lens0.shape)} do not fit nh={nh}')
+  n = q.shape[0] // B
+  _chunk_counts(n_new, B, 'attn_extend')
+  Tmax = kv.shape[1]
+  ws, nbytes = attn_extend_workspace(B, n, nh, hd, Tmax, splits, q.device) if workspace is None else workspace
+  out = torch.empty((B * n, nh * hd), dtype=BF16, device=q.device)
+  lse = torch.empty((B, nh, n), dtype=F32, device=q.device) if want_lse else None
+  _lib.check(_lib.load().plm_attn_extend(_p(q), _p(kv), kv.stride(1), _p(lens0), _p(n_new), _p(out), _p(lse), B, n, Tmax, nh, hd, int(splits),
+                                         _p(ws), nbytes, _stream()), 'plm_attn_extend')
+  return (out, lse) if want_lse else out
+
+
 SampleLogits = collections.namedtuple('SampleLogits', ['tokens', 'logprob', 'n_kept', 'cutoff'])
 
 

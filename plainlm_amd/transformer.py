@@ -610,6 +610,76 @@ class Transformer(nn.Module):
       r = ops.head_predict(y, wb)
     return HeadPrediction(r.pred, r.logp, r.entropy, None)
 
+  # ---- cache extension ------------------------------------------------------------------------------------
+  def new_cache(self, B, max_len=None):
+    """An empty KVCache for B sequences (lens 0) of max_len rows each (default and at most cfg.seq_len): the start of a chunked prefill
+    through ``extend``."""
+    if self.cfg.linear_precision == 'mxfp8':
+      raise NotImplementedError("Transformer.new_cache: linear_precision: mxfp8 has no cached decode path (the decode step runs the bf16 shadows)")
+    Tmax = self.cfg.seq_len if max_len is None else int(max_len)
+    if int(B) < 1 or Tmax < 1 or Tmax > self.cfg.seq_len:
+      raise ValueError(f'new_cache: need B >= 1 and 1 <= max_len <= cfg.seq_len {self.cfg.seq_len}, got B={B} max_len={Tmax}')
+    device = self.lm_head.weight.device
+    if device.type != 'cuda':
+      raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (the model is on CPU; there is no CPU fallback)')
+    return G.KVCache(self.n_layers, int(B), Tmax, self.cfg.n_heads, self.head_dim, device)
+
+  @torch.compiler.disable
+  def extend(self, tokens, cache, token_lens=None, logits=False, all_rows=False):
+    """Append a chunk of tokens to a live cache: tokens int64 [B, n], right-padded; sequence b's first token_lens[b] tokens are appended
+    at positions cache.lens[b] .. (then lens += token_lens, on the device).  token_lens: None (all n), host integers in [0, n], or an
+    int32 [B] device tensor (clamped to [0, n], never read back).  A new user turn on top of a cached conversation, one chunk of a long
+    prompt's prefill (start from ``new_cache``), or k drafted tokens to verify (roll back with ``cache.set_lens``).
+    Returns the HeadPrediction [B] of the token after each sequence's last appended row (row token_lens[b] - 1; a sequence that appended
+    nothing gets row 0's, which means nothing) - with logits=True the bf16 logits [B, V] of that row; with all_rows=True the [B, n]
+    predictions, or [B, n, V] logits, of every chunk row (rows at and beyond token_lens[b] belong to padding and mean nothing).
+    The Block structure as decode_step runs it, through ops calls on the bf16 shadows at M = B * n: the same launches as one decode step,
+    whatever n.  A chunk that does not fit the cache (or the RoPE table) stores nothing for that sequence and surfaces through
+    ``cache.check()``.  Runs under no_grad."""
+    if isinstance(tokens, torch.Tensor) and (tokens.dim() != 2 or tokens.shape[0] != cache.B or tokens.shape[1] < 1):
+      raise ValueError(f'extend: tokens {tuple(tokens.shape)} are not a [B, n] chunk for the cache\'s batch of {cache.B}')
+    self._check_decode('extend', tokens)
+    if tokens.dim() != 2:
+      raise TypeError('inputs must be an int64 [B, n] tensor')
+    if len(cache.kv) != self.n_layers or cache.n_heads != self.cfg.n_heads or cache.head_dim != self.head_dim:
+      raise ValueError('extend: the cache was made for another model shape (layers, heads or head_dim differ)')
+    B, n = tokens.shape
+    nh = self.cfg.n_heads
+    with torch.no_grad():
+      adv, n_new = G.chunk_lens(token_lens, B, n, tokens.device)
+      self.refresh_shadows()
+      rope = self._rope(tokens.device)
+      ws = cache.extend_workspace(n)
+      lens0 = cache.lens  # the lengths before the chunk: what every layer's append and attention see; moved once, after the last layer
+      x = ops.embed_fwd(tokens.reshape(-1).contiguous(), self.embed_tokens.weight)
+      branch = None
+      for i, layer in enumerate(self.layers):
+        xo, n1, _ = ops.rmsnorm_fwd(x, layer.attn_norm.weight, layer.attn_norm.eps, branch=branch)
+        x = x if xo is None else xo
+        qkv = ops.gemm_nt(n1, layer.attn.w_qkv.shadow()[0])
+        q, _ = ops.kv_append_rope_rows(qkv, lens0, rope[0], rope[1], cache.kv[i], nh, n_new=n_new, status=cache.status)
+        a = ops.attn_extend(q, cache.kv[i], lens0, nh, n_new=n_new, workspace=ws)
+        a = ops.gemm_nt(a, layer.attn.w_out.shadow()[0])
+        x, n2, _ = ops.rmsnorm_fwd(x, layer.mlp_norm.weight, layer.mlp_norm.eps, branch=a)
+        u = ops.gemm_nt(n2, layer.mlp.fc1.shadow()[0])
+        act = ops.swiglu_fwd(u) if isinstance(layer.mlp, GLU) else ops.act_fwd(u, layer.mlp.kind)
+        branch = ops.gemm_nt(act, layer.mlp.fc2.shadow()[0])
+      _, y, _ = ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps, branch=branch)
+      cache.advance_by(adv)
+      wb, _ = self.lm_head.shadow()
+      if all_rows:
+        shape = (B, n)
+      else:
+        shape = (B,)
+        if n_new is None:
+          y = y.view(B, n, self.cfg.dim)[:, -1].contiguous()
+        else:
+          y = G.last_rows(y, B, n, n_new.clamp(min=1))
+      if logits:
+        return ops.gemm_nt(y, wb).view(shape + (self.cfg.vocab_size,))
+      r = ops.head_predict(y, wb)
+    return HeadPrediction(r.pred.view(shape), r.logp.view(shape), r.entropy.view(shape), None)
+
   @torch.compiler.disable
   def generate(self, prompt, max_new_tokens, prompt_lens=None, eos_id=None, sample=None, return_logprobs=False, temperature=None,
                top_k=None, top_p=None, seed=None):
