@@ -1,9 +1,10 @@
-"""KV-cached generation: the cache, and the host logic of ``Transformer.prefill / decode_step / generate``
-(and of ``Transformer.extend``, DESIGN.md section 14: a chunk of tokens per sequence on top of a live cache).
+"""KV-cached generation (DESIGN.md sections 12 and 14): the cache, and the host logic of ``Transformer.prefill / decode_step / extend /
+generate`` (``extend``: a chunk of tokens per sequence on top of a live cache).
 
 Everything that can be stated without a GPU lives here as plain functions over tensors on any device - the length checks, the choice of
 the row a padded prompt is continued from, the token loop with its EOS freezing - so that tests/test_decode_host.py runs them on the CPU
-with a fake step function.  The kernels are reached through ops.kv_append_rope / ops.attn_decode from transformer.py.  On-device
+with a fake step function.  The kernels are reached through two ops per cached step from transformer.py: ops.kv_append_rope /
+ops.attn_decode for one token per sequence, ops.kv_append_rope_rows / ops.attn_extend for a chunk.  On-device
 sampling adds the argument rules (check_sampling), the one draw of uniforms per call (draw_uniforms) and the
 per-step pick (sampling_pick over ops.sample_logits).
 """
@@ -19,7 +20,7 @@ FINISH_CHECK_EVERY = 16  # generate: the one device-to-host read of the loop (ha
 
 class KVCache:
   """Per-layer ``kv`` bf16 [B, Tmax, 2*dim] (row (b, j): the k | v columns of token j's rotated qkv row), ``lens`` int32 [B] on the
-  device, one decode workspace shared by all layers, and the status flag of the append kernel (checked by ``check``)."""
+  device, the attention workspaces (shared by all layers), and the status flag of the append kernel (checked by ``check``)."""
 
   def __init__(self, n_layers, B, Tmax, n_heads, head_dim, device):
     dim = n_heads * head_dim
@@ -28,9 +29,10 @@ class KVCache:
     # [pos | lens] = [lens - 1 | lens] during a decode step: one in-place add per step moves both, every layer reads the same pair
     self._pl = torch.zeros((2, B), dtype=torch.int32, device=device)
     self._pl[0] -= 1
-    self.workspace = ops.attn_decode_workspace(B, n_heads, head_dim, Tmax, 0, device)  # automatic split count
     self.status = torch.zeros((1,), dtype=torch.int32, device=device)
-    self._extend_ws = {}  # chunk width n -> (workspace, bytes) of ops.attn_extend, made at the first extend of that width
+    # (workspace, bytes) pairs at the automatic split count: key 0 is ops.attn_decode's, made here; key n >= 1 ops.attn_extend's for
+    # chunks of n rows, made at the first extend of that width
+    self._ws = {0: ops.attn_decode_workspace(B, n_heads, head_dim, Tmax, 0, device)}
 
   @property
   def lens(self):
@@ -52,12 +54,16 @@ class KVCache:
     """Move [pos | lens] by n_new - an int32 [B] device tensor, or an int - with one in-place add (Transformer.extend, after its chunk)."""
     self._pl += n_new
 
+  @property
+  def workspace(self):
+    """The (workspace, bytes) pair of ops.attn_decode."""
+    return self._ws[0]
+
   def extend_workspace(self, n):
-    """The (workspace, bytes) pair of ops.attn_extend for chunks of n rows (automatic split count): allocated at the first chunk of that
-    width and kept, shared by all layers."""
-    ws = self._extend_ws.get(n)
+    """The (workspace, bytes) pair of ops.attn_extend for chunks of n rows: allocated at the first chunk of that width and kept."""
+    ws = self._ws.get(n)
     if ws is None:
-      ws = self._extend_ws[n] = ops.attn_extend_workspace(self.B, n, self.n_heads, self.head_dim, self.Tmax, 0, self.status.device)
+      ws = self._ws[n] = ops.attn_extend_workspace(self.B, n, self.n_heads, self.head_dim, self.Tmax, 0, self.status.device)
     return ws
 
   def check(self):

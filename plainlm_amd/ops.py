@@ -705,7 +705,7 @@ def attn_bwd_masked(qkv, out, dout, lse, rope_cos, rope_sin, bits, tile_class, B
   return dqkv
 
 
-# ---- KV-cached generation ------------------------------------------
+# ---- the cached step (DESIGN.md sections 12 and 14): one token per sequence on top of a KV cache, or a chunk of them -------------
 def _need_kv(kv, nh, hd, name):
   """kv bf16 [B, Tmax, >= 2*nh*hd]: rows may be padded (stride(1) a multiple of 8), sequences are Tmax rows apart."""
   if not kv.is_cuda:
@@ -715,43 +715,86 @@ def _need_kv(kv, nh, hd, name):
   return kv
 
 
+def _cached_operands(name, rows, width, kv, nh, lens, lens_name, chunk, n_new=None, rope=None):
+  """The operand checks of the four cached-step ops, returns (B, n, hd).  rows: bf16 [B*n, width*nh*hd] - width 3 the UN-rotated qkv
+  (row stride free), width 1 the rotated q; kv: the cache; lens int32 [B]; n_new None | int32 [B]; rope None | (cos, sin) fp32
+  [rows, hd/2].  chunk False: one row per sequence (n = 1), the batch is the rows'; True: n = rows / the cache's batch."""
+  try:  # the per-tensor checks name the tensor; the op's name is put in front only when one fails (no string is built per call)
+    if width == 3:
+      if not rows.is_cuda:
+        raise RuntimeError('qkv: tensor must live on the GPU (plainlm_amd has no CPU path)')
+      if rows.dtype != BF16 or rows.dim() != 2 or rows.stride(1) != 1 or rows.shape[1] % (3 * nh) != 0:
+        raise ValueError(f'qkv: need a 2-D bf16 GPU tensor [{"B*n" if chunk else "B"}, 3*nh*hd] with unit inner stride')
+    else:
+      _need(rows, BF16, 'q', 2)
+    hd = rows.shape[1] // (width * nh)
+    _need_kv(kv, nh, hd, 'kv')
+    _need(lens, torch.int32, lens_name, 1)
+    if rope is not None:
+      _need(rope[0], F32, 'rope_cos', 2)
+      _need(rope[1], F32, 'rope_sin', 2)
+    if n_new is not None:
+      _need(n_new, torch.int32, 'n_new', 1)
+  except (RuntimeError, TypeError, ValueError) as e:
+    raise type(e)(f'{name}.{e}') from None
+  B = kv.shape[0] if chunk else rows.shape[0]
+  fits = rows.shape[1] == width * nh * hd and kv.shape[0] == B and lens.shape[0] == B
+  if chunk:
+    fits = fits and B >= 1 and rows.shape[0] >= B and rows.shape[0] % B == 0
+  if rope is not None:
+    fits = fits and rope[0].shape == rope[1].shape and rope[0].shape[1] == hd // 2
+  if not fits:
+    raise ValueError(f'{name}: {"qkv" if width == 3 else "q"} {tuple(rows.shape)}, kv {tuple(kv.shape)}, {lens_name} {tuple(lens.shape)} do not '
+                     f'fit nh={nh}' + ('' if rope is None else f', or the RoPE tables {tuple(rope[0].shape)} / {tuple(rope[1].shape)} the head_dim'))
+  if n_new is not None and n_new.shape[0] != B:
+    raise ValueError(f'{name}: n_new {tuple(n_new.shape)} does not fit the batch of {B}')
+  return B, rows.shape[0] // B if chunk else 1, hd
+
+
+def _append_outputs(name, qkv, rows, dm, q_out, status):
+  """(q_out bf16 [rows, dm], status int32 [1]) of an append: the caller's, checked, or made here (status zeroed)."""
+  try:
+    if q_out is not None and tuple(_need(q_out, BF16, 'q_out', 2).shape) != (rows, dm):
+      raise ValueError(f'q_out: need [{rows}, {dm}], got {tuple(q_out.shape)}')
+    if status is not None:
+      _need(status, torch.int32, 'status')
+  except (RuntimeError, TypeError, ValueError) as e:
+    raise type(e)(f'{name}.{e}') from None
+  return (torch.empty((rows, dm), dtype=BF16, device=qkv.device) if q_out is None else q_out,
+          torch.zeros((1,), dtype=torch.int32, device=qkv.device) if status is None else status)
+
+
+_cached_ws = {}  # (kernel, B, n, nh, hd, Tmax, splits, device) -> (uint8 workspace, bytes)
+
+
+def _cached_workspace(kernel, B, n, nh, hd, Tmax, splits, device):
+  key = (kernel, B, n, nh, hd, Tmax, int(splits), device)
+  ent = _cached_ws.get(key)
+  if ent is None:
+    lib = _lib.load()
+    nbytes = int(lib.plm_attn_decode_workspace_bytes(B, nh, hd, Tmax, int(splits)) if kernel == 'attn_decode' else
+                 lib.plm_attn_extend_workspace_bytes(B, n, nh, hd, Tmax, int(splits)))
+    if nbytes == 0:
+      raise ValueError(f'{kernel}: unsupported shape B={B} n={n} nh={nh} hd={hd} Tmax={Tmax} or splits={splits} (0 = automatic, 1..64)')
+    ent = _cached_ws[key] = (torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes)
+  return ent
+
+
 def kv_append_rope(qkv, pos, rope_cos, rope_sin, kv, nh, q_out=None, status=None):
   """One decode token per sequence: qkv bf16 [B, 3*nh*hd] UN-rotated (row stride may exceed it), pos int32 [B].  Rotates q and k at
   position pos[b] (rope_qk_'s bits), returns rotated q [B, nh*hd] and writes rotated k | untouched v into kv[b, pos[b]].  A pos[b] outside
   [0, min(Tmax, rope rows)) writes nothing for that sequence and sets status[0] = 1 (int32 [1], zeroed by the caller; made here when
   absent).  Returns (q_out, status): status is a device tensor, the caller decides when to look."""
-  if not qkv.is_cuda:
-    raise RuntimeError('kv_append_rope.qkv: tensor must live on the GPU (plainlm_amd has no CPU path)')
-  if qkv.dtype != BF16 or qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[1] % (3 * nh) != 0:
-    raise ValueError('kv_append_rope.qkv: need a 2-D bf16 GPU tensor [B, 3*nh*hd] with unit inner stride')
-  B = qkv.shape[0]
-  hd = qkv.shape[1] // (3 * nh)
-  _need(pos, torch.int32, 'kv_append_rope.pos', 1)
-  _need(rope_cos, F32, 'kv_append_rope.rope_cos', 2)
-  _need(rope_sin, F32, 'kv_append_rope.rope_sin', 2)
-  _need_kv(kv, nh, hd, 'kv_append_rope.kv')
-  if pos.shape[0] != B or kv.shape[0] != B or rope_cos.shape != rope_sin.shape or rope_cos.shape[1] != hd // 2:
-    raise ValueError('kv_append_rope: pos / kv do not fit the batch, or the RoPE tables the head_dim')
-  q_out = torch.empty((B, nh * hd), dtype=BF16, device=qkv.device) if q_out is None else _need(q_out, BF16, 'kv_append_rope.q_out', 2)
-  status = torch.zeros((1,), dtype=torch.int32, device=qkv.device) if status is None else _need(status, torch.int32, 'kv_append_rope.status')
+  B, _, hd = _cached_operands('kv_append_rope', qkv, 3, kv, nh, pos, 'pos', False, rope=(rope_cos, rope_sin))
+  q_out, status = _append_outputs('kv_append_rope', qkv, B, nh * hd, q_out, status)
   _lib.check(_lib.load().plm_kv_append_rope(_p(qkv), qkv.stride(0), _p(pos), _p(rope_cos), _p(rope_sin), rope_cos.shape[0], _p(q_out), _p(kv),
                                             kv.stride(1), _p(status), B, kv.shape[1], nh, hd, _stream()), 'plm_kv_append_rope')
   return q_out, status
 
 
-_decode_ws = {}
-
-
 def attn_decode_workspace(B, nh, hd, Tmax, splits, device):
   """(uint8 workspace, bytes) of attn_decode for this shape and splits argument, cached per shape."""
-  key = (B, nh, hd, Tmax, int(splits), device)
-  ent = _decode_ws.get(key)
-  if ent is None:
-    nbytes = int(_lib.load().plm_attn_decode_workspace_bytes(B, nh, hd, Tmax, int(splits)))
-    if nbytes == 0:
-      raise ValueError(f'attn_decode: unsupported shape B={B} nh={nh} hd={hd} Tmax={Tmax} or splits={splits} (0 = automatic, 1..64)')
-    ent = _decode_ws[key] = (torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes)
-  return ent
+  return _cached_workspace('attn_decode', B, 1, nh, hd, Tmax, splits, device)
 
 
 def attn_decode(q, kv, lens, nh, splits=0, want_lse=False, workspace=None):
@@ -759,13 +802,7 @@ def attn_decode(q, kv, lens, nh, splits=0, want_lse=False, workspace=None):
   layout), lens int32 [B] (clamped to [0, Tmax]; sequence b attends keys 0 .. lens[b]-1, lens[b] == 0 gives out = 0 and lse = +inf).
   splits: 0 automatic (from the shape alone) | 1..64 forced.  Returns out bf16 [B, nh*hd], or (out, lse fp32 [B, nh], base 2 like
   attn_fwd's) with want_lse.  workspace: (uint8 tensor, bytes) of attn_decode_workspace for the same splits, else a cached one per shape."""
-  _need(q, BF16, 'attn_decode.q', 2)
-  B = q.shape[0]
-  hd = q.shape[1] // nh
-  _need_kv(kv, nh, hd, 'attn_decode.kv')
-  _need(lens, torch.int32, 'attn_decode.lens', 1)
-  if q.shape[1] != nh * hd or kv.shape[0] != B or lens.shape[0] != B:
-    raise ValueError(f'attn_decode: q {tuple(q.shape)}, kv {tuple(kv.shape)}, lens {tuple(lens.shape)} do not fit nh={nh}')
+  B, _, hd = _cached_operands('attn_decode', q, 1, kv, nh, lens, 'lens', False)
   Tmax = kv.shape[1]
   ws, nbytes = attn_decode_workspace(B, nh, hd, Tmax, splits, q.device) if workspace is None else workspace
   out = torch.empty((B, nh * hd), dtype=BF16, device=q.device)
@@ -775,15 +812,6 @@ def attn_decode(q, kv, lens, nh, splits=0, want_lse=False, workspace=None):
   return (out, lse) if want_lse else out
 
 
-# ---- cache extension: a chunk of tokens per sequence on top of a live cache ------------------------------
-def _chunk_counts(n_new, B, name):
-  if n_new is not None:
-    _need(n_new, torch.int32, f'{name}.n_new', 1)
-    if n_new.shape[0] != B:
-      raise ValueError(f'{name}: n_new {tuple(n_new.shape)} does not fit the batch of {B}')
-  return n_new
-
-
 def kv_append_rope_rows(qkv, lens0, rope_cos, rope_sin, kv, nh, n_new=None, q_out=None, status=None):
   """A chunk of n tokens per sequence: qkv bf16 [B*n, 3*nh*hd] UN-rotated (row b*n + r = chunk row r of sequence b; the row stride may
   exceed the width), lens0 int32 [B] the cache lengths before the chunk, n_new int32 [B] the real rows of every chunk (clamped to
@@ -791,43 +819,17 @@ def kv_append_rope_rows(qkv, lens0, rope_cos, rope_sin, kv, nh, n_new=None, q_ou
   [B*n, nh*hd], rotated k | untouched v into kv[b, lens0[b] + r].  Rows past n_new[b] write no cache row and zeros to q_out.  A sequence
   with lens0[b] < 0 or lens0[b] + n_new[b] > min(Tmax, rope rows) stores nothing, gets zero q_out rows and sets status[0] = 1 (int32 [1],
   zeroed by the caller; made here when absent).  Returns (q_out, status): status is a device tensor, the caller decides when to look."""
-  if not qkv.is_cuda:
-    raise RuntimeError('kv_append_rope_rows.qkv: tensor must live on the GPU (plainlm_amd has no CPU path)')
-  if qkv.dtype != BF16 or qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[1] % (3 * nh) != 0:
-    raise ValueError('kv_append_rope_rows.qkv: need a 2-D bf16 GPU tensor [B*n, 3*nh*hd] with unit inner stride')
-  hd = qkv.shape[1] // (3 * nh)
-  _need(lens0, torch.int32, 'kv_append_rope_rows.lens0', 1)
-  _need(rope_cos, F32, 'kv_append_rope_rows.rope_cos', 2)
-  _need(rope_sin, F32, 'kv_append_rope_rows.rope_sin', 2)
-  _need_kv(kv, nh, hd, 'kv_append_rope_rows.kv')
-  B = kv.shape[0]
-  if B < 1 or qkv.shape[0] < B or qkv.shape[0] % B != 0 or lens0.shape[0] != B or rope_cos.shape != rope_sin.shape or rope_cos.shape[1] != hd // 2:
-    raise ValueError('kv_append_rope_rows: qkv rows are not a multiple of the cache\'s batch, lens0 does not fit it, or the RoPE tables the head_dim')
-  n = qkv.shape[0] // B
-  _chunk_counts(n_new, B, 'kv_append_rope_rows')
-  q_out = torch.empty((B * n, nh * hd), dtype=BF16, device=qkv.device) if q_out is None else _need(q_out, BF16, 'kv_append_rope_rows.q_out', 2)
-  if tuple(q_out.shape) != (B * n, nh * hd):
-    raise ValueError(f'kv_append_rope_rows.q_out: need [{B * n}, {nh * hd}], got {tuple(q_out.shape)}')
-  status = torch.zeros((1,), dtype=torch.int32, device=qkv.device) if status is None else _need(status, torch.int32, 'kv_append_rope_rows.status')
+  B, n, hd = _cached_operands('kv_append_rope_rows', qkv, 3, kv, nh, lens0, 'lens0', True, n_new=n_new, rope=(rope_cos, rope_sin))
+  q_out, status = _append_outputs('kv_append_rope_rows', qkv, B * n, nh * hd, q_out, status)
   _lib.check(_lib.load().plm_kv_append_rope_rows(_p(qkv), qkv.stride(0), _p(lens0), _p(n_new), _p(rope_cos), _p(rope_sin), rope_cos.shape[0],
                                                  _p(q_out), _p(kv), kv.stride(1), _p(status), B, n, kv.shape[1], nh, hd, _stream()),
              'plm_kv_append_rope_rows')
   return q_out, status
 
 
-_extend_ws = {}
-
-
 def attn_extend_workspace(B, n, nh, hd, Tmax, splits, device):
   """(uint8 workspace, bytes) of attn_extend for this shape and splits argument, cached per shape (and so per chunk width n)."""
-  key = (B, n, nh, hd, Tmax, int(splits), device)
-  ent = _extend_ws.get(key)
-  if ent is None:
-    nbytes = int(_lib.load().plm_attn_extend_workspace_bytes(B, n, nh, hd, Tmax, int(splits)))
-    if nbytes == 0:
-      raise ValueError(f'attn_extend: unsupported shape B={B} n={n} nh={nh} hd={hd} Tmax={Tmax} or splits={splits} (0 = automatic, 1..64)')
-    ent = _extend_ws[key] = (torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes)
-  return ent
+  return _cached_workspace('attn_extend', B, n, nh, hd, Tmax, splits, device)
 
 
 def attn_extend(q, kv, lens0, nh, n_new=None, splits=0, want_lse=False, workspace=None):
@@ -837,15 +839,7 @@ def attn_extend(q, kv, lens0, nh, n_new=None, splits=0, want_lse=False, workspac
   and lse = +inf.  splits: 0 automatic (from the shape alone) | 1..64 forced.  Returns out bf16 [B*n, nh*hd], or (out, lse fp32
   [B, nh, n], base 2 like attn_fwd's) with want_lse.  workspace: (uint8 tensor, bytes) of attn_extend_workspace for the same splits, else
   a cached one per shape."""
-  _need(q, BF16, 'attn_extend.q', 2)
-  hd = q.shape[1] // nh
-  _need_kv(kv, nh, hd, 'attn_extend.kv')
-  _need(lens0, torch.int32, 'attn_extend.lens0', 1)
-  B = kv.shape[0]
-  if q.shape[1] != nh * hd or B < 1 or q.shape[0] < B or q.shape[0] % B != 0 or lens0.shape[0] != B:
-    raise ValueError(f'attn_extend: q {tuple(q.shape)}, kv {tuple(kv.shape)}, lens0 {tuple(lens0.shape)} do not fit nh={nh}')
-  n = q.shape[0] // B
-  _chunk_counts(n_new, B, 'attn_extend')
+  B, n, hd = _cached_operands('attn_extend', q, 1, kv, nh, lens0, 'lens0', True, n_new=n_new)
   Tmax = kv.shape[1]
   ws, nbytes = attn_extend_workspace(B, n, nh, hd, Tmax, splits, q.device) if workspace is None else workspace
   out = torch.empty((B * n, nh * hd), dtype=BF16, device=q.device)

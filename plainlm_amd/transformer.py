@@ -536,10 +536,13 @@ class Transformer(nn.Module):
     """log p(target) per token, fp32 [B, T] (0 where the target is ignored): ``-score(x, targets, attn_mask, 'none')``."""
     return -self.score(x, targets, attn_mask, reduction='none')
 
-  # ---- KV-cached generation (DESIGN.md section 12; host logic in generate.py) ---------------------------------------------------
-  def _check_decode(self, what, t):
+  # ---- KV-cached generation (DESIGN.md sections 12 and 14; host logic in generate.py) ------------------------------------------
+  def _refuse_mxfp8(self, what):
     if self.cfg.linear_precision == 'mxfp8':
       raise NotImplementedError(f"Transformer.{what}: linear_precision: mxfp8 has no cached decode path (the decode step runs the bf16 shadows)")
+
+  def _check_decode(self, what, t):
+    self._refuse_mxfp8(what)
     if not isinstance(t, torch.Tensor) or t.dtype != torch.int64:
       raise TypeError(f'Transformer.{what}: tokens must be an int64 tensor')
     if not t.is_cuda:
@@ -569,53 +572,61 @@ class Transformer(nn.Module):
       lens_dev = torch.tensor(lens, dtype=torch.int32).to(x.device)
       cache.set_lens(lens_dev)
       y, _, _ = self._trunk(x.contiguous(), None, cache)
-      rows = G.last_rows(y, B, Tp, lens_dev)
-      wb, _ = self.lm_head.shadow()
-      if logits:
-        return cache, ops.gemm_nt(rows, wb)
-      r = ops.head_predict(rows, wb)
-    return cache, HeadPrediction(r.pred, r.logp, r.entropy, None)
+      return cache, self._head(G.last_rows(y, B, Tp, lens_dev), logits, (B,))
+
+  def _cached_layers(self, tokens, cache, attend):
+    """The trunk on top of ``cache`` for tokens int64 [M] (M = B rows of a decode step, B * n of a chunk): the Block structure as it is,
+    through ops calls on the bf16 shadows - about ten launches per layer, none of them sized by the context except attention.
+    ``attend(i, qkv)`` is layer i's two-call attention stage (append the rotated k | v rows of qkv [M, 3*dim] to cache.kv[i], attend the
+    rotated q rows over it) and returns its [M, dim] output.  Returns the final normed rows [M, dim]."""
+    self.refresh_shadows()
+    x = ops.embed_fwd(tokens, self.embed_tokens.weight)
+    branch = None
+    for i, layer in enumerate(self.layers):
+      xo, n1, _ = ops.rmsnorm_fwd(x, layer.attn_norm.weight, layer.attn_norm.eps, branch=branch)
+      x = x if xo is None else xo
+      a = attend(i, ops.gemm_nt(n1, layer.attn.w_qkv.shadow()[0]))
+      a = ops.gemm_nt(a, layer.attn.w_out.shadow()[0])
+      x, n2, _ = ops.rmsnorm_fwd(x, layer.mlp_norm.weight, layer.mlp_norm.eps, branch=a)
+      u = ops.gemm_nt(n2, layer.mlp.fc1.shadow()[0])
+      act = ops.swiglu_fwd(u) if isinstance(layer.mlp, GLU) else ops.act_fwd(u, layer.mlp.kind)
+      branch = ops.gemm_nt(act, layer.mlp.fc2.shadow()[0])
+    return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps, branch=branch)[1]
+
+  def _head(self, y, logits, shape):
+    """The head on normed rows y [prod(shape), dim]: the HeadPrediction of that shape (ops.head_predict, no logits buffer), or with
+    ``logits`` the bf16 logits [*shape, V]."""
+    wb, _ = self.lm_head.shadow()
+    if logits:
+      return ops.gemm_nt(y, wb).view(shape + (self.cfg.vocab_size,))
+    r = ops.head_predict(y, wb)
+    return HeadPrediction(r.pred.view(shape), r.logp.view(shape), r.entropy.view(shape), None)
 
   @torch.compiler.disable
   def decode_step(self, tokens, cache, logits=False):
     """One token per sequence on top of ``cache``: tokens int64 [B] are appended at positions cache.lens (then lens += 1, on the device)
     and the HeadPrediction [B] of the NEXT token is returned - or, with logits=True, its bf16 logits [B, V].  The Block structure as it
-    is, through ops calls on the bf16 shadows: about ten launches per layer, none of them sized by the context except decode attention."""
+    is (``_cached_layers``), with ops.kv_append_rope / ops.attn_decode as the attention stage."""
     self._check_decode('decode_step', tokens)
     B = cache.B
     if tuple(tokens.shape) != (B,):
       raise ValueError(f'decode_step: tokens {tuple(tokens.shape)} do not match the cache\'s batch of {B}')
     nh = self.cfg.n_heads
     with torch.no_grad():
-      self.refresh_shadows()
       rope = self._rope(tokens.device)
+      ws = cache.workspace
       cache.advance()  # pos = the appended token's position, lens = pos + 1: what this step's attention sees
-      x = ops.embed_fwd(tokens.contiguous(), self.embed_tokens.weight)
-      branch = None
-      for i, layer in enumerate(self.layers):
-        xo, n1, _ = ops.rmsnorm_fwd(x, layer.attn_norm.weight, layer.attn_norm.eps, branch=branch)
-        x = x if xo is None else xo
-        qkv = ops.gemm_nt(n1, layer.attn.w_qkv.shadow()[0])
+
+      def attend(i, qkv):
         q, _ = ops.kv_append_rope(qkv, cache.pos, rope[0], rope[1], cache.kv[i], nh, status=cache.status)
-        a = ops.attn_decode(q, cache.kv[i], cache.lens, nh, workspace=cache.workspace)
-        a = ops.gemm_nt(a, layer.attn.w_out.shadow()[0])
-        x, n2, _ = ops.rmsnorm_fwd(x, layer.mlp_norm.weight, layer.mlp_norm.eps, branch=a)
-        u = ops.gemm_nt(n2, layer.mlp.fc1.shadow()[0])
-        act = ops.swiglu_fwd(u) if isinstance(layer.mlp, GLU) else ops.act_fwd(u, layer.mlp.kind)
-        branch = ops.gemm_nt(act, layer.mlp.fc2.shadow()[0])
-      _, y, _ = ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps, branch=branch)
-      wb, _ = self.lm_head.shadow()
-      if logits:
-        return ops.gemm_nt(y, wb)
-      r = ops.head_predict(y, wb)
-    return HeadPrediction(r.pred, r.logp, r.entropy, None)
+        return ops.attn_decode(q, cache.kv[i], cache.lens, nh, workspace=ws)
+      return self._head(self._cached_layers(tokens.contiguous(), cache, attend), logits, (B,))
 
   # ---- cache extension (DESIGN.md section 14) ------------------------------------------------------------------------------------
   def new_cache(self, B, max_len=None):
     """An empty KVCache for B sequences (lens 0) of max_len rows each (default and at most cfg.seq_len): the start of a chunked prefill
     through ``extend``."""
-    if self.cfg.linear_precision == 'mxfp8':
-      raise NotImplementedError("Transformer.new_cache: linear_precision: mxfp8 has no cached decode path (the decode step runs the bf16 shadows)")
+    self._refuse_mxfp8('new_cache')
     Tmax = self.cfg.seq_len if max_len is None else int(max_len)
     if int(B) < 1 or Tmax < 1 or Tmax > self.cfg.seq_len:
       raise ValueError(f'new_cache: need B >= 1 and 1 <= max_len <= cfg.seq_len {self.cfg.seq_len}, got B={B} max_len={Tmax}')
@@ -647,38 +658,22 @@ class Transformer(nn.Module):
     nh = self.cfg.n_heads
     with torch.no_grad():
       adv, n_new = G.chunk_lens(token_lens, B, n, tokens.device)
-      self.refresh_shadows()
       rope = self._rope(tokens.device)
       ws = cache.extend_workspace(n)
       lens0 = cache.lens  # the lengths before the chunk: what every layer's append and attention see; moved once, after the last layer
-      x = ops.embed_fwd(tokens.reshape(-1).contiguous(), self.embed_tokens.weight)
-      branch = None
-      for i, layer in enumerate(self.layers):
-        xo, n1, _ = ops.rmsnorm_fwd(x, layer.attn_norm.weight, layer.attn_norm.eps, branch=branch)
-        x = x if xo is None else xo
-        qkv = ops.gemm_nt(n1, layer.attn.w_qkv.shadow()[0])
+
+      def attend(i, qkv):
         q, _ = ops.kv_append_rope_rows(qkv, lens0, rope[0], rope[1], cache.kv[i], nh, n_new=n_new, status=cache.status)
-        a = ops.attn_extend(q, cache.kv[i], lens0, nh, n_new=n_new, workspace=ws)
-        a = ops.gemm_nt(a, layer.attn.w_out.shadow()[0])
-        x, n2, _ = ops.rmsnorm_fwd(x, layer.mlp_norm.weight, layer.mlp_norm.eps, branch=a)
-        u = ops.gemm_nt(n2, layer.mlp.fc1.shadow()[0])
-        act = ops.swiglu_fwd(u) if isinstance(layer.mlp, GLU) else ops.act_fwd(u, layer.mlp.kind)
-        branch = ops.gemm_nt(act, layer.mlp.fc2.shadow()[0])
-      _, y, _ = ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps, branch=branch)
+        return ops.attn_extend(q, cache.kv[i], lens0, nh, n_new=n_new, workspace=ws)
+      y = self._cached_layers(tokens.reshape(-1).contiguous(), cache, attend)
       cache.advance_by(adv)
-      wb, _ = self.lm_head.shadow()
       if all_rows:
-        shape = (B, n)
+        return self._head(y, logits, (B, n))
+      if n_new is None:
+        y = y.view(B, n, self.cfg.dim)[:, -1].contiguous()
       else:
-        shape = (B,)
-        if n_new is None:
-          y = y.view(B, n, self.cfg.dim)[:, -1].contiguous()
-        else:
-          y = G.last_rows(y, B, n, n_new.clamp(min=1))
-      if logits:
-        return ops.gemm_nt(y, wb).view(shape + (self.cfg.vocab_size,))
-      r = ops.head_predict(y, wb)
-    return HeadPrediction(r.pred.view(shape), r.logp.view(shape), r.entropy.view(shape), None)
+        y = G.last_rows(y, B, n, n_new.clamp(min=1))
+      return self._head(y, logits, (B,))
 
   @torch.compiler.disable
   def generate(self, prompt, max_new_tokens, prompt_lens=None, eos_id=None, sample=None, return_logprobs=False, temperature=None,

@@ -233,6 +233,39 @@ def test_cached_logits_with_ragged_prompt_lens(P, mdl):
     assert e < 2e-2, (b, e)
 
 
+# What one decode_step of the golden 2-layer model issues through the C ABI, recorded with the hook below on commit 37fafa5 (the last
+# one with decode_step and extend written out separately): embedding; per layer norm, qkv, append, attention, out, norm, fc1, SwiGLU,
+# fc2; the out norm; the fused prediction head.
+DECODE_STEP_LAUNCHES = [
+  'plm_embed_fwd',
+  'plm_rmsnorm_fwd', 'plm_gemm_bf16_nt', 'plm_kv_append_rope', 'plm_attn_decode', 'plm_gemm_bf16_nt', 'plm_rmsnorm_fwd', 'plm_gemm_bf16_nt',
+  'plm_swiglu_fwd', 'plm_gemm_bf16_nt',
+  'plm_rmsnorm_fwd', 'plm_gemm_bf16_nt', 'plm_kv_append_rope', 'plm_attn_decode', 'plm_gemm_bf16_nt', 'plm_rmsnorm_fwd', 'plm_gemm_bf16_nt',
+  'plm_swiglu_fwd', 'plm_gemm_bf16_nt',
+  'plm_rmsnorm_fwd', 'plm_head_predict_bf16']
+
+
+def test_decode_step_and_extend_issue_the_same_launches(P, mdl, monkeypatch):
+  """'The same launches as one decode step, whatever n': one decode_step issues the recorded list, one extend of n = 3 the same list with
+  the two cached-attention entry points replaced by their chunk forms."""
+  from plainlm_amd import _lib
+  m = _small(P, mdl)
+  tok = mdl['tokens'].cuda()
+  cache, _ = m.prefill(tok[:, :16])
+  calls = []
+  real = _lib.check
+  monkeypatch.setattr(_lib, 'check', lambda rc, what: calls.append(what) or real(rc, what))
+  m.decode_step(tok[:, 16], cache)
+  assert calls == DECODE_STEP_LAUNCHES, calls
+  del calls[:]
+  m.extend(tok[:, 17:20], cache)
+  chunk = {'plm_kv_append_rope': 'plm_kv_append_rope_rows', 'plm_attn_decode': 'plm_attn_extend'}
+  assert calls == [chunk.get(c, c) for c in DECODE_STEP_LAUNCHES], calls
+  monkeypatch.undo()
+  cache.check()
+  assert cache.lens.tolist() == [20, 20]
+
+
 @pytest.mark.parametrize('mlp,nh', [('mlp', 2), ('mlp_relu_sq', 2), ('glu', 4), ('glu', 1)])
 def test_cached_logits_other_mlp_classes_and_head_dims_vs_oracle(P, mlp, nh):
   ocfg = O.OracleConfig(vocab_size=256, seq_len=64, dim=128, n_layers=2, n_heads=nh, mlp=mlp)
