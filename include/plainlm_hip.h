@@ -323,6 +323,34 @@ int plm_attn_extend(const uint16_t* q, const uint16_t* kv, int64_t ld_kv, const 
 int plm_sample_logits_bf16(const uint16_t* logits, int64_t ld, const float* u, float temperature, int64_t top_k, float top_p,
                            int64_t* tok, float* logp, int32_t* n_kept, float* cutoff, int64_t B, int64_t V, void* stream);
 
+/* ---- speculative-sampling acceptance of k drafted tokens per sequence -----
+ * Every argument check comes before any HIP call.
+ * p_logits bf16 [B*(k+1), ldp]: the target's chunk rows, row b*(k+1) + r (what extend(all_rows, logits) returns); q_logits bf16
+ * [k*B, ldq]: the draft's rows, step-major, row r*B + b.  Any 2-byte aligned bases and any ld >= V: columns >= V are never loaded.
+ * draft_tok int64 [k, B]: the token the draft drew at step r.  p_cutoff fp32 [B*(k+1)] and q_cutoff fp32 [k*B]: the `cutoff` output of
+ * plm_sample_logits_bf16 on those rows at this temperature - a row's distribution is that sampler's: weight exp((x - x_max) /
+ * temperature) on {i : x_i finite and x_i >= cutoff}, 0 elsewhere (a NaN cutoff keeps nothing), with the sampler's own fixed-point
+ * weights.  p_tok int64 [B*(k+1)]: that sampler's token of every target row.  u_accept fp32 [k, B] and u_resid fp32 [B]: uniforms, clamped
+ * on the device as the sampler clamps u.
+ *
+ * The rule, per sequence b.  For r = 0 .. k-1 in order, with x = draft_tok[r, b]: alpha = min(1, p_r(x) / q_r(x)); alpha = 0 when x is
+ * outside [0, V) or p_r(x) = 0 (outside p's kept set), alpha = 1 when q_r(x) = 0 < p_r(x); row r is accepted while u_accept[r, b] < alpha.
+ * n_accept counts the accepted rows.  n_accept = k: next_tok = p_tok of row k (the bonus token).  Else, at the first rejected row a,
+ * next_tok = the lowest i with C_i > u_resid[b] * R, C the running sum in ascending column order of max(0, p_a(i) - q_a(i)) and R its
+ * total; R = 0 (or a row without a finite logit): next_tok = p_tok of row a.
+ * Outputs: n_accept int32 [B] in [0, k]; next_tok int64 [B], always in [0, V); logp fp32 [B, k+1]: entry j <= n_accept is
+ * log softmax over all V raw logits of target row j at temperature 1 (as plm_sample_logits_bf16 states it) of the token emitted there -
+ * draft_tok[j, b], or next_tok at j = n_accept - and 0 beyond.
+ * Two launches (one workgroup per drafted row, then one per sequence; logp carries the verdicts between them), no workspace, nothing read
+ * back.  Sequence b's outputs depend on sequence b's inputs alone, and the same inputs give the same bits on every run (64-bit
+ * fixed-point sums; the quotients are fp64 expressions of those integers).
+ * PLM_E_INVALID before anything is launched for: a NULL pointer, B < 1 or B >= 2^26, k < 1 or k > 31, V < 1 or V >= 2^31, ldp < V or
+ * ldq < V, a logits base that is not 2-byte aligned, a temperature that is not finite or <= 0. */
+int plm_spec_verify_bf16(const uint16_t* p_logits, int64_t ldp, const uint16_t* q_logits, int64_t ldq, const int64_t* draft_tok,
+                         const float* p_cutoff, const float* q_cutoff, const int64_t* p_tok, const float* u_accept, const float* u_resid,
+                         float temperature, int32_t* n_accept, int64_t* next_tok, float* logp, int64_t B, int64_t k, int64_t V,
+                         void* stream);
+
 /* ---- fused cross-entropy forward+backward (engine/engine.py:81,111) -----
  * logits bf16[M, ld] (row stride ld >= V) are OVERWRITTEN with dlogits = (softmax - onehot) * grad_scale
  * (grad_scale = g/M); pad columns V..ld are set to zero so the buffer can feed a GEMM with K = ld.

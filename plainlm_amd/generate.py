@@ -6,7 +6,9 @@ the row a padded prompt is continued from, the token loop with its EOS freezing 
 with a fake step function.  The kernels are reached through two ops per cached step from transformer.py: ops.kv_append_rope /
 ops.attn_decode for one token per sequence, ops.kv_append_rope_rows / ops.attn_extend for a chunk.  On-device
 sampling adds the argument rules (check_sampling), the one draw of uniforms per call (draw_uniforms) and the
-per-step pick (sampling_pick over ops.sample_logits).
+per-step pick (sampling_pick over ops.sample_logits).  Speculative decoding adds the host logic of
+``Transformer.generate_speculative``: its refusals (check_speculative), greedy acceptance (greedy_accept), the bookkeeping of a round
+(commit_round), the round loop over callables (speculative_loop) and the one draw of all its uniforms (speculative_uniforms).
 """
 
 import math
@@ -219,3 +221,145 @@ def sampling_pick(u, temperature, top_k, top_p, sampler=None):
     n[0] += 1
     return r[0], r[1]
   return pick
+
+
+# ---- speculative decoding ---------------------------------------------------------------------------------------
+MAX_DRAFT = 31  # a chunk of n_draft + 1 <= 32 rows is one wave's queries in attn_extend_kernel; plm_spec_verify_bf16 holds the same limit
+
+
+def check_speculative(T, max_new_tokens, n_draft, cfg, draft_cfg, device=None, draft_device=None, temperature=None, top_k=None, top_p=None,
+                      seed=None, sample=None):
+  """The refusals of generate_speculative that need no GPU.  cfg / draft_cfg: the two models' ModelConfig.  Returns (cache rows per
+  sequence - the same for both models -, check_sampling's normalised (temperature, top_k, top_p) or None for greedy).  A round may write
+  n_draft + 1 rows past the last token a sequence keeps, hence the longer cache."""
+  if sample is not None:
+    raise ValueError('generate_speculative: sample= callables are not supported (the acceptance rule needs both models\' distributions on the '
+                     'device): use temperature / top_k / top_p, or generate()')
+  if isinstance(n_draft, bool) or not isinstance(n_draft, int):
+    raise TypeError(f'generate_speculative: n_draft must be an int, got {type(n_draft).__name__}')
+  if n_draft < 1 or n_draft > MAX_DRAFT:
+    raise ValueError(f'generate_speculative: n_draft must be in [1, {MAX_DRAFT}], got {n_draft}')
+  if draft_cfg.vocab_size != cfg.vocab_size:
+    raise ValueError(f'generate_speculative: the draft\'s vocab_size {draft_cfg.vocab_size} is not the target\'s {cfg.vocab_size}')
+  if device is not None and draft_device is not None and torch.device(device) != torch.device(draft_device):
+    raise ValueError(f'generate_speculative: the draft is on {draft_device}, the target on {device}')
+  if int(max_new_tokens) < 1:
+    raise ValueError(f'generate_speculative: max_new_tokens must be at least 1, got {max_new_tokens}')
+  if T < 1:
+    raise ValueError('generate_speculative: empty prompt')
+  need = T + int(max_new_tokens) + n_draft + 1
+  for who, c in (('the target', cfg), ('the draft', draft_cfg)):
+    if need > c.seq_len:
+      raise ValueError(f'generate_speculative: prompt length {T} + max_new_tokens {max_new_tokens} + n_draft {n_draft} + 1 exceeds '
+                       f'{who}\'s cfg.seq_len {c.seq_len}')
+  return need, check_sampling(temperature, top_k, top_p, None, seed)
+
+
+def greedy_accept(draft_tok, target_pred):
+  """Greedy acceptance: draft_tok int64 [B, k], target_pred int64 [B, k + 1] (row r: the target's prediction after the round's first r + 1
+  tokens).  Returns (n_accept int32 [B] = the number of leading draft tokens the target predicts too, next_token int64 [B] = the target's
+  prediction at the first mismatch, or at row k).  Integer ops only, any device."""
+  k = draft_tok.shape[1]
+  n = (draft_tok == target_pred[:, :k]).to(torch.int32).cumprod(dim=1).sum(dim=1)
+  return n.to(torch.int32), target_pred.gather(1, n.to(torch.int64)[:, None])[:, 0]
+
+
+def commit_round(out_tok, out_lp, count, done, draft_tok, n_accept, next_tok, logp, eos_id=None):
+  """The bookkeeping of one round, plain tensor ops on any device.  out_tok int64 [B, N] / out_lp fp32 [B, N] are updated in place;
+  count int [B] (tokens emitted so far) and done bool [B] are not.  The round offers sequence b the tokens draft_tok[b, :n_accept[b]]
+  followed by next_tok[b], with log-probabilities logp[b, :n_accept[b] + 1]; a live sequence takes them at columns count[b] .., cut at N
+  and after the first eos_id, a finished one takes nothing.  A sequence that has emitted eos_id holds eos_id with log-probability 0 from
+  there on, as generate_loop leaves it.  Returns (count, done, moved): the new counts and flags, and moved int32 [B] = the number of tokens
+  each sequence took - how far its caches move."""
+  B, N = out_tok.shape
+  k = draft_tok.shape[1]
+  dev = out_tok.device
+  j = torch.arange(k + 1, device=dev)[None, :]
+  na = n_accept.to(torch.int64)[:, None]
+  cand = torch.where(j < na, torch.nn.functional.pad(draft_tok, (0, 1)), next_tok[:, None])
+  m = torch.minimum(na[:, 0] + 1, N - count.to(torch.int64))
+  m = torch.where(done, torch.zeros_like(m), m)
+  if eos_id is not None:  # cut after the first eos_id among the tokens taken
+    is_eos = (cand == eos_id) & (j < m[:, None])
+    hit = is_eos.any(dim=1)
+    m = torch.where(hit, is_eos.to(torch.int32).argmax(dim=1) + 1, m)
+  pos = torch.arange(N, device=dev)[None, :] - count.to(torch.int64)[:, None]  # column n of the outputs is round entry pos[b, n]
+  take = (pos >= 0) & (pos < m[:, None])
+  src = pos.clamp(0, k)
+  out_tok.copy_(torch.where(take, cand.gather(1, src), out_tok))
+  out_lp.copy_(torch.where(take, logp.gather(1, src), out_lp))
+  new_count = count + m.to(count.dtype)
+  new_done = done | (new_count >= N)
+  if eos_id is not None:
+    new_done = new_done | hit
+    tail = new_done[:, None] & (pos >= m[:, None])  # nothing for a sequence that filled up: it has no column left
+    out_tok.masked_fill_(tail, eos_id)
+    out_lp.masked_fill_(tail, 0.0)
+  return new_count, new_done, m.to(torch.int32)
+
+
+def speculative_loop(first, draft_round, target_round, accept, max_new_tokens, n_draft, eos_id=None, advance=None, all_done=None):
+  """The round loop of speculative decoding over callables (tests/test_spec_host.py runs it on the CPU with fake models).
+    first                                       (tokens int64 [B], logprob fp32 [B]) of the target's prefill
+    draft_round(last, carry_tok, carry, live)   -> (draft_tok int64 [B, k], whatever accept needs of the draft).  last [B]: every
+                                                sequence's newest token; carry bool [B]: the draft has not seen carry_tok [B] yet (the
+                                                last draft token of a round that accepted all k), which then precedes ``last``
+    target_round(last, draft_tok, live)         -> whatever accept needs of the target's k + 1 chunk rows
+    accept(draft_tok, draft_out, target_out)    -> (n_accept [B], next_token [B], logprob [B, k + 1])
+    advance(moved, live)                        moves the caches: moved int32 [B] from commit_round (0 for a finished sequence); a live
+                                                sequence's draft cache keeps min(moved, k) of the round's rows
+  Returns (tokens [B, N], logprobs [B, N], stats) with stats = dict(rounds, drafted int64 [B], accepted int64 [B]) over the rounds a
+  sequence was live in.  A round emits at least one token per live sequence, so there are at most N - 1 rounds.  ``all_done(done)`` - the
+  one device-to-host read, one int32 per round - ends the loop."""
+  tok, lp = first
+  N, k = int(max_new_tokens), int(n_draft)
+  B, dev = tok.shape[0], tok.device
+  out_tok = torch.zeros((B, N), dtype=torch.int64, device=dev)
+  out_lp = torch.zeros((B, N), dtype=torch.float32, device=dev)
+  out_tok[:, 0] = tok
+  out_lp[:, 0] = lp
+  count = torch.ones((B,), dtype=torch.int32, device=dev)
+  done = torch.full((B,), N <= 1, dtype=torch.bool, device=dev)
+  if eos_id is not None:
+    done = done | (tok == eos_id)
+    out_tok[:, 1:] = torch.where(done[:, None], torch.full_like(out_tok[:, 1:], eos_id), out_tok[:, 1:])
+  if all_done is None:
+    all_done = lambda d: bool(d.all())  # noqa: E731
+  last, carry_tok = tok, tok
+  carry = torch.zeros((B,), dtype=torch.bool, device=dev)
+  drafted = torch.zeros((B,), dtype=torch.int64, device=dev)
+  accepted = torch.zeros((B,), dtype=torch.int64, device=dev)
+  rounds = 0
+  while rounds < N - 1 and not all_done(done):
+    live = ~done
+    draft_tok, draft_out = draft_round(last, carry_tok, carry, live)
+    n_accept, next_tok, logp = accept(draft_tok, draft_out, target_round(last, draft_tok, live))
+    count, done, moved = commit_round(out_tok, out_lp, count, done, draft_tok, n_accept, next_tok, logp, eos_id)
+    if advance is not None:
+      advance(moved, live)
+    carry = live & (moved == k + 1)
+    carry_tok = draft_tok[:, k - 1]
+    last = torch.where(live, next_tok, last)
+    drafted += live.to(torch.int64) * k
+    accepted += torch.where(live, n_accept.to(torch.int64), torch.zeros_like(accepted))
+    rounds += 1
+  return out_tok, out_lp, dict(rounds=rounds, drafted=drafted, accepted=accepted)
+
+
+def uniforms_per_round(k):
+  """Uniforms a round uses per sequence: k draft draws, k + 1 draws of the target's sampler, k acceptance tests, one residual draw."""
+  return 3 * k + 2
+
+
+def speculative_uniforms(max_new_tokens, n_draft, B, device, seed=None):
+  """All uniforms of one generate_speculative call, drawn once through draw_uniforms: fp32 [1 + (N - 1) * (3k + 2), B].  Row 0 draws the
+  first token; round i owns the next 3k + 2 rows (``round_uniforms``).  Every entry is used at most once, so the four roles are
+  independent of one another."""
+  return draw_uniforms(1 + (int(max_new_tokens) - 1) * uniforms_per_round(int(n_draft)), B, device, seed)
+
+
+def round_uniforms(u, i, n_draft):
+  """Round i's rows of ``speculative_uniforms``: (draft draws [k, B], target sampler's [k + 1, B], acceptance [k, B], residual [B])."""
+  k = int(n_draft)
+  r = u[1 + i * uniforms_per_round(k):1 + (i + 1) * uniforms_per_round(k)]
+  return r[:k], r[k:2 * k + 1], r[2 * k + 1:3 * k + 1], r[3 * k + 1]

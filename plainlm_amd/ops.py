@@ -876,6 +876,49 @@ def sample_logits(logits, u, temperature=1.0, top_k=0, top_p=1.0, want_stats=Fal
   return SampleLogits(tok, logp, n_kept, cutoff)
 
 
+SpecVerify = collections.namedtuple('SpecVerify', ['n_accept', 'next_token', 'logprob'])
+
+
+def _logits_rows(t, rows, name):
+  if not t.is_cuda:
+    raise RuntimeError(f'{name}: tensor must live on the GPU (plainlm_amd has no CPU path)')
+  if t.dtype != BF16 or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < 1 or t.stride(1) != 1 or (rows > 1 and t.stride(0) < t.shape[1]):
+    raise ValueError(f'{name}: need a 2-D bf16 GPU tensor [{rows}, V] with unit inner stride and row stride >= V, got {t.dtype} '
+                     f'{tuple(t.shape)}')
+  return t.stride(0) if rows > 1 else t.shape[1]
+
+
+def spec_verify(target_logits, draft_logits, draft_tokens, target_cutoff, draft_cutoff, target_tokens, u_accept, u_resid, temperature=1.0):
+  """The speculative-sampling acceptance rule on k drafted tokens per sequence (include/plainlm_hip.h states the
+  rule).  target_logits bf16 [B*(k+1), V], row b*(k+1) + r (extend(all_rows=True, logits=True), flattened); draft_logits bf16 [k*B, V],
+  step-major (row r*B + b); both with unit inner stride and any row stride >= V.  draft_tokens int64 [k, B]; target_cutoff fp32
+  [B*(k+1)] / draft_cutoff fp32 [k*B] and target_tokens int64 [B*(k+1)]: the ``cutoff`` and ``tokens`` of ops.sample_logits(...,
+  want_stats=True) on those rows at this temperature; u_accept fp32 [k, B], u_resid fp32 [B].  Two launches, bit-reproducible, nothing is
+  read back.  Returns the named tuple (n_accept int32 [B], next_token int64 [B], logprob fp32 [B, k+1]: the target's log-probability at
+  temperature 1 of every emitted token, 0 beyond entry n_accept)."""
+  _need(draft_tokens, torch.int64, 'spec_verify.draft_tokens', 2)
+  k, B = draft_tokens.shape
+  ldp = _logits_rows(target_logits, B * (k + 1), 'spec_verify.target_logits')
+  ldq = _logits_rows(draft_logits, k * B, 'spec_verify.draft_logits')
+  V = target_logits.shape[1]
+  if draft_logits.shape[1] != V:
+    raise ValueError(f'spec_verify: draft_logits have {draft_logits.shape[1]} columns, target_logits {V}')
+  for t, dtype, n, name in ((target_cutoff, F32, B * (k + 1), 'target_cutoff'), (draft_cutoff, F32, k * B, 'draft_cutoff'),
+                            (target_tokens, torch.int64, B * (k + 1), 'target_tokens'), (u_accept, F32, k * B, 'u_accept'),
+                            (u_resid, F32, B, 'u_resid')):
+    _need(t, dtype, f'spec_verify.{name}')
+    if t.numel() != n:
+      raise ValueError(f'spec_verify: {name} {tuple(t.shape)} does not hold {n} elements (B={B}, k={k})')
+  dev = target_logits.device
+  n_accept = torch.empty((B,), dtype=torch.int32, device=dev)
+  next_tok = torch.empty((B,), dtype=torch.int64, device=dev)
+  logp = torch.empty((B, k + 1), dtype=F32, device=dev)
+  _lib.check(_lib.load().plm_spec_verify_bf16(_p(target_logits), ldp, _p(draft_logits), ldq, _p(draft_tokens), _p(target_cutoff),
+                                              _p(draft_cutoff), _p(target_tokens), _p(u_accept), _p(u_resid), float(temperature),
+                                              _p(n_accept), _p(next_tok), _p(logp), B, k, V, _stream()), 'plm_spec_verify_bf16')
+  return SpecVerify(n_accept, next_tok, logp)
+
+
 # ---- cross entropy --------------------------------------------------------------------
 def ce_fwd_bwd_(logits, targets, grad_scale, V=None):
   """In place: logits[:, :V] <- (softmax - onehot) * grad_scale, logits[:, V:] <- 0 (logits is bf16 [M, ld], ld >= V).

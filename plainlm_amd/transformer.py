@@ -705,3 +705,92 @@ class Transformer(nn.Module):
     toks, lps = G.generate_loop(pick(r), lambda t: pick(self.decode_step(t, cache, logits=want_logits)), max_new_tokens, eos_id)
     cache.check()
     return (toks, lps) if return_logprobs else toks
+
+  # ---- speculative decoding (host logic in generate.py) -----------------------------------------------------
+  @torch.compiler.disable
+  def generate_speculative(self, prompt, max_new_tokens, draft, n_draft=4, prompt_lens=None, eos_id=None, return_logprobs=False,
+                           temperature=None, top_k=None, top_p=None, seed=None, return_stats=False):
+    """``generate`` by draft-and-verify rounds: ``draft`` - another Transformer of the same vocabulary, any shape - proposes n_draft
+    tokens with decode steps, this model checks them in one ``extend`` of n_draft + 1 rows, and a sequence keeps the accepted tokens
+    plus one of this model's own, so a round of one target step yields 1 .. n_draft + 1 tokens.  Greedy (temperature None or 0 without
+    a filter): the tokens are what ``generate`` decodes greedily, the target side runs through the fused prediction head.  With
+    temperature / top_k / top_p the draft samples on the device and ops.spec_verify applies the speculative-sampling acceptance rule, which
+    leaves every token distributed as ``generate`` samples it (not the same tokens: the uniforms are used differently).  All uniforms of
+    the call are drawn once, under ``seed`` (bit-reproducible) or from torch's default generator.  Returns the tokens int64 [B, N]; with
+    return_logprobs also this model's log-probabilities at temperature 1, with return_stats also dict(rounds, drafted int64 [B], accepted
+    int64 [B]).  After eos_id a sequence holds eos_id with log-probability 0.  One int32 is read from the device per round (are all
+    sequences finished?); both caches move by device tensors only."""
+    if isinstance(prompt, torch.Tensor) and not prompt.is_cuda:
+      raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (inputs are on CPU; there is no CPU fallback)')
+    if not isinstance(draft, Transformer):
+      raise TypeError(f'generate_speculative: draft must be a plainlm_amd.Transformer, got {type(draft).__name__}')
+    if torch.is_grad_enabled() and any(p.requires_grad for m in (self, draft) for p in m.parameters()):
+      raise RuntimeError('Transformer.generate_speculative is forward-only (no backward): call it under torch.no_grad(), or use loss() to train')
+    self._check_decode('generate_speculative', prompt)
+    draft._refuse_mxfp8('generate_speculative')
+    if prompt.dim() != 2:
+      raise TypeError('inputs must be an int64 [B, T] tensor')
+    B, T = prompt.shape
+    k, N, dev = n_draft, int(max_new_tokens), prompt.device
+    max_len, on_device = G.check_speculative(T, max_new_tokens, k, self.cfg, draft.cfg, self.lm_head.weight.device,
+                                             draft.lm_head.weight.device, temperature, top_k, top_p, seed)
+    V = self.cfg.vocab_size
+    sampled = on_device is not None
+    tcache, r = self.prefill(prompt, prompt_lens, max_len=max_len, logits=sampled)
+    dcache, _ = draft.prefill(prompt, prompt_lens, max_len=max_len)
+    # the lengths the caches are set to after every round: both hold the sequence up to, not including, its newest token - the draft one
+    # row less while it has not seen the last draft token of a fully accepted round
+    tlen, dlen = tcache.lens.clone(), dcache.lens.clone()
+    if sampled:
+      u = G.speculative_uniforms(N, k, B, dev, seed)
+      s = ops.sample_logits(r, u[0], *on_device)
+      first = (s.tokens, s.logprob)
+      qbuf = torch.empty((k, B, V), dtype=torch.bfloat16, device=dev)
+    else:
+      first = (r.tokens, r.logprob)
+    rnd = [0]
+
+    def draft_round(last, carry_tok, carry, live):
+      ur = G.round_uniforms(u, rnd[0], k)[0] if sampled else None
+      toks, cuts = [], []
+      for i in range(k):
+        if i == 0:  # [carry_tok, last] where the draft still lacks carry_tok, else [last, -]; a finished sequence appends nothing
+          pair = torch.stack([torch.where(carry, carry_tok, last), last], dim=1)
+          out = draft.extend(pair, dcache, token_lens=(live.to(torch.int32) * (1 + carry.to(torch.int32))), logits=sampled)
+        else:
+          out = draft.decode_step(toks[-1], dcache, logits=sampled)
+        if sampled:
+          qbuf[i].copy_(out)
+          sq = ops.sample_logits(qbuf[i], ur[i], *on_device, want_stats=True)
+          toks.append(sq.tokens)
+          cuts.append(sq.cutoff)
+        else:
+          toks.append(out.tokens)
+      return torch.stack(toks, dim=1), (torch.stack(toks, dim=0), torch.stack(cuts, dim=0)) if sampled else None
+
+    def target_round(last, draft_tok, live):
+      chunk = torch.cat([last[:, None], draft_tok], dim=1)
+      return self.extend(chunk, tcache, token_lens=live.to(torch.int32) * (k + 1), logits=sampled, all_rows=True)
+
+    def accept(draft_tok, draft_out, out):
+      if not sampled:
+        return G.greedy_accept(draft_tok, out.tokens) + (out.logprob,)
+      _, ut, ua, ures = G.round_uniforms(u, rnd[0], k)
+      rows = out.view(B * (k + 1), V)
+      st = ops.sample_logits(rows, ut.t().reshape(-1), *on_device, want_stats=True)  # row b * (k + 1) + r draws with ut[r, b]
+      return tuple(ops.spec_verify(rows, qbuf.view(k * B, V), draft_out[0], st.cutoff, draft_out[1].reshape(-1), st.tokens, ua, ures,
+                                   on_device[0]))
+
+    def advance(moved, live):
+      dlen.copy_(torch.where(live, tlen + moved.clamp(max=k), dlen))
+      tlen.add_(moved)
+      tcache.set_lens(tlen)
+      dcache.set_lens(dlen)
+      rnd[0] += 1
+
+    with torch.no_grad():
+      toks, lps, stats = G.speculative_loop(first, draft_round, target_round, accept, N, k, eos_id, advance)
+    tcache.check()
+    dcache.check()
+    res = (toks,) + ((lps,) if return_logprobs else ()) + ((stats,) if return_stats else ())
+    return res[0] if len(res) == 1 else res
