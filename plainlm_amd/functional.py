@@ -13,6 +13,14 @@ import torch
 from . import ops
 
 
+def _operand_bytes(t):
+  """Bytes that a queued dW operand keeps alive: a bf16 tensor, or an MxTensor (linear_precision 'mxfp8': blocked along the tokens);
+  None for anything else, which is queued without byte accounting."""
+  if isinstance(t, ops.MxTensor):
+    return t.nbytes()
+  return t.numel() * t.element_size() if isinstance(t, torch.Tensor) else None
+
+
 class GradSink:
   """Routes parameter gradients into ``param.main_grad`` views of one flat fp32 buffer.
 
@@ -52,11 +60,11 @@ class GradSink:
 
   def defer_dw(self, dy, x, p):
     """Queue dW(p) (+)= dy^T x; runs when the group is full or at flush_dw()."""
-    mx = isinstance(dy, ops.MxTensor) and isinstance(x, ops.MxTensor)  # linear_precision 'mxfp8': both blocked along the tokens
-    if mx or (isinstance(dy, torch.Tensor) and isinstance(x, torch.Tensor)):
-      nbytes = dy.nbytes() + x.nbytes() if mx else dy.numel() * dy.element_size() + x.numel() * x.element_size()
+    sizes = _operand_bytes(dy), _operand_bytes(x)
+    if None not in sizes:
+      nbytes = sum(sizes)
       if self.dw_queue_bytes_max is None:
-        self.resolve_queue_budget(dy.data.device if mx else dy.device)
+        self.resolve_queue_budget(dy.data.device)  # .data: the tensor itself, or the MxTensor's bytes
       if self.dw_queue and self.dw_queue_bytes + nbytes > self.dw_queue_bytes_max:
         self._flush_linear_dw()  # BEFORE the append: the queue never pins more than the budget
       self.dw_queue_bytes += nbytes
@@ -129,229 +137,137 @@ class GradSink:
       self.on_ready(p)
 
 
+# ---- the block linears: three Functions, the precision a policy ---------------------------------------------------------------------
+# A policy answers, for one linear_precision, how a bf16 input or dY becomes (the operand of the forward / dX GEMM,
+# what dW needs) and which GEMMs run.  'bf16': the tensor itself, twice, on the NT / TN kernels over the bf16 shadows.  'mxfp8': quantized
+# once into both orientations - the row-blocked copy feeds the forward / dX GEMM and is dropped, the copy blocked along the tokens is what is
+# kept for dW - on MX GEMMs over the MX weight copies.  A stale shadow or MX copy is refreshed where a GEMM asks for it; the bf16 MLP asks for
+# both of its shadows before its first kernel ('ready').  HipLinear.mx chooses (set by Transformer on the block linears).
+_BF16 = dict(
+  quant=lambda t: (t, t),
+  ready=lambda *lins: [lin.shadow() for lin in lins],
+  nt=lambda a, lin: ops.gemm_nt(a, lin.shadow()[0]),
+  dx=lambda dy, lin: ops.gemm_nt(dy, lin.shadow()[1][:, :lin.out_features]),
+  dw=lambda dy, x: ops.gemm_tn(dy, x))
+_MXFP8 = dict(
+  quant=lambda t: ops.mx_quant(t),  # (the ops functions are looked up per call: host tests replace them)
+  ready=lambda *lins: None,
+  nt=lambda a, lin: ops.gemm_mx_nt(a, lin.mx_weights()[0]),
+  dx=lambda dy, lin: ops.gemm_mx_nt(dy, lin.mx_weights()[1]),
+  dw=lambda dyt, xt: ops.gemm_mx_nt(dyt, xt, out_dtype=torch.float32))
+_POLICY = {False: _BF16, True: _MXFP8}
+
+
+def _keep(ctx, *items):
+  """What backward needs: tensors through save_for_backward, MxTensors (not tensors) as a plain attribute; _kept returns them in order."""
+  ctx.save_for_backward(*[t for t in items if isinstance(t, torch.Tensor)])
+  ctx.kept = [None if isinstance(t, torch.Tensor) else t for t in items]
+
+
+def _kept(ctx):
+  saved = iter(ctx.saved_tensors)
+  return [next(saved) if t is None else t for t in ctx.kept]
+
+
+def _weight_grad(lin, dy, x):
+  """dW = dY^T X of ``lin`` from the dW operands of its policy: queued in the sink (None), else returned fp32 to autograd."""
+  sink, p = lin.sink, lin.weight
+  if sink is not None and sink.active_for(p):
+    sink.defer_dw(dy, x, p)
+    return None
+  return _POLICY[lin.mx]['dw'](dy, x)
+
+
 class LinearFn(torch.autograd.Function):
   """y = x W^T (nn.Linear, bias-free: transformer.py:36-37,97; components.py:50-51)."""
 
   @staticmethod
   def forward(ctx, x, weight, lin):
-    wb, _ = lin.shadow()
-    ctx.save_for_backward(x)
+    P = _POLICY[lin.mx]
+    xg, xk = P['quant'](x)
     ctx.lin = lin
-    return ops.gemm_nt(x, wb)
+    _keep(ctx, xk)
+    return P['nt'](xg, lin)
 
   @staticmethod
   def backward(ctx, dy):
-    (x,) = ctx.saved_tensors
+    (xk,) = _kept(ctx)
     lin = ctx.lin
-    dy = dy.contiguous()
-    _, wbt = lin.shadow()
-    dx = ops.gemm_nt(dy, wbt[:, :lin.out_features]) if ctx.needs_input_grad[0] else None
-    dw = None
-    if ctx.needs_input_grad[1]:
-      sink, p = lin.sink, lin.weight
-      if sink is not None and sink.active_for(p):
-        sink.defer_dw(dy, x, p)
-      else:
-        dw = ops.gemm_tn(dy, x)
+    P = _POLICY[lin.mx]
+    dyg, dyk = P['quant'](dy.contiguous())
+    dx = P['dx'](dyg, lin) if ctx.needs_input_grad[0] else None
+    dw = _weight_grad(lin, dyk, xk) if ctx.needs_input_grad[1] else None
     return dx, dw, None
 
 
-class SwiGLUMLPFn(torch.autograd.Function):
-  """y = fc2(silu(gate) * up) with (gate | up) = x W_fc1^T (components.py:50-57): the whole MLP as one autograd node, so that both
-  activations live in GEMM epilogues.  Forward: fc1 with the SwiGLU gate in its epilogue (ops.fc1_swiglu), then fc2.  Backward: the
-  dX GEMM of fc2 with the SwiGLU backward in ITS epilogue (ops.fc2_dx_swiglu_bwd: d(act) never reaches memory), then the plain
-  Linear backward of fc1.  Every intermediate carries the bits of the unfused chain (Linear -> SwiGLU -> Linear)."""
-
-  @staticmethod
-  def forward(ctx, x, w1, w2, fc1, fc2):
-    w1b, _ = fc1.shadow()
-    w2b, _ = fc2.shadow()
-    u, act = ops.fc1_swiglu(x, w1b)
-    ctx.save_for_backward(x, u, act)
-    ctx.fc1, ctx.fc2 = fc1, fc2
-    return ops.gemm_nt(act, w2b)
-
-  @staticmethod
-  def backward(ctx, dy):
-    x, u, act = ctx.saved_tensors
-    fc1, fc2 = ctx.fc1, ctx.fc2
-    dy = dy.contiguous()
-    _, w1t = fc1.shadow()
-    _, w2t = fc2.shadow()
-    du = ops.fc2_dx_swiglu_bwd(dy, w2t[:, :fc2.out_features], u)
-    dw2 = dw1 = None
-    if ctx.needs_input_grad[2]:
-      sink, p = fc2.sink, fc2.weight
-      if sink is not None and sink.active_for(p):
-        sink.defer_dw(dy, act, p)
-      else:
-        dw2 = ops.gemm_tn(dy, act)
-    dx = ops.gemm_nt(du, w1t[:, :fc1.out_features]) if ctx.needs_input_grad[0] else None
-    if ctx.needs_input_grad[1]:
-      sink, p = fc1.sink, fc1.weight
-      if sink is not None and sink.active_for(p):
-        sink.defer_dw(du, x, p)
-      else:
-        dw1 = ops.gemm_tn(du, x)
-    return dx, dw1, dw2, None, None
-
-
-class PlainMLPFn(torch.autograd.Function):
-  """y = fc2(act(fc1 x)) for the reference's plain MLP classes (components.py:31-40 `MLP`: silu; :59-70 `MLPReluSquared`: relu squared)
-  as one autograd node: two NT GEMMs around a stand-alone activation kernel (these classes are off every shipped config's path, so no
-  fused epilogue is built for them), backward = dX of fc2 -> activation backward -> the plain Linear backward of fc1."""
-
-  @staticmethod
-  def forward(ctx, x, w1, w2, fc1, fc2, kind):
-    w1b, _ = fc1.shadow()
-    w2b, _ = fc2.shadow()
-    u = ops.gemm_nt(x, w1b)
-    act = ops.act_fwd(u, kind)
-    ctx.save_for_backward(x, u, act)
-    ctx.fc1, ctx.fc2, ctx.kind = fc1, fc2, kind
-    return ops.gemm_nt(act, w2b)
-
-  @staticmethod
-  def backward(ctx, dy):
-    x, u, act = ctx.saved_tensors
-    fc1, fc2 = ctx.fc1, ctx.fc2
-    dy = dy.contiguous()
-    _, w1t = fc1.shadow()
-    _, w2t = fc2.shadow()
-    du = ops.act_bwd(ops.gemm_nt(dy, w2t[:, :fc2.out_features]), u, ctx.kind)
-    dw2 = dw1 = None
-    if ctx.needs_input_grad[2]:
-      sink, p = fc2.sink, fc2.weight
-      if sink is not None and sink.active_for(p):
-        sink.defer_dw(dy, act, p)
-      else:
-        dw2 = ops.gemm_tn(dy, act)
-    dx = ops.gemm_nt(du, w1t[:, :fc1.out_features]) if ctx.needs_input_grad[0] else None
-    if ctx.needs_input_grad[1]:
-      sink, p = fc1.sink, fc1.weight
-      if sink is not None and sink.active_for(p):
-        sink.defer_dw(du, x, p)
-      else:
-        dw1 = ops.gemm_tn(du, x)
-    return dx, dw1, dw2, None, None, None
-
-
 class QKVRopeFn(torch.autograd.Function):
-  """w_qkv projection + RoPE (transformer.py:42-47): returns the projection with q | k ALREADY rotated.
+  """w_qkv projection + RoPE (transformer.py:42-47): returns the projection with q | k ALREADY rotated - in the GEMM's epilogue
+  (ops.qkv_rope) in bf16, by the stand-alone kernel after the MX GEMM in mxfp8.
   Contract with AttnFn: AttnFn.backward returns the gradient w.r.t. the UN-rotated projection (the inverse
   rotation is folded into the attention backward epilogues), so this backward is the plain Linear backward."""
 
   @staticmethod
   def forward(ctx, x, weight, lin, cos, sin, B, T, nh):
-    wb, _ = lin.shadow()
-    ctx.save_for_backward(x)
+    P = _POLICY[lin.mx]
+    xg, xk = P['quant'](x)
     ctx.lin = lin
-    return ops.qkv_rope(x, wb, cos, sin, B, T, nh)
+    _keep(ctx, xk)
+    if P is _BF16:
+      return ops.qkv_rope(xg, lin.shadow()[0], cos, sin, B, T, nh)
+    return ops.rope_qk_(P['nt'](xg, lin), cos, sin, B, T, nh)
 
   @staticmethod
   def backward(ctx, dy):
-    dx, dw, _ = LinearFn.backward(ctx, dy)
-    return dx, dw, None, None, None, None, None, None
+    return LinearFn.backward(ctx, dy)[:2] + (None,) * 6
 
 
-# ---- linear_precision 'mxfp8': the block linears on MX GEMMs (DESIGN.md section 9) ------------------------------------------------------
-# Separate Functions; the bf16 ones above are untouched.  Every bf16 input of a linear is quantized once into both orientations: the
-# row-blocked copy feeds the forward / dX GEMM, the column-blocked copy (blocked along the tokens) is what is kept for dW.  The fused RoPE
-# and SwiGLU epilogues are not used: the stand-alone kernels run between the GEMMs.
-def _mx_dw(lin, dyt, xt):
-  """dW = dY^T X from the copies of dY and X blocked along the tokens: queued in the sink, else returned fp32 to autograd."""
-  sink, p = lin.sink, lin.weight
-  if sink is not None and sink.active_for(p):
-    sink.defer_dw(dyt, xt, p)
-    return None
-  return ops.gemm_mx_nt(dyt, xt, out_dtype=torch.float32)
+def _fc1_act(P, kind, xg, fc1):
+  """fc1 and the activation -> (u, act as fc2's operand, act as kept for fc2's dW)."""
+  if kind == 'glu' and P is _BF16:
+    u, act = ops.fc1_swiglu(xg, fc1.shadow()[0])
+    return u, act, act
+  u = P['nt'](xg, fc1)
+  return (u,) + P['quant'](ops.swiglu_fwd(u) if kind == 'glu' else ops.act_fwd(u, kind))
 
 
-def _mx_linear_bwd(ctx, lin, dy, xt):
-  """(dx, dW) of y = x W^T: dY quantized once into both orientations."""
-  dyr, dyt = ops.mx_quant(dy.contiguous())
-  dx = ops.gemm_mx_nt(dyr, lin.mx_weights()[1]) if ctx.needs_input_grad[0] else None
-  dw = _mx_dw(lin, dyt, xt) if ctx.needs_input_grad[1] else None
-  return dx, dw
+def _fc2_dx_act_bwd(P, kind, dyg, fc2, u):
+  """du = activation backward of fc2's dX."""
+  if kind == 'glu' and P is _BF16:
+    return ops.fc2_dx_swiglu_bwd(dyg, fc2.shadow()[1][:, :fc2.out_features], u)
+  dact = P['dx'](dyg, fc2)
+  return ops.swiglu_bwd(dact, u) if kind == 'glu' else ops.act_bwd(dact, u, kind)
 
 
-class MxLinearFn(torch.autograd.Function):
-  """LinearFn on MX GEMMs."""
-
-  @staticmethod
-  def forward(ctx, x, weight, lin):
-    xr, xt = ops.mx_quant(x)
-    ctx.xt, ctx.lin = xt, lin
-    return ops.gemm_mx_nt(xr, lin.mx_weights()[0])
-
-  @staticmethod
-  def backward(ctx, dy):
-    dx, dw = _mx_linear_bwd(ctx, ctx.lin, dy, ctx.xt)
-    return dx, dw, None
-
-
-class MxQKVRopeFn(torch.autograd.Function):
-  """QKVRopeFn on an MX GEMM followed by the stand-alone RoPE kernel (same contract with AttnFn: the backward is the Linear's)."""
-
-  @staticmethod
-  def forward(ctx, x, weight, lin, cos, sin, B, T, nh):
-    xr, xt = ops.mx_quant(x)
-    ctx.xt, ctx.lin = xt, lin
-    y = ops.gemm_mx_nt(xr, lin.mx_weights()[0])
-    ops.rope_qk_(y, cos, sin, B, T, nh)
-    return y
-
-  @staticmethod
-  def backward(ctx, dy):
-    dx, dw = _mx_linear_bwd(ctx, ctx.lin, dy, ctx.xt)
-    return dx, dw, None, None, None, None, None, None
-
-
-def _mx_mlp_bwd(ctx, dy, act_bwd):
-  fc1, fc2 = ctx.fc1, ctx.fc2
-  (u,) = ctx.saved_tensors
-  dyr, dyt = ops.mx_quant(dy.contiguous())
-  du = act_bwd(ops.gemm_mx_nt(dyr, fc2.mx_weights()[1]), u)
-  dw2 = _mx_dw(fc2, dyt, ctx.actt) if ctx.needs_input_grad[2] else None
-  dur, dut = ops.mx_quant(du)
-  dx = ops.gemm_mx_nt(dur, fc1.mx_weights()[1]) if ctx.needs_input_grad[0] else None
-  dw1 = _mx_dw(fc1, dut, ctx.xt) if ctx.needs_input_grad[1] else None
-  return dx, dw1, dw2
-
-
-class MxSwiGLUMLPFn(torch.autograd.Function):
-  """SwiGLUMLPFn on MX GEMMs: fc1 -> plm_swiglu_fwd -> fc2; backward fc2 dX -> plm_swiglu_bwd -> fc1."""
-
-  @staticmethod
-  def forward(ctx, x, w1, w2, fc1, fc2):
-    xr, xt = ops.mx_quant(x)
-    u = ops.gemm_mx_nt(xr, fc1.mx_weights()[0])
-    actr, actt = ops.mx_quant(ops.swiglu_fwd(u))
-    ctx.save_for_backward(u)
-    ctx.xt, ctx.actt, ctx.fc1, ctx.fc2 = xt, actt, fc1, fc2
-    return ops.gemm_mx_nt(actr, fc2.mx_weights()[0])
-
-  @staticmethod
-  def backward(ctx, dy):
-    dx, dw1, dw2 = _mx_mlp_bwd(ctx, dy, ops.swiglu_bwd)
-    return dx, dw1, dw2, None, None
-
-
-class MxPlainMLPFn(torch.autograd.Function):
-  """PlainMLPFn on MX GEMMs: fc1 -> plm_act_fwd -> fc2; backward fc2 dX -> plm_act_bwd -> fc1."""
+class MLPFn(torch.autograd.Function):
+  """y = fc2(act(fc1 x)), the whole MLP as one autograd node.  kind 'glu' (components.py:43-57): act = silu(gate) * up with (gate | up) =
+  fc1 x; 'silu' / 'relu_sq' (components.py:31-40 `MLP`, :59-70 `MLPReluSquared`): act elementwise.  Backward: dX of fc2 -> activation
+  backward -> the plain Linear backward of fc1.
+  'glu' in bf16 keeps both activations in GEMM epilogues: fc1 with the SwiGLU gate in its epilogue (ops.fc1_swiglu), the dX GEMM of fc2
+  with the SwiGLU backward in ITS epilogue (ops.fc2_dx_swiglu_bwd: d(act) never reaches memory); every intermediate carries the bits of
+  the unfused chain (Linear -> SwiGLU -> Linear).  Everything else runs the stand-alone activation kernel between the two GEMMs (the
+  plain classes are off every shipped config's path, and the MX GEMM has no fused epilogue)."""
 
   @staticmethod
   def forward(ctx, x, w1, w2, fc1, fc2, kind):
-    xr, xt = ops.mx_quant(x)
-    u = ops.gemm_mx_nt(xr, fc1.mx_weights()[0])
-    actr, actt = ops.mx_quant(ops.act_fwd(u, kind))
-    ctx.save_for_backward(u)
-    ctx.xt, ctx.actt, ctx.fc1, ctx.fc2, ctx.kind = xt, actt, fc1, fc2, kind
-    return ops.gemm_mx_nt(actr, fc2.mx_weights()[0])
+    P = _POLICY[fc1.mx]
+    xg, xk = P['quant'](x)
+    P['ready'](fc1, fc2)
+    u, actg, actk = _fc1_act(P, kind, xg, fc1)
+    ctx.fc1, ctx.fc2, ctx.kind = fc1, fc2, kind
+    _keep(ctx, xk, u, actk)
+    return P['nt'](actg, fc2)
 
   @staticmethod
   def backward(ctx, dy):
-    dx, dw1, dw2 = _mx_mlp_bwd(ctx, dy, lambda d, u: ops.act_bwd(d, u, ctx.kind))
+    xk, u, actk = _kept(ctx)
+    fc1, fc2 = ctx.fc1, ctx.fc2
+    P = _POLICY[fc1.mx]
+    dyg, dyk = P['quant'](dy.contiguous())
+    du = _fc2_dx_act_bwd(P, ctx.kind, dyg, fc2, u)
+    dw2 = _weight_grad(fc2, dyk, actk) if ctx.needs_input_grad[2] else None
+    dug, duk = P['quant'](du)
+    dx = P['dx'](dug, fc1) if ctx.needs_input_grad[0] else None
+    dw1 = _weight_grad(fc1, duk, xk) if ctx.needs_input_grad[1] else None
     return dx, dw1, dw2, None, None, None
 
 
@@ -448,20 +364,6 @@ class AddNormFn(torch.autograd.Function):
     gin = g_xout.contiguous() if g_xout is not None else None
     dx, dxb, dw = _norm_dw(ctx.norm, g_y.contiguous(), xout, w, rstd, gin, True)
     return dx, dxb, dw, None
-
-
-class SwiGLUFn(torch.autograd.Function):
-  """silu(u[:, :h]) * u[:, h:] (components.py:55-56) in the reference's bf16 rounding order."""
-
-  @staticmethod
-  def forward(ctx, u):
-    ctx.save_for_backward(u)
-    return ops.swiglu_fwd(u)
-
-  @staticmethod
-  def backward(ctx, dout):
-    (u,) = ctx.saved_tensors
-    return ops.swiglu_bwd(dout.contiguous(), u)
 
 
 class DocMask:

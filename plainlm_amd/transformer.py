@@ -137,8 +137,7 @@ class HipLinear(nn.Module):
 
   def forward(self, x):
     lead = x.shape[:-1]
-    fn = Fn.MxLinearFn if self.mx else Fn.LinearFn
-    y = fn.apply(x.reshape(-1, self.in_features), self.weight, self)
+    y = Fn.LinearFn.apply(x.reshape(-1, self.in_features), self.weight, self)
     return y.view(*lead, self.out_features)
 
   def extra_repr(self):
@@ -174,44 +173,38 @@ class RMSNorm(nn.Module):
     return y.view(lead)
 
 
-class GLU(nn.Module):
+class _MLPBase(nn.Module):
+  """The reference's three MLP classes (models/components.py): fc1 [fc1_mult * h, d], fc2 [d, h], y = fc2(act(fc1 x)) as one autograd node
+  (functional.MLPFn) whose activation is the class's ``kind``."""
+  kind, fc1_mult = None, 1
+
+  def __init__(self, dim, hidden_dim, multiple_of=256):
+    super().__init__()
+    hidden_dim = multiple_of * ((hidden_dim + multiple_of - 1) // multiple_of)
+    self.hidden_dim = hidden_dim
+    self.fc1 = HipLinear(dim, self.fc1_mult * hidden_dim)
+    self.fc2 = HipLinear(hidden_dim, dim)
+
+  def apply_fn(self, x2d):
+    return Fn.MLPFn.apply(x2d, self.fc1.weight, self.fc2.weight, self.fc1, self.fc2, self.kind)
+
+  def forward(self, x):
+    lead = x.shape[:-1]
+    return self.apply_fn(x.reshape(-1, x.shape[-1])).view(*lead, -1)
+
+
+class GLU(_MLPBase):
   """SwiGLU MLP with fused fc1 [2h, d] (models/components.py:43-56)."""
-
-  def __init__(self, dim, hidden_dim, multiple_of=256):
-    super().__init__()
-    hidden_dim = multiple_of * ((hidden_dim + multiple_of - 1) // multiple_of)
-    self.hidden_dim = hidden_dim
-    self.fc1 = HipLinear(dim, 2 * hidden_dim)
-    self.fc2 = HipLinear(hidden_dim, dim)
-
-  def apply_fn(self, x2d):
-    return (Fn.MxSwiGLUMLPFn if self.fc1.mx else Fn.SwiGLUMLPFn).apply(x2d, self.fc1.weight, self.fc2.weight, self.fc1, self.fc2)
-
-  def forward(self, x):
-    lead = x.shape[:-1]
-    return self.apply_fn(x.reshape(-1, x.shape[-1])).view(*lead, -1)
+  kind, fc1_mult = 'glu', 2
 
 
-class MLP(nn.Module):
-  """models/components.py:31-40 (`MLP`: fc2(silu(fc1 x))) and :59-70 (`MLPReluSquared`: fc2(relu(fc1 x)^2)): fc1 [h, d], fc2 [d, h]."""
+class MLP(_MLPBase):
+  """models/components.py:31-40: fc2(silu(fc1 x))."""
   kind = 'silu'
-
-  def __init__(self, dim, hidden_dim, multiple_of=256):
-    super().__init__()
-    hidden_dim = multiple_of * ((hidden_dim + multiple_of - 1) // multiple_of)
-    self.hidden_dim = hidden_dim
-    self.fc1 = HipLinear(dim, hidden_dim)
-    self.fc2 = HipLinear(hidden_dim, dim)
-
-  def apply_fn(self, x2d):
-    return (Fn.MxPlainMLPFn if self.fc1.mx else Fn.PlainMLPFn).apply(x2d, self.fc1.weight, self.fc2.weight, self.fc1, self.fc2, self.kind)
-
-  def forward(self, x):
-    lead = x.shape[:-1]
-    return self.apply_fn(x.reshape(-1, x.shape[-1])).view(*lead, -1)
 
 
 class MLPReluSquared(MLP):
+  """models/components.py:59-70: fc2(relu(fc1 x)^2)."""
   kind = 'relu_sq'
 
 
@@ -230,7 +223,7 @@ class Attention(nn.Module):
     self.w_out = HipLinear(cfg.dim, cfg.dim)
 
   def forward(self, x2d, rope, doc_start, B, T, cache=None):
-    qkv = (Fn.MxQKVRopeFn if self.w_qkv.mx else Fn.QKVRopeFn).apply(x2d, self.w_qkv.weight, self.w_qkv, rope[0], rope[1], B, T, self.n_heads)
+    qkv = Fn.QKVRopeFn.apply(x2d, self.w_qkv.weight, self.w_qkv, rope[0], rope[1], B, T, self.n_heads)
     if cache is not None:  # prefill: this layer's kv [B, Tmax, 2*dim] takes the k | v columns of the rotated qkv, as they are
       d = self.n_heads * self.head_dim
       cache[:, :T].copy_(qkv.detach().view(B, T, 3 * d)[:, :, d:])

@@ -78,7 +78,7 @@ def _run_linear(lin, x, dy, sink):
 
 @pytest.mark.parametrize('sink', [False, True])
 def test_mx_linear_fn_against_emulation(P, sink):
-  """MxLinearFn (w_out of block 0) with ragged M = 1000: y and dx within two bf16 roundings of the emulation, dW (fp32) too; the sink path
+  """LinearFn on an mx linear (w_out of block 0) with ragged M = 1000: y and dx within two bf16 roundings of the emulation, dW (fp32) too; the sink path
   (deferred MX dW GEMM storing into main_grad) and the autograd path give the same bits."""
   m = _model(P, 'mxfp8')
   lin = m.layers[0].attn.w_out
@@ -149,7 +149,7 @@ def test_mx_qkv_rope_fn_against_emulation(P):
   cos, sin = m._rope(torch.device('cuda'))
   xx = x.cuda().requires_grad_(True)
   from plainlm_amd import functional as Fn
-  y = Fn.MxQKVRopeFn.apply(xx, att.w_qkv.weight, att.w_qkv, cos, sin, B, T, att.n_heads)
+  y = Fn.QKVRopeFn.apply(xx, att.w_qkv.weight, att.w_qkv, cos, sin, B, T, att.n_heads)
   y.backward(dy.cuda())
   w = att.w_qkv.weight.detach().cpu().to(BF)
   ry, rdx, rdw = _emul_linear(x, w, dy)
