@@ -22,7 +22,8 @@ FINISH_CHECK_EVERY = 16  # generate: the one device-to-host read of the loop (ha
 
 class KVCache:
   """Per-layer ``kv`` bf16 [B, Tmax, 2*dim] (row (b, j): the k | v columns of token j's rotated qkv row), ``lens`` int32 [B] on the
-  device, the attention workspaces (shared by all layers), and the status flag of the append kernel (checked by ``check``)."""
+  device, and the status flag of the append kernel (checked by ``check``).  It owns no workspace: ops.attn_decode / ops.attn_extend take
+  theirs from the workspace arena of the current stream."""
 
   def __init__(self, n_layers, B, Tmax, n_heads, head_dim, device):
     dim = n_heads * head_dim
@@ -32,9 +33,6 @@ class KVCache:
     self._pl = torch.zeros((2, B), dtype=torch.int32, device=device)
     self._pl[0] -= 1
     self.status = torch.zeros((1,), dtype=torch.int32, device=device)
-    # (workspace, bytes) pairs at the automatic split count: key 0 is ops.attn_decode's, made here; key n >= 1 ops.attn_extend's for
-    # chunks of n rows, made at the first extend of that width
-    self._ws = {0: ops.attn_decode_workspace(B, n_heads, head_dim, Tmax, 0, device)}
 
   @property
   def lens(self):
@@ -55,18 +53,6 @@ class KVCache:
   def advance_by(self, n_new):
     """Move [pos | lens] by n_new - an int32 [B] device tensor, or an int - with one in-place add (Transformer.extend, after its chunk)."""
     self._pl += n_new
-
-  @property
-  def workspace(self):
-    """The (workspace, bytes) pair of ops.attn_decode."""
-    return self._ws[0]
-
-  def extend_workspace(self, n):
-    """The (workspace, bytes) pair of ops.attn_extend for chunks of n rows: allocated at the first chunk of that width and kept."""
-    ws = self._ws.get(n)
-    if ws is None:
-      ws = self._ws[n] = ops.attn_extend_workspace(self.B, n, self.n_heads, self.head_dim, self.Tmax, 0, self.status.device)
-    return ws
 
   def check(self):
     """Raises if a decode step tried to append past the cache (or past the RoPE table); reads the device flag, so it waits for the GPU."""

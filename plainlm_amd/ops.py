@@ -6,7 +6,6 @@ Every function here launches hand-written gfx950 kernels; none has a torch fallb
 
 import collections
 import ctypes as C
-import os
 
 import torch
 
@@ -14,6 +13,7 @@ from . import _lib
 
 BF16 = torch.bfloat16
 F32 = torch.float32
+_DTYPE_NAMES = {BF16: 'bf16', F32: 'fp32'}
 
 
 def _stream():
@@ -29,11 +29,16 @@ PROFILE = None
 LAUNCH_HOOK = None
 
 
-class _Timed:
-  __slots__ = ('family', 'flops', 'start')
+class _Launch:
+  """One launch's (family, work), stated once.  Constructing it reports an MFMA launch to LAUNCH_HOOK (the 'hbm:' families are not
+  reported), so construct it BEFORE the call's workspace query: the hook may change the CU reserve, and plans (tile shape, stream-K /
+  split-K workspace) are functions of it.  Entered, it brackets the launch with events for PROFILE."""
+  __slots__ = ('family', 'work', 'start')
 
-  def __init__(self, family, flops):
-    self.family, self.flops, self.start = family, flops, None
+  def __init__(self, family, work):
+    self.family, self.work, self.start = family, work, None
+    if LAUNCH_HOOK is not None and not family.startswith('hbm:'):
+      LAUNCH_HOOK(family, work)
 
   def __enter__(self):
     if PROFILE is not None:
@@ -45,24 +50,23 @@ class _Timed:
     if self.start is not None:
       end = torch.cuda.Event(enable_timing=True)
       end.record()
-      PROFILE.append((self.family, self.flops, self.start, end))
+      PROFILE.append((self.family, self.work, self.start, end))
     return False
-
-
-def _hook(family, flops):
-  """First thing in every MFMA op, BEFORE its workspace query: the hook may change the CU reserve, and plans (tile shape, stream-K /
-  split-K workspace) are functions of it."""
-  if LAUNCH_HOOK is not None:
-    LAUNCH_HOOK(family, flops)
 
 
 def _p(t):
   return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
-def _need(t, dtype, name, dim=None):
+def _need(t, dtype, name, dim=None, strided=False):
+  """The operand contract: a GPU tensor of this dtype, contiguous (and of ``dim`` dims when given) - or, with strided, 2-D with unit
+  inner stride, its rows any distance apart (a column slice of a wider buffer)."""
   if not t.is_cuda:
     raise RuntimeError(f'{name}: tensor must live on the GPU (plainlm_amd has no CPU path)')
+  if strided:
+    if t.dtype != dtype or t.dim() != 2 or t.stride(1) != 1:
+      raise ValueError(f'{name}: need a 2-D {_DTYPE_NAMES[dtype]} GPU tensor with unit inner stride')
+    return t
   if t.dtype != dtype:
     raise TypeError(f'{name}: expected {dtype}, got {t.dtype}')
   if not t.is_contiguous():
@@ -70,6 +74,81 @@ def _need(t, dtype, name, dim=None):
   if dim is not None and t.dim() != dim:
     raise ValueError(f'{name}: expected {dim} dims, got {t.dim()}')
   return t
+
+
+def _need_shadows(dst, dst_t, R, Cc, name, on_gpu=True):
+  """The bf16 copies of an fp32 [R, C] weight: dst contiguous [R, C] (None: made by the caller, not checked), dst_t [C, >= R] with unit
+  inner stride (its rows may be padded: K-padding for the dX GEMM)."""
+  if dst is not None and (dst.dtype != BF16 or tuple(dst.shape) != (R, Cc) or not dst.is_contiguous() or not dst.is_cuda):
+    raise ValueError(f'{name}: need contiguous bf16 [rows, cols] on the GPU')
+  if dst_t.dtype != BF16 or dst_t.dim() != 2 or dst_t.shape[0] != Cc or dst_t.shape[1] < R or dst_t.stride(1) != 1 or \
+     (on_gpu and not dst_t.is_cuda):
+    raise ValueError(f'{name}_t: need bf16 [cols, >= rows]' + (' on the GPU' if on_gpu else ''))
+
+
+# ---- workspaces -------------------------------------------------------------------
+# Every workspace (split-K / stream-K slabs, the heads' and the decode / extend partials, the embedding sort) is used on the current stream
+# and dead when its wrapper returns: the reduce that reads it runs inside the entry point that filled it, and none reads a byte it did not
+# write (tests/footprint.py).  So one grow-only buffer per (device, stream) serves all: the largest request is held, not the sum over shapes.
+_arenas = {}    # (device, stream handle) -> uint8 buffer
+_ws_sizes = {}  # (size query, its arguments, CU reserve, env epoch) -> bytes
+
+
+def _workspace(device, nbytes, stream):
+  """nbytes of scratch for one launch on ``stream`` (what _stream() gave): the arena of that device and stream, grown when too small."""
+  key = (device, stream.value)
+  buf = _arenas.get(key)
+  if buf is None or buf.numel() < nbytes:
+    del buf
+    _arenas.pop(key, None)  # the old buffer goes back to the allocator before the larger one is asked for
+    buf = _arenas[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+  return buf
+
+
+def release_workspaces():
+  """Drop every workspace arena (torch's caching allocator gets the memory back); the next launch that needs one allocates again."""
+  _arenas.clear()
+
+
+def workspace_bytes():
+  """Bytes held by the workspace arenas of all devices and streams."""
+  return sum(buf.numel() for buf in _arenas.values())
+
+
+def _ws_bytes(query, *shape):
+  """The answer of a library size query, cached: the plan behind it depends on the shape, the library's environment switches (see
+  reload_env) and the CU reserve - all part of the key."""
+  key = (query, shape, _cu_reserve, _env_epoch)
+  v = _ws_sizes.get(key)
+  if v is None:
+    v = _ws_sizes[key] = int(getattr(_lib.load(), query)(*shape))
+  return v
+
+
+_cu_reserve = 0
+
+
+def set_cu_reserve(n):
+  """Leave n CUs out of the persistent GEMM grids (RCCL's kernels run there while gradient buckets are in flight); every
+  plan (tile shape, hybrid stream-K, split-K) is recomputed per launch from the current value."""
+  global _cu_reserve
+  _lib.check(_lib.load().plm_set_cu_reserve(int(n)), 'plm_set_cu_reserve')
+  _cu_reserve = int(n)
+
+
+def cu_reserve():
+  return _cu_reserve
+
+
+_env_epoch = 0
+
+
+def reload_env():
+  """Have the library read its PLM_* environment switches again (it reads them once, at its first call; tests and A/B tools
+  that change os.environ afterwards call this)."""
+  global _env_epoch
+  _lib.load().plm_reload_env()
+  _env_epoch += 1
 
 
 # ---- casts ------------------------------------------------------------------
@@ -87,8 +166,7 @@ def cast_bf16_t(src, out=None, out_t=None):
   R, Cc = src.shape
   out = torch.empty((R, Cc), dtype=BF16, device=src.device) if out is None else out
   out_t = torch.empty((Cc, R), dtype=BF16, device=src.device) if out_t is None else out_t
-  if out_t.dtype != BF16 or out_t.dim() != 2 or out_t.shape[0] != Cc or out_t.shape[1] < R or out_t.stride(1) != 1:
-    raise ValueError('cast_bf16_t.out_t: need bf16 [C, >=R]')
+  _need_shadows(None, out_t, R, Cc, 'cast_bf16_t.out', on_gpu=False)
   _lib.check(_lib.load().plm_cast_f32_bf16_t(_p(src), _p(out), _p(out_t), R, Cc, out_t.stride(0), _stream()),
              'plm_cast_f32_bf16_t')
   return out, out_t
@@ -102,12 +180,9 @@ def cast_bf16_t_multi(items):
   for i, (src, out, out_t) in enumerate(items):
     _need(src, F32, 'cast_bf16_t_multi.src', 2)
     R, Cc = src.shape
-    if out.dtype != BF16 or out.shape != (R, Cc) or not out.is_contiguous() or not out.is_cuda:
-      raise ValueError('cast_bf16_t_multi.out: need contiguous bf16 [R, C] on the GPU')
-    if out_t.dtype != BF16 or out_t.dim() != 2 or out_t.shape[0] != Cc or out_t.shape[1] < R or out_t.stride(1) != 1 or not out_t.is_cuda:
-      raise ValueError('cast_bf16_t_multi.out_t: need bf16 [C, >=R] on the GPU')
+    _need_shadows(out, out_t, R, Cc, 'cast_bf16_t_multi.out')
     arr[i] = _lib.CastItem(src.data_ptr(), out.data_ptr(), out_t.data_ptr(), R, Cc, out_t.stride(0))
-  with _Timed('hbm:cast_bf16_t_multi', 8.0 * sum(src.numel() for src, _, _ in items)):  # one fp32 read, the bf16 copy and its transpose written
+  with _Launch('hbm:cast_bf16_t_multi', 8.0 * sum(src.numel() for src, _, _ in items)):  # one fp32 read, the bf16 copy and its transpose written
     _lib.check(_lib.load().plm_cast_f32_bf16_t_multi(arr, len(items), _stream()), 'plm_cast_f32_bf16_t_multi')
 
 
@@ -136,8 +211,7 @@ class MxTensor:
 
 
 def _mx_item(x, rows, cols, device):
-  if not x.is_cuda or x.dtype != BF16 or x.dim() != 2 or x.stride(1) != 1:
-    raise ValueError('mx_quant.x: need a 2-D bf16 GPU tensor with unit inner stride')
+  _need(x, BF16, 'mx_quant.x', strided=True)
   R, Cc = x.shape
   r = MxTensor.empty(R, Cc, x.device) if rows else None
   c = MxTensor.empty(Cc, R, x.device) if cols else None
@@ -152,7 +226,7 @@ def mx_quant(x, rows=True, cols=True):
   if not (rows or cols):
     raise ValueError('mx_quant: ask for at least one orientation')
   item, r, c = _mx_item(x, rows, cols, x.device)
-  with _Timed('hbm:mx_quant', 2.0 * x.numel() + (1.03125 * x.numel() if rows else 0) + (1.03125 * x.numel() if cols else 0)):
+  with _Launch('hbm:mx_quant', 2.0 * x.numel() + (1.03125 * x.numel() if rows else 0) + (1.03125 * x.numel() if cols else 0)):
     _lib.check(_lib.load().plm_mx_quant(item.x, item.ld, item.rows, item.cols, item.q, item.s, item.qt, item.st, _stream()), 'plm_mx_quant')
   return r, c
 
@@ -167,7 +241,7 @@ def mx_quant_multi(xs, rows=True, cols=True):
     arr[i], r, c = _mx_item(x, rows, cols, x.device)
     out.append((r, c))
   n = sum(x.numel() for x in xs)
-  with _Timed('hbm:mx_quant_multi', 2.0 * n + 1.03125 * n * (int(rows) + int(cols))):
+  with _Launch('hbm:mx_quant_multi', 2.0 * n + 1.03125 * n * (int(rows) + int(cols))):
     _lib.check(_lib.load().plm_mx_quant_multi(arr, len(xs), _stream()), 'plm_mx_quant_multi')
   return out
 
@@ -195,11 +269,9 @@ def gemm_mx_nt(a, b, out=None, accumulate=False, out_dtype=BF16):
     mode = _lib.MX_OUT_F32_ACC if accumulate else _lib.MX_OUT_F32
   else:
     raise TypeError(f'gemm_mx_nt.out: bf16 or fp32, got {out.dtype}')
-  lib = _lib.load()
-  _hook('gemm_mx_nt', 2.0 * M * N * K)
-  with _Timed('gemm_mx_nt', 2.0 * M * N * K):
-    _lib.check(lib.plm_gemm_mx_nt(_p(a.data), _p(a.scales), _p(b.data), _p(b.scales), _p(out), out.stride(0), M, N, a.data.shape[1], mode,
-                                  _stream()), 'plm_gemm_mx_nt')
+  with _Launch('gemm_mx_nt', 2.0 * M * N * K):
+    _lib.check(_lib.load().plm_gemm_mx_nt(_p(a.data), _p(a.scales), _p(b.data), _p(b.scales), _p(out), out.stride(0), M, N, a.data.shape[1],
+                                          mode, _stream()), 'plm_gemm_mx_nt')
   return out
 
 
@@ -209,7 +281,7 @@ def embed_fwd(ids, W):
   _need(W, F32, 'embed_fwd.W', 2)
   M = ids.numel()
   out = torch.empty((M, W.shape[1]), dtype=F32, device=W.device)
-  with _Timed('hbm:embed_fwd', 8.0 * M * W.shape[1] + 8.0 * M):
+  with _Launch('hbm:embed_fwd', 8.0 * M * W.shape[1] + 8.0 * M):
     _lib.check(_lib.load().plm_embed_fwd(_p(ids), _p(W), _p(out), M, W.shape[1], W.shape[0], _stream()), 'plm_embed_fwd')
   return out
 
@@ -222,9 +294,6 @@ def embed_bwd(ids, dout, dW):
   _lib.check(_lib.load().plm_embed_bwd(_p(ids), _p(dout), _p(dW), ids.numel(), dW.shape[1], dW.shape[0], _stream()),
              'plm_embed_bwd')
   return dW
-
-
-_embed_ws = {}
 
 
 def embed_bwd_sorted(ids, dout, dW, accumulate):
@@ -248,12 +317,11 @@ def embed_bwd_sorted(ids, dout, dW, accumulate):
   nbytes = lib.plm_embed_bwd_workspace_bytes(ids.numel(), dW.shape[0])
   if nbytes == 0:
     return False
-  ws = _embed_ws.get(dout.device)
-  if ws is None or ws.numel() < nbytes:
-    ws = _embed_ws[dout.device] = torch.empty(nbytes, dtype=torch.uint8, device=dout.device)
-  with _Timed('hbm:embed_bwd', 4.0 * dout.numel() + (8.0 if accumulate else 4.0) * dW.numel() + 8.0 * ids.numel()):
+  stream = _stream()
+  ws = _workspace(dout.device, nbytes, stream)
+  with _Launch('hbm:embed_bwd', 4.0 * dout.numel() + (8.0 if accumulate else 4.0) * dW.numel() + 8.0 * ids.numel()):
     _lib.check(lib.plm_embed_bwd_sorted(_p(ids), _p(dout), _p(dW), ids.numel(), dW.shape[1], dW.shape[0], int(bool(accumulate)),
-                                        _p(ws), nbytes, _stream()), 'plm_embed_bwd_sorted')
+                                        _p(ws), nbytes, stream), 'plm_embed_bwd_sorted')
   return True
 
 
@@ -268,7 +336,7 @@ def rmsnorm_fwd(x, w, eps, branch=None, write_xout=False):
   xout = torch.empty_like(x) if (write_xout or branch is not None) else None
   y = torch.empty((M, d), dtype=BF16, device=x.device)
   rstd = torch.empty((M,), dtype=F32, device=x.device)
-  with _Timed('hbm:rmsnorm_fwd', (6.0 + (2.0 if branch is not None else 0.0) + (4.0 if xout is not None else 0.0)) * M * d):
+  with _Launch('hbm:rmsnorm_fwd', (6.0 + (2.0 if branch is not None else 0.0) + (4.0 if xout is not None else 0.0)) * M * d):
     _lib.check(_lib.load().plm_rmsnorm_fwd(_p(x), _p(branch), _p(xout), _p(w), _p(y), _p(rstd), M, d, float(eps), _stream()),
                'plm_rmsnorm_fwd')
   return xout, y, rstd
@@ -288,7 +356,7 @@ def rmsnorm_bwd(dy, x, w, rstd, gin=None, want_bf16=False, dw_out=None, dw_accum
   dxb = torch.empty((M, d), dtype=BF16, device=x.device) if want_bf16 else None
   nblk = lib.plm_rmsnorm_bwd_blocks(M)
   part = torch.empty((nblk, d), dtype=F32, device=x.device)
-  with _Timed('hbm:rmsnorm_bwd', (10.0 + (4.0 if gin is not None else 0.0) + (2.0 if want_bf16 else 0.0)) * M * d):
+  with _Launch('hbm:rmsnorm_bwd', (10.0 + (4.0 if gin is not None else 0.0) + (2.0 if want_bf16 else 0.0)) * M * d):
     _lib.check(lib.plm_rmsnorm_bwd(_p(dy), _p(x), _p(w), _p(rstd), _p(gin), _p(dx), _p(dxb), _p(part), M, d, _stream()),
                'plm_rmsnorm_bwd')
   if defer_dw:
@@ -352,62 +420,15 @@ def act_bwd(dout, u, kind):
 
 
 # ---- GEMMs ------------------------------------------------------------------------
-_tn_ws = {}
-_nt_ws_cache = {}
-
-
-_cu_reserve = 0
-
-
-def set_cu_reserve(n):
-  """Leave n CUs out of the persistent GEMM grids (RCCL's kernels run there while gradient buckets are in flight); every
-  plan (tile shape, hybrid stream-K, split-K) is recomputed per launch from the current value."""
-  global _cu_reserve
-  _lib.check(_lib.load().plm_set_cu_reserve(int(n)), 'plm_set_cu_reserve')
-  _cu_reserve = int(n)
-
-
-def cu_reserve():
-  return _cu_reserve
-
-
-_env_epoch = 0
-
-
-def reload_env():
-  """Have the library read its PLM_* environment switches again (it reads them once, at its first call; tests and A/B tools
-  that change os.environ afterwards call this)."""
-  global _env_epoch
-  _lib.load().plm_reload_env()
-  _env_epoch += 1
-
-
-def _nt_ws_bytes(lib, M, N, K):
-  """Workspace query of the hybrid NT schedule, cached per shape (the plan depends on the shape, the library's environment
-  switches - see reload_env - and the CU reserve: all part of the key)."""
-  key = (M, N, K, _cu_reserve, _env_epoch)
-  v = _nt_ws_cache.get(key)
-  if v is None:
-    v = _nt_ws_cache[key] = int(lib.plm_gemm_nt_workspace_bytes(M, N, K))
-  return v
-
-
-def _tn_workspace(nbytes, device):
-  """One grow-only split-K slab buffer per device (owned by torch's allocator)."""
-  buf = _tn_ws.get(device)
-  if buf is None or buf.numel() < nbytes:
-    buf = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
-    _tn_ws[device] = buf
-  return buf
+_C_DTYPE = {BF16: 0, F32: 1}  # c_dtype of plm_gemm_bf16_nt_ws
 
 
 def gemm_nt(A, B, out=None, out_dtype=BF16, accumulate=False, alpha=None, variant=0):
   """C[M,N] = alpha * A[M,K] @ B[N,K]^T ; A, B bf16 (row stride may exceed K).
   variant: 0 auto | 1 128x128 register-staged | 2 128x128 LDS-DMA | 3 persistent 256x256, plain 4-phase ring |
   4 / 5 / 6 / 7 persistent 256x256 / 256x192 / 256x128 / 128x192, deep-prefetch ring with offset wave groups (what auto picks from)."""
-  for t, n in ((A, 'A'), (B, 'B')):
-    if not t.is_cuda or t.dtype != BF16 or t.dim() != 2 or t.stride(1) != 1:
-      raise ValueError(f'gemm_nt.{n}: need a 2-D bf16 GPU tensor with unit inner stride')
+  _need(A, BF16, 'gemm_nt.A', strided=True)
+  _need(B, BF16, 'gemm_nt.B', strided=True)
   M, K = A.shape
   N = B.shape[0]
   if B.shape[1] != K:
@@ -416,24 +437,23 @@ def gemm_nt(A, B, out=None, out_dtype=BF16, accumulate=False, alpha=None, varian
     out = torch.empty((M, N), dtype=out_dtype, device=A.device)
   if out.dim() != 2 or out.shape != (M, N) or out.stride(1) != 1:
     raise ValueError('gemm_nt.out: bad shape/stride')
-  cd = {BF16: 0, F32: 1}[out.dtype]
+  cd = _C_DTYPE[out.dtype]
   if alpha is not None:
     _need(alpha, F32, 'gemm_nt.alpha')
-  lib = _lib.load()
-  _hook('gemm_nt', 2.0 * M * N * K)
-  nbytes = _nt_ws_bytes(lib, M, N, K) if (variant == 0 and cd == 0) else 0
-  ws = _tn_workspace(nbytes, A.device) if nbytes else None  # the split-K slab buffer is shared with gemm_tn (same stream)
-  with _Timed('gemm_nt', 2.0 * M * N * K):
-    _lib.check(lib.plm_gemm_bf16_nt_ws(_p(A), A.stride(0), _p(B), B.stride(0), _p(out), out.stride(0), M, N, K, cd,
-                                       int(bool(accumulate)), _p(alpha), int(variant), _p(ws), nbytes, _stream()), 'plm_gemm_bf16_nt')
+  launch = _Launch('gemm_nt', 2.0 * M * N * K)
+  nbytes = _ws_bytes('plm_gemm_nt_workspace_bytes', M, N, K) if (variant == 0 and cd == 0) else 0
+  stream = _stream()
+  ws = _workspace(A.device, nbytes, stream) if nbytes else None
+  with launch:
+    _lib.check(_lib.load().plm_gemm_bf16_nt_ws(_p(A), A.stride(0), _p(B), B.stride(0), _p(out), out.stride(0), M, N, K, cd,
+                                               int(bool(accumulate)), _p(alpha), int(variant), _p(ws), nbytes, stream), 'plm_gemm_bf16_nt')
   return out
 
 
 def gemm_tn(A, B, out=None, accumulate=False, alpha=None):
   """C[M,N] (+)= alpha * A[K,M]^T @ B[K,N] ; A, B bf16, C fp32."""
-  for t, n in ((A, 'A'), (B, 'B')):
-    if not t.is_cuda or t.dtype != BF16 or t.dim() != 2 or t.stride(1) != 1:
-      raise ValueError(f'gemm_tn.{n}: need a 2-D bf16 GPU tensor with unit inner stride')
+  _need(A, BF16, 'gemm_tn.A', strided=True)
+  _need(B, BF16, 'gemm_tn.B', strided=True)
   K, M = A.shape
   N = B.shape[1]
   if B.shape[0] != K:
@@ -443,15 +463,16 @@ def gemm_tn(A, B, out=None, accumulate=False, alpha=None):
     accumulate = False
   if out.dtype != F32 or out.shape != (M, N) or out.stride(1) != 1:
     raise ValueError('gemm_tn.out: need fp32 [M, N] with unit inner stride')
-  lib = _lib.load()
-  _hook('gemm_tn', 2.0 * M * N * K)
-  nbytes = lib.plm_gemm_tn_workspace_bytes(M, N, K)
-  ws = _tn_workspace(nbytes, A.device) if nbytes else None
   if alpha is not None:
     _need(alpha, F32, 'gemm_tn.alpha')
-  with _Timed('gemm_tn', 2.0 * M * N * K):
+  lib = _lib.load()
+  launch = _Launch('gemm_tn', 2.0 * M * N * K)
+  nbytes = lib.plm_gemm_tn_workspace_bytes(M, N, K)
+  stream = _stream()
+  ws = _workspace(A.device, nbytes, stream) if nbytes else None
+  with launch:
     _lib.check(lib.plm_gemm_bf16_tn(_p(A), A.stride(0), _p(B), B.stride(0), _p(out), out.stride(0), M, N, K,
-                                    int(bool(accumulate)), _p(alpha), _p(ws), nbytes, _stream()), 'plm_gemm_bf16_tn')
+                                    int(bool(accumulate)), _p(alpha), _p(ws), nbytes, stream), 'plm_gemm_bf16_tn')
   return out
 
 
@@ -470,9 +491,8 @@ def gemm_tn_grouped(problems):
   arr = (_lib.TnProblem * n)()
   Ms, Ns = (C.c_int64 * n)(), (C.c_int64 * n)()
   for i, (A, B, out, accumulate, alpha) in enumerate(problems):
-    for t, nm in ((A, 'A'), (B, 'B')):
-      if not t.is_cuda or t.dtype != BF16 or t.dim() != 2 or t.stride(1) != 1:
-        raise ValueError(f'gemm_tn_grouped.{nm}: need a 2-D bf16 GPU tensor with unit inner stride')
+    _need(A, BF16, 'gemm_tn_grouped.A', strided=True)
+    _need(B, BF16, 'gemm_tn_grouped.B', strided=True)
     if A.shape[0] != K or B.shape[0] != K:
       return False
     M, N = A.shape[1], B.shape[1]
@@ -486,11 +506,12 @@ def gemm_tn_grouped(problems):
   if lib.plm_gemm_tn_grouped_workspace_bytes(Ms, Ns, n, K) == 0:  # unsupported shapes (independent of the CU reserve): the caller's
     return False                                                  # per-problem gemm_tn calls report to the launch hook themselves
   flops = sum(2.0 * a.shape[1] * b.shape[1] * K for a, b, *_ in problems)
-  _hook('gemm_tn', flops)  # may change the CU reserve: the plan is taken after it
+  launch = _Launch('gemm_tn', flops)  # the hook may change the CU reserve: the plan is taken after it
   nbytes = lib.plm_gemm_tn_grouped_workspace_bytes(Ms, Ns, n, K)
-  ws = _tn_workspace(nbytes, problems[0][0].device)
-  with _Timed('gemm_tn', flops):
-    _lib.check(lib.plm_gemm_bf16_tn_grouped(arr, n, K, _p(ws), nbytes, _stream()), 'plm_gemm_bf16_tn_grouped')
+  stream = _stream()
+  ws = _workspace(problems[0][0].device, nbytes, stream)
+  with launch:
+    _lib.check(lib.plm_gemm_bf16_tn_grouped(arr, n, K, _p(ws), nbytes, stream), 'plm_gemm_bf16_tn_grouped')
   return True
 
 
@@ -505,8 +526,7 @@ def fc1_swiglu(x, w_fc1):
   h = N // 2
   u = torch.empty((M, N), dtype=BF16, device=x.device)
   act = torch.empty((M, h), dtype=BF16, device=x.device)
-  _hook('gemm_nt_fused', 2.0 * M * N * K)
-  with _Timed('gemm_nt_fused', 2.0 * M * N * K):
+  with _Launch('gemm_nt_fused', 2.0 * M * N * K):
     _lib.check(_lib.load().plm_fc1_swiglu_bf16(_p(x), x.stride(0), _p(w_fc1), w_fc1.stride(0), _p(u), _p(act), M, h, K, _stream()),
                'plm_fc1_swiglu_bf16')
   return u, act
@@ -524,8 +544,7 @@ def fc2_dx_swiglu_bwd(dy, w2t, u):
     raise ValueError('fc2_dx_swiglu_bwd: need dy [M, K], w2t [h, K], contiguous u [M, 2h]')
   du = torch.empty((M, 2 * h), dtype=BF16, device=dy.device)
   lib = _lib.load()
-  _hook('gemm_nt_fused', 2.0 * M * h * K)
-  with _Timed('gemm_nt_fused', 2.0 * M * h * K):
+  with _Launch('gemm_nt_fused', 2.0 * M * h * K):
     # first without the d(act) scratch: the one-launch path never touches it; the library answers PLM_E_WORKSPACE (-4) when this
     # shape takes the two-launch path, and only then is the buffer allocated
     rc = lib.plm_fc2_dx_swiglu_bwd_bf16(_p(dy), dy.stride(0), _p(w2t), w2t.stride(0), _p(u), _p(du), _p(None), M, h, K, _stream())
@@ -558,8 +577,7 @@ def qkv_rope(x, w_qkv, rope_cos, rope_sin, B, T, nh):
   N = w_qkv.shape[0]
   hd = N // (3 * nh)
   out = torch.empty((M, N), dtype=BF16, device=x.device)
-  _hook('gemm_nt_fused', 2.0 * M * N * K)
-  with _Timed('gemm_nt_fused', 2.0 * M * N * K):
+  with _Launch('gemm_nt_fused', 2.0 * M * N * K):
     _lib.check(_lib.load().plm_qkv_rope_bf16(_p(x), x.stride(0), _p(w_qkv), w_qkv.stride(0), _p(out), N, M, K, _p(rope_cos),
                                              _p(rope_sin), B, T, nh, hd, _stream()), 'plm_qkv_rope_bf16')
   return out
@@ -605,19 +623,32 @@ def attn_flops(B, T, nh, hd, doc_start=None):
   return 4.0 * nh * hd * pairs
 
 
+def _attn_outputs(qkv, B, T, nh, fwd):
+  """(hd, out bf16 [B*T, nh*hd], lse fp32 [B, nh, T]) of a forward pass over this projection output, (hd, dqkv, delta) of a backward."""
+  hd = qkv.shape[1] // (3 * nh)
+  big = torch.empty((B * T, nh * hd), dtype=BF16, device=qkv.device) if fwd else torch.empty_like(qkv)
+  return hd, big, torch.empty((B, nh, T), dtype=F32, device=qkv.device)
+
+
+def _attn_launch(family, passes, B, T, nh, hd, doc_start):
+  """The bracket of a causal / document-masked launch: the hook's clock only needs an estimate, so it gets the causal figure; the visible
+  pairs under doc_start cost a device reduction, which is paid only when PROFILE is on - never on the launch path."""
+  launch = _Launch(family, passes * attn_flops(B, T, nh, hd))
+  if PROFILE is not None:
+    launch.work = passes * attn_flops(B, T, nh, hd, doc_start)
+  return launch
+
+
 def attn_fwd(qkv_rot, B, T, nh, doc_start=None, plan=None):
   """qkv_rot: projection output with q, k already rotated (rope_qk_).  doc_start: int32 [B,T] document mask; plan: attn_doc_plan(doc_start)
   (built here when absent - pass it when the same batch goes through several layers)."""
   _need(qkv_rot, BF16, 'attn_fwd.qkv', 2)
-  hd = qkv_rot.shape[1] // (3 * nh)
   if doc_start is not None:
     _need(doc_start, torch.int32, 'attn_fwd.doc_start', 2)
     if plan is None:
       plan = attn_doc_plan(doc_start, nh)
-  out = torch.empty((B * T, nh * hd), dtype=BF16, device=qkv_rot.device)
-  lse = torch.empty((B, nh, T), dtype=F32, device=qkv_rot.device)
-  _hook('attn_fwd', attn_flops(B, T, nh, hd))  # the reducer's clock only needs an estimate: no device reduction on the launch path
-  with _Timed('attn_fwd', attn_flops(B, T, nh, hd, doc_start) if PROFILE is not None else 0.0):
+  hd, out, lse = _attn_outputs(qkv_rot, B, T, nh, True)
+  with _attn_launch('attn_fwd', 1.0, B, T, nh, hd, doc_start):
     _lib.check(_lib.load().plm_attn_fwd(_p(qkv_rot), _p(doc_start), _p(plan), _p(out), _p(lse), B, T, nh, hd, _stream()), 'plm_attn_fwd')
   return out, lse
 
@@ -626,13 +657,10 @@ def attn_bwd(qkv, out, dout, lse, rope_cos, rope_sin, B, T, nh, doc_start=None, 
   """dqkv w.r.t. the UN-rotated projection.  return_delta: also return the kernels' delta = rowsum(dO * O), fp32 [B, nh, T] (the hd = 64
   families store it negated for their dK/dV kernel; it is returned here with the plain sign)."""
   _need(dout, BF16, 'attn_bwd.dout', 2)
-  hd = qkv.shape[1] // (3 * nh)
   if doc_start is not None and plan is None:
     plan = attn_doc_plan(doc_start, nh)
-  dqkv = torch.empty_like(qkv)
-  delta = torch.empty((B, nh, T), dtype=F32, device=qkv.device)
-  _hook('attn_bwd', 2.0 * attn_flops(B, T, nh, hd))
-  with _Timed('attn_bwd', 2.0 * attn_flops(B, T, nh, hd, doc_start) if PROFILE is not None else 0.0):
+  hd, dqkv, delta = _attn_outputs(qkv, B, T, nh, False)
+  with _attn_launch('attn_bwd', 2.0, B, T, nh, hd, doc_start):
     _lib.check(_lib.load().plm_attn_bwd(_p(qkv), _p(out), _p(dout), _p(lse), _p(rope_cos), _p(rope_sin), _p(doc_start), _p(plan),
                                         _p(dqkv), _p(delta), B, T, nh, hd, _stream()), 'plm_attn_bwd')
   if return_delta:
@@ -680,11 +708,9 @@ def attn_fwd_masked(qkv_rot, bits, tile_class, B, T, nh):
   """attn_fwd under a packed dense mask (attn_mask_pack).  A query row with no allowed key gives out = 0 and lse = +inf (torch's SDPA
   returns 0 for such a row)."""
   _need(qkv_rot, BF16, 'attn_fwd_masked.qkv', 2)
-  hd = qkv_rot.shape[1] // (3 * nh)
   bs = _mask_stride(bits, tile_class, B, T, 'attn_fwd_masked')
-  out = torch.empty((B * T, nh * hd), dtype=BF16, device=qkv_rot.device)
-  lse = torch.empty((B, nh, T), dtype=F32, device=qkv_rot.device)
-  _hook('attn_fwd', attn_flops(B, T, nh, hd))
+  hd, out, lse = _attn_outputs(qkv_rot, B, T, nh, True)
+  _Launch('attn_fwd', attn_flops(B, T, nh, hd))  # reported to the hook, not timed
   _lib.check(_lib.load().plm_attn_fwd_masked(_p(qkv_rot), _p(bits), _p(tile_class), bs, _p(out), _p(lse), B, T, nh, hd, _stream()),
              'plm_attn_fwd_masked')
   return out, lse
@@ -693,11 +719,9 @@ def attn_fwd_masked(qkv_rot, bits, tile_class, B, T, nh):
 def attn_bwd_masked(qkv, out, dout, lse, rope_cos, rope_sin, bits, tile_class, B, T, nh, return_delta=False):
   """attn_bwd under a packed dense mask: dqkv w.r.t. the UN-rotated projection; return_delta: also delta = rowsum(dO * O), fp32 [B, nh, T]."""
   _need(dout, BF16, 'attn_bwd_masked.dout', 2)
-  hd = qkv.shape[1] // (3 * nh)
   bs = _mask_stride(bits, tile_class, B, T, 'attn_bwd_masked')
-  dqkv = torch.empty_like(qkv)
-  delta = torch.empty((B, nh, T), dtype=F32, device=qkv.device)
-  _hook('attn_bwd', 2.0 * attn_flops(B, T, nh, hd))
+  hd, dqkv, delta = _attn_outputs(qkv, B, T, nh, False)
+  _Launch('attn_bwd', 2.0 * attn_flops(B, T, nh, hd))  # reported to the hook, not timed
   _lib.check(_lib.load().plm_attn_bwd_masked(_p(qkv), _p(out), _p(dout), _p(lse), _p(rope_cos), _p(rope_sin), _p(bits), _p(tile_class), bs,
                                              _p(dqkv), _p(delta), B, T, nh, hd, _stream()), 'plm_attn_bwd_masked')
   if return_delta:
@@ -721,10 +745,8 @@ def _cached_operands(name, rows, width, kv, nh, lens, lens_name, chunk, n_new=No
   [rows, hd/2].  chunk False: one row per sequence (n = 1), the batch is the rows'; True: n = rows / the cache's batch."""
   try:  # the per-tensor checks name the tensor; the op's name is put in front only when one fails (no string is built per call)
     if width == 3:
-      if not rows.is_cuda:
-        raise RuntimeError('qkv: tensor must live on the GPU (plainlm_amd has no CPU path)')
-      if rows.dtype != BF16 or rows.dim() != 2 or rows.stride(1) != 1 or rows.shape[1] % (3 * nh) != 0:
-        raise ValueError(f'qkv: need a 2-D bf16 GPU tensor [{"B*n" if chunk else "B"}, 3*nh*hd] with unit inner stride')
+      if _need(rows, BF16, 'qkv', strided=True).shape[1] % (3 * nh) != 0:
+        raise ValueError(f'qkv: need {"B*n" if chunk else "B"} rows of 3*nh*hd columns, got {rows.shape[1]} for nh={nh}')
     else:
       _need(rows, BF16, 'q', 2)
     hd = rows.shape[1] // (width * nh)
@@ -764,20 +786,23 @@ def _append_outputs(name, qkv, rows, dm, q_out, status):
           torch.zeros((1,), dtype=torch.int32, device=qkv.device) if status is None else status)
 
 
-_cached_ws = {}  # (kernel, B, n, nh, hd, Tmax, splits, device) -> (uint8 workspace, bytes)
+def _cached_ws_bytes(kernel, B, n, nh, hd, Tmax, splits):
+  """Workspace bytes of attn_decode / attn_extend for this shape and splits argument; a shape the library refuses raises."""
+  nbytes = _ws_bytes('plm_attn_decode_workspace_bytes', B, nh, hd, Tmax, int(splits)) if kernel == 'attn_decode' else \
+      _ws_bytes('plm_attn_extend_workspace_bytes', B, n, nh, hd, Tmax, int(splits))
+  if nbytes == 0:
+    raise ValueError(f'{kernel}: unsupported shape B={B} n={n} nh={nh} hd={hd} Tmax={Tmax} or splits={splits} (0 = automatic, 1..64)')
+  return nbytes
 
 
-def _cached_workspace(kernel, B, n, nh, hd, Tmax, splits, device):
-  key = (kernel, B, n, nh, hd, Tmax, int(splits), device)
-  ent = _cached_ws.get(key)
-  if ent is None:
-    lib = _lib.load()
-    nbytes = int(lib.plm_attn_decode_workspace_bytes(B, nh, hd, Tmax, int(splits)) if kernel == 'attn_decode' else
-                 lib.plm_attn_extend_workspace_bytes(B, n, nh, hd, Tmax, int(splits)))
-    if nbytes == 0:
-      raise ValueError(f'{kernel}: unsupported shape B={B} n={n} nh={nh} hd={hd} Tmax={Tmax} or splits={splits} (0 = automatic, 1..64)')
-    ent = _cached_ws[key] = (torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes)
-  return ent
+def _cached_workspace(kernel, B, n, nh, hd, Tmax, splits, device, workspace):
+  """(workspace, bytes, stream) of one attn_decode / attn_extend launch: the caller's pair, else the arena of the launch's stream at the
+  size the library asks for."""
+  stream = _stream()
+  if workspace is not None:
+    return workspace[0], workspace[1], stream
+  nbytes = _cached_ws_bytes(kernel, B, n, nh, hd, Tmax, splits)
+  return _workspace(device, nbytes, stream), nbytes, stream
 
 
 def kv_append_rope(qkv, pos, rope_cos, rope_sin, kv, nh, q_out=None, status=None):
@@ -793,22 +818,22 @@ def kv_append_rope(qkv, pos, rope_cos, rope_sin, kv, nh, q_out=None, status=None
 
 
 def attn_decode_workspace(B, nh, hd, Tmax, splits, device):
-  """(uint8 workspace, bytes) of attn_decode for this shape and splits argument, cached per shape."""
-  return _cached_workspace('attn_decode', B, 1, nh, hd, Tmax, splits, device)
+  """A caller-owned (uint8 workspace, bytes) pair for attn_decode(..., workspace=) at this shape and splits argument."""
+  return torch.empty(nbytes := _cached_ws_bytes('attn_decode', B, 1, nh, hd, Tmax, splits), dtype=torch.uint8, device=device), nbytes
 
 
 def attn_decode(q, kv, lens, nh, splits=0, want_lse=False, workspace=None):
   """Attention of one rotated query row per sequence over its cache: q bf16 [B, nh*hd], kv bf16 [B, Tmax, 2*nh*hd] (kv_append_rope's
   layout), lens int32 [B] (clamped to [0, Tmax]; sequence b attends keys 0 .. lens[b]-1, lens[b] == 0 gives out = 0 and lse = +inf).
   splits: 0 automatic (from the shape alone) | 1..64 forced.  Returns out bf16 [B, nh*hd], or (out, lse fp32 [B, nh], base 2 like
-  attn_fwd's) with want_lse.  workspace: (uint8 tensor, bytes) of attn_decode_workspace for the same splits, else a cached one per shape."""
+  attn_fwd's) with want_lse.  workspace: the caller's (uint8 tensor, bytes) of attn_decode_workspace for the same splits, else the stream's arena."""
   B, _, hd = _cached_operands('attn_decode', q, 1, kv, nh, lens, 'lens', False)
   Tmax = kv.shape[1]
-  ws, nbytes = attn_decode_workspace(B, nh, hd, Tmax, splits, q.device) if workspace is None else workspace
+  ws, nbytes, stream = _cached_workspace('attn_decode', B, 1, nh, hd, Tmax, splits, q.device, workspace)
   out = torch.empty((B, nh * hd), dtype=BF16, device=q.device)
   lse = torch.empty((B, nh), dtype=F32, device=q.device) if want_lse else None
   _lib.check(_lib.load().plm_attn_decode(_p(q), _p(kv), kv.stride(1), _p(lens), _p(out), _p(lse), B, Tmax, nh, hd, int(splits), _p(ws), nbytes,
-                                         _stream()), 'plm_attn_decode')
+                                         stream), 'plm_attn_decode')
   return (out, lse) if want_lse else out
 
 
@@ -828,8 +853,8 @@ def kv_append_rope_rows(qkv, lens0, rope_cos, rope_sin, kv, nh, n_new=None, q_ou
 
 
 def attn_extend_workspace(B, n, nh, hd, Tmax, splits, device):
-  """(uint8 workspace, bytes) of attn_extend for this shape and splits argument, cached per shape (and so per chunk width n)."""
-  return _cached_workspace('attn_extend', B, n, nh, hd, Tmax, splits, device)
+  """A caller-owned (uint8 workspace, bytes) pair for attn_extend(..., workspace=) at this shape (chunk width n) and splits argument."""
+  return torch.empty(nbytes := _cached_ws_bytes('attn_extend', B, n, nh, hd, Tmax, splits), dtype=torch.uint8, device=device), nbytes
 
 
 def attn_extend(q, kv, lens0, nh, n_new=None, splits=0, want_lse=False, workspace=None):
@@ -837,15 +862,15 @@ def attn_extend(q, kv, lens0, nh, n_new=None, splits=0, want_lse=False, workspac
   [B, Tmax, 2*nh*hd] with the chunk already appended, lens0 int32 [B] the lengths BEFORE the chunk (clamped to [0, Tmax]), n_new int32 [B]
   the real rows of every chunk (None: n).  Row r < n_new[b] of sequence b attends keys 0 .. lens0[b] + r; rows past n_new[b] give out = 0
   and lse = +inf.  splits: 0 automatic (from the shape alone) | 1..64 forced.  Returns out bf16 [B*n, nh*hd], or (out, lse fp32
-  [B, nh, n], base 2 like attn_fwd's) with want_lse.  workspace: (uint8 tensor, bytes) of attn_extend_workspace for the same splits, else
-  a cached one per shape."""
+  [B, nh, n], base 2 like attn_fwd's) with want_lse.  workspace: the caller's (uint8 tensor, bytes) of attn_extend_workspace for the same splits, else
+  the stream's arena."""
   B, n, hd = _cached_operands('attn_extend', q, 1, kv, nh, lens0, 'lens0', True, n_new=n_new)
   Tmax = kv.shape[1]
-  ws, nbytes = attn_extend_workspace(B, n, nh, hd, Tmax, splits, q.device) if workspace is None else workspace
+  ws, nbytes, stream = _cached_workspace('attn_extend', B, n, nh, hd, Tmax, splits, q.device, workspace)
   out = torch.empty((B * n, nh * hd), dtype=BF16, device=q.device)
   lse = torch.empty((B, nh, n), dtype=F32, device=q.device) if want_lse else None
   _lib.check(_lib.load().plm_attn_extend(_p(q), _p(kv), kv.stride(1), _p(lens0), _p(n_new), _p(out), _p(lse), B, n, Tmax, nh, hd, int(splits),
-                                         _p(ws), nbytes, _stream()), 'plm_attn_extend')
+                                         _p(ws), nbytes, stream), 'plm_attn_extend')
   return (out, lse) if want_lse else out
 
 
@@ -858,10 +883,8 @@ def sample_logits(logits, u, temperature=1.0, top_k=0, top_p=1.0, want_stats=Fal
   tie with the k-th value, top-p keeps or drops equal logits together; top_k = 0 and top_p = 1 are off).  One launch, bit-reproducible.
   Returns the named tuple (tokens int64 [B], logprob fp32 [B] = log softmax(logits)[tokens] at temperature 1, n_kept int32 [B],
   cutoff fp32 [B]): the size of the kept set and its lowest logit with want_stats, else None."""
-  if not logits.is_cuda:
-    raise RuntimeError('sample_logits.logits: tensor must live on the GPU (plainlm_amd has no CPU path)')
-  if logits.dtype != BF16 or logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or \
-     (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1]):
+  _need(logits, BF16, 'sample_logits.logits', strided=True)
+  if logits.shape[0] < 1 or logits.shape[1] < 1 or (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1]):
     raise ValueError('sample_logits.logits: need a 2-D bf16 GPU tensor [B, V] with unit inner stride and row stride >= V')
   B, V = logits.shape
   _need(u, F32, 'sample_logits.u', 1)
@@ -880,9 +903,8 @@ SpecVerify = collections.namedtuple('SpecVerify', ['n_accept', 'next_token', 'lo
 
 
 def _logits_rows(t, rows, name):
-  if not t.is_cuda:
-    raise RuntimeError(f'{name}: tensor must live on the GPU (plainlm_amd has no CPU path)')
-  if t.dtype != BF16 or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < 1 or t.stride(1) != 1 or (rows > 1 and t.stride(0) < t.shape[1]):
+  _need(t, BF16, name, strided=True)
+  if t.shape[0] != rows or t.shape[1] < 1 or (rows > 1 and t.stride(0) < t.shape[1]):
     raise ValueError(f'{name}: need a 2-D bf16 GPU tensor [{rows}, V] with unit inner stride and row stride >= V, got {t.dtype} '
                      f'{tuple(t.shape)}')
   return t.stride(0) if rows > 1 else t.shape[1]
@@ -928,47 +950,51 @@ def ce_fwd_bwd_(logits, targets, grad_scale, V=None):
   M, ld = logits.shape
   V = ld if V is None else V
   rows = torch.empty((M,), dtype=F32, device=logits.device)
-  with _Timed('hbm:ce_fwd_bwd', 4.0 * M * V):  # one read + one write of the bf16 logits
+  with _Launch('hbm:ce_fwd_bwd', 4.0 * M * V):  # one read + one write of the bf16 logits
     _lib.check(_lib.load().plm_ce_fwd_bwd(_p(logits), _p(targets), _p(rows), M, V, ld, float(grad_scale), _stream()),
                'plm_ce_fwd_bwd')
   return rows
 
 
-_score_ws = {}
+HeadPredict = collections.namedtuple('HeadPredict', ['pred', 'logp', 'entropy', 'nll', 'lse'])
+_HEAD_ABI = {'head_score': ('plm_head_score_bf16', 'plm_head_score_workspace_bytes'),
+             'head_predict': ('plm_head_predict_bf16', 'plm_head_predict_workspace_bytes')}
+
+
+def _head(name, y, w, targets, wants):
+  """What head_score and head_predict share: the operand checks, the launch bracket, the workspace (the library is handed at least 16
+  bytes) and the call plm_<name>_bf16(y, ld, w, ld, targets, outputs ..., M, V, K, workspace, bytes, stream).  wants: one
+  (wanted, dtype) per output of the entry point; returns the [M] outputs, None for those not wanted."""
+  try:  # the op's name is put in front only when a check fails (no string is built per call)
+    _need(y, BF16, 'y', strided=True)
+    _need(w, BF16, 'w', strided=True)
+    if targets is not None:
+      _need(targets, torch.int64, 'targets', 1)
+  except (RuntimeError, TypeError, ValueError) as e:
+    raise type(e)(f'{name}.{e}') from None
+  M, K = y.shape
+  V = w.shape[0]
+  if w.shape[1] != K or (targets is not None and targets.shape[0] != M):
+    raise ValueError(f'{name}: y {tuple(y.shape)}, w {tuple(w.shape)}, targets {None if targets is None else tuple(targets.shape)} do not fit')
+  entry, query = _HEAD_ABI[name]
+  launch = _Launch('gemm_nt', 2.0 * M * V * K)
+  nbytes = _ws_bytes(query, M, V, K)
+  stream = _stream()
+  ws = _workspace(y.device, max(nbytes, 16), stream)
+  outs = [torch.empty((M,), dtype=dtype, device=y.device) if want else None for want, dtype in wants]
+  with launch:
+    _lib.check(getattr(_lib.load(), entry)(_p(y), y.stride(0), _p(w), w.stride(0), _p(targets), *[_p(o) for o in outs], M, V, K, _p(ws),
+                                           nbytes, stream), entry)
+  return outs
 
 
 def head_score(y, w, targets, want_lse=False):
   """Forward-only scoring head: nll fp32[M] = logsumexp(l) - l[target] of the rows l = bf16(y[M,K] @ w[V,K]^T) - the training head's
   logits, bit for bit - without the [M, V] buffer (the NT GEMM reduces every tile to per-row (max, sum-exp) pairs).
   A target outside [0, V) is ignored (nll = 0).  want_lse: also return lse fp32[M].  No gradient."""
-  for t, n in ((y, 'y'), (w, 'w')):
-    if not t.is_cuda:
-      raise RuntimeError(f'head_score.{n}: tensor must live on the GPU (plainlm_amd has no CPU path)')
-    if t.dtype != BF16 or t.dim() != 2 or t.stride(1) != 1:
-      raise ValueError(f'head_score.{n}: need a 2-D bf16 GPU tensor with unit inner stride')
   _need(targets, torch.int64, 'head_score.targets', 1)
-  M, K = y.shape
-  V = w.shape[0]
-  if w.shape[1] != K or targets.shape[0] != M:
-    raise ValueError(f'head_score: y {tuple(y.shape)}, w {tuple(w.shape)}, targets {tuple(targets.shape)} do not fit')
-  lib = _lib.load()
-  _hook('gemm_nt', 2.0 * M * V * K)
-  key = (M, V, K, y.device)
-  ent = _score_ws.get(key)
-  if ent is None:
-    nbytes = int(lib.plm_head_score_workspace_bytes(M, V, K))
-    ent = _score_ws[key] = (torch.empty(max(nbytes, 16), dtype=torch.uint8, device=y.device), nbytes)
-  ws, nbytes = ent
-  nll = torch.empty((M,), dtype=F32, device=y.device)
-  lse = torch.empty((M,), dtype=F32, device=y.device) if want_lse else None
-  with _Timed('gemm_nt', 2.0 * M * V * K):
-    _lib.check(lib.plm_head_score_bf16(_p(y), y.stride(0), _p(w), w.stride(0), _p(targets), _p(nll), _p(lse), M, V, K, _p(ws), nbytes,
-                                       _stream()), 'plm_head_score_bf16')
+  nll, lse = _head('head_score', y, w, targets, ((True, F32), (want_lse, F32)))
   return (nll, lse) if want_lse else nll
-
-
-HeadPredict = collections.namedtuple('HeadPredict', ['pred', 'logp', 'entropy', 'nll', 'lse'])
-_predict_ws = {}
 
 
 def head_predict(y, w, targets=None, want_entropy=True, want_lse=False):
@@ -976,33 +1002,8 @@ def head_predict(y, w, targets=None, want_entropy=True, want_lse=False):
   pred int64[M] (first index of the maximum, always in [0, V)), logp fp32[M] = log softmax(l)[pred], entropy fp32[M] in nats, and with
   ``targets`` nll fp32[M] as head_score gives it (0 where the target is outside [0, V)); want_lse: lse fp32[M].  Returns the named tuple
   (pred, logp, entropy, nll, lse) with None for the parts not asked for.  No gradient."""
-  for t, n in ((y, 'y'), (w, 'w')):
-    if not t.is_cuda:
-      raise RuntimeError(f'head_predict.{n}: tensor must live on the GPU (plainlm_amd has no CPU path)')
-    if t.dtype != BF16 or t.dim() != 2 or t.stride(1) != 1:
-      raise ValueError(f'head_predict.{n}: need a 2-D bf16 GPU tensor with unit inner stride')
-  if targets is not None:
-    _need(targets, torch.int64, 'head_predict.targets', 1)
-  M, K = y.shape
-  V = w.shape[0]
-  if w.shape[1] != K or (targets is not None and targets.shape[0] != M):
-    raise ValueError(f'head_predict: y {tuple(y.shape)}, w {tuple(w.shape)}, targets '
-                     f'{None if targets is None else tuple(targets.shape)} do not fit')
-  lib = _lib.load()
-  _hook('gemm_nt', 2.0 * M * V * K)
-  key = (M, V, K, y.device)
-  ent = _predict_ws.get(key)
-  if ent is None:
-    nbytes = int(lib.plm_head_predict_workspace_bytes(M, V, K))
-    ent = _predict_ws[key] = (torch.empty(max(nbytes, 16), dtype=torch.uint8, device=y.device), nbytes)
-  ws, nbytes = ent
-  new = lambda want, dtype=F32: torch.empty((M,), dtype=dtype, device=y.device) if want else None  # noqa: E731
-  pred, logp = new(True, torch.int64), new(True)
-  entropy, nll, lse = new(want_entropy), new(targets is not None), new(want_lse)
-  with _Timed('gemm_nt', 2.0 * M * V * K):
-    _lib.check(lib.plm_head_predict_bf16(_p(y), y.stride(0), _p(w), w.stride(0), _p(targets), _p(pred), _p(logp), _p(entropy), _p(nll),
-                                         _p(lse), M, V, K, _p(ws), nbytes, _stream()), 'plm_head_predict_bf16')
-  return HeadPredict(pred, logp, entropy, nll, lse)
+  return HeadPredict(*_head('head_predict', y, w, targets,
+                            ((True, torch.int64), (True, F32), (want_entropy, F32), (targets is not None, F32), (want_lse, F32))))
 
 
 def mean(x):
@@ -1104,10 +1105,7 @@ def optim_cast_multi_(hp, items, clip_coef=None, table=None):
           if t.shape != p.shape:
             raise ValueError(f'optim_cast_multi.{n}: shape {tuple(t.shape)}, p has {tuple(p.shape)}')
       R, Cc = p.shape
-      if dst.dtype != BF16 or tuple(dst.shape) != (R, Cc) or not dst.is_contiguous() or not dst.is_cuda:
-        raise ValueError('optim_cast_multi.dst: need contiguous bf16 [rows, cols] on the GPU')
-      if dst_t.dtype != BF16 or dst_t.dim() != 2 or dst_t.shape[0] != Cc or dst_t.shape[1] < R or dst_t.stride(1) != 1 or not dst_t.is_cuda:
-        raise ValueError('optim_cast_multi.dst_t: need bf16 [cols, >= rows] on the GPU')
+      _need_shadows(dst, dst_t, R, Cc, 'optim_cast_multi.dst')
       ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
       table[i] = _lib.OptimItem(p.data_ptr(), g.data_ptr(), ptr(m), ptr(v), dst.data_ptr(), dst_t.data_ptr(), R, Cc, dst_t.stride(0))
   _lib.check(_lib.load().plm_optim_cast_multi(C.byref(hp), table, len(table), _p(clip_coef), _stream()), 'plm_optim_cast_multi')

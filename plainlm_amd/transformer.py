@@ -607,12 +607,11 @@ class Transformer(nn.Module):
     nh = self.cfg.n_heads
     with torch.no_grad():
       rope = self._rope(tokens.device)
-      ws = cache.workspace
       cache.advance()  # pos = the appended token's position, lens = pos + 1: what this step's attention sees
 
       def attend(i, qkv):
         q, _ = ops.kv_append_rope(qkv, cache.pos, rope[0], rope[1], cache.kv[i], nh, status=cache.status)
-        return ops.attn_decode(q, cache.kv[i], cache.lens, nh, workspace=ws)
+        return ops.attn_decode(q, cache.kv[i], cache.lens, nh)
       return self._head(self._cached_layers(tokens.contiguous(), cache, attend), logits, (B,))
 
   # ---- cache extension ------------------------------------------------------------------------------------
@@ -652,12 +651,11 @@ class Transformer(nn.Module):
     with torch.no_grad():
       adv, n_new = G.chunk_lens(token_lens, B, n, tokens.device)
       rope = self._rope(tokens.device)
-      ws = cache.extend_workspace(n)
       lens0 = cache.lens  # the lengths before the chunk: what every layer's append and attention see; moved once, after the last layer
 
       def attend(i, qkv):
         q, _ = ops.kv_append_rope_rows(qkv, lens0, rope[0], rope[1], cache.kv[i], nh, n_new=n_new, status=cache.status)
-        return ops.attn_extend(q, cache.kv[i], lens0, nh, n_new=n_new, workspace=ws)
+        return ops.attn_extend(q, cache.kv[i], lens0, nh, n_new=n_new)
       y = self._cached_layers(tokens.reshape(-1).contiguous(), cache, attend)
       cache.advance_by(adv)
       if all_rows:

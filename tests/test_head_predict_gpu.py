@@ -211,7 +211,7 @@ def test_bench_shape_predictions_and_memory(P):
   from plainlm_amd import ops
   M, V, K = HEAD
   Y, W, t = _head_operands()
-  ops._predict_ws.clear()  # the workspace is part of the cost
+  ops.release_workspaces()  # the workspace is part of the cost
   torch.cuda.synchronize()
   torch.cuda.reset_peak_memory_stats()
   base = torch.cuda.memory_allocated()

@@ -65,7 +65,7 @@ def main():
     def fs():
       return ops.mean(ops.head_score(Y, W, t))
 
-    ops._predict_ws.clear()
+    ops.release_workspaces()
     pb = peak(fb)
     pa = peak(fa)
     for _ in range(a.warmup):
@@ -80,8 +80,7 @@ def main():
     lines.append('  %-20s %26s %26s %26s %7.3f %7.3f %11.1f %11.1f'
                  % ('%d, %d, %d' % (M, V, K), cell(ma, ta), cell(mb, tb), cell(ms, ts), mb / ma, mb / ms, pa / 2**20, pb / 2**20))
     del Y, W
-    ops._predict_ws.clear()
-    ops._score_ws.clear()
+    ops.release_workspaces()
     torch.cuda.empty_cache()
   text = '\n'.join(lines) + '\n'
   print(text, end='')

@@ -60,7 +60,7 @@ def main():
     def fb():
       return ops.mean(ops.head_score(Y, W, t))
 
-    ops._score_ws.clear()
+    ops.release_workspaces()
     pb = peak(fb)
     pa = peak(fa)
     keep = torch.empty((M, pad), dtype=BF, device='cuda')
