@@ -1,14 +1,15 @@
-"""KV-cached generation (DESIGN.md sections 12 and 14): the cache, and the host logic of ``Transformer.prefill / decode_step / extend /
-generate`` (``extend``: a chunk of tokens per sequence on top of a live cache).
+"""KV-cached generation (DESIGN.md sections 12 to 15): the cache, the ``Generation`` mixin that gives ``Transformer`` its ``prefill /
+decode_step / new_cache / extend / generate / generate_speculative``, and the host logic under them.
 
-Everything that can be stated without a GPU lives here as plain functions over tensors on any device - the length checks, the choice of
-the row a padded prompt is continued from, the token loop with its EOS freezing - so that tests/test_decode_host.py runs them on the CPU
-with a fake step function.  The kernels are reached through two ops per cached step from transformer.py: ops.kv_append_rope /
-ops.attn_decode for one token per sequence, ops.kv_append_rope_rows / ops.attn_extend for a chunk.  On-device
+The mixin alone takes a model, through the seam its docstring states (transformer.py imports this module, never the other way round);
+``guard`` holds the refusals its methods share.  Everything else is plain functions over tensors on any device - the length checks, the
+choice of the row a padded prompt is continued from, the token loop with its EOS freezing - so that tests/test_decode_host.py runs them
+on the CPU with a fake step function.  The kernels are reached through two ops per cached step:
+ops.kv_append_rope / ops.attn_decode for one token per sequence, ops.kv_append_rope_rows / ops.attn_extend for a chunk.  On-device
 sampling adds the argument rules (check_sampling), the one draw of uniforms per call (draw_uniforms) and the
-per-step pick (sampling_pick over ops.sample_logits).  Speculative decoding adds the host logic of
-``Transformer.generate_speculative``: its refusals (check_speculative), greedy acceptance (greedy_accept), the bookkeeping of a round
-(commit_round), the round loop over callables (speculative_loop) and the one draw of all its uniforms (speculative_uniforms).
+per-step pick (sampling_pick over ops.sample_logits).  Speculative decoding adds its refusals (check_speculative),
+greedy acceptance (greedy_accept), the bookkeeping of a round (commit_round), the round loop over callables (speculative_loop), the one draw
+of all its uniforms (speculative_uniforms) and ``_SpecSession``, the state of one call and the four callables the loop drives.
 """
 
 import math
@@ -61,6 +62,38 @@ class KVCache:
                          '(prefill with a larger max_len)')
 
 
+def refuse_cpu(tokens):
+  if isinstance(tokens, torch.Tensor) and not tokens.is_cuda:
+    raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (inputs are on CPU; there is no CPU fallback)')
+
+
+def refuse_mxfp8(what, model):
+  if model.cfg.linear_precision == 'mxfp8':
+    raise NotImplementedError(f"Transformer.{what}: linear_precision: mxfp8 has no cached decode path (the decode step runs the bf16 shadows)")
+
+
+def guard(what, tokens, model, *drafts, forward_only=False, rank2=False):
+  """The refusals the generation methods share.  Their order decides which one an input that is bad in two ways gets; it is pinned by
+  tests/test_generate_trace_host.py and tests/test_generate_trace_gpu.py.  A forward-only method (generate, generate_speculative) first
+  refuses CPU tokens, a draft that is no Generation, and grad mode while any of the models has a trainable parameter.  Then every method
+  refuses an mxfp8 model, tokens that are no int64 tensor, CPU tokens, an mxfp8 draft and, with ``rank2``, tokens that are not [B, T]."""
+  if forward_only:
+    refuse_cpu(tokens)
+    for d in drafts:
+      if not isinstance(d, Generation):
+        raise TypeError(f'{what}: draft must be a plainlm_amd.Transformer, got {type(d).__name__}')
+    if torch.is_grad_enabled() and any(p.requires_grad for m in (model,) + drafts for p in m.parameters()):
+      raise RuntimeError(f'Transformer.{what} is forward-only (no backward): call it under torch.no_grad(), or use loss() to train')
+  refuse_mxfp8(what, model)
+  if not isinstance(tokens, torch.Tensor) or tokens.dtype != torch.int64:
+    raise TypeError(f'Transformer.{what}: tokens must be an int64 tensor')
+  refuse_cpu(tokens)
+  for d in drafts:
+    refuse_mxfp8(what, d)
+  if rank2 and tokens.dim() != 2:
+    raise TypeError('inputs must be an int64 [B, T] tensor')
+
+
 def chunk_lens(token_lens, B, n, device):
   """token_lens of Transformer.extend as (what advance_by takes, the int32 [B] device tensor the kernels take or None for "n
   everywhere").  None: every sequence appends all n tokens.  Host integers (a sequence of B ints in [0, n], or a CPU tensor) are checked
@@ -103,15 +136,28 @@ def prompt_lens_list(prompt_lens, B, T):
   return lens
 
 
+def _check_new_tokens(who, T, max_new_tokens, extra, extra_text, limits):
+  """The length refusals of ``who``: returns T + max_new_tokens + extra (spelled extra_text), which must fit every (owner, seq_len)."""
+  if int(max_new_tokens) < 1:
+    raise ValueError(f'{who}: max_new_tokens must be at least 1, got {max_new_tokens}')
+  if T < 1:
+    raise ValueError(f'{who}: empty prompt')
+  need = T + int(max_new_tokens) + extra
+  for owner, seq_len in limits:
+    if need > seq_len:
+      raise ValueError(f'{who}: prompt length {T} + max_new_tokens {max_new_tokens}{extra_text} exceeds {owner}cfg.seq_len {seq_len}')
+  return need
+
+
 def check_lengths(T, max_new_tokens, seq_len):
   """The refusals of generate that need no GPU; returns the cache length (the padded prompt must fit it too)."""
-  if int(max_new_tokens) < 1:
-    raise ValueError(f'generate: max_new_tokens must be at least 1, got {max_new_tokens}')
-  if T < 1:
-    raise ValueError('generate: empty prompt')
-  if T + int(max_new_tokens) > seq_len:
-    raise ValueError(f'generate: prompt length {T} + max_new_tokens {max_new_tokens} exceeds cfg.seq_len {seq_len}')
-  return max(pad4(T), T + int(max_new_tokens))
+  return max(pad4(T), _check_new_tokens('generate', T, max_new_tokens, 0, '', [('', seq_len)]))
+
+
+def cache_rows(max_len, seq_len, least=1):
+  """max_len of prefill / new_cache as (cache rows per sequence, default cfg.seq_len; do they hold ``least`` rows and fit cfg.seq_len?)."""
+  rows = seq_len if max_len is None else int(max_len)
+  return rows, least <= rows <= seq_len
 
 
 def last_rows(y, B, T, lens):
@@ -200,11 +246,10 @@ def sampling_pick(u, temperature, top_k, top_p, sampler=None):
   """pick(logits bf16 [B, V]) -> (tokens, logprob) for generate_loop: its n-th call samples with row n of u, through ops.sample_logits
   (``sampler`` stands in for it in the host tests)."""
   sampler = ops.sample_logits if sampler is None else sampler
-  n = [0]
+  rows = iter(u)
 
   def pick(logits):
-    r = sampler(logits, u[n[0]], temperature, top_k, top_p)
-    n[0] += 1
+    r = sampler(logits, next(rows), temperature, top_k, top_p)
     return r[0], r[1]
   return pick
 
@@ -229,15 +274,8 @@ def check_speculative(T, max_new_tokens, n_draft, cfg, draft_cfg, device=None, d
     raise ValueError(f'generate_speculative: the draft\'s vocab_size {draft_cfg.vocab_size} is not the target\'s {cfg.vocab_size}')
   if device is not None and draft_device is not None and torch.device(device) != torch.device(draft_device):
     raise ValueError(f'generate_speculative: the draft is on {draft_device}, the target on {device}')
-  if int(max_new_tokens) < 1:
-    raise ValueError(f'generate_speculative: max_new_tokens must be at least 1, got {max_new_tokens}')
-  if T < 1:
-    raise ValueError('generate_speculative: empty prompt')
-  need = T + int(max_new_tokens) + n_draft + 1
-  for who, c in (('the target', cfg), ('the draft', draft_cfg)):
-    if need > c.seq_len:
-      raise ValueError(f'generate_speculative: prompt length {T} + max_new_tokens {max_new_tokens} + n_draft {n_draft} + 1 exceeds '
-                       f'{who}\'s cfg.seq_len {c.seq_len}')
+  need = _check_new_tokens('generate_speculative', T, max_new_tokens, n_draft + 1, f' + n_draft {n_draft} + 1',
+                           [("the target's ", cfg.seq_len), ("the draft's ", draft_cfg.seq_len)])
   return need, check_sampling(temperature, top_k, top_p, None, seed)
 
 
@@ -349,3 +387,211 @@ def round_uniforms(u, i, n_draft):
   k = int(n_draft)
   r = u[1 + i * uniforms_per_round(k):1 + (i + 1) * uniforms_per_round(k)]
   return r[:k], r[k:2 * k + 1], r[2 * k + 1:3 * k + 1], r[3 * k + 1]
+
+
+class _SpecSession:
+  """One generate_speculative call between its rounds: the two models and their caches, the lengths the caches are set to after every
+  round, the round counter and - when the call samples (``sampling`` = check_sampling's triple, else None) - its uniforms ``u`` and the
+  draft's logits of the current round.  The four methods are the callables ``speculative_loop`` documents."""
+
+  def __init__(self, target, draft, tcache, dcache, k, sampling, u):
+    self.target, self.draft, self.tcache, self.dcache = target, draft, tcache, dcache
+    self.k, self.sampling, self.sampled, self.u, self.round = k, sampling, sampling is not None, u, 0
+    # the lengths the caches are set to after every round: both hold the sequence up to, not including, its newest token - the draft one
+    # row less while it has not seen the last draft token of a fully accepted round
+    self.tlen, self.dlen = tcache.lens.clone(), dcache.lens.clone()
+    self.qbuf = torch.empty((k, tcache.B, target.cfg.vocab_size), dtype=torch.bfloat16, device=u.device) if self.sampled else None
+
+  def draft_round(self, last, carry_tok, carry, live):
+    sampled = self.sampled
+    ur = round_uniforms(self.u, self.round, self.k)[0] if sampled else None
+    toks, cuts = [], []
+    for i in range(self.k):
+      if i == 0:  # [carry_tok, last] where the draft still lacks carry_tok, else [last, -]; a finished sequence appends nothing
+        pair = torch.stack([torch.where(carry, carry_tok, last), last], dim=1)
+        out = self.draft.extend(pair, self.dcache, token_lens=(live.to(torch.int32) * (1 + carry.to(torch.int32))), logits=sampled)
+      else:
+        out = self.draft.decode_step(toks[-1], self.dcache, logits=sampled)
+      if sampled:
+        self.qbuf[i].copy_(out)
+        sq = ops.sample_logits(self.qbuf[i], ur[i], *self.sampling, want_stats=True)
+        toks.append(sq.tokens)
+        cuts.append(sq.cutoff)
+      else:
+        toks.append(out.tokens)
+    return torch.stack(toks, dim=1), (torch.stack(toks, dim=0), torch.stack(cuts, dim=0)) if sampled else None
+
+  def target_round(self, last, draft_tok, live):
+    chunk = torch.cat([last[:, None], draft_tok], dim=1)
+    return self.target.extend(chunk, self.tcache, token_lens=live.to(torch.int32) * (self.k + 1), logits=self.sampled, all_rows=True)
+
+  def accept(self, draft_tok, draft_out, out):
+    if not self.sampled:
+      return greedy_accept(draft_tok, out.tokens) + (out.logprob,)
+    _, ut, ua, ures = round_uniforms(self.u, self.round, self.k)
+    V = out.shape[-1]
+    rows = out.view(-1, V)  # [B * (k + 1), V]
+    st = ops.sample_logits(rows, ut.t().reshape(-1), *self.sampling, want_stats=True)  # row b * (k + 1) + r draws with ut[r, b]
+    return tuple(ops.spec_verify(rows, self.qbuf.view(-1, V), draft_out[0], st.cutoff, draft_out[1].reshape(-1), st.tokens, ua, ures,
+                                 self.sampling[0]))
+
+  def advance(self, moved, live):
+    self.dlen.copy_(torch.where(live, self.tlen + moved.clamp(max=self.k), self.dlen))
+    self.tlen.add_(moved)
+    self.tcache.set_lens(self.tlen)
+    self.dcache.set_lens(self.dlen)
+    self.round += 1
+
+
+class Generation:
+  """KV-cached generation, mixed into ``Transformer`` (DESIGN.md sections 12 to 15).  What it asks of its host class:
+    attributes  cfg (the ModelConfig), n_layers, head_dim, lm_head (its weight tells the model's device)
+    methods     _rope(device), trunk(x, attn_mask, cache), cached_layers(tokens, cache, attend), head(y, logits, shape); the middle two
+                call refresh_shadows() themselves.  _rope keeps its underscore: tools and tests from before the mixin call it by that name."""
+
+  @torch.compiler.disable
+  def prefill(self, x, prompt_lens=None, max_len=None, logits=False):
+    """Run the prompt x int64 [B, T] through the trunk once and keep every layer's rotated k | v: returns (KVCache, HeadPrediction [B]) -
+    the greedy next token of every sequence, its log-probability and the entropy, from row prompt_lens[b] - 1 (host integers; default T).
+    Prompts are right-padded to a multiple of 4 (the attention kernels' granularity), which under a causal mask changes no earlier row;
+    with prompt_lens shorter rows hold padding the cache never reads (lens = prompt_lens).  max_len: cache rows per sequence (default
+    cfg.seq_len).  logits=True returns the bf16 [B, V] logits of those rows in
+    place of the prediction.  Runs under no_grad."""
+    guard('prefill', x, self, rank2=True)
+    B, T = x.shape
+    lens = prompt_lens_list(prompt_lens, B, T)
+    Tp = pad4(T)
+    Tmax, fits = cache_rows(max_len, self.cfg.seq_len, least=Tp)
+    if not fits:
+      raise ValueError(f'prefill: the padded prompt ({Tp} rows) must fit max_len {Tmax}, and max_len cfg.seq_len {self.cfg.seq_len}')
+    with torch.no_grad():
+      if Tp != T:
+        x = torch.nn.functional.pad(x, (0, Tp - T))
+      cache = KVCache(self.n_layers, B, Tmax, self.cfg.n_heads, self.head_dim, x.device)
+      lens_dev = torch.tensor(lens, dtype=torch.int32).to(x.device)
+      cache.set_lens(lens_dev)
+      y, _, _ = self.trunk(x.contiguous(), None, cache)
+      return cache, self.head(last_rows(y, B, Tp, lens_dev), logits, (B,))
+
+  @torch.compiler.disable
+  def decode_step(self, tokens, cache, logits=False):
+    """One token per sequence on top of ``cache``: tokens int64 [B] are appended at positions cache.lens (then lens += 1, on the device)
+    and the HeadPrediction [B] of the NEXT token is returned - or, with logits=True, its bf16 logits [B, V].  The Block structure as it
+    is (``cached_layers``), with ops.kv_append_rope / ops.attn_decode as the attention stage."""
+    guard('decode_step', tokens, self)
+    B = cache.B
+    if tuple(tokens.shape) != (B,):
+      raise ValueError(f'decode_step: tokens {tuple(tokens.shape)} do not match the cache\'s batch of {B}')
+    nh = self.cfg.n_heads
+    with torch.no_grad():
+      rope = self._rope(tokens.device)
+      cache.advance()  # pos = the appended token's position, lens = pos + 1: what this step's attention sees
+
+      def attend(i, qkv):
+        q, _ = ops.kv_append_rope(qkv, cache.pos, rope[0], rope[1], cache.kv[i], nh, status=cache.status)
+        return ops.attn_decode(q, cache.kv[i], cache.lens, nh)
+      return self.head(self.cached_layers(tokens.contiguous(), cache, attend), logits, (B,))
+
+  def new_cache(self, B, max_len=None):
+    """An empty KVCache for B sequences (lens 0) of max_len rows each (default and at most cfg.seq_len): the start of a chunked prefill
+    through ``extend``."""
+    refuse_mxfp8('new_cache', self)
+    Tmax, fits = cache_rows(max_len, self.cfg.seq_len)
+    if int(B) < 1 or not fits:
+      raise ValueError(f'new_cache: need B >= 1 and 1 <= max_len <= cfg.seq_len {self.cfg.seq_len}, got B={B} max_len={Tmax}')
+    device = self.lm_head.weight.device
+    if device.type != 'cuda':
+      raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (the model is on CPU; there is no CPU fallback)')
+    return KVCache(self.n_layers, int(B), Tmax, self.cfg.n_heads, self.head_dim, device)
+
+  @torch.compiler.disable
+  def extend(self, tokens, cache, token_lens=None, logits=False, all_rows=False):
+    """Append a chunk of tokens to a live cache: tokens int64 [B, n], right-padded; sequence b's first token_lens[b] tokens are appended
+    at positions cache.lens[b] .. (then lens += token_lens, on the device).  token_lens: None (all n), host integers in [0, n], or an
+    int32 [B] device tensor (clamped to [0, n], never read back).  A new user turn on top of a cached conversation, one chunk of a long
+    prompt's prefill (start from ``new_cache``), or k drafted tokens to verify (roll back with ``cache.set_lens``).
+    Returns the HeadPrediction [B] of the token after each sequence's last appended row (row token_lens[b] - 1; a sequence that appended
+    nothing gets row 0's, which means nothing) - with logits=True the bf16 logits [B, V] of that row; with all_rows=True the [B, n]
+    predictions, or [B, n, V] logits, of every chunk row (rows at and beyond token_lens[b] belong to padding and mean nothing).
+    The Block structure as decode_step runs it, through ops calls on the bf16 shadows at M = B * n: the same launches as one decode step,
+    whatever n.  A chunk that does not fit the cache (or the RoPE table) stores nothing for that sequence and surfaces through
+    ``cache.check()``.  Runs under no_grad."""
+    if isinstance(tokens, torch.Tensor) and (tokens.dim() != 2 or tokens.shape[0] != cache.B or tokens.shape[1] < 1):
+      raise ValueError(f'extend: tokens {tuple(tokens.shape)} are not a [B, n] chunk for the cache\'s batch of {cache.B}')
+    guard('extend', tokens, self)
+    if len(cache.kv) != self.n_layers or cache.n_heads != self.cfg.n_heads or cache.head_dim != self.head_dim:
+      raise ValueError('extend: the cache was made for another model shape (layers, heads or head_dim differ)')
+    B, n = tokens.shape
+    nh = self.cfg.n_heads
+    with torch.no_grad():
+      adv, n_new = chunk_lens(token_lens, B, n, tokens.device)
+      rope = self._rope(tokens.device)
+      lens0 = cache.lens  # the lengths before the chunk: what every layer's append and attention see; moved once, after the last layer
+
+      def attend(i, qkv):
+        q, _ = ops.kv_append_rope_rows(qkv, lens0, rope[0], rope[1], cache.kv[i], nh, n_new=n_new, status=cache.status)
+        return ops.attn_extend(q, cache.kv[i], lens0, nh, n_new=n_new)
+      y = self.cached_layers(tokens.reshape(-1).contiguous(), cache, attend)
+      cache.advance_by(adv)
+      if all_rows:
+        return self.head(y, logits, (B, n))
+      if n_new is None:
+        y = y.view(B, n, self.cfg.dim)[:, -1].contiguous()
+      else:
+        y = last_rows(y, B, n, n_new.clamp(min=1))
+      return self.head(y, logits, (B,))
+
+  @torch.compiler.disable
+  def generate(self, prompt, max_new_tokens, prompt_lens=None, eos_id=None, sample=None, return_logprobs=False, temperature=None,
+               top_k=None, top_p=None, seed=None):
+    """Continue prompt int64 [B, T] by max_new_tokens tokens: returns the new tokens int64 [B, max_new_tokens], with return_logprobs
+    also their log-probabilities fp32 [B, max_new_tokens].  Greedy by default, through the fused prediction head (no logits are built);
+    ``sample`` is an optional callable fp32 logits [B, V] -> int64 [B] (temperature, top-k, nucleus: the caller's few lines of torch),
+    with which every step returns logits instead.  prompt_lens: host integers, the true length of every right-padded prompt.  After a
+    sequence emits eos_id its later tokens are eos_id and their log-probabilities 0.  No device-to-host copy happens per token.
+    temperature / top_k / top_p sample on the device (one ops.sample_logits launch per token next to the logits
+    GEMM; top-k keeps ties with the k-th value, top-p keeps or drops equal logits together; the returned log-probabilities stay the
+    model's, at temperature 1).  The uniforms of the whole call are drawn once, from a generator seeded with ``seed`` (bit-reproducible)
+    or from torch's default generator.  temperature None or 0 without a filter is greedy; ``sample`` excludes all four."""
+    guard('generate', prompt, self, forward_only=True, rank2=True)
+    max_len = check_lengths(prompt.shape[1], max_new_tokens, self.cfg.seq_len)
+    on_device = check_sampling(temperature, top_k, top_p, sample, seed)
+    want_logits = sample is not None or on_device is not None
+    if on_device is not None:
+      pick = sampling_pick(draw_uniforms(max_new_tokens, prompt.shape[0], prompt.device, seed), *on_device)
+    else:
+      pick = (lambda r: sampled(sample, r)) if want_logits else (lambda r: (r.tokens, r.logprob))  # noqa: E731
+    cache, r = self.prefill(prompt, prompt_lens, max_len=max_len, logits=want_logits)
+    toks, lps = generate_loop(pick(r), lambda t: pick(self.decode_step(t, cache, logits=want_logits)), max_new_tokens, eos_id)
+    cache.check()
+    return (toks, lps) if return_logprobs else toks
+
+  @torch.compiler.disable
+  def generate_speculative(self, prompt, max_new_tokens, draft, n_draft=4, prompt_lens=None, eos_id=None, return_logprobs=False,
+                           temperature=None, top_k=None, top_p=None, seed=None, return_stats=False):
+    """``generate`` by draft-and-verify rounds: ``draft`` - another Transformer of the same vocabulary, any shape - proposes n_draft
+    tokens with decode steps, this model checks them in one ``extend`` of n_draft + 1 rows, and a sequence keeps the accepted tokens
+    plus one of this model's own, so a round of one target step yields 1 .. n_draft + 1 tokens.  Greedy (temperature None or 0 without
+    a filter): the tokens are what ``generate`` decodes greedily, the target side runs through the fused prediction head.  With
+    temperature / top_k / top_p the draft samples on the device and ops.spec_verify applies the speculative-sampling acceptance rule, which
+    leaves every token distributed as ``generate`` samples it (not the same tokens: the uniforms are used differently).  All uniforms of
+    the call are drawn once, under ``seed`` (bit-reproducible) or from torch's default generator.  Returns the tokens int64 [B, N]; with
+    return_logprobs also this model's log-probabilities at temperature 1, with return_stats also dict(rounds, drafted int64 [B], accepted
+    int64 [B]).  After eos_id a sequence holds eos_id with log-probability 0.  One int32 is read from the device per round (are all
+    sequences finished?); both caches move by device tensors only."""
+    guard('generate_speculative', prompt, self, draft, forward_only=True, rank2=True)
+    B, T = prompt.shape
+    k, N = n_draft, int(max_new_tokens)
+    max_len, sampling = check_speculative(T, max_new_tokens, k, self.cfg, draft.cfg, self.lm_head.weight.device,
+                                          draft.lm_head.weight.device, temperature, top_k, top_p, seed)
+    tcache, r = self.prefill(prompt, prompt_lens, max_len=max_len, logits=sampling is not None)
+    dcache, _ = draft.prefill(prompt, prompt_lens, max_len=max_len)
+    u = None if sampling is None else speculative_uniforms(N, k, B, prompt.device, seed)
+    s = _SpecSession(self, draft, tcache, dcache, k, sampling, u)
+    first = (r.tokens, r.logprob) if sampling is None else ops.sample_logits(r, u[0], *sampling)[:2]
+    with torch.no_grad():
+      toks, lps, stats = speculative_loop(first, s.draft_round, s.target_round, s.accept, N, k, eos_id, s.advance)
+    tcache.check()
+    dcache.check()
+    res = (toks,) + ((lps,) if return_logprobs else ()) + ((stats,) if return_stats else ())
+    return res[0] if len(res) == 1 else res

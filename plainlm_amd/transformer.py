@@ -257,7 +257,7 @@ class Block(nn.Module):
 HeadPrediction = namedtuple('HeadPrediction', ['tokens', 'logprob', 'entropy', 'nll'])  # Transformer.predict
 
 
-class Transformer(nn.Module):
+class Transformer(nn.Module, G.Generation):
   def __init__(self, cfg):
     super().__init__()
     self.cfg = cfg
@@ -439,11 +439,18 @@ class Transformer(nn.Module):
       raise ValueError('attn_mask: a row of the previous bool mask was not exactly True on [first allowed key, query]: only block-diagonal causal '
                        'masks (data_prep_utils.py:7-23) are supported (any other mask: attn_mask_mode: dense, or pass a functional.DenseMask)')
 
-  def _trunk(self, x, attn_mask, cache=None):
+  def _refuse(self, x, forward_only=None):
+    """The CPU refusal and, for the method ``forward_only`` names, the refusal to run where a backward could be asked for."""
+    if isinstance(x, torch.Tensor) and not x.is_cuda:
+      raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (inputs are on CPU; there is no CPU fallback)')
+    if forward_only is not None and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+      raise RuntimeError(f'Transformer.{forward_only} is forward-only (no backward): call it under torch.no_grad(), or use loss() to train')
+
+  def trunk(self, x, attn_mask, cache=None):
+    """inputs int64 [B, T] -> (the out norm's bf16 rows [B*T, dim], B, T); ``cache`` (prefill) takes every layer's rotated k | v rows."""
     if x.dim() != 2 or x.dtype != torch.int64:
       raise TypeError('inputs must be an int64 [B, T] tensor')
-    if not x.is_cuda:
-      raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (inputs are on CPU; there is no CPU fallback)')
+    self._refuse(x)
     B, T = x.shape
     if T > self.cfg.seq_len:
       raise ValueError(f'sequence length {T} exceeds cfg.seq_len {self.cfg.seq_len}')
@@ -468,13 +475,13 @@ class Transformer(nn.Module):
   @torch.compiler.disable  # engine/engine.py:68-70 may wrap the model in torch.compile: the kernels are hand-written, there is nothing to trace -
   def forward(self, x, attn_mask=None):  # the compiled module runs this forward as it is (same bits), instead of graph-breaking on every ctypes call
     """inputs int64 [B,T], attn_mask -> bf16 logits [B,T,V] (models/transformer.py:108-114)."""
-    y, B, T = self._trunk(x, attn_mask)
+    y, B, T = self.trunk(x, attn_mask)
     return self.lm_head(y).view(B, T, self.cfg.vocab_size)
 
   @torch.compiler.disable
   def loss(self, x, targets, attn_mask=None):
     """Mean token cross-entropy (fp32 scalar) with lm_head + CE fused (never keeps fp32 logits)."""
-    y, B, T = self._trunk(x, attn_mask)
+    y, B, T = self.trunk(x, attn_mask)
     tg = targets.reshape(-1).contiguous()
     return Fn.HeadLossFn.apply(y, self.lm_head.weight, self.lm_head, tg, self.head_chunk_rows)
 
@@ -486,11 +493,8 @@ class Transformer(nn.Module):
     There is no backward: use ``loss`` to train."""
     if reduction not in ('none', 'sum', 'mean'):
       raise ValueError(f"score: reduction must be 'none', 'sum' or 'mean' (got {reduction!r})")
-    if isinstance(x, torch.Tensor) and not x.is_cuda:
-      raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (inputs are on CPU; there is no CPU fallback)')
-    if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-      raise RuntimeError('Transformer.score is forward-only (no backward): call it under torch.no_grad(), or use loss() to train')
-    y, B, T = self._trunk(x, attn_mask)
+    self._refuse(x, forward_only='score')
+    y, B, T = self.trunk(x, attn_mask)
     tg = targets.reshape(-1).contiguous()
     wb, _ = self.lm_head.shadow()
     nll = ops.head_score(y, wb, tg)
@@ -507,67 +511,20 @@ class Transformer(nn.Module):
     entropy fp32 in nats, nll fp32 or None) of every position, [B, T] - or [B], the last position alone, with ``last_only`` (the
     next-token call; the head then sees the B last rows of the trunk's output through a strided view, no copy).  tokens is the first
     index of the largest logit of ``forward``; with ``targets`` [B, T] nll is what ``score`` returns.  There is no backward."""
-    if isinstance(x, torch.Tensor) and not x.is_cuda:
-      raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (inputs are on CPU; there is no CPU fallback)')
-    if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-      raise RuntimeError('Transformer.predict is forward-only (no backward): call it under torch.no_grad(), or use loss() to train')
+    self._refuse(x, forward_only='predict')
     if targets is not None and isinstance(x, torch.Tensor) and tuple(targets.shape) != tuple(x.shape):
       raise ValueError(f'predict: targets {tuple(targets.shape)} do not match the inputs {tuple(x.shape)}')
-    y, B, T = self._trunk(x, attn_mask)
-    wb, _ = self.lm_head.shadow()
+    y, B, T = self.trunk(x, attn_mask)
     if last_only:
       y = y.view(B, T, self.cfg.dim)[:, -1]  # row stride T * dim
-      tg = None if targets is None else targets[:, -1].contiguous()
-      shape = (B,)
-    else:
-      tg = None if targets is None else targets.reshape(-1).contiguous()
-      shape = (B, T)
-    r = ops.head_predict(y, wb, tg)
-    return HeadPrediction(r.pred.view(shape), r.logp.view(shape), r.entropy.view(shape), None if r.nll is None else r.nll.view(shape))
+      return self.head(y, False, (B,), None if targets is None else targets[:, -1].contiguous())
+    return self.head(y, False, (B, T), None if targets is None else targets.reshape(-1).contiguous())
 
   def token_logprobs(self, x, targets, attn_mask=None):
     """log p(target) per token, fp32 [B, T] (0 where the target is ignored): ``-score(x, targets, attn_mask, 'none')``."""
     return -self.score(x, targets, attn_mask, reduction='none')
 
-  # ---- KV-cached generation (DESIGN.md sections 12 and 14; host logic in generate.py) ------------------------------------------
-  def _refuse_mxfp8(self, what):
-    if self.cfg.linear_precision == 'mxfp8':
-      raise NotImplementedError(f"Transformer.{what}: linear_precision: mxfp8 has no cached decode path (the decode step runs the bf16 shadows)")
-
-  def _check_decode(self, what, t):
-    self._refuse_mxfp8(what)
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.int64:
-      raise TypeError(f'Transformer.{what}: tokens must be an int64 tensor')
-    if not t.is_cuda:
-      raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (inputs are on CPU; there is no CPU fallback)')
-
-  @torch.compiler.disable
-  def prefill(self, x, prompt_lens=None, max_len=None, logits=False):
-    """Run the prompt x int64 [B, T] through the trunk once and keep every layer's rotated k | v: returns (KVCache, HeadPrediction [B]) -
-    the greedy next token of every sequence, its log-probability and the entropy, from row prompt_lens[b] - 1 (host integers; default T).
-    Prompts are right-padded to a multiple of 4 (the attention kernels' granularity), which under a causal mask changes no earlier row;
-    with prompt_lens shorter rows hold padding the cache never reads (lens = prompt_lens).  max_len: cache rows per sequence (default
-    cfg.seq_len).  logits=True returns the bf16 [B, V] logits of those rows in
-    place of the prediction.  Runs under no_grad."""
-    self._check_decode('prefill', x)
-    if x.dim() != 2:
-      raise TypeError('inputs must be an int64 [B, T] tensor')
-    B, T = x.shape
-    lens = G.prompt_lens_list(prompt_lens, B, T)
-    Tp = G.pad4(T)
-    Tmax = self.cfg.seq_len if max_len is None else int(max_len)
-    if Tp > Tmax or Tmax > self.cfg.seq_len:
-      raise ValueError(f'prefill: the padded prompt ({Tp} rows) must fit max_len {Tmax}, and max_len cfg.seq_len {self.cfg.seq_len}')
-    with torch.no_grad():
-      if Tp != T:
-        x = torch.nn.functional.pad(x, (0, Tp - T))
-      cache = G.KVCache(self.n_layers, B, Tmax, self.cfg.n_heads, self.head_dim, x.device)
-      lens_dev = torch.tensor(lens, dtype=torch.int32).to(x.device)
-      cache.set_lens(lens_dev)
-      y, _, _ = self._trunk(x.contiguous(), None, cache)
-      return cache, self._head(G.last_rows(y, B, Tp, lens_dev), logits, (B,))
-
-  def _cached_layers(self, tokens, cache, attend):
+  def cached_layers(self, tokens, cache, attend):
     """The trunk on top of ``cache`` for tokens int64 [M] (M = B rows of a decode step, B * n of a chunk): the Block structure as it is,
     through ops calls on the bf16 shadows - about ten launches per layer, none of them sized by the context except attention.
     ``attend(i, qkv)`` is layer i's two-call attention stage (append the rotated k | v rows of qkv [M, 3*dim] to cache.kv[i], attend the
@@ -586,202 +543,11 @@ class Transformer(nn.Module):
       branch = ops.gemm_nt(act, layer.mlp.fc2.shadow()[0])
     return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps, branch=branch)[1]
 
-  def _head(self, y, logits, shape):
-    """The head on normed rows y [prod(shape), dim]: the HeadPrediction of that shape (ops.head_predict, no logits buffer), or with
-    ``logits`` the bf16 logits [*shape, V]."""
+  def head(self, y, logits, shape, targets=None):
+    """The head on normed rows y [prod(shape), dim]: the HeadPrediction of that shape (ops.head_predict, no logits buffer; nll of the
+    flat ``targets`` when given), or with ``logits`` the bf16 logits [*shape, V]."""
     wb, _ = self.lm_head.shadow()
     if logits:
       return ops.gemm_nt(y, wb).view(shape + (self.cfg.vocab_size,))
-    r = ops.head_predict(y, wb)
-    return HeadPrediction(r.pred.view(shape), r.logp.view(shape), r.entropy.view(shape), None)
-
-  @torch.compiler.disable
-  def decode_step(self, tokens, cache, logits=False):
-    """One token per sequence on top of ``cache``: tokens int64 [B] are appended at positions cache.lens (then lens += 1, on the device)
-    and the HeadPrediction [B] of the NEXT token is returned - or, with logits=True, its bf16 logits [B, V].  The Block structure as it
-    is (``_cached_layers``), with ops.kv_append_rope / ops.attn_decode as the attention stage."""
-    self._check_decode('decode_step', tokens)
-    B = cache.B
-    if tuple(tokens.shape) != (B,):
-      raise ValueError(f'decode_step: tokens {tuple(tokens.shape)} do not match the cache\'s batch of {B}')
-    nh = self.cfg.n_heads
-    with torch.no_grad():
-      rope = self._rope(tokens.device)
-      cache.advance()  # pos = the appended token's position, lens = pos + 1: what this step's attention sees
-
-      def attend(i, qkv):
-        q, _ = ops.kv_append_rope(qkv, cache.pos, rope[0], rope[1], cache.kv[i], nh, status=cache.status)
-        return ops.attn_decode(q, cache.kv[i], cache.lens, nh)
-      return self._head(self._cached_layers(tokens.contiguous(), cache, attend), logits, (B,))
-
-  # ---- cache extension (DESIGN.md section 14) ------------------------------------------------------------------------------------
-  def new_cache(self, B, max_len=None):
-    """An empty KVCache for B sequences (lens 0) of max_len rows each (default and at most cfg.seq_len): the start of a chunked prefill
-    through ``extend``."""
-    self._refuse_mxfp8('new_cache')
-    Tmax = self.cfg.seq_len if max_len is None else int(max_len)
-    if int(B) < 1 or Tmax < 1 or Tmax > self.cfg.seq_len:
-      raise ValueError(f'new_cache: need B >= 1 and 1 <= max_len <= cfg.seq_len {self.cfg.seq_len}, got B={B} max_len={Tmax}')
-    device = self.lm_head.weight.device
-    if device.type != 'cuda':
-      raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (the model is on CPU; there is no CPU fallback)')
-    return G.KVCache(self.n_layers, int(B), Tmax, self.cfg.n_heads, self.head_dim, device)
-
-  @torch.compiler.disable
-  def extend(self, tokens, cache, token_lens=None, logits=False, all_rows=False):
-    """Append a chunk of tokens to a live cache: tokens int64 [B, n], right-padded; sequence b's first token_lens[b] tokens are appended
-    at positions cache.lens[b] .. (then lens += token_lens, on the device).  token_lens: None (all n), host integers in [0, n], or an
-    int32 [B] device tensor (clamped to [0, n], never read back).  A new user turn on top of a cached conversation, one chunk of a long
-    prompt's prefill (start from ``new_cache``), or k drafted tokens to verify (roll back with ``cache.set_lens``).
-    Returns the HeadPrediction [B] of the token after each sequence's last appended row (row token_lens[b] - 1; a sequence that appended
-    nothing gets row 0's, which means nothing) - with logits=True the bf16 logits [B, V] of that row; with all_rows=True the [B, n]
-    predictions, or [B, n, V] logits, of every chunk row (rows at and beyond token_lens[b] belong to padding and mean nothing).
-    The Block structure as decode_step runs it, through ops calls on the bf16 shadows at M = B * n: the same launches as one decode step,
-    whatever n.  A chunk that does not fit the cache (or the RoPE table) stores nothing for that sequence and surfaces through
-    ``cache.check()``.  Runs under no_grad."""
-    if isinstance(tokens, torch.Tensor) and (tokens.dim() != 2 or tokens.shape[0] != cache.B or tokens.shape[1] < 1):
-      raise ValueError(f'extend: tokens {tuple(tokens.shape)} are not a [B, n] chunk for the cache\'s batch of {cache.B}')
-    self._check_decode('extend', tokens)
-    if tokens.dim() != 2:
-      raise TypeError('inputs must be an int64 [B, n] tensor')
-    if len(cache.kv) != self.n_layers or cache.n_heads != self.cfg.n_heads or cache.head_dim != self.head_dim:
-      raise ValueError('extend: the cache was made for another model shape (layers, heads or head_dim differ)')
-    B, n = tokens.shape
-    nh = self.cfg.n_heads
-    with torch.no_grad():
-      adv, n_new = G.chunk_lens(token_lens, B, n, tokens.device)
-      rope = self._rope(tokens.device)
-      lens0 = cache.lens  # the lengths before the chunk: what every layer's append and attention see; moved once, after the last layer
-
-      def attend(i, qkv):
-        q, _ = ops.kv_append_rope_rows(qkv, lens0, rope[0], rope[1], cache.kv[i], nh, n_new=n_new, status=cache.status)
-        return ops.attn_extend(q, cache.kv[i], lens0, nh, n_new=n_new)
-      y = self._cached_layers(tokens.reshape(-1).contiguous(), cache, attend)
-      cache.advance_by(adv)
-      if all_rows:
-        return self._head(y, logits, (B, n))
-      if n_new is None:
-        y = y.view(B, n, self.cfg.dim)[:, -1].contiguous()
-      else:
-        y = G.last_rows(y, B, n, n_new.clamp(min=1))
-      return self._head(y, logits, (B,))
-
-  @torch.compiler.disable
-  def generate(self, prompt, max_new_tokens, prompt_lens=None, eos_id=None, sample=None, return_logprobs=False, temperature=None,
-               top_k=None, top_p=None, seed=None):
-    """Continue prompt int64 [B, T] by max_new_tokens tokens: returns the new tokens int64 [B, max_new_tokens], with return_logprobs
-    also their log-probabilities fp32 [B, max_new_tokens].  Greedy by default, through the fused prediction head (no logits are built);
-    ``sample`` is an optional callable fp32 logits [B, V] -> int64 [B] (temperature, top-k, nucleus: the caller's few lines of torch),
-    with which every step returns logits instead.  prompt_lens: host integers, the true length of every right-padded prompt.  After a
-    sequence emits eos_id its later tokens are eos_id and their log-probabilities 0.  No device-to-host copy happens per token.
-    temperature / top_k / top_p sample on the device (one ops.sample_logits launch per token next to the logits
-    GEMM; top-k keeps ties with the k-th value, top-p keeps or drops equal logits together; the returned log-probabilities stay the
-    model's, at temperature 1).  The uniforms of the whole call are drawn once, from a generator seeded with ``seed`` (bit-reproducible)
-    or from torch's default generator.  temperature None or 0 without a filter is greedy; ``sample`` excludes all four."""
-    if isinstance(prompt, torch.Tensor) and not prompt.is_cuda:
-      raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (inputs are on CPU; there is no CPU fallback)')
-    if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-      raise RuntimeError('Transformer.generate is forward-only (no backward): call it under torch.no_grad(), or use loss() to train')
-    self._check_decode('generate', prompt)
-    if prompt.dim() != 2:
-      raise TypeError('inputs must be an int64 [B, T] tensor')
-    max_len = G.check_lengths(prompt.shape[1], max_new_tokens, self.cfg.seq_len)
-    on_device = G.check_sampling(temperature, top_k, top_p, sample, seed)
-    want_logits = sample is not None or on_device is not None
-    if on_device is not None:
-      pick = G.sampling_pick(G.draw_uniforms(max_new_tokens, prompt.shape[0], prompt.device, seed), *on_device)
-    else:
-      pick = (lambda r: G.sampled(sample, r)) if want_logits else (lambda r: (r.tokens, r.logprob))  # noqa: E731
-    cache, r = self.prefill(prompt, prompt_lens, max_len=max_len, logits=want_logits)
-    toks, lps = G.generate_loop(pick(r), lambda t: pick(self.decode_step(t, cache, logits=want_logits)), max_new_tokens, eos_id)
-    cache.check()
-    return (toks, lps) if return_logprobs else toks
-
-  # ---- speculative decoding (DESIGN.md section 15; host logic in generate.py) -----------------------------------------------------
-  @torch.compiler.disable
-  def generate_speculative(self, prompt, max_new_tokens, draft, n_draft=4, prompt_lens=None, eos_id=None, return_logprobs=False,
-                           temperature=None, top_k=None, top_p=None, seed=None, return_stats=False):
-    """``generate`` by draft-and-verify rounds: ``draft`` - another Transformer of the same vocabulary, any shape - proposes n_draft
-    tokens with decode steps, this model checks them in one ``extend`` of n_draft + 1 rows, and a sequence keeps the accepted tokens
-    plus one of this model's own, so a round of one target step yields 1 .. n_draft + 1 tokens.  Greedy (temperature None or 0 without
-    a filter): the tokens are what ``generate`` decodes greedily, the target side runs through the fused prediction head.  With
-    temperature / top_k / top_p the draft samples on the device and ops.spec_verify applies the speculative-sampling acceptance rule, which
-    leaves every token distributed as ``generate`` samples it (not the same tokens: the uniforms are used differently).  All uniforms of
-    the call are drawn once, under ``seed`` (bit-reproducible) or from torch's default generator.  Returns the tokens int64 [B, N]; with
-    return_logprobs also this model's log-probabilities at temperature 1, with return_stats also dict(rounds, drafted int64 [B], accepted
-    int64 [B]).  After eos_id a sequence holds eos_id with log-probability 0.  One int32 is read from the device per round (are all
-    sequences finished?); both caches move by device tensors only."""
-    if isinstance(prompt, torch.Tensor) and not prompt.is_cuda:
-      raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (inputs are on CPU; there is no CPU fallback)')
-    if not isinstance(draft, Transformer):
-      raise TypeError(f'generate_speculative: draft must be a plainlm_amd.Transformer, got {type(draft).__name__}')
-    if torch.is_grad_enabled() and any(p.requires_grad for m in (self, draft) for p in m.parameters()):
-      raise RuntimeError('Transformer.generate_speculative is forward-only (no backward): call it under torch.no_grad(), or use loss() to train')
-    self._check_decode('generate_speculative', prompt)
-    draft._refuse_mxfp8('generate_speculative')
-    if prompt.dim() != 2:
-      raise TypeError('inputs must be an int64 [B, T] tensor')
-    B, T = prompt.shape
-    k, N, dev = n_draft, int(max_new_tokens), prompt.device
-    max_len, on_device = G.check_speculative(T, max_new_tokens, k, self.cfg, draft.cfg, self.lm_head.weight.device,
-                                             draft.lm_head.weight.device, temperature, top_k, top_p, seed)
-    V = self.cfg.vocab_size
-    sampled = on_device is not None
-    tcache, r = self.prefill(prompt, prompt_lens, max_len=max_len, logits=sampled)
-    dcache, _ = draft.prefill(prompt, prompt_lens, max_len=max_len)
-    # the lengths the caches are set to after every round: both hold the sequence up to, not including, its newest token - the draft one
-    # row less while it has not seen the last draft token of a fully accepted round
-    tlen, dlen = tcache.lens.clone(), dcache.lens.clone()
-    if sampled:
-      u = G.speculative_uniforms(N, k, B, dev, seed)
-      s = ops.sample_logits(r, u[0], *on_device)
-      first = (s.tokens, s.logprob)
-      qbuf = torch.empty((k, B, V), dtype=torch.bfloat16, device=dev)
-    else:
-      first = (r.tokens, r.logprob)
-    rnd = [0]
-
-    def draft_round(last, carry_tok, carry, live):
-      ur = G.round_uniforms(u, rnd[0], k)[0] if sampled else None
-      toks, cuts = [], []
-      for i in range(k):
-        if i == 0:  # [carry_tok, last] where the draft still lacks carry_tok, else [last, -]; a finished sequence appends nothing
-          pair = torch.stack([torch.where(carry, carry_tok, last), last], dim=1)
-          out = draft.extend(pair, dcache, token_lens=(live.to(torch.int32) * (1 + carry.to(torch.int32))), logits=sampled)
-        else:
-          out = draft.decode_step(toks[-1], dcache, logits=sampled)
-        if sampled:
-          qbuf[i].copy_(out)
-          sq = ops.sample_logits(qbuf[i], ur[i], *on_device, want_stats=True)
-          toks.append(sq.tokens)
-          cuts.append(sq.cutoff)
-        else:
-          toks.append(out.tokens)
-      return torch.stack(toks, dim=1), (torch.stack(toks, dim=0), torch.stack(cuts, dim=0)) if sampled else None
-
-    def target_round(last, draft_tok, live):
-      chunk = torch.cat([last[:, None], draft_tok], dim=1)
-      return self.extend(chunk, tcache, token_lens=live.to(torch.int32) * (k + 1), logits=sampled, all_rows=True)
-
-    def accept(draft_tok, draft_out, out):
-      if not sampled:
-        return G.greedy_accept(draft_tok, out.tokens) + (out.logprob,)
-      _, ut, ua, ures = G.round_uniforms(u, rnd[0], k)
-      rows = out.view(B * (k + 1), V)
-      st = ops.sample_logits(rows, ut.t().reshape(-1), *on_device, want_stats=True)  # row b * (k + 1) + r draws with ut[r, b]
-      return tuple(ops.spec_verify(rows, qbuf.view(k * B, V), draft_out[0], st.cutoff, draft_out[1].reshape(-1), st.tokens, ua, ures,
-                                   on_device[0]))
-
-    def advance(moved, live):
-      dlen.copy_(torch.where(live, tlen + moved.clamp(max=k), dlen))
-      tlen.add_(moved)
-      tcache.set_lens(tlen)
-      dcache.set_lens(dlen)
-      rnd[0] += 1
-
-    with torch.no_grad():
-      toks, lps, stats = G.speculative_loop(first, draft_round, target_round, accept, N, k, eos_id, advance)
-    tcache.check()
-    dcache.check()
-    res = (toks,) + ((lps,) if return_logprobs else ()) + ((stats,) if return_stats else ())
-    return res[0] if len(res) == 1 else res
+    r = ops.head_predict(y, wb, targets)
+    return HeadPrediction(r.pred.view(shape), r.logp.view(shape), r.entropy.view(shape), None if r.nll is None else r.nll.view(shape))
