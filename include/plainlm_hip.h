@@ -351,6 +351,53 @@ int plm_spec_verify_bf16(const uint16_t* p_logits, int64_t ldp, const uint16_t* 
                          float temperature, int32_t* n_accept, int64_t* next_tok, float* logp, int64_t B, int64_t k, int64_t V,
                          void* stream);
 
+/* ---- draft-free speculative decoding: n-gram lookup drafts and their one-hot acceptance -----
+ * Every argument check of these entry points comes before any HIP call.
+ *
+ * plm_lookup_draft_i64: a sequence proposes the tokens that followed the most recent earlier occurrence of its own last few tokens.
+ * hist int64 [B, ld] (in/out): every sequence's token history, lens int32 [B] (in/out) its length; add_tok int64 [B, ld_add] and n_add
+ * int32 [B]: tokens to append first, c_b = n_add[b] clamped to [0, ld_add] of them (n_add NULL: c_b = ld_add; add_tok NULL: c_b = 0 and
+ * n_add must be NULL too).  Integers only, one launch, one workgroup per sequence, no workspace, nothing read back; sequence b's outputs
+ * depend on sequence b's inputs alone.
+ *   append   add_tok[b, 0 : c_b] goes to hist[b, lens[b] : lens[b] + c_b] and lens[b] moves by c_b.  A sequence with lens[b] < 0 or
+ *            lens[b] + c_b > ld is refused on the device: nothing of it is stored, lens[b] stays, n_prop[b] = match_len[b] = 0, its draft_tok
+ *            row is zeros and the caller-zeroed status[0] is set to 1 (plm_kv_append_rope's convention); the others are unaffected.
+ *   search   with L the new length: for every end e in [1, L-1], m(e) = the number of consecutive t = 1, 2, .. with hist[b, e-t] ==
+ *            hist[b, L-t], counted up to min(g_max, e).  The candidates are the ends with m(e) >= g_min; the winner has the largest m and,
+ *            among those, the largest e (the longest match, then the most recent one).
+ *   propose  with a winner e and its period P = L - e: draft_tok[b, i] = hist[b, e + (i mod P)] for i < k (an overlapped copy: a loop
+ *            shorter than k still yields k tokens), n_prop[b] = k, match_len[b] = m(e).  Without a candidate (always when L < 2):
+ *            n_prop[b] = match_len[b] = 0 and the draft_tok row is zeros - a valid token id, so the padded chunk rows can be embedded.
+ * Outputs: draft_tok int64 [B, k], n_prop int32 [B], match_len int32 [B] (may be NULL); every element is written.  hist beyond the new
+ * length is neither read nor written.
+ * PLM_E_INVALID before anything is launched for: a NULL pointer (add_tok, n_add, match_len excepted), n_add without add_tok, k < 1 or
+ * k > 31, g_min < 1, g_min > g_max or g_max > 16, B < 1 or B >= 2^31, ld < 1 or ld >= 2^31, with add_tok ld_add < 1 or ld_add >= 2^31,
+ * hist / add_tok / draft_tok not 8-byte aligned.
+ *
+ * plm_spec_verify_lookup_bf16: the acceptance rule of plm_spec_verify_bf16 for a deterministic draft (q one-hot on the proposed token).
+ * p_logits bf16 [B*(k+1), ldp], row b*(k+1) + r, p_cutoff fp32 [B*(k+1)] and p_tok int64 [B*(k+1)] as plm_spec_verify_bf16 takes them
+ * (plm_sample_logits_bf16 on those rows at this temperature); draft_tok int64 [B, k] (plm_lookup_draft_i64's layout); n_prop int32 [B]:
+ * the rows of sequence b that hold a proposal - any value in [0, k] is honoured, others are clamped to it on the device; u_accept fp32
+ * [k, B] and u_resid fp32 [B], clamped on the device as the sampler clamps u.
+ * The rule, per sequence b.  For r = 0 .. n_prop[b]-1 in order, with x = draft_tok[b, r]: alpha = p_r(x), the sampler's own distribution -
+ * its fixed-point weight w_x over the kept set's sum Z; alpha = 0 when x is outside [0, V), outside the kept set, or w_x rounds to 0.  Row
+ * r is accepted while u_accept[r, b] < alpha, evaluated in integers as floor(u Z) < w_x.  a = the first rejected row, or n_prop[b] when
+ * none is.  a = n_prop[b]: next_tok = p_tok of row a (the bonus token; with n_prop[b] = 0 the plain next token).  Else next_tok = the
+ * lowest i with C_i > floor(u_resid[b] * R), C the running sum in ascending column order of row a's integer weights with column x's set
+ * to 0 and R = Z - w_x its total; R = 0 (or a row without a finite logit): next_tok = p_tok of row a.
+ * Outputs n_accept int32 [B] (= a, in [0, n_prop[b]]), next_tok int64 [B] in [0, V) and logp fp32 [B, k+1] with exactly the meanings
+ * plm_spec_verify_bf16 states.  Two launches of its shape (logp carries the verdicts between them), no workspace, nothing read back;
+ * every sum is a 64-bit integer and there is no quotient: bit-reproducible, sequence b's outputs depend on sequence b's inputs alone.
+ * Rows at and beyond n_prop[b] of p_logits (row a itself excepted) and of draft_tok are never loaded.
+ * PLM_E_INVALID before anything is launched for: a NULL pointer, B < 1 or B >= 2^26, k < 1 or k > 31, V < 1 or V >= 2^31, ldp < V, a
+ * logits base that is not 2-byte aligned, a temperature that is not finite or <= 0. */
+int plm_lookup_draft_i64(int64_t* hist, int64_t ld, int32_t* lens, const int64_t* add_tok, int64_t ld_add, const int32_t* n_add,
+                         int64_t* draft_tok, int32_t* n_prop, int32_t* match_len, int32_t* status, int64_t B, int64_t k, int64_t g_min,
+                         int64_t g_max, void* stream);
+int plm_spec_verify_lookup_bf16(const uint16_t* p_logits, int64_t ldp, const int64_t* draft_tok, const int32_t* n_prop,
+                                const float* p_cutoff, const int64_t* p_tok, const float* u_accept, const float* u_resid, float temperature,
+                                int32_t* n_accept, int64_t* next_tok, float* logp, int64_t B, int64_t k, int64_t V, void* stream);
+
 /* ---- fused cross-entropy forward+backward (engine/engine.py:81,111) -----
  * logits bf16[M, ld] (row stride ld >= V) are OVERWRITTEN with dlogits = (softmax - onehot) * grad_scale
  * (grad_scale = g/M); pad columns V..ld are set to zero so the buffer can feed a GEMM with K = ld.

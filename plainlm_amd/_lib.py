@@ -114,6 +114,8 @@ SIGNATURES = {
   'plm_attn_extend': (_I, [_P, _P, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
   'plm_sample_logits_bf16': (_I, [_P, _I64, _P, _F, _I64, _F, _P, _P, _P, _P, _I64, _I64, _P]),
   'plm_spec_verify_bf16': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I64, _I64, _I64, _P]),
+  'plm_lookup_draft_i64': (_I, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P]),
+  'plm_spec_verify_lookup_bf16': (_I, [_P, _I64, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I64, _I64, _I64, _P]),
   'plm_ce_fwd_bwd': (_I, [_P, _P, _P, _I64, _I64, _I64, _F, _P]),
   'plm_mean_f32': (_I, [_P, _P, _I64, _P]),
   'plm_head_score_workspace_bytes': (_SZ, [_I64, _I64, _I64]),

@@ -245,3 +245,143 @@ extern "C" int plm_spec_verify_bf16(const uint16_t* p_logits, int64_t ldp, const
   PLM_CHECK_LAUNCH("plm_spec_verify_bf16");
   return PLM_OK;
 }
+
+// ---- one-hot acceptance: the draft is a deterministic proposal (plm_lookup_draft_i64) ----------------------------
+// q is one-hot on the proposed token x, so alpha = p(x) and the residual is p with x removed.  In the sampler's fixed point both are
+// integers: u < w_x / Z is floor(u Z) < w_x (w_x is an integer), the test the sampler's own draw makes of a running sum; the residual
+// weight of a column is the column's own weight, R = Z - w_x, and the draw is the sampler's walk with column x's weight set to 0.  No
+// quotient of two distributions is left.  The launches have plm_spec_verify_bf16's shape; rows at and beyond n_prop[b] are never loaded.
+__device__ __forceinline__ int spl_n_prop(const int32_t* __restrict__ n_prop, int64_t b, int k) {
+  const int n = n_prop[b];
+  return n < 0 ? 0 : (n > k ? k : n);
+}
+
+// launch 1: block r + k * b decides proposed row r of sequence b; a row at or beyond n_prop[b] leaves its slot alone (launch 2 reads none)
+__global__ __launch_bounds__(SMP_THREADS) void spec_lookup_rows_kernel(const uint16_t* __restrict__ p, int64_t ldp,
+                                                                       const int64_t* __restrict__ draft_tok, const int32_t* __restrict__ n_prop,
+                                                                       const float* __restrict__ p_cutoff, const float* __restrict__ u_acc,
+                                                                       float c_tau, float scale, float* __restrict__ logp, int64_t B, int k,
+                                                                       int V) {
+  __shared__ smp_u64 s_part[SMP_WAVES];
+  const int64_t b = blockIdx.x / k;
+  const int r = (int)(blockIdx.x - b * k);
+  if (r >= spl_n_prop(n_prop, b, k)) return;  // the whole block
+  const int64_t pr = b * (k + 1) + r;
+  const uint16_t* prow = p + pr * ldp;
+  const float cp = p_cutoff[pr];
+  const int64_t x = draft_tok[b * k + r];
+  float* slot = logp + pr;
+
+  // alpha = 0 without a pass over the row: a token outside [0, V) or outside p's kept set (the same for every thread)
+  unsigned xbits = 0, xk = 0;
+  bool accept = x >= 0 && x < V;
+  if (accept) {
+    xbits = prow[x];
+    xk = smp_key(xbits);
+    accept = xk != 0u && smp_value(xk) >= cp;
+  }
+  if (!accept) {
+    if (threadIdx.x == 0) *slot = SPV_REJECTED;
+    return;
+  }
+  const SpvRow P = spv_row_stats<true>(prow, V, cp, c_tau, scale, s_part);
+  const smp_u64 wx = smp_fix(smp_value(xk) - P.xmax, c_tau, scale);  // 0: p(x) rounds to 0, alpha = 0
+  accept = (smp_u64)((double)spv_clamp_u(u_acc[(int64_t)r * B + b]) * (double)P.Z) < wx;  // floor(u Z) < w_x; u < 1, so the product is < 2^63
+  if (threadIdx.x == 0) *slot = accept ? spv_logp(xbits, P, scale) : SPV_REJECTED;
+}
+
+// launch 2: block b finishes sequence b
+__global__ __launch_bounds__(SMP_THREADS) void spec_lookup_finish_kernel(const uint16_t* __restrict__ p, int64_t ldp,
+                                                                         const int64_t* __restrict__ draft_tok,
+                                                                         const int32_t* __restrict__ n_prop, const float* __restrict__ p_cutoff,
+                                                                         const int64_t* __restrict__ p_tok, const float* __restrict__ u_res,
+                                                                         float c_tau, float scale, int32_t* __restrict__ n_accept,
+                                                                         int64_t* __restrict__ next_tok, float* logp, int k, int V) {
+  __shared__ smp_u64 s_part[SMP_WAVES];
+  __shared__ smp_u64 s_res;
+  const int tid = threadIdx.x, lane = tid % PLM_WAVE, wave = tid / PLM_WAVE;
+  const int64_t b = blockIdx.x;
+  const int np = spl_n_prop(n_prop, b, k);
+  int a = np;  // the first rejected row; every thread reads the same slots, thread 0 writes them only after the barriers below
+  for (int r = np - 1; r >= 0; --r)
+    if (logp[b * (k + 1) + r] > 0.f) a = r;
+  const int64_t pr = b * (k + 1) + a;
+  const uint16_t* prow = p + pr * ldp;
+  const float cp = p_cutoff[pr];
+  const SpvRow P = spv_row_stats<true>(prow, V, cp, c_tau, scale, s_part);
+  int64_t tok = p_tok[pr];  // the bonus token (a = n_prop), and what a row without a residual falls back to
+  tok = tok < 0 ? 0 : (tok >= V ? (int64_t)V - 1 : tok);
+
+  if (a < np && P.Z != 0ull) {  // the same for the whole block
+    const int64_t x = draft_tok[b * k + a];
+    auto residual = [&](int64_t i) -> smp_u64 { return i == x ? 0ull : spv_weight(prow[i], P.xmax, cp, c_tau, scale); };
+    // spec_finish_kernel's walk: wave w owns the columns [w * seg, (w + 1) * seg), its lanes stride through them
+    const int64_t seg = ((int64_t)V + SMP_WAVES - 1) / SMP_WAVES;
+    const int64_t c0 = min((int64_t)V, wave * seg), c1 = min((int64_t)V, c0 + seg);
+    smp_u64 mine = 0;
+    for (int64_t i = c0 + lane; i < c1; i += PLM_WAVE) mine += residual(i);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, PLM_WAVE);
+    if (lane == 0) s_part[wave] = mine;
+    if (tid == 0) s_res = SMP_NONE;
+    __syncthreads();
+    smp_u64 R = 0, base = 0;  // R = Z - w_x
+#pragma unroll
+    for (int w = 0; w < SMP_WAVES; ++w) {
+      const smp_u64 t = s_part[w];
+      base += w < wave ? t : 0ull;
+      R += t;
+    }
+    const smp_u64 T = (smp_u64)((double)spv_clamp_u(u_res[b]) * (double)R);  // floor(u R) < R
+    if (base <= T && T < base + mine) {  // one wave at most (none when R = 0)
+      smp_u64 acc = base;
+      for (int64_t i0 = c0; i0 < c1; i0 += PLM_WAVE) {
+        const int64_t i = i0 + lane;
+        smp_u64 v = i < c1 ? residual(i) : 0ull;
+#pragma unroll
+        for (int o = 1; o < PLM_WAVE; o <<= 1) {
+          const smp_u64 t = __shfl_up(v, o, PLM_WAVE);
+          if (lane >= o) v += t;
+        }
+        const unsigned long long crossed = __ballot(acc + v > T);
+        if (crossed != 0ull) {
+          if (lane == __ffsll(crossed) - 1) s_res = (smp_u64)i;
+          break;
+        }
+        acc += __shfl(v, PLM_WAVE - 1, PLM_WAVE);
+      }
+    }
+    __syncthreads();
+    if (s_res != SMP_NONE) tok = (int64_t)s_res;
+  }
+  if (tid == 0) {
+    n_accept[b] = a;
+    next_tok[b] = tok;
+    logp[pr] = spv_logp(prow[tok], P, scale);
+    for (int j = a + 1; j <= k; ++j) logp[b * (k + 1) + j] = 0.f;
+  }
+}
+
+extern "C" int plm_spec_verify_lookup_bf16(const uint16_t* p_logits, int64_t ldp, const int64_t* draft_tok, const int32_t* n_prop,
+                                           const float* p_cutoff, const int64_t* p_tok, const float* u_accept, const float* u_resid,
+                                           float temperature, int32_t* n_accept, int64_t* next_tok, float* logp, int64_t B, int64_t k,
+                                           int64_t V, void* stream) {
+  PLM_REQUIRE(p_logits && draft_tok && n_prop && p_cutoff && p_tok && u_accept && u_resid && n_accept && next_tok && logp,
+              "plm_spec_verify_lookup_bf16: null pointer");
+  PLM_REQUIRE(k >= 1 && k <= SPV_MAX_DRAFT, "plm_spec_verify_lookup_bf16: k=%ld drafted tokens (need 1 <= k <= %d)", (long)k, SPV_MAX_DRAFT);
+  PLM_REQUIRE(B >= 1 && B < ((int64_t)1 << 26) && V >= 1 && V < ((int64_t)1 << 31) && ldp >= V,
+              "plm_spec_verify_lookup_bf16: bad shape B=%ld V=%ld ldp=%ld (need 1 <= B < 2^26, 1 <= V < 2^31 and ldp >= V)", (long)B, (long)V,
+              (long)ldp);
+  PLM_REQUIRE((reinterpret_cast<uintptr_t>(p_logits) & 1) == 0, "plm_spec_verify_lookup_bf16: logits must be 2-byte aligned");
+  PLM_REQUIRE(std::isfinite(temperature) && temperature > 0.f, "plm_spec_verify_lookup_bf16: temperature %g must be finite and > 0",
+              (double)temperature);
+  const float scale = smp_host_scale(V), c_tau = smp_host_ctau(temperature);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(spec_lookup_rows_kernel, dim3((unsigned)(B * k)), dim3(SMP_THREADS), 0, s, p_logits, ldp, draft_tok, n_prop, p_cutoff,
+                     u_accept, c_tau, scale, logp, B, (int)k, (int)V);
+  PLM_CHECK_LAUNCH("plm_spec_verify_lookup_bf16");
+  hipLaunchKernelGGL(spec_lookup_finish_kernel, dim3((unsigned)B), dim3(SMP_THREADS), 0, s, p_logits, ldp, draft_tok, n_prop, p_cutoff, p_tok,
+                     u_resid, c_tau, scale, n_accept, next_tok, logp, (int)k, (int)V);
+  PLM_CHECK_LAUNCH("plm_spec_verify_lookup_bf16");
+  return PLM_OK;
+}

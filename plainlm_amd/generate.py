@@ -1,5 +1,5 @@
 """KV-cached generation (DESIGN.md sections 12 to 15): the cache, the ``Generation`` mixin that gives ``Transformer`` its ``prefill /
-decode_step / new_cache / extend / generate / generate_speculative``, and the host logic under them.
+decode_step / new_cache / extend / generate / generate_speculative / generate_lookup``, and the host logic under them.
 
 The mixin alone takes a model, through the seam its docstring states (transformer.py imports this module, never the other way round);
 ``guard`` holds the refusals its methods share.  Everything else is plain functions over tensors on any device - the length checks, the
@@ -9,7 +9,9 @@ ops.kv_append_rope / ops.attn_decode for one token per sequence, ops.kv_append_r
 sampling adds the argument rules (check_sampling), the one draw of uniforms per call (draw_uniforms) and the
 per-step pick (sampling_pick over ops.sample_logits).  Speculative decoding adds its refusals (check_speculative),
 greedy acceptance (greedy_accept), the bookkeeping of a round (commit_round), the round loop over callables (speculative_loop), the one draw
-of all its uniforms (speculative_uniforms) and ``_SpecSession``, the state of one call and the four callables the loop drives.
+of all its uniforms (speculative_uniforms) and ``_SpecSession``, the state of one call and the four callables the loop drives.  Draft-free
+speculative decoding reuses that loop with ``_LookupSession``: the draft is ops.lookup_draft over the sequence's own
+token history (check_lookup, lookup_uniforms, lookup_round_uniforms).
 """
 
 import math
@@ -279,12 +281,16 @@ def check_speculative(T, max_new_tokens, n_draft, cfg, draft_cfg, device=None, d
   return need, check_sampling(temperature, top_k, top_p, None, seed)
 
 
-def greedy_accept(draft_tok, target_pred):
+def greedy_accept(draft_tok, target_pred, n_prop=None):
   """Greedy acceptance: draft_tok int64 [B, k], target_pred int64 [B, k + 1] (row r: the target's prediction after the round's first r + 1
   tokens).  Returns (n_accept int32 [B] = the number of leading draft tokens the target predicts too, next_token int64 [B] = the target's
-  prediction at the first mismatch, or at row k).  Integer ops only, any device."""
+  prediction at the first mismatch, or at row k).  n_prop int [B]: only the first n_prop[b] columns of sequence b hold a proposal - a
+  column at or beyond it never counts as a match, whatever it holds (None: all k do).  Integer ops only, any device."""
   k = draft_tok.shape[1]
-  n = (draft_tok == target_pred[:, :k]).to(torch.int32).cumprod(dim=1).sum(dim=1)
+  match = draft_tok == target_pred[:, :k]
+  if n_prop is not None:
+    match = match & (torch.arange(k, device=draft_tok.device)[None, :] < n_prop[:, None])
+  n = match.to(torch.int32).cumprod(dim=1).sum(dim=1)
   return n.to(torch.int32), target_pred.gather(1, n.to(torch.int64)[:, None])[:, 0]
 
 
@@ -322,7 +328,8 @@ def commit_round(out_tok, out_lp, count, done, draft_tok, n_accept, next_tok, lo
   return new_count, new_done, m.to(torch.int32)
 
 
-def speculative_loop(first, draft_round, target_round, accept, max_new_tokens, n_draft, eos_id=None, advance=None, all_done=None):
+def speculative_loop(first, draft_round, target_round, accept, max_new_tokens, n_draft, eos_id=None, advance=None, all_done=None,
+                     drafted_in_round=None):
   """The round loop of speculative decoding over callables (tests/test_spec_host.py runs it on the CPU with fake models).
     first                                       (tokens int64 [B], logprob fp32 [B]) of the target's prefill
     draft_round(last, carry_tok, carry, live)   -> (draft_tok int64 [B, k], whatever accept needs of the draft).  last [B]: every
@@ -332,6 +339,8 @@ def speculative_loop(first, draft_round, target_round, accept, max_new_tokens, n
     accept(draft_tok, draft_out, target_out)    -> (n_accept [B], next_token [B], logprob [B, k + 1])
     advance(moved, live)                        moves the caches: moved int32 [B] from commit_round (0 for a finished sequence); a live
                                                 sequence's draft cache keeps min(moved, k) of the round's rows
+    drafted_in_round()                          -> int [B]: the proposals the round just run made per sequence, for a draft that does not
+                                                always make k of them (called after accept; None: k for every live sequence)
   Returns (tokens [B, N], logprobs [B, N], stats) with stats = dict(rounds, drafted int64 [B], accepted int64 [B]) over the rounds a
   sequence was live in.  A round emits at least one token per live sequence, so there are at most N - 1 rounds.  ``all_done(done)`` - the
   one device-to-host read, one int32 per round - ends the loop."""
@@ -364,7 +373,7 @@ def speculative_loop(first, draft_round, target_round, accept, max_new_tokens, n
     carry = live & (moved == k + 1)
     carry_tok = draft_tok[:, k - 1]
     last = torch.where(live, next_tok, last)
-    drafted += live.to(torch.int64) * k
+    drafted += live.to(torch.int64) * (k if drafted_in_round is None else drafted_in_round().to(torch.int64))
     accepted += torch.where(live, n_accept.to(torch.int64), torch.zeros_like(accepted))
     rounds += 1
   return out_tok, out_lp, dict(rounds=rounds, drafted=drafted, accepted=accepted)
@@ -443,8 +452,107 @@ class _SpecSession:
     self.round += 1
 
 
+# ---- draft-free speculative decoding: n-gram lookup drafts -----------------------------------------------------------
+MAX_NGRAM = 16  # plm_lookup_draft_i64 compares at most this many tokens of a match
+
+
+def check_lookup(T, max_new_tokens, n_draft, ngram, cfg, temperature=None, top_k=None, top_p=None, seed=None):
+  """The refusals of generate_lookup that need no GPU.  Returns (cache rows per sequence, check_sampling's normalised (temperature, top_k,
+  top_p) or None for greedy).  A round may write n_draft + 1 rows past the last token a sequence keeps, hence the longer cache."""
+  if isinstance(n_draft, bool) or not isinstance(n_draft, int):
+    raise TypeError(f'generate_lookup: n_draft must be an int, got {type(n_draft).__name__}')
+  if n_draft < 1 or n_draft > MAX_DRAFT:
+    raise ValueError(f'generate_lookup: n_draft must be in [1, {MAX_DRAFT}], got {n_draft}')
+  if not isinstance(ngram, (tuple, list)) or len(ngram) != 2 or any(isinstance(g, bool) or not isinstance(g, int) for g in ngram):
+    raise TypeError(f'generate_lookup: ngram must be two ints (g_min, g_max), got {ngram!r}')
+  if not 1 <= ngram[0] <= ngram[1] <= MAX_NGRAM:
+    raise ValueError(f'generate_lookup: ngram must satisfy 1 <= g_min <= g_max <= {MAX_NGRAM}, got {tuple(ngram)}')
+  need = _check_new_tokens('generate_lookup', T, max_new_tokens, n_draft + 1, f' + n_draft {n_draft} + 1', [('', cfg.seq_len)])
+  return need, check_sampling(temperature, top_k, top_p, None, seed)
+
+
+def lookup_uniforms_per_round(k):
+  """Uniforms a lookup round uses per sequence: k + 1 draws of the sampler, k acceptance tests, one residual draw (the draft draws none)."""
+  return 2 * k + 2
+
+
+def lookup_uniforms(max_new_tokens, n_draft, B, device, seed=None):
+  """All uniforms of one sampled generate_lookup call, drawn once through draw_uniforms: fp32 [1 + (N - 1) * (2k + 2), B].  Row 0 draws
+  the first token; round i owns the next 2k + 2 rows (``lookup_round_uniforms``).  Every entry is used at most once."""
+  return draw_uniforms(1 + (int(max_new_tokens) - 1) * lookup_uniforms_per_round(int(n_draft)), B, device, seed)
+
+
+def lookup_round_uniforms(u, i, n_draft):
+  """Round i's rows of ``lookup_uniforms``: (the sampler's [k + 1, B], acceptance [k, B], residual [B])."""
+  k = int(n_draft)
+  r = u[1 + i * lookup_uniforms_per_round(k):1 + (i + 1) * lookup_uniforms_per_round(k)]
+  return r[:k + 1], r[k + 1:2 * k + 1], r[2 * k + 1]
+
+
+class _LookupSession:
+  """One generate_lookup call between its rounds: the model and its cache, the length the cache is set to after every round, every
+  sequence's token history (prompt and emitted tokens, the newest included) with the tokens the next ops.lookup_draft launch appends to
+  it, the round counter and - when the call samples (``sampling`` = check_sampling's triple, else None) - its uniforms ``u``.  The methods
+  are the callables ``speculative_loop`` documents; there is no draft cache, so the loop's carry arguments are not used.  ``lookup``,
+  ``sampler`` and ``verify`` stand in for ops.lookup_draft / ops.sample_logits / ops.spec_verify_lookup in the host tests."""
+
+  def __init__(self, model, cache, prompt, first_tok, k, ngram, max_new_tokens, sampling, u, lookup=None, sampler=None, verify=None):
+    self.model, self.cache, self.k, self.ngram = model, cache, k, tuple(ngram)
+    self.sampling, self.sampled, self.u, self.round = sampling, sampling is not None, u, 0
+    self.lookup = ops.lookup_draft if lookup is None else lookup
+    self.sampler = ops.sample_logits if sampler is None else sampler
+    self.verify = ops.spec_verify_lookup if verify is None else verify
+    B, T = prompt.shape
+    self.tlen = cache.lens.clone()  # the cache holds the sequence up to, not including, its newest token
+    # a sequence emits at most max_new_tokens tokens, so T + max_new_tokens columns hold every history; columns beyond hlen are never read
+    self.hist = torch.zeros((B, T + int(max_new_tokens)), dtype=torch.int64, device=prompt.device)
+    self.hist[:, :T] = prompt
+    self.hlen = cache.lens.clone()
+    self.status = torch.zeros((1,), dtype=torch.int32, device=prompt.device)
+    self.add, self.n_add = first_tok[:, None].contiguous(), None  # round 0 appends the first token
+    self.n_prop = self.n_accept = self.next_tok = None
+
+  def draft_round(self, last, carry_tok, carry, live):
+    d = self.lookup(self.hist, self.hlen, self.add, self.n_add, k=self.k, ngram=self.ngram, status=self.status)
+    self.n_prop = d.n_prop
+    return d.draft_tokens, None
+
+  def target_round(self, last, draft_tok, live):
+    chunk = torch.cat([last[:, None], draft_tok], dim=1)
+    return self.model.extend(chunk, self.cache, token_lens=live.to(torch.int32) * (self.n_prop + 1), logits=self.sampled, all_rows=True)
+
+  def accept(self, draft_tok, draft_out, out):
+    if not self.sampled:
+      res = greedy_accept(draft_tok, out.tokens, self.n_prop) + (out.logprob,)
+    else:
+      ut, ua, ures = lookup_round_uniforms(self.u, self.round, self.k)
+      rows = out.view(-1, out.shape[-1])  # [B * (k + 1), V]
+      st = self.sampler(rows, ut.t().reshape(-1), *self.sampling, want_stats=True)  # row b * (k + 1) + r draws with ut[r, b]
+      res = tuple(self.verify(rows, draft_tok, self.n_prop, st.cutoff, st.tokens, ua, ures, self.sampling[0]))
+    self.n_accept, self.next_tok = res[0], res[1]
+    self.draft_tok = draft_tok
+    return res
+
+  def drafted(self):
+    return self.n_prop
+
+  def advance(self, moved, live):
+    self.tlen.add_(moved)
+    self.cache.set_lens(self.tlen)
+    # what the round committed, for the next launch to append: the accepted proposals, then the round's own token; `moved` of them
+    j = torch.arange(self.k + 1, device=moved.device)[None, :]
+    self.add = torch.where(j < self.n_accept.to(torch.int64)[:, None], torch.nn.functional.pad(self.draft_tok, (0, 1)), self.next_tok[:, None])
+    self.n_add = moved
+    self.round += 1
+
+  def check(self):
+    """Raises if a round's tokens did not fit the history (reads the device flag, so it waits for the GPU)."""
+    if int(self.status.item()) != 0:
+      raise RuntimeError('generate_lookup: a round\'s tokens did not fit the token history: they were not stored')
+
+
 class Generation:
-  """KV-cached generation, mixed into ``Transformer`` (DESIGN.md sections 12 to 15).  What it asks of its host class:
+  """KV-cached generation, mixed into ``Transformer`` (DESIGN.md sections 12 to 16).  What it asks of its host class:
     attributes  cfg (the ModelConfig), n_layers, head_dim, lm_head (its weight tells the model's device)
     methods     _rope(device), trunk(x, attn_mask, cache), cached_layers(tokens, cache, attend), head(y, logits, shape); the middle two
                 call refresh_shadows() themselves.  _rope keeps its underscore: tools and tests from before the mixin call it by that name."""
@@ -593,5 +701,34 @@ class Generation:
       toks, lps, stats = speculative_loop(first, s.draft_round, s.target_round, s.accept, N, k, eos_id, s.advance)
     tcache.check()
     dcache.check()
+    res = (toks,) + ((lps,) if return_logprobs else ()) + ((stats,) if return_stats else ())
+    return res[0] if len(res) == 1 else res
+
+  @torch.compiler.disable
+  def generate_lookup(self, prompt, max_new_tokens, n_draft=8, ngram=(1, 4), prompt_lens=None, eos_id=None, return_logprobs=False,
+                      temperature=None, top_k=None, top_p=None, seed=None, return_stats=False):
+    """``generate_speculative`` without a draft model: every round, one ops.lookup_draft launch finds the most recent
+    earlier occurrence of the sequence's last ngram[0] .. ngram[1] tokens (the longest match wins) in its own prompt and output and
+    proposes the n_draft tokens that followed; this model checks them in one ``extend`` of n_draft + 1 rows and a sequence keeps the
+    accepted tokens plus one of this model's own.  A sequence without a match proposes nothing and the round is a plain decode step for
+    it.  Greedy: the tokens are what ``generate`` decodes greedily.  With temperature / top_k / top_p, ops.spec_verify_lookup applies the
+    acceptance rule of a deterministic draft (accept x with probability p(x), else draw from p without x), which leaves every token
+    distributed as ``generate`` samples it.  The uniforms of the call are drawn once, under ``seed`` (bit-reproducible) or from torch's
+    default generator.  Returns what generate_speculative returns: the tokens int64 [B, N]; with return_logprobs also this model's
+    log-probabilities at temperature 1, with return_stats also dict(rounds, drafted int64 [B] = the proposals actually made, accepted
+    int64 [B]).  After eos_id a sequence holds eos_id with log-probability 0.  One int32 is read from the device per round; there is no
+    second cache and no draft prefill."""
+    guard('generate_lookup', prompt, self, forward_only=True, rank2=True)
+    B, T = prompt.shape
+    k, N = n_draft, int(max_new_tokens)
+    max_len, sampling = check_lookup(T, max_new_tokens, k, ngram, self.cfg, temperature, top_k, top_p, seed)
+    cache, r = self.prefill(prompt, prompt_lens, max_len=max_len, logits=sampling is not None)
+    u = None if sampling is None else lookup_uniforms(N, k, B, prompt.device, seed)
+    first = (r.tokens, r.logprob) if sampling is None else ops.sample_logits(r, u[0], *sampling)[:2]
+    with torch.no_grad():
+      s = _LookupSession(self, cache, prompt, first[0], k, ngram, N, sampling, u)
+      toks, lps, stats = speculative_loop(first, s.draft_round, s.target_round, s.accept, N, k, eos_id, s.advance, drafted_in_round=s.drafted)
+    cache.check()
+    s.check()
     res = (toks,) + ((lps,) if return_logprobs else ()) + ((stats,) if return_stats else ())
     return res[0] if len(res) == 1 else res

@@ -1135,3 +1135,7 @@ def probe_mfma32(A, B):
   out = torch.empty((32, 32), dtype=F32, device=A.device)
   _lib.check(_lib.load().plm_probe_mfma32(_p(A), _p(B), _p(out), _stream()), 'plm_probe_mfma32')
   return out
+
+
+# ---- draft-free speculative decoding: the two wrappers live in ops_lookup.py, on this module's contract ------
+from .ops_lookup import LookupDraft, lookup_draft, spec_verify_lookup  # noqa: E402,F401
