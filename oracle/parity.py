@@ -18,6 +18,10 @@ BOUNDS holds every bound the GPU tests and tests/test_parity_budget.py share.  E
 honest floor (oracle/cpu_ref_bf16.py's attention, which rounds where the kernels round) and the worst value the MI355X
 kernels show, with at least a 2x margin above the larger and at least 2x below the smallest planted defect of
 tests/test_parity_budget.py.  Layout: tensors are [B, nh, T, hd] (rows along dim 2), LSE / delta [B, nh, T].
+
+``attn_inputs`` draws the operands of the input classes beyond unit-normal data (peaked, ramp, sink, spike), ``late_rescales`` counts from
+fp64 scores how often a class makes the deferred running-max update of the forward kernels fire, and BOUNDS_BY_CLASS holds the few
+bounds a class needs of its own (profiles/attn_parity_classes.md has the measurements).
 """
 
 from __future__ import annotations
@@ -40,6 +44,15 @@ BOUNDS = {
     'proj_slice': {'out': 3e-3, 'dq': 1e-2, 'dk': 1e-2, 'dv': 3e-3},  # |c - 1| of each (batch, head) slice
     'lse': 1e-4,                                                      # max |LSE2 - ref|, log2 units
     'delta': 1e-6,                                                    # max |delta - ref| / rowsum |dO * O|
+}
+
+# Bounds of their own for the input classes of ``attn_inputs`` on which BOUNDS keeps no 2x margin; everything absent here is BOUNDS.
+# The same rule, from the measurements in profiles/attn_parity_classes.md: near one-hot rows make dS = P (dP - D) cancel, so the bf16
+# rounding of dS is large against a row's own dQ / dK.  row dq: stand-in floor 0.13 (peaked) / 0.14 (ramp), MI355X 0.11 / 0.10, smallest
+# planted defect it must catch on the class 1.9 (delta_zero); row dk: floor 0.087 / 0.085, MI355X 0.089 / 0.085, defect 0.52 (dk_tile).
+BOUNDS_BY_CLASS: Dict[str, dict] = {
+    'peaked': {'row': {'dq': 0.3, 'dk': 0.2}},
+    'ramp': {'row': {'dq': 0.3, 'dk': 0.2}},
 }
 
 
@@ -153,28 +166,33 @@ def metrics(got: Dict[str, Tensor], ref: Dict[str, Tensor]) -> Dict[str, float]:
   return m
 
 
-def violations(m: Dict[str, float]) -> Dict[str, tuple]:
-  """{metric: (value, bound)} for every metric above its bound."""
+def bound_of(key: str, cls: Optional[str] = None) -> float:
+  """The bound of one metric of ``metrics`` ('row_dq', 'proj_slice_out', 'lse', ...): BOUNDS, or the input class's own entry."""
+  by_cls = BOUNDS_BY_CLASS.get(cls, {})
+  if key.startswith('row_'):
+    return by_cls.get('row', {}).get(key[4:], BOUNDS['row'][key[4:]])
+  if key.startswith('proj_slice_'):
+    return by_cls.get('proj_slice', {}).get(key[11:], BOUNDS['proj_slice'][key[11:]])
+  if key.startswith('proj_'):
+    return by_cls.get('proj', {}).get(key[5:], BOUNDS['proj'][key[5:]])
+  return by_cls.get(key, BOUNDS[key])
+
+
+def violations(m: Dict[str, float], cls: Optional[str] = None) -> Dict[str, tuple]:
+  """{metric: (value, bound)} for every metric above its bound (``cls``: an input class of attn_inputs with bounds of its own)."""
   bad = {}
   for key, val in m.items():
-    if key.startswith('row_'):
-      bound = BOUNDS['row'][key[4:]]
-    elif key.startswith('proj_slice_'):
-      bound = BOUNDS['proj_slice'][key[11:]]
-    elif key.startswith('proj_'):
-      bound = BOUNDS['proj'][key[5:]]
-    else:
-      bound = BOUNDS[key]
+    bound = bound_of(key, cls)
     if not val <= bound:
       bad[key] = (val, bound)
   return bad
 
 
-def check(got: Dict[str, Tensor], ref: Dict[str, Tensor], tag: str) -> Dict[str, float]:
-  """Assert every metric of ``got`` within BOUNDS; prints them (one line, 'parity <tag>: ...') either way."""
+def check(got: Dict[str, Tensor], ref: Dict[str, Tensor], tag: str, cls: Optional[str] = None) -> Dict[str, float]:
+  """Assert every metric of ``got`` within BOUNDS (``cls``: BOUNDS_BY_CLASS); prints them (one line, 'parity <tag>: ...') either way."""
   m = metrics(got, ref)
   print(f'parity {tag}: ' + ' '.join(f'{k}={v:.2e}' for k, v in m.items()))
-  bad = violations(m)
+  bad = violations(m, cls)
   assert not bad, f'{tag}: ' + ', '.join(f'{k} {v:.3e} > {b:.1e}' for k, (v, b) in bad.items())
   return m
 
@@ -193,6 +211,95 @@ def kernel_result(B: int, T: int, nh: int, hd: int, out=None, lse=None, dqkv=Non
     for i, n in enumerate(('dq', 'dk', 'dv')):
       got[n] = heads(dqkv[:, i * d:(i + 1) * d], B, T, nh, hd)
   return got
+
+
+# --------------------------------------------------------------------------------------
+# input classes: attention operands off unit-normal data
+# --------------------------------------------------------------------------------------
+CLASSES = ('randn', 'peaked', 'ramp', 'sink', 'spike')
+STRUCT_DIMS = 16  # structured parts live in the last 16 dims of a head: RoPE's lowest frequencies, <= ~0.13 rad over 1024 positions
+
+
+def _doc_ranges(doc_start_row: Tensor, T: int):
+  """[(start, end)] of the documents of one doc_start row [T]."""
+  starts = torch.unique(doc_start_row[:T].long()).tolist()
+  return list(zip(starts, starts[1:] + [T]))
+
+
+def attn_inputs(cls: str, B: int, T: int, nh: int, hd: int, seed: int, doc_start: Optional[Tensor] = None):
+  """Deterministic attention operands of one class: (qkv bf16 UN-rotated [B*T, 3*nh*hd], dout bf16 [B*T, nh*hd]), on the CPU.
+
+    randn   what every other attention test draws: unit normal.
+    peaked  randn with the q and k blocks times 3: scaled scores of std ~ 13 log2 units at any head dim, near one-hot P.
+    ramp    randn; q's last 16 dims += 3, key j's last 16 dims += floor(j / 64): the running max grows in every key tile.
+    sink    randn; q's last 16 dims += 2, the k row of every sequence's (with doc_start: every document's) first token has its
+            last 16 dims set to 6: the maximum is fixed in the first visible tile and every later weight is tiny.
+    spike   0.3 * randn; one key at 0.78 of the sequence (of every document) set to 6 in every dim, the queries after 0.9 of it
+            += 2: tests/test_kernels_gpu.py::test_attention_softmax_rescale_branch's late jump of the running max, at any shape.
+  """
+  if cls not in CLASSES:
+    raise ValueError(cls)
+  g = torch.Generator().manual_seed(seed)
+  d = nh * hd
+  qkv = torch.randn(B * T, 3 * d, generator=g)
+  dout = torch.randn(B * T, d, generator=g)
+  x = qkv.view(B, T, 3, nh, hd)
+  q, k = x[:, :, 0], x[:, :, 1]  # views: [B, T, nh, hd]
+  lo = hd - STRUCT_DIMS
+  if cls == 'peaked':
+    q *= 3.0
+    k *= 3.0
+  elif cls == 'ramp':
+    q[..., lo:] += 3.0
+    k[..., lo:] += (torch.arange(T) // 64).float().view(1, T, 1, 1)
+  elif cls == 'sink':
+    q[..., lo:] += 2.0
+    if doc_start is None:
+      k[:, 0, :, lo:] = 6.0
+    else:
+      first = doc_start.cpu().long()[:, :T] == torch.arange(T).view(1, T)  # [B, T]
+      k[..., lo:] = torch.where(first.view(B, T, 1, 1), torch.full_like(k[..., lo:], 6.0), k[..., lo:])
+  elif cls == 'spike':
+    qkv *= 0.3
+    for b in range(B):
+      for s, e in ([(0, T)] if doc_start is None else _doc_ranges(doc_start[b].cpu(), T)):
+        n = e - s
+        k[b, s + int(0.78125 * n)] = 6.0
+        q[b, s + int(0.9 * n):e] += 2.0
+  return qkv.to(torch.bfloat16), dout.to(torch.bfloat16)
+
+
+def scores_log2(qkv_rot: Tensor, B: int, T: int, nh: int, hd: int) -> Tensor:
+  """fp64 scaled scores q k^T / sqrt(hd) * log2(e) [B, nh, T, T] (unmasked) from the rotated bf16 operands: what the kernels' exp2 sees."""
+  q, k, _ = split_qkv(qkv_rot, B, T, nh, hd)
+  return torch.matmul(q, k.transpose(-1, -2)) * (LOG2E / math.sqrt(hd))
+
+
+def late_rescales(s2: Tensor, allow: Tensor, tile: int = 64, defer: float = 8.0) -> Tensor:
+  """How often the deferred running-max update of the causal / document forward kernels fires AFTER a row's first visible key tile:
+  the number of (row, ``tile``-key tile) pairs at which the tile's largest visible score exceeds the row's running maximum by more
+  than ``defer`` (both in log2 units; the kernels' ATTN_DEFER_LOG2 / DOC_DEFER_LOG2).  s2 [B, nh, Tq, Tk] from ``scores_log2``,
+  allow bool broadcastable to it.  Returns the count per (batch, head), int64 [B, nh].  0 on unit-normal data: there the rescale
+  (lsum *= alpha, o *= alpha) only ever runs on lsum = 0, o = 0."""
+  B, nh, Tq, Tk = s2.shape
+  s = s2.masked_fill(~allow.expand(B, nh, Tq, Tk), float('-inf'))
+  mc = torch.full((B, nh, Tq), float('-inf'), dtype=s.dtype)
+  count = torch.zeros(B, nh, dtype=torch.int64)
+  for k0 in range(0, Tk, tile):
+    tm = s[..., k0:k0 + tile].amax(-1)
+    fire = tm > mc + defer  # -inf > -inf + defer: False
+    count += (fire & torch.isfinite(mc)).sum(-1)
+    mc = torch.where(fire, tm, mc)
+  return count
+
+
+def assert_class_precondition(cls: str, late: Tensor, tag: str = ''):
+  """The classes stay honest when someone retunes them: randn never takes a late rescale, peaked / ramp / spike take one in every
+  (batch, head); sink (the maximum sits in the first visible tile) is left to its own count."""
+  if cls == 'randn':
+    assert int(late.max()) == 0, (tag, cls, late.tolist())
+  elif cls in ('peaked', 'ramp', 'spike'):
+    assert int(late.min()) > 0, (tag, cls, late.tolist())
 
 
 # --------------------------------------------------------------------------------------
