@@ -299,6 +299,51 @@ int plm_attn_extend(const uint16_t* q, const uint16_t* kv, int64_t ld_kv, const 
                     float* lse, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, int splits, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ---- the fused decode step: skinny-M layer kernels and one call per layer -----
+ * Every argument check of these entry points comes before any HIP call; none falls back to another path.
+ * M = B rows, one decode token per sequence, 1 <= M <= 32.  Weights are the bf16 shadows [N, K], contiguous (the layout plm_gemm_bf16_nt
+ * consumes), read once per launch; accumulation is fp32; the K split across the four waves of a workgroup is added in wave order (no
+ * atomics: two runs are bit-equal).  Every rounding point of the unfused step is kept; only the order of the fp32 sums differs.
+ *
+ * plm_decode_norm_qkv_append_bf16 (replaces plm_rmsnorm_fwd + plm_gemm_bf16_nt + plm_kv_append_rope): x fp32 [B, d], d = nh*hd;
+ * n = bf16(x * rstd * norm_w) with plm_rmsnorm_fwd's rounding; qkv = bf16(n w_qkv^T), w_qkv bf16 [3d, d]; the q and k columns are rotated
+ * at position pos[b] with plm_kv_append_rope's arithmetic on the bf16 values; rotated q goes to q_out bf16 [B, d], rotated k | v to
+ * kv[b, pos[b], 0 : 2d] of the cache kv[B, Tmax, ld_kv] above.  A pos[b] outside [0, min(Tmax, rope_T)) stores nothing for that sequence,
+ * writes a q_out row of zeros and sets the caller-zeroed status[0] to 1.  One launch.
+ *
+ * plm_decode_gemm_residual_bf16 (replaces plm_gemm_bf16_nt and the residual add of the next norm): x[M, N] += float(bf16(A W^T)) in place
+ * on the fp32 stream; A bf16 [M, K], W bf16 [N, K].  One launch.
+ *
+ * plm_decode_norm_fc1_act_bf16 (replaces plm_rmsnorm_fwd + plm_gemm_bf16_nt + plm_swiglu_fwd / plm_act_fwd): the norm as above, u =
+ * bf16(n w_fc1^T), then on the bf16 values act bf16 [M, hidden] = PLM_DECODE_MLP_GLU: plm_swiglu_fwd of u = gate | up, w_fc1 [2*hidden, d];
+ * PLM_DECODE_MLP_SILU / PLM_DECODE_MLP_RELU_SQ: plm_act_fwd kind 0 / 1, w_fc1 [hidden, d].  One launch.
+ *
+ * plm_decode_layer_bf16: a whole decode layer on `stream` from one call - the qkv stage, plm_attn_decode's two launches (lens, splits as
+ * there), the residual stage with w_out [d, d], the fc1 stage, the residual stage with w_fc2 [d, hidden]: six launches.  x fp32 [B, d] is
+ * updated in place.  q, the attention output, the activation and plm_attn_decode's partials live in the workspace:
+ * plm_decode_layer_workspace_bytes(B, nh, hd, hidden, Tmax, splits) bytes for the same splits argument, 16-byte aligned, caller-owned; the
+ * query is a function of its arguments alone and returns 0 for arguments the launch refuses.
+ *
+ * PLM_E_INVALID before anything is launched: NULL pointers, M (B) outside 1..32, a head_dim other than 32 / 64 / 128, d % 32 != 0,
+ * hidden % 32 != 0, N % 16 != 0 or K % 32 != 0, an unknown mlp_kind, a cache row stride that is no multiple of 8 or shorter than 2d, splits
+ * outside 0..64, x / norm weights / weights / q_out / kv / A / act / workspace not 16-byte aligned; a short workspace gives
+ * PLM_E_WORKSPACE. */
+#define PLM_DECODE_MLP_GLU 0
+#define PLM_DECODE_MLP_SILU 1
+#define PLM_DECODE_MLP_RELU_SQ 2
+int plm_decode_norm_qkv_append_bf16(const float* x, const float* norm_w, float eps, const uint16_t* w_qkv, const int32_t* pos,
+                                    const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv,
+                                    int32_t* status, int64_t B, int64_t Tmax, int64_t nh, int64_t hd, void* stream);
+int plm_decode_gemm_residual_bf16(float* x, const uint16_t* A, const uint16_t* W, int64_t M, int64_t N, int64_t K, void* stream);
+int plm_decode_norm_fc1_act_bf16(const float* x, const float* norm_w, float eps, const uint16_t* w_fc1, uint16_t* act, int64_t M, int64_t d,
+                                 int64_t hidden, int mlp_kind, void* stream);
+size_t plm_decode_layer_workspace_bytes(int64_t B, int64_t nh, int64_t hd, int64_t hidden, int64_t Tmax, int splits);
+int plm_decode_layer_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv, const uint16_t* w_out,
+                          const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* pos, const int32_t* lens, const float* rope_cos,
+                          const float* rope_sin, int64_t rope_T, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t Tmax,
+                          int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
 /* ---- temperature / top-k / top-p sampling of one token per row -----
  * Every argument check comes before any HIP call.
  * logits bf16 [B, ld] (ld >= V; any 2-byte aligned base and any ld: columns >= V are never loaded); u fp32 [B], one uniform per row,

@@ -112,6 +112,12 @@ SIGNATURES = {
   'plm_kv_append_rope_rows': (_I, [_P, _I64, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P]),
   'plm_attn_extend_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I]),
   'plm_attn_extend': (_I, [_P, _P, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
+  'plm_decode_norm_qkv_append_bf16': (_I, [_P, _P, _F, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
+  'plm_decode_gemm_residual_bf16': (_I, [_P, _P, _P, _I64, _I64, _I64, _P]),
+  'plm_decode_norm_fc1_act_bf16': (_I, [_P, _P, _F, _P, _P, _I64, _I64, _I64, _I, _P]),
+  'plm_decode_layer_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I]),
+  'plm_decode_layer_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I, _I, _P,
+                                 _SZ, _P]),
   'plm_sample_logits_bf16': (_I, [_P, _I64, _P, _F, _I64, _F, _P, _P, _P, _P, _I64, _I64, _P]),
   'plm_spec_verify_bf16': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I64, _I64, _I64, _P]),
   'plm_lookup_draft_i64': (_I, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P]),

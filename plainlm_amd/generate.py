@@ -11,7 +11,9 @@ per-step pick (sampling_pick over ops.sample_logits).  Speculative decoding (DES
 greedy acceptance (greedy_accept), the bookkeeping of a round (commit_round), the round loop over callables (speculative_loop), the one draw
 of all its uniforms (speculative_uniforms) and ``_SpecSession``, the state of one call and the four callables the loop drives.  Draft-free
 speculative decoding reuses that loop with ``_LookupSession``: the draft is ops.lookup_draft over the sequence's own
-token history (check_lookup, lookup_uniforms, lookup_round_uniforms).
+token history (check_lookup, lookup_uniforms, lookup_round_uniforms).  The fused decode step is a keyword of
+decode_step, ``fused=True``, which runs every layer as one ops.decode_layer call, and generate_fused is generate over it (check_fused holds
+its refusals).
 """
 
 import math
@@ -116,6 +118,14 @@ def chunk_lens(token_lens, B, n, device):
     raise ValueError(f'extend: every token_lens must be in [0, {n}] (the token tensor\'s width), got {vals}')
   t = torch.tensor(vals, dtype=torch.int32).to(device)
   return t, t
+
+
+def check_fused(who, B, dim):
+  """The refusals of fused=True that need no GPU: the skinny-M kernels take at most ops.FUSED_DECODE_MAX_ROWS rows and dim % 32 == 0."""
+  if B > ops.FUSED_DECODE_MAX_ROWS:
+    raise ValueError(f'{who}: fused=True serves at most {ops.FUSED_DECODE_MAX_ROWS} sequences, got {B}: leave fused off')
+  if dim % 32 != 0:
+    raise ValueError(f'{who}: fused=True needs cfg.dim % 32 == 0, got {dim}: leave fused off')
 
 
 def pad4(n):
@@ -554,8 +564,9 @@ class _LookupSession:
 class Generation:
   """KV-cached generation, mixed into ``Transformer`` (DESIGN.md sections 12 to 16).  What it asks of its host class:
     attributes  cfg (the ModelConfig), n_layers, head_dim, lm_head (its weight tells the model's device)
-    methods     _rope(device), trunk(x, attn_mask, cache), cached_layers(tokens, cache, attend), head(y, logits, shape); the middle two
-                call refresh_shadows() themselves.  _rope keeps its underscore: tools and tests from before the mixin call it by that name."""
+    methods     _rope(device), trunk(x, attn_mask, cache), cached_layers(tokens, cache, attend), fused_layers(tokens, cache, rope),
+                head(y, logits, shape); the middle three call refresh_shadows() themselves.  _rope keeps its underscore: tools and tests
+                from before the mixin call it by that name."""
 
   @torch.compiler.disable
   def prefill(self, x, prompt_lens=None, max_len=None, logits=False):
@@ -582,18 +593,24 @@ class Generation:
       return cache, self.head(last_rows(y, B, Tp, lens_dev), logits, (B,))
 
   @torch.compiler.disable
-  def decode_step(self, tokens, cache, logits=False):
+  def decode_step(self, tokens, cache, logits=False, fused=False):
     """One token per sequence on top of ``cache``: tokens int64 [B] are appended at positions cache.lens (then lens += 1, on the device)
     and the HeadPrediction [B] of the NEXT token is returned - or, with logits=True, its bf16 logits [B, V].  The Block structure as it
-    is (``cached_layers``), with ops.kv_append_rope / ops.attn_decode as the attention stage."""
+    is (``cached_layers``), with ops.kv_append_rope / ops.attn_decode as the attention stage.  fused=True runs
+    every layer as one library call over the skinny-M kernels (``fused_layers``: the same rounding points, other fp32 summation orders,
+    so close to but not the bits of the default); it serves B <= ops.FUSED_DECODE_MAX_ROWS and raises ValueError otherwise."""
     guard('decode_step', tokens, self)
     B = cache.B
     if tuple(tokens.shape) != (B,):
       raise ValueError(f'decode_step: tokens {tuple(tokens.shape)} do not match the cache\'s batch of {B}')
+    if fused:
+      check_fused('decode_step', B, self.cfg.dim)
     nh = self.cfg.n_heads
     with torch.no_grad():
       rope = self._rope(tokens.device)
       cache.advance()  # pos = the appended token's position, lens = pos + 1: what this step's attention sees
+      if fused:
+        return self.head(self.fused_layers(tokens.contiguous(), cache, rope), logits, (B,))
 
       def attend(i, qkv):
         q, _ = ops.kv_append_rope(qkv, cache.pos, rope[0], rope[1], cache.kv[i], nh, status=cache.status)
@@ -660,17 +677,35 @@ class Generation:
     temperature / top_k / top_p sample on the device (one ops.sample_logits launch per token next to the logits
     GEMM; top-k keeps ties with the k-th value, top-p keeps or drops equal logits together; the returned log-probabilities stay the
     model's, at temperature 1).  The uniforms of the whole call are drawn once, from a generator seeded with ``seed`` (bit-reproducible)
-    or from torch's default generator.  temperature None or 0 without a filter is greedy; ``sample`` excludes all four."""
-    guard('generate', prompt, self, forward_only=True, rank2=True)
+    or from torch's default generator.  temperature None or 0 without a filter is greedy; ``sample`` excludes all four.
+    ``generate_fused`` is the same call with the decode steps run fused."""
+    return self._generate('generate', False, prompt, max_new_tokens, prompt_lens, eos_id, sample, return_logprobs, temperature, top_k,
+                          top_p, seed)
+
+  @torch.compiler.disable
+  def generate_fused(self, prompt, max_new_tokens, prompt_lens=None, eos_id=None, sample=None, return_logprobs=False, temperature=None,
+                     top_k=None, top_p=None, seed=None):
+    """``generate`` with every decode step run as ``decode_step(..., fused=True)`` (the prefill is unchanged): the
+    same arguments, refusals and return values, tokens close to but not bit for bit those of ``generate`` (other fp32 summation
+    orders).  Serves B <= ops.FUSED_DECODE_MAX_ROWS sequences and raises ValueError beyond, before anything is launched.  It is a method
+    of its own, not a keyword of ``generate``, whose parameter list is pinned."""
+    return self._generate('generate_fused', True, prompt, max_new_tokens, prompt_lens, eos_id, sample, return_logprobs, temperature, top_k,
+                          top_p, seed)
+
+  def _generate(self, who, fused, prompt, max_new_tokens, prompt_lens, eos_id, sample, return_logprobs, temperature, top_k, top_p, seed):
+    guard(who, prompt, self, forward_only=True, rank2=True)
     max_len = check_lengths(prompt.shape[1], max_new_tokens, self.cfg.seq_len)
     on_device = check_sampling(temperature, top_k, top_p, sample, seed)
+    if fused:
+      check_fused(who, prompt.shape[0], self.cfg.dim)
     want_logits = sample is not None or on_device is not None
     if on_device is not None:
       pick = sampling_pick(draw_uniforms(max_new_tokens, prompt.shape[0], prompt.device, seed), *on_device)
     else:
       pick = (lambda r: sampled(sample, r)) if want_logits else (lambda r: (r.tokens, r.logprob))  # noqa: E731
     cache, r = self.prefill(prompt, prompt_lens, max_len=max_len, logits=want_logits)
-    toks, lps = generate_loop(pick(r), lambda t: pick(self.decode_step(t, cache, logits=want_logits)), max_new_tokens, eos_id)
+    toks, lps = generate_loop(pick(r), lambda t: pick(self.decode_step(t, cache, logits=want_logits, fused=fused)), max_new_tokens,
+                               eos_id)
     cache.check()
     return (toks, lps) if return_logprobs else toks
 

@@ -1139,3 +1139,7 @@ def probe_mfma32(A, B):
 
 # ---- draft-free speculative decoding: the two wrappers live in ops_lookup.py, on this module's contract ------
 from .ops_lookup import LookupDraft, lookup_draft, spec_verify_lookup  # noqa: E402,F401
+
+# ---- the fused decode step: its wrappers live in ops_decode.py, on this module's contract ---------------------------
+from .ops_decode import (DECODE_MLP_KINDS, FUSED_DECODE_MAX_ROWS, decode_gemm_residual, decode_layer, decode_layer_workspace,  # noqa: E402,F401
+                         decode_norm_fc1_act, decode_norm_qkv_append)

@@ -1,0 +1,147 @@
+"""The ops wrappers of the fused decode step: ``ops.decode_norm_qkv_append``, ``ops.decode_gemm_residual``,
+``ops.decode_norm_fc1_act`` (the three skinny-M stages) and ``ops.decode_layer`` (a whole decode layer from one library call).
+
+They are part of ``plainlm_amd.ops`` (which re-exports them) and stand on its contract - the operand validator (``ops._need``), the launch
+bracket (``ops._Launch``), the workspace arena of the current stream, ``_lib.check`` around the one library call - and, like every wrapper
+there, launch hand-written gfx950 kernels with no torch fallback.  They live in a module of their own for ops_lookup.py's reason:
+tests/test_ops_trace_host.py holds every function defined in ops.py to a trace recorded on an earlier commit."""
+
+import torch
+
+from . import _lib
+from . import ops as O
+
+FUSED_DECODE_MAX_ROWS = 32  # M = B of the plm_decode_* entry points: one decode token per sequence
+DECODE_MLP_KINDS = {'glu': 0, 'silu': 1, 'relu_sq': 2}  # PLM_DECODE_MLP_*
+
+
+def _decode_operands(name, x, norms, weights):
+  """The operand checks the fused decode ops share: x fp32 [M, d] with 1 <= M <= FUSED_DECODE_MAX_ROWS, fp32 [d] norm weights, contiguous
+  bf16 2-D weights.  Returns (M, d)."""
+  try:
+    O._need(x, O.F32, 'x', 2)
+    for w in norms:
+      if O._need(w, O.F32, 'norm weight', 1).shape[0] != x.shape[1]:
+        raise ValueError(f'norm weight: need [{x.shape[1]}], got {tuple(w.shape)}')
+    for w in weights:
+      O._need(w, O.BF16, 'weight', 2)
+  except (RuntimeError, TypeError, ValueError) as e:
+    raise type(e)(f'{name}.{e}') from None
+  M, d = x.shape
+  if not 1 <= M <= FUSED_DECODE_MAX_ROWS:
+    raise ValueError(f'{name}: {M} rows; the fused decode kernels take 1 to {FUSED_DECODE_MAX_ROWS} (one token per sequence)')
+  return M, d
+
+
+def _decode_mlp_kind(name, kind):
+  if kind not in DECODE_MLP_KINDS:
+    raise ValueError(f'{name}: mlp kind {kind!r} is not one of {sorted(DECODE_MLP_KINDS)}')
+  return DECODE_MLP_KINDS[kind]
+
+
+def decode_norm_qkv_append(x, norm_w, eps, w_qkv, pos, rope_cos, rope_sin, kv, nh, q_out=None, status=None):
+  """rmsnorm_fwd -> gemm_nt -> kv_append_rope of one decode step in one launch: x fp32 [B, d] (B <= FUSED_DECODE_MAX_ROWS), w_qkv bf16
+  [3d, d].  Returns (rotated q bf16 [B, d], status); rotated k | v went into kv[b, pos[b]].  A pos[b] outside [0, min(Tmax, rope rows))
+  stores nothing for that sequence, leaves a q row of zeros and sets status[0] = 1 (int32 [1], zeroed by the caller; made here when absent)."""
+  name = 'decode_norm_qkv_append'
+  B, d = _decode_operands(name, x, (norm_w,), (w_qkv,))
+  if d % nh != 0 or tuple(w_qkv.shape) != (3 * d, d):
+    raise ValueError(f'{name}: x {tuple(x.shape)}, w_qkv {tuple(w_qkv.shape)} do not fit nh={nh}')
+  hd = d // nh
+  try:
+    O._need_kv(kv, nh, hd, 'kv')
+    O._need(pos, torch.int32, 'pos', 1)
+    O._need(rope_cos, O.F32, 'rope_cos', 2)
+    O._need(rope_sin, O.F32, 'rope_sin', 2)
+  except (RuntimeError, TypeError, ValueError) as e:
+    raise type(e)(f'{name}.{e}') from None
+  if kv.shape[0] != B or pos.shape[0] != B or rope_cos.shape != rope_sin.shape or rope_cos.shape[1] != hd // 2:
+    raise ValueError(f'{name}: kv {tuple(kv.shape)}, pos {tuple(pos.shape)} or the RoPE tables {tuple(rope_cos.shape)} / {tuple(rope_sin.shape)} do '
+                     f'not fit B={B}, head_dim={hd}')
+  q_out, status = O._append_outputs(name, x, B, d, q_out, status)
+  with O._Launch('hbm:decode_fused', 2.0 * w_qkv.numel()):
+    _lib.check(_lib.load().plm_decode_norm_qkv_append_bf16(O._p(x), O._p(norm_w), float(eps), O._p(w_qkv), O._p(pos), O._p(rope_cos), O._p(rope_sin),
+                                                           rope_cos.shape[0], O._p(q_out), O._p(kv), kv.stride(1), O._p(status), B, kv.shape[1], nh,
+                                                           hd, O._stream()), 'plm_decode_norm_qkv_append_bf16')
+  return q_out, status
+
+
+def decode_gemm_residual(x, a, w):
+  """x[M, N] += float(bf16(a[M, K] @ w[N, K]^T)) in place on the fp32 residual stream (gemm_nt and the add of the next norm in one launch);
+  M <= FUSED_DECODE_MAX_ROWS.  Returns x."""
+  name = 'decode_gemm_residual'
+  M, N = _decode_operands(name, x, (), (a, w))
+  if a.shape[0] != M or w.shape[0] != N or w.shape[1] != a.shape[1]:
+    raise ValueError(f'{name}: x {tuple(x.shape)}, a {tuple(a.shape)}, w {tuple(w.shape)} do not fit')
+  with O._Launch('hbm:decode_fused', 2.0 * w.numel()):
+    _lib.check(_lib.load().plm_decode_gemm_residual_bf16(O._p(x), O._p(a), O._p(w), M, N, a.shape[1], O._stream()), 'plm_decode_gemm_residual_bf16')
+  return x
+
+
+def decode_norm_fc1_act(x, norm_w, eps, w_fc1, kind):
+  """rmsnorm_fwd -> gemm_nt -> swiglu_fwd / act_fwd of one decode step in one launch: x fp32 [M, d], w_fc1 bf16 [2h, d] ('glu': gate | up)
+  or [h, d] ('silu', 'relu_sq').  Returns the activation bf16 [M, h]."""
+  name = 'decode_norm_fc1_act'
+  M, d = _decode_operands(name, x, (norm_w,), (w_fc1,))
+  k = _decode_mlp_kind(name, kind)
+  mult = 2 if kind == 'glu' else 1
+  if w_fc1.shape[1] != d or w_fc1.shape[0] % mult != 0:
+    raise ValueError(f'{name}: x {tuple(x.shape)}, w_fc1 {tuple(w_fc1.shape)} do not fit kind {kind!r}')
+  h = w_fc1.shape[0] // mult
+  act = torch.empty((M, h), dtype=O.BF16, device=x.device)
+  with O._Launch('hbm:decode_fused', 2.0 * w_fc1.numel()):
+    _lib.check(_lib.load().plm_decode_norm_fc1_act_bf16(O._p(x), O._p(norm_w), float(eps), O._p(w_fc1), O._p(act), M, d, h, k, O._stream()),
+               'plm_decode_norm_fc1_act_bf16')
+  return act
+
+
+def decode_layer_workspace(B, nh, hd, hidden, Tmax, splits, device):
+  """A caller-owned (uint8 workspace, bytes) pair for decode_layer(..., workspace=) at this shape and splits argument."""
+  nbytes = O._ws_bytes('plm_decode_layer_workspace_bytes', B, nh, hd, hidden, Tmax, int(splits))
+  if nbytes == 0:
+    raise ValueError(f'decode_layer: unsupported shape B={B} nh={nh} hd={hd} hidden={hidden} Tmax={Tmax} or splits={splits}')
+  return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def decode_layer(x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, pos, lens, rope_cos, rope_sin, kv, nh, kind, status, splits=0,
+                 workspace=None):
+  """One decode layer from one library call (six launches): decode_norm_qkv_append, attn_decode, decode_gemm_residual with w_out,
+  decode_norm_fc1_act, decode_gemm_residual with w_fc2.  x fp32 [B, d] is updated in place and returned; status is the cache's int32 [1]
+  flag; every intermediate lives in the workspace (the caller's pair of decode_layer_workspace for the same splits, else the stream's
+  arena).  Shapes the kernels do not serve raise ValueError."""
+  name = 'decode_layer'
+  B, d = _decode_operands(name, x, (attn_norm_w, mlp_norm_w), (w_qkv, w_out, w_fc1, w_fc2))
+  k = _decode_mlp_kind(name, kind)
+  hidden = w_fc2.shape[1]
+  if d % nh != 0 or tuple(w_qkv.shape) != (3 * d, d) or tuple(w_out.shape) != (d, d) or w_fc2.shape[0] != d or \
+     tuple(w_fc1.shape) != ((2 if kind == 'glu' else 1) * hidden, d):
+    raise ValueError(f'{name}: the weights {tuple(w_qkv.shape)}, {tuple(w_out.shape)}, {tuple(w_fc1.shape)}, {tuple(w_fc2.shape)} do not fit '
+                     f'x {tuple(x.shape)}, nh={nh}, kind {kind!r}')
+  hd = d // nh
+  try:
+    O._need_kv(kv, nh, hd, 'kv')
+    O._need(pos, torch.int32, 'pos', 1)
+    O._need(lens, torch.int32, 'lens', 1)
+    O._need(rope_cos, O.F32, 'rope_cos', 2)
+    O._need(rope_sin, O.F32, 'rope_sin', 2)
+    O._need(status, torch.int32, 'status')
+  except (RuntimeError, TypeError, ValueError) as e:
+    raise type(e)(f'{name}.{e}') from None
+  if kv.shape[0] != B or pos.shape[0] != B or lens.shape[0] != B or rope_cos.shape != rope_sin.shape or rope_cos.shape[1] != hd // 2:
+    raise ValueError(f'{name}: kv {tuple(kv.shape)}, pos {tuple(pos.shape)}, lens {tuple(lens.shape)} or the RoPE tables {tuple(rope_cos.shape)} do '
+                     f'not fit B={B}, head_dim={hd}')
+  Tmax = kv.shape[1]
+  stream = O._stream()
+  if workspace is not None:
+    ws, nbytes = workspace
+  else:
+    nbytes = O._ws_bytes('plm_decode_layer_workspace_bytes', B, nh, hd, hidden, Tmax, int(splits))
+    if nbytes == 0:
+      raise ValueError(f'{name}: unsupported shape B={B} nh={nh} hd={hd} hidden={hidden} Tmax={Tmax} or splits={splits}')
+    ws = O._workspace(x.device, nbytes, stream)
+  with O._Launch('hbm:decode_fused', 2.0 * (w_qkv.numel() + w_out.numel() + w_fc1.numel() + w_fc2.numel())):
+    _lib.check(_lib.load().plm_decode_layer_bf16(O._p(x), O._p(attn_norm_w), O._p(mlp_norm_w), float(eps), O._p(w_qkv), O._p(w_out), O._p(w_fc1), O._p(w_fc2),
+                                                 O._p(pos), O._p(lens), O._p(rope_cos), O._p(rope_sin), rope_cos.shape[0], O._p(kv), kv.stride(1),
+                                                 O._p(status), B, Tmax, nh, hd, hidden, k, int(splits), O._p(ws), nbytes, stream),
+               'plm_decode_layer_bf16')
+  return x

@@ -543,6 +543,19 @@ class Transformer(nn.Module, G.Generation):
       branch = ops.gemm_nt(act, layer.mlp.fc2.shadow()[0])
     return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps, branch=branch)[1]
 
+  def fused_layers(self, tokens, cache, rope):
+    """``cached_layers`` for one decode token per sequence (tokens int64 [B], B <= ops.FUSED_DECODE_MAX_ROWS) through the skinny-M
+    kernels: the embedding, ONE library call per layer (ops.decode_layer: six launches, every intermediate in
+    the workspace arena), the out norm.  The fp32 residual stream is one buffer updated in place: a layer's MLP output is added by its
+    own fc2 launch, not by the next norm.  Returns the final normed rows [B, dim]."""
+    self.refresh_shadows()
+    x = ops.embed_fwd(tokens, self.embed_tokens.weight)
+    for i, layer in enumerate(self.layers):
+      ops.decode_layer(x, layer.attn_norm.weight, layer.mlp_norm.weight, layer.attn_norm.eps, layer.attn.w_qkv.shadow()[0],
+                       layer.attn.w_out.shadow()[0], layer.mlp.fc1.shadow()[0], layer.mlp.fc2.shadow()[0], cache.pos, cache.lens, rope[0],
+                       rope[1], cache.kv[i], self.cfg.n_heads, layer.mlp.kind, cache.status)
+    return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps)[1]
+
   def head(self, y, logits, shape, targets=None):
     """The head on normed rows y [prod(shape), dim]: the HeadPrediction of that shape (ops.head_predict, no logits buffer; nll of the
     flat ``targets`` when given), or with ``logits`` the bf16 logits [*shape, V]."""

@@ -5,7 +5,12 @@ Both alternate in one process, random weights (the model's own init) and random 
 after --warmup.  Also: the host time to enqueue C (its launches return before the kernels finish: a step that takes no longer than
 its enqueue is launch-bound), the two new kernels alone (append; decode attention per split count), and whether C and R pick the
 same tokens.
-Usage: python tools/gen_bench.py [--runs 20] [--out profiles/generate_bench.txt]"""
+With --fused the two sides are the decode step as it is (U) and the fused one (F, decode_step(fused=True)): both
+alternate in one process at the same shape (and at every --batch / --context given besides), HIP events, median of --runs with [min max];
+per side the device time of a step, the host time to enqueue it, the library calls it makes (counted at _lib.check) and the kernel
+launches they stand for (the per-entry-point counts of include/plainlm_hip.h, plus the one torch launch that moves the cache lengths).
+Usage: python tools/gen_bench.py [--runs 20] [--out profiles/generate_bench.txt]
+       python tools/gen_bench.py --fused [--batch 1 32] [--context 4096] --out profiles/fused_decode_bench.txt"""
 import argparse
 import os
 import statistics
@@ -33,12 +38,84 @@ def med(v):
   return '%.3f [%.3f %.3f]' % (statistics.median(v), min(v), max(v))
 
 
+# kernel launches behind one call of an entry point at the decode shapes (include/plainlm_hip.h)
+LAUNCHES = {'plm_attn_decode': 2, 'plm_head_predict_bf16': 2, 'plm_decode_layer_bf16': 6}
+
+
+def fused_side_by_side(m, a, batch, ctx):
+  """One row of the --fused report: U and F alternating at batch x ctx.  Returns the report lines."""
+  from plainlm_amd import _lib
+  cfg = m.cfg
+  tok = torch.randint(0, cfg.vocab_size, (batch, ctx + 4), device='cuda')
+  lens = torch.full((batch,), ctx, dtype=torch.int32, device='cuda')
+  with torch.no_grad():
+    cache, _ = m.prefill(tok[:, :ctx].contiguous(), max_len=ctx + 4)
+    nxt = tok[:, ctx].contiguous()
+    sides = {'U': lambda: m.decode_step(nxt, cache), 'F': lambda: m.decode_step(nxt, cache, fused=True)}
+    calls, real = {}, _lib.check
+    for k, fn in sides.items():  # the library calls of one step, counted once outside the timed runs
+      seen = []
+      _lib.check = lambda rc, what: seen.append(what) or real(rc, what)
+      try:
+        cache.set_lens(lens)
+        r = fn()
+      finally:
+        _lib.check = real
+      calls[k] = (len(seen), 1 + sum(LAUNCHES.get(w, 1) for w in seen), r)
+    same = (calls['U'][2].tokens == calls['F'][2].tokens).float().mean().item()
+    dlp = (calls['U'][2].logprob - calls['F'][2].logprob).abs().max().item()
+    dev, host = {k: [] for k in sides}, {k: [] for k in sides}
+    for i in range(a.warmup + a.runs):
+      for k, fn in sides.items():
+        cache.set_lens(lens)
+        torch.cuda.synchronize()
+        e = timed(fn)
+        cache.set_lens(lens)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        h = (time.perf_counter() - t0) * 1e3
+        torch.cuda.synchronize()
+        if i >= a.warmup:
+          dev[k].append(e), host[k].append(h)
+  name = {'U': 'decode step as it is (U)', 'F': 'fused decode step (F)   '}
+  out = ['B = %d, context %d' % (batch, ctx)]
+  for k in sides:
+    out.append('  %s  device %s   host enqueue %s   library calls %3d   kernel launches %3d'
+               % (name[k], med(dev[k]), med(host[k]), calls[k][0], calls[k][1]))
+  below = max(dev['F']) < min(dev['U'])
+  out.append('  U / F (medians) %.2f; F\'s [min max] lies %s U\'s; same greedy token %.3f of %d sequences, max |dlogp| %.2e'
+             % (statistics.median(dev['U']) / statistics.median(dev['F']), 'wholly below' if below else 'NOT wholly below', same, batch, dlp))
+  return out
+
+
+def main_fused(a):
+  torch.manual_seed(0)
+  ctxs = [CTX] + [c for c in a.context if c != CTX]
+  cfg = ModelConfig(vocab_size=50280, seq_len=max(ctxs) + 4, dim=768, expand=8 / 3, n_layers=12, n_heads=12, mlp='glu')
+  m = Transformer(cfg).cuda()
+  lines = ['# tools/gen_bench.py --fused: 160M (12 layers, d 768, 12 heads, V 50280); one process, sides alternating; ms per step, HIP events, '
+           'median of %d [min max]; host enqueue = wall time of the call, not waited for' % a.runs]
+  for batch, ctx in [(B, CTX)] + [(b, CTX) for b in a.batch if b != B] + [(B, c) for c in ctxs[1:]]:
+    lines += fused_side_by_side(m, a, batch, ctx)
+  text = '\n'.join(lines) + '\n'
+  print(text, end='')
+  if a.out:
+    with open(a.out, 'w') as f:
+      f.write(text)
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--runs', type=int, default=20)
   ap.add_argument('--warmup', type=int, default=3)
   ap.add_argument('--out', default=None)
+  ap.add_argument('--fused', action='store_true', help='compare the fused decode step with the decode step as it is')
+  ap.add_argument('--batch', type=int, nargs='*', default=[], help='--fused: extra batch sizes at context %d' % CTX)
+  ap.add_argument('--context', type=int, nargs='*', default=[], help='--fused: extra contexts at B = %d' % B)
   a = ap.parse_args()
+  if a.fused:
+    return main_fused(a)
   torch.manual_seed(0)
   cfg = ModelConfig(vocab_size=50280, seq_len=SEQ, dim=768, expand=8 / 3, n_layers=12, n_heads=12, mlp='glu')
   m = Transformer(cfg).cuda()
