@@ -344,6 +344,40 @@ int plm_decode_layer_bf16(float* x, const float* attn_norm_w, const float* mlp_n
                           int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* ---- the fused extend: chunk rows on the skinny-M layer kernels -----
+ * Every argument check of these entry points comes before any HIP call; none falls back to another path.  A chunk is n rows per sequence,
+ * row b*n + r = chunk row r of sequence b, M = B*n rows with 1 <= B*n <= 32; lens0 int32[B], n_new int32[B] or NULL and c_b are those of
+ * the cache extension above.  plm_decode_gemm_residual_bf16 and plm_decode_norm_fc1_act_bf16 serve chunk rows as they are (they never
+ * look at positions).
+ *
+ * plm_extend_norm_qkv_append_bf16 (replaces plm_rmsnorm_fwd + plm_gemm_bf16_nt + plm_kv_append_rope_rows): x fp32 [B*n, d]; the norm, the
+ * GEMM and the rounding points of plm_decode_norm_qkv_append_bf16 (the same core: a full chunk gives the bits that entry point gives for
+ * the same rows at pos = lens0[b] + r), then plm_kv_append_rope_rows's contract on the bf16 values.  Rows r < c_b of a sequence that
+ * fits: q and k rotated at position lens0[b] + r, rotated q to q_out bf16 [B*n, d] row b*n + r, rotated k | v to kv[b, lens0[b] + r,
+ * 0 : 2d].  Rows r >= c_b write no cache row and a q_out row of zeros.  A sequence with lens0[b] < 0 or lens0[b] + c_b > min(Tmax, rope_T)
+ * is refused on the device: none of its cache rows is written, its n q_out rows are zeros and the caller-zeroed status[0] is set to 1; the
+ * other sequences are unaffected.  Every byte of q_out is defined.  One launch.
+ *
+ * plm_extend_layer_bf16: a whole layer over a chunk on `stream` from one call - the qkv stage above, plm_attn_extend's two launches (one
+ * when it resolves to a single split; lens0, n_new, splits as there), the residual stage with w_out [d, d], the fc1 stage, the residual
+ * stage with w_fc2 [d, hidden]: at most six launches.  x fp32 [B*n, d] is updated in place (padding rows too: they hold finite values
+ * that mean nothing).  q, the attention output, the activation and plm_attn_extend's partials live in the workspace:
+ * plm_extend_layer_workspace_bytes(B, n, nh, hd, hidden, Tmax, splits) bytes for the same splits argument, 16-byte aligned, caller-owned;
+ * the query is a function of its arguments alone and returns 0 for arguments the launch refuses.
+ *
+ * PLM_E_INVALID before anything is launched: what the fused decode step refuses, with B*n in place of M; NULL pointers (n_new
+ * excepted), n < 1, B*n outside 1..32; a short workspace gives PLM_E_WORKSPACE. */
+int plm_extend_norm_qkv_append_bf16(const float* x, const float* norm_w, float eps, const uint16_t* w_qkv, const int32_t* lens0,
+                                    const int32_t* n_new, const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out,
+                                    uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd,
+                                    void* stream);
+size_t plm_extend_layer_workspace_bytes(int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t hidden, int64_t Tmax, int splits);
+int plm_extend_layer_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv, const uint16_t* w_out,
+                          const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* lens0, const int32_t* n_new, const float* rope_cos,
+                          const float* rope_sin, int64_t rope_T, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t n,
+                          int64_t Tmax, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* ---- temperature / top-k / top-p sampling of one token per row -----
  * Every argument check comes before any HIP call.
  * logits bf16 [B, ld] (ld >= V; any 2-byte aligned base and any ld: columns >= V are never loaded); u fp32 [B], one uniform per row,

@@ -13,7 +13,8 @@ of all its uniforms (speculative_uniforms) and ``_SpecSession``, the state of on
 speculative decoding reuses that loop with ``_LookupSession``: the draft is ops.lookup_draft over the sequence's own
 token history (check_lookup, lookup_uniforms, lookup_round_uniforms).  The fused decode step is a keyword of
 decode_step, ``fused=True``, which runs every layer as one ops.decode_layer call, and generate_fused is generate over it (check_fused holds
-its refusals).
+its refusals).  The fused extend is the same keyword of extend, one ops.extend_layer call per layer, and
+generate_lookup_fused is generate_lookup over it (check_fused_rows).
 """
 
 import math
@@ -124,6 +125,14 @@ def check_fused(who, B, dim):
   """The refusals of fused=True that need no GPU: the skinny-M kernels take at most ops.FUSED_DECODE_MAX_ROWS rows and dim % 32 == 0."""
   if B > ops.FUSED_DECODE_MAX_ROWS:
     raise ValueError(f'{who}: fused=True serves at most {ops.FUSED_DECODE_MAX_ROWS} sequences, got {B}: leave fused off')
+  if dim % 32 != 0:
+    raise ValueError(f'{who}: fused=True needs cfg.dim % 32 == 0, got {dim}: leave fused off')
+
+
+def check_fused_rows(who, B, n, dim):
+  """check_fused for a chunk of n rows per sequence: the skinny-M kernels take at most ops.FUSED_EXTEND_MAX_ROWS rows, B * n of them."""
+  if B * n > ops.FUSED_EXTEND_MAX_ROWS:
+    raise ValueError(f'{who}: fused=True serves at most {ops.FUSED_EXTEND_MAX_ROWS} chunk rows, got {B} sequences x {n} rows = {B * n}: leave fused off')
   if dim % 32 != 0:
     raise ValueError(f'{who}: fused=True needs cfg.dim % 32 == 0, got {dim}: leave fused off')
 
@@ -503,11 +512,13 @@ class _LookupSession:
   """One generate_lookup call between its rounds: the model and its cache, the length the cache is set to after every round, every
   sequence's token history (prompt and emitted tokens, the newest included) with the tokens the next ops.lookup_draft launch appends to
   it, the round counter and - when the call samples (``sampling`` = check_sampling's triple, else None) - its uniforms ``u``.  The methods
-  are the callables ``speculative_loop`` documents; there is no draft cache, so the loop's carry arguments are not used.  ``lookup``,
+  are the callables ``speculative_loop`` documents; there is no draft cache, so the loop's carry arguments are not used.  ``fused`` adds
+  fused=True to the round's ``extend`` call and changes nothing else.  ``lookup``,
   ``sampler`` and ``verify`` stand in for ops.lookup_draft / ops.sample_logits / ops.spec_verify_lookup in the host tests."""
 
-  def __init__(self, model, cache, prompt, first_tok, k, ngram, max_new_tokens, sampling, u, lookup=None, sampler=None, verify=None):
+  def __init__(self, model, cache, prompt, first_tok, k, ngram, max_new_tokens, sampling, u, lookup=None, sampler=None, verify=None, fused=False):
     self.model, self.cache, self.k, self.ngram = model, cache, k, tuple(ngram)
+    self.extend_kw = dict(fused=True) if fused else {}  # what target_round adds to its extend call (generate_lookup_fused)
     self.sampling, self.sampled, self.u, self.round = sampling, sampling is not None, u, 0
     self.lookup = ops.lookup_draft if lookup is None else lookup
     self.sampler = ops.sample_logits if sampler is None else sampler
@@ -529,7 +540,8 @@ class _LookupSession:
 
   def target_round(self, last, draft_tok, live):
     chunk = torch.cat([last[:, None], draft_tok], dim=1)
-    return self.model.extend(chunk, self.cache, token_lens=live.to(torch.int32) * (self.n_prop + 1), logits=self.sampled, all_rows=True)
+    return self.model.extend(chunk, self.cache, token_lens=live.to(torch.int32) * (self.n_prop + 1), logits=self.sampled, all_rows=True,
+                             **self.extend_kw)
 
   def accept(self, draft_tok, draft_out, out):
     if not self.sampled:
@@ -565,7 +577,8 @@ class Generation:
   """KV-cached generation, mixed into ``Transformer`` (DESIGN.md sections 12 to 16).  What it asks of its host class:
     attributes  cfg (the ModelConfig), n_layers, head_dim, lm_head (its weight tells the model's device)
     methods     _rope(device), trunk(x, attn_mask, cache), cached_layers(tokens, cache, attend), fused_layers(tokens, cache, rope),
-                head(y, logits, shape); the middle three call refresh_shadows() themselves.  _rope keeps its underscore: tools and tests
+                fused_chunk_layers(tokens, cache, rope, lens0, n_new, n), head(y, logits, shape); the middle four call refresh_shadows()
+                themselves.  _rope keeps its underscore: tools and tests
                 from before the mixin call it by that name."""
 
   @torch.compiler.disable
@@ -630,7 +643,7 @@ class Generation:
     return KVCache(self.n_layers, int(B), Tmax, self.cfg.n_heads, self.head_dim, device)
 
   @torch.compiler.disable
-  def extend(self, tokens, cache, token_lens=None, logits=False, all_rows=False):
+  def extend(self, tokens, cache, token_lens=None, logits=False, all_rows=False, fused=False):
     """Append a chunk of tokens to a live cache: tokens int64 [B, n], right-padded; sequence b's first token_lens[b] tokens are appended
     at positions cache.lens[b] .. (then lens += token_lens, on the device).  token_lens: None (all n), host integers in [0, n], or an
     int32 [B] device tensor (clamped to [0, n], never read back).  A new user turn on top of a cached conversation, one chunk of a long
@@ -640,13 +653,17 @@ class Generation:
     predictions, or [B, n, V] logits, of every chunk row (rows at and beyond token_lens[b] belong to padding and mean nothing).
     The Block structure as decode_step runs it, through ops calls on the bf16 shadows at M = B * n: the same launches as one decode step,
     whatever n.  A chunk that does not fit the cache (or the RoPE table) stores nothing for that sequence and surfaces through
-    ``cache.check()``.  Runs under no_grad."""
+    ``cache.check()``.  Runs under no_grad.  fused=True runs every layer as one library call over the skinny-M
+    kernels (``fused_chunk_layers``: the same rounding points, other fp32 summation orders, so close to but not the bits of the default);
+    it serves B * n <= ops.FUSED_EXTEND_MAX_ROWS chunk rows and raises ValueError otherwise, before anything is launched."""
     if isinstance(tokens, torch.Tensor) and (tokens.dim() != 2 or tokens.shape[0] != cache.B or tokens.shape[1] < 1):
       raise ValueError(f'extend: tokens {tuple(tokens.shape)} are not a [B, n] chunk for the cache\'s batch of {cache.B}')
     guard('extend', tokens, self)
     if len(cache.kv) != self.n_layers or cache.n_heads != self.cfg.n_heads or cache.head_dim != self.head_dim:
       raise ValueError('extend: the cache was made for another model shape (layers, heads or head_dim differ)')
     B, n = tokens.shape
+    if fused:
+      check_fused_rows('extend', B, n, self.cfg.dim)
     nh = self.cfg.n_heads
     with torch.no_grad():
       adv, n_new = chunk_lens(token_lens, B, n, tokens.device)
@@ -656,7 +673,8 @@ class Generation:
       def attend(i, qkv):
         q, _ = ops.kv_append_rope_rows(qkv, lens0, rope[0], rope[1], cache.kv[i], nh, n_new=n_new, status=cache.status)
         return ops.attn_extend(q, cache.kv[i], lens0, nh, n_new=n_new)
-      y = self.cached_layers(tokens.reshape(-1).contiguous(), cache, attend)
+      flat = tokens.reshape(-1).contiguous()
+      y = self.fused_chunk_layers(flat, cache, rope, lens0, n_new, n) if fused else self.cached_layers(flat, cache, attend)
       cache.advance_by(adv)
       if all_rows:
         return self.head(y, logits, (B, n))
@@ -752,16 +770,33 @@ class Generation:
     default generator.  Returns what generate_speculative returns: the tokens int64 [B, N]; with return_logprobs also this model's
     log-probabilities at temperature 1, with return_stats also dict(rounds, drafted int64 [B] = the proposals actually made, accepted
     int64 [B]).  After eos_id a sequence holds eos_id with log-probability 0.  One int32 is read from the device per round; there is no
-    second cache and no draft prefill."""
-    guard('generate_lookup', prompt, self, forward_only=True, rank2=True)
+    second cache and no draft prefill.  ``generate_lookup_fused`` is the same call with the rounds' chunks run fused."""
+    return self._generate_lookup('generate_lookup', False, prompt, max_new_tokens, n_draft, ngram, prompt_lens, eos_id, return_logprobs,
+                                 temperature, top_k, top_p, seed, return_stats)
+
+  @torch.compiler.disable
+  def generate_lookup_fused(self, prompt, max_new_tokens, n_draft=8, ngram=(1, 4), prompt_lens=None, eos_id=None, return_logprobs=False,
+                            temperature=None, top_k=None, top_p=None, seed=None, return_stats=False):
+    """``generate_lookup`` with every round's chunk - the first token's included - run as ``extend(..., fused=True)`` (DESIGN.md section
+    18; the prefill is unchanged): the same arguments, refusals and return values, tokens close to but not bit for bit those of
+    ``generate_lookup`` (other fp32 summation orders).  Serves B * (n_draft + 1) <= ops.FUSED_EXTEND_MAX_ROWS chunk rows and raises
+    ValueError beyond, before anything is launched.  A method of its own, as ``generate_fused`` is."""
+    return self._generate_lookup('generate_lookup_fused', True, prompt, max_new_tokens, n_draft, ngram, prompt_lens, eos_id, return_logprobs,
+                                 temperature, top_k, top_p, seed, return_stats)
+
+  def _generate_lookup(self, who, fused, prompt, max_new_tokens, n_draft, ngram, prompt_lens, eos_id, return_logprobs, temperature, top_k, top_p,
+                       seed, return_stats):
+    guard(who, prompt, self, forward_only=True, rank2=True)
     B, T = prompt.shape
     k, N = n_draft, int(max_new_tokens)
     max_len, sampling = check_lookup(T, max_new_tokens, k, ngram, self.cfg, temperature, top_k, top_p, seed)
+    if fused:
+      check_fused_rows(who, B, k + 1, self.cfg.dim)
     cache, r = self.prefill(prompt, prompt_lens, max_len=max_len, logits=sampling is not None)
     u = None if sampling is None else lookup_uniforms(N, k, B, prompt.device, seed)
     first = (r.tokens, r.logprob) if sampling is None else ops.sample_logits(r, u[0], *sampling)[:2]
     with torch.no_grad():
-      s = _LookupSession(self, cache, prompt, first[0], k, ngram, N, sampling, u)
+      s = _LookupSession(self, cache, prompt, first[0], k, ngram, N, sampling, u, fused=fused)
       toks, lps, stats = speculative_loop(first, s.draft_round, s.target_round, s.accept, N, k, eos_id, s.advance, drafted_in_round=s.drafted)
     cache.check()
     s.check()

@@ -1143,3 +1143,5 @@ from .ops_lookup import LookupDraft, lookup_draft, spec_verify_lookup  # noqa: E
 # ---- the fused decode step: its wrappers live in ops_decode.py, on this module's contract ---------------------------
 from .ops_decode import (DECODE_MLP_KINDS, FUSED_DECODE_MAX_ROWS, decode_gemm_residual, decode_layer, decode_layer_workspace,  # noqa: E402,F401
                          decode_norm_fc1_act, decode_norm_qkv_append)
+# ---- the fused extend: chunk rows on the same kernels, same module ------------------------------------------------------
+from .ops_decode import FUSED_EXTEND_MAX_ROWS, extend_layer, extend_layer_workspace, extend_norm_qkv_append  # noqa: E402,F401

@@ -1,5 +1,6 @@
 """The ops wrappers of the fused decode step: ``ops.decode_norm_qkv_append``, ``ops.decode_gemm_residual``,
-``ops.decode_norm_fc1_act`` (the three skinny-M stages) and ``ops.decode_layer`` (a whole decode layer from one library call).
+``ops.decode_norm_fc1_act`` (the three skinny-M stages) and ``ops.decode_layer`` (a whole decode layer from one library call); and of
+the fused extend (section 18): ``ops.extend_norm_qkv_append`` (the qkv stage over chunk rows) and ``ops.extend_layer``.
 
 They are part of ``plainlm_amd.ops`` (which re-exports them) and stand on its contract - the operand validator (``ops._need``), the launch
 bracket (``ops._Launch``), the workspace arena of the current stream, ``_lib.check`` around the one library call - and, like every wrapper
@@ -144,4 +145,92 @@ def decode_layer(x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, po
                                                  O._p(pos), O._p(lens), O._p(rope_cos), O._p(rope_sin), rope_cos.shape[0], O._p(kv), kv.stride(1),
                                                  O._p(status), B, Tmax, nh, hd, hidden, k, int(splits), O._p(ws), nbytes, stream),
                'plm_decode_layer_bf16')
+  return x
+
+
+# ---- the fused extend: chunk rows on the same kernels ------------------------------------------------------------------
+FUSED_EXTEND_MAX_ROWS = 32  # M = B * n of the plm_extend_* entry points: n chunk rows per sequence
+
+
+def _extend_operands(name, M, hd, kv, lens0, n_new, rope_cos, rope_sin, nh):
+  """The operand checks the fused extend ops share beyond _decode_operands: the cache, lens0 int32 [B], n_new int32 [B] or None, the RoPE
+  tables.  Returns (B, n) with M = B * n."""
+  try:
+    O._need_kv(kv, nh, hd, 'kv')
+    O._need(lens0, torch.int32, 'lens0', 1)
+    if n_new is not None:
+      O._need(n_new, torch.int32, 'n_new', 1)
+    O._need(rope_cos, O.F32, 'rope_cos', 2)
+    O._need(rope_sin, O.F32, 'rope_sin', 2)
+  except (RuntimeError, TypeError, ValueError) as e:
+    raise type(e)(f'{name}.{e}') from None
+  B = kv.shape[0]
+  if B < 1 or M % B != 0 or lens0.shape[0] != B or (n_new is not None and n_new.shape[0] != B) or rope_cos.shape != rope_sin.shape or \
+     rope_cos.shape[1] != hd // 2:
+    raise ValueError(f'{name}: kv {tuple(kv.shape)}, lens0 {tuple(lens0.shape)}, n_new {None if n_new is None else tuple(n_new.shape)} or the RoPE '
+                     f'tables {tuple(rope_cos.shape)} / {tuple(rope_sin.shape)} do not fit {M} chunk rows, head_dim={hd}')
+  return B, M // B
+
+
+def extend_norm_qkv_append(x, norm_w, eps, w_qkv, lens0, rope_cos, rope_sin, kv, nh, n_new=None, q_out=None, status=None):
+  """rmsnorm_fwd -> gemm_nt -> kv_append_rope_rows of a chunk in one launch: x fp32 [B*n, d] (B*n <= FUSED_EXTEND_MAX_ROWS; row b*n + r =
+  chunk row r of sequence b, B = kv.shape[0]), w_qkv bf16 [3d, d], lens0 / n_new as kv_append_rope_rows takes them.  Returns (rotated q
+  bf16 [B*n, d], status); rows r < n_new[b] went, rotated at lens0[b] + r, into kv[b, lens0[b] + r]; rows past n_new[b] and the rows of a
+  sequence whose chunk does not fit (status[0] = 1) store nothing and leave zeros in q."""
+  name = 'extend_norm_qkv_append'
+  M, d = _decode_operands(name, x, (norm_w,), (w_qkv,))
+  if d % nh != 0 or tuple(w_qkv.shape) != (3 * d, d):
+    raise ValueError(f'{name}: x {tuple(x.shape)}, w_qkv {tuple(w_qkv.shape)} do not fit nh={nh}')
+  hd = d // nh
+  B, n = _extend_operands(name, M, hd, kv, lens0, n_new, rope_cos, rope_sin, nh)
+  q_out, status = O._append_outputs(name, x, M, d, q_out, status)
+  with O._Launch('hbm:decode_fused', 2.0 * w_qkv.numel()):
+    _lib.check(_lib.load().plm_extend_norm_qkv_append_bf16(O._p(x), O._p(norm_w), float(eps), O._p(w_qkv), O._p(lens0), O._p(n_new), O._p(rope_cos),
+                                                           O._p(rope_sin), rope_cos.shape[0], O._p(q_out), O._p(kv), kv.stride(1), O._p(status), B, n,
+                                                           kv.shape[1], nh, hd, O._stream()), 'plm_extend_norm_qkv_append_bf16')
+  return q_out, status
+
+
+def extend_layer_workspace(B, n, nh, hd, hidden, Tmax, splits, device):
+  """A caller-owned (uint8 workspace, bytes) pair for extend_layer(..., workspace=) at this shape (chunk width n) and splits argument."""
+  nbytes = O._ws_bytes('plm_extend_layer_workspace_bytes', B, n, nh, hd, hidden, Tmax, int(splits))
+  if nbytes == 0:
+    raise ValueError(f'extend_layer: unsupported shape B={B} n={n} nh={nh} hd={hd} hidden={hidden} Tmax={Tmax} or splits={splits}')
+  return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+def extend_layer(x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, lens0, n_new, rope_cos, rope_sin, kv, nh, kind, status, splits=0,
+                 workspace=None):
+  """One layer over a chunk from one library call: extend_norm_qkv_append, attn_extend, decode_gemm_residual with w_out,
+  decode_norm_fc1_act, decode_gemm_residual with w_fc2.  x fp32 [B*n, d] (B = kv.shape[0], B*n <= FUSED_EXTEND_MAX_ROWS) is updated in
+  place and returned; n_new may be None; status is the cache's int32 [1] flag; every intermediate lives in the workspace (the caller's
+  pair of extend_layer_workspace for the same splits, else the stream's arena).  Shapes the kernels do not serve raise ValueError."""
+  name = 'extend_layer'
+  M, d = _decode_operands(name, x, (attn_norm_w, mlp_norm_w), (w_qkv, w_out, w_fc1, w_fc2))
+  k = _decode_mlp_kind(name, kind)
+  hidden = w_fc2.shape[1]
+  if d % nh != 0 or tuple(w_qkv.shape) != (3 * d, d) or tuple(w_out.shape) != (d, d) or w_fc2.shape[0] != d or \
+     tuple(w_fc1.shape) != ((2 if kind == 'glu' else 1) * hidden, d):
+    raise ValueError(f'{name}: the weights {tuple(w_qkv.shape)}, {tuple(w_out.shape)}, {tuple(w_fc1.shape)}, {tuple(w_fc2.shape)} do not fit '
+                     f'x {tuple(x.shape)}, nh={nh}, kind {kind!r}')
+  hd = d // nh
+  B, n = _extend_operands(name, M, hd, kv, lens0, n_new, rope_cos, rope_sin, nh)
+  try:
+    O._need(status, torch.int32, 'status')
+  except (RuntimeError, TypeError, ValueError) as e:
+    raise type(e)(f'{name}.{e}') from None
+  Tmax = kv.shape[1]
+  stream = O._stream()
+  if workspace is not None:
+    ws, nbytes = workspace
+  else:
+    nbytes = O._ws_bytes('plm_extend_layer_workspace_bytes', B, n, nh, hd, hidden, Tmax, int(splits))
+    if nbytes == 0:
+      raise ValueError(f'{name}: unsupported shape B={B} n={n} nh={nh} hd={hd} hidden={hidden} Tmax={Tmax} or splits={splits}')
+    ws = O._workspace(x.device, nbytes, stream)
+  with O._Launch('hbm:decode_fused', 2.0 * (w_qkv.numel() + w_out.numel() + w_fc1.numel() + w_fc2.numel())):
+    _lib.check(_lib.load().plm_extend_layer_bf16(O._p(x), O._p(attn_norm_w), O._p(mlp_norm_w), float(eps), O._p(w_qkv), O._p(w_out), O._p(w_fc1), O._p(w_fc2),
+                                                 O._p(lens0), O._p(n_new), O._p(rope_cos), O._p(rope_sin), rope_cos.shape[0], O._p(kv), kv.stride(1),
+                                                 O._p(status), B, n, Tmax, nh, hd, hidden, k, int(splits), O._p(ws), nbytes, stream),
+               'plm_extend_layer_bf16')
   return x

@@ -556,6 +556,20 @@ class Transformer(nn.Module, G.Generation):
                        rope[1], cache.kv[i], self.cfg.n_heads, layer.mlp.kind, cache.status)
     return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps)[1]
 
+  def fused_chunk_layers(self, tokens, cache, rope, lens0, n_new, n):
+    """``fused_layers`` for a chunk of n tokens per sequence (tokens int64 [B * n], B * n <= ops.FUSED_EXTEND_MAX_ROWS; DESIGN.md section
+    18): the embedding, ONE library call per layer (ops.extend_layer: row b * n + r is appended at lens0[b] + r, n_new int32 [B] or None
+    as ops.kv_append_rope_rows takes it), the out norm.  Returns the final normed rows [B * n, dim]."""
+    if tokens.shape[0] != cache.B * n:
+      raise ValueError(f'fused_chunk_layers: {tokens.shape[0]} tokens are not {cache.B} chunks of {n}')
+    self.refresh_shadows()
+    x = ops.embed_fwd(tokens, self.embed_tokens.weight)
+    for i, layer in enumerate(self.layers):
+      ops.extend_layer(x, layer.attn_norm.weight, layer.mlp_norm.weight, layer.attn_norm.eps, layer.attn.w_qkv.shadow()[0],
+                       layer.attn.w_out.shadow()[0], layer.mlp.fc1.shadow()[0], layer.mlp.fc2.shadow()[0], lens0, n_new, rope[0], rope[1],
+                       cache.kv[i], self.cfg.n_heads, layer.mlp.kind, cache.status)
+    return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps)[1]
+
   def head(self, y, logits, shape, targets=None):
     """The head on normed rows y [prod(shape), dim]: the HeadPrediction of that shape (ops.head_predict, no logits buffer; nll of the
     flat ``targets`` when given), or with ``logits`` the bf16 logits [*shape, V]."""

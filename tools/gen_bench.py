@@ -9,8 +9,13 @@ With --fused the two sides are the decode step as it is (
 alternate in one process at the same shape (and at every --batch / --context given besides), HIP events, median of --runs with [min max];
 per side the device time of a step, the host time to enqueue it, the library calls it makes (counted at _lib.check) and the kernel
 launches they stand for (the per-entry-point counts of include/plainlm_hip.h, plus the one torch launch that moves the cache lengths).
+With --fused-extend the sides are ``extend`` as it is and ``extend(fused=True)`` at (B, n) = (8, 4), (4, 8) and
+(1, 32) on 1024 cached tokens, then one generate_lookup round against one generate_lookup_fused round at B = 4, n_draft = 7 (the round
+of tools/lookup_bench.py: draft launch, the extend of n_draft + 1 rows, acceptance, commit_round and the cache move, on a periodic prompt
+so that every round carries n_draft proposals), with the fused decode step at B = 8 beside them for scale: the same columns.
 Usage: python tools/gen_bench.py [--runs 20] [--out profiles/generate_bench.txt]
-       python tools/gen_bench.py --fused [--batch 1 32] [--context 4096] --out profiles/fused_decode_bench.txt"""
+       python tools/gen_bench.py --fused [--batch 1 32] [--context 4096] --out profiles/fused_decode_bench.txt
+       python tools/gen_bench.py --fused-extend --out profiles/fused_extend_bench.txt"""
 import argparse
 import os
 import statistics
@@ -21,6 +26,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from plainlm_amd import ModelConfig, Transformer, ops  # noqa: E402
+from plainlm_amd import generate as G  # noqa: E402
 
 B, CTX, SEQ = 8, 1024, 1028  # the timed step appends token number CTX + 1; the recompute route sees CTX + 4 rows (rows are 4 at a time)
 
@@ -42,9 +48,147 @@ def med(v):
 LAUNCHES = {'plm_attn_decode': 2, 'plm_head_predict_bf16': 2, 'plm_decode_layer_bf16': 6}
 
 
+def alternate(sides, reset, a):
+  """sides: {key: callable}, run alternately after reset() (outside the timed region).  Returns ({key: device ms}, {key: host enqueue
+  ms}, {key: the library calls of one run, counted at _lib.check outside the timed runs}, {key: what that run returned})."""
+  from plainlm_amd import _lib
+  calls, ret, real = {}, {}, _lib.check
+  for k, fn in sides.items():
+    seen = []
+    _lib.check = lambda rc, what: seen.append(what) or real(rc, what)
+    try:
+      reset()
+      ret[k] = fn()
+    finally:
+      _lib.check = real
+    calls[k] = seen
+  dev, host = {k: [] for k in sides}, {k: [] for k in sides}
+  for i in range(a.warmup + a.runs):
+    for k, fn in sides.items():
+      reset()
+      torch.cuda.synchronize()
+      e = timed(fn)
+      reset()
+      torch.cuda.synchronize()
+      t0 = time.perf_counter()
+      fn()
+      h = (time.perf_counter() - t0) * 1e3
+      torch.cuda.synchronize()
+      if i >= a.warmup:
+        dev[k].append(e), host[k].append(h)
+  return dev, host, calls, ret
+
+
+def extend_launches(seen, nh, hd, n, B, Tmax):
+  """Kernel launches behind the library calls of one extend (include/plainlm_hip.h): plm_attn_extend is two launches, one when it
+  resolves to a single split (read off its workspace query: fp32 partials of 2 + hd per (row, head, split)); plm_extend_layer_bf16 is
+  four more; the head is two."""
+  from plainlm_amd import _lib
+  one = (B * n * nh * (2 + hd) * 4 + 15) // 16 * 16
+  ext = 1 if _lib.load().plm_attn_extend_workspace_bytes(B, n, nh, hd, Tmax, 0) == one else 2
+  per = {'plm_attn_extend': ext, 'plm_extend_layer_bf16': 4 + ext, 'plm_head_predict_bf16': 2, 'plm_decode_layer_bf16': 6}
+  return sum(per.get(w, 1) for w in seen)
+
+
+def report(name, k, dev, host, calls, launches):
+  return '  %-34s device %s   host enqueue %s   library calls %3d   kernel launches %s' % (name, med(dev[k]), med(host[k]), len(calls[k]), launches)
+
+
+def verdict(dev, u, f):
+  below = max(dev[f]) < min(dev[u])
+  return 'U / F (medians) %.2f; F\'s [min max] lies %s U\'s' % (statistics.median(dev[u]) / statistics.median(dev[f]),
+                                                                  'wholly below' if below else 'NOT wholly below')
+
+
+class LookupRound:
+  """One round of a _LookupSession run again and again from the same state (tools/lookup_bench.py's Round): reset() winds the cache, the
+  lengths and the history back."""
+
+  def __init__(self, session, cache, first, lens0, new):
+    B = first.shape[0]
+    self.s, self.cache, self.first, self.lens0 = session, cache, first, lens0
+    self.live = torch.ones((B,), dtype=torch.bool, device='cuda')
+    self.carry = torch.zeros((B,), dtype=torch.bool, device='cuda')
+    self.out_tok = torch.zeros((B, new), dtype=torch.int64, device='cuda')
+    self.out_lp = torch.zeros((B, new), dtype=torch.float32, device='cuda')
+    self.count = torch.ones((B,), dtype=torch.int32, device='cuda')
+    self.done = torch.zeros((B,), dtype=torch.bool, device='cuda')
+
+  def reset(self):
+    s = self.s
+    self.cache.set_lens(self.lens0)
+    s.tlen.copy_(self.lens0)
+    s.hlen.copy_(self.lens0)
+    s.round = 0
+    s.add, s.n_add = self.first[:, None].contiguous(), None
+
+  def __call__(self):
+    s = self.s
+    d, dout = s.draft_round(self.first, self.first, self.carry, self.live)
+    res = s.accept(d, dout, s.target_round(self.first, d, self.live))
+    _, _, moved = G.commit_round(self.out_tok, self.out_lp, self.count, self.done, d, *res)
+    s.advance(moved, self.live)
+    return s.n_prop.clone(), res[1]
+
+
+def main_fused_extend(a):
+  torch.manual_seed(0)
+  room = 64  # cache rows beyond the context: a chunk of 32 rows, a lookup round of 8
+  cfg = ModelConfig(vocab_size=50280, seq_len=CTX + room, dim=768, expand=8 / 3, n_layers=12, n_heads=12, mlp='glu')
+  m = Transformer(cfg).cuda()
+  nh = cfg.n_heads
+  lines = ['# tools/gen_bench.py --fused-extend: 160M (12 layers, d 768, 12 heads, V 50280), %d cached tokens, cache of %d rows; one process, '
+           'sides alternating; ms per call, HIP events, median of %d [min max]; host enqueue = wall time of the call, not waited for; kernel '
+           'launches counted from the documented launch counts of the entry points, the one torch launch that moves the lengths included'
+           % (CTX, CTX + room, a.runs)]
+  with torch.no_grad():
+    for Bx, n in ((8, 4), (4, 8), (1, 32)):
+      tok = torch.randint(0, cfg.vocab_size, (Bx, CTX + n), device='cuda')
+      lens = torch.full((Bx,), CTX, dtype=torch.int32, device='cuda')
+      cache, _ = m.prefill(tok[:, :CTX].contiguous())
+      chunk = tok[:, CTX:].contiguous()
+      sides = {'U': lambda: m.extend(chunk, cache), 'F': lambda: m.extend(chunk, cache, fused=True)}
+      dev, host, calls, ret = alternate(sides, lambda: cache.set_lens(lens), a)
+      same = (ret['U'].tokens == ret['F'].tokens).float().mean().item()
+      dlp = (ret['U'].logprob - ret['F'].logprob).abs().max().item()
+      lines.append('extend, B = %d, n = %d (%d chunk rows)' % (Bx, n, Bx * n))
+      for k, name in (('U', 'extend as it is (U)'), ('F', 'extend(fused=True) (F)')):
+        lines.append(report(name, k, dev, host, calls, '%3d' % (1 + extend_launches(calls[k], nh, m.head_dim, n, Bx, cache.Tmax))))
+      lines.append('  %s; same greedy token %.3f of %d sequences, max |dlogp| %.2e' % (verdict(dev, 'U', 'F'), same, Bx, dlp))
+      del cache
+    # a lookup round, B = 4, n_draft = 7, on a periodic prompt: every round carries n_draft proposals
+    Bx, k, new = 4, 7, 64
+    block = torch.randint(0, cfg.vocab_size, (Bx, 37), device='cuda')
+    prompt = block.repeat(1, CTX // 37 + 1)[:, :CTX].contiguous()
+    lens0 = torch.full((Bx,), CTX, dtype=torch.int32, device='cuda')
+    first = prompt[:, CTX - 37].contiguous()  # the token the block continues with: the lookup matches the whole suffix
+    cache, _ = m.prefill(prompt)
+    rounds = {key: LookupRound(G._LookupSession(m, cache, prompt, first, k, (1, 4), new, None, None, fused=fused), cache, first, lens0, new)
+              for key, fused in (('U', False), ('F', True))}
+    dev, host, calls, ret = alternate(rounds, lambda: [r.reset() for r in rounds.values()], a)
+    lines.append('lookup round, greedy, B = %d, n_draft = %d (%d chunk rows)' % (Bx, k, Bx * (k + 1)))
+    for key, name in (('U', 'generate_lookup round (U)'), ('F', 'generate_lookup_fused round (F)')):
+      lines.append(report(name, key, dev, host, calls, '%3d + torch\'s own' % extend_launches(calls[key], nh, m.head_dim, k + 1, Bx, cache.Tmax)))
+    lines.append('  %s; proposals per sequence in the timed round U %s, F %s; same next token %.3f of %d sequences'
+                 % (verdict(dev, 'U', 'F'), ret['U'][0].tolist(), ret['F'][0].tolist(), (ret['U'][1] == ret['F'][1]).float().mean().item(), Bx))
+    del cache, rounds
+    # for scale: the fused decode step at B = 8 (tools/gen_bench.py --fused), in this process
+    tok = torch.randint(0, cfg.vocab_size, (B, CTX + 4), device='cuda')
+    lens = torch.full((B,), CTX, dtype=torch.int32, device='cuda')
+    cache, _ = m.prefill(tok[:, :CTX].contiguous())
+    nxt = tok[:, CTX].contiguous()
+    dev, host, calls, _ = alternate({'D': lambda: m.decode_step(nxt, cache, fused=True)}, lambda: cache.set_lens(lens), a)
+    lines.append('for scale: fused decode step, B = %d' % B)
+    lines.append(report('decode_step(fused=True)', 'D', dev, host, calls, '%3d' % (1 + sum(LAUNCHES.get(w, 1) for w in calls['D']))))
+  text = '\n'.join(lines) + '\n'
+  print(text, end='')
+  if a.out:
+    with open(a.out, 'w') as f:
+      f.write(text)
+
+
 def fused_side_by_side(m, a, batch, ctx):
   """One row of the --fused report: U and F alternating at batch x ctx.  Returns the report lines."""
-  from plainlm_amd import _lib
   cfg = m.cfg
   tok = torch.randint(0, cfg.vocab_size, (batch, ctx + 4), device='cuda')
   lens = torch.full((batch,), ctx, dtype=torch.int32, device='cuda')
@@ -52,32 +196,10 @@ def fused_side_by_side(m, a, batch, ctx):
     cache, _ = m.prefill(tok[:, :ctx].contiguous(), max_len=ctx + 4)
     nxt = tok[:, ctx].contiguous()
     sides = {'U': lambda: m.decode_step(nxt, cache), 'F': lambda: m.decode_step(nxt, cache, fused=True)}
-    calls, real = {}, _lib.check
-    for k, fn in sides.items():  # the library calls of one step, counted once outside the timed runs
-      seen = []
-      _lib.check = lambda rc, what: seen.append(what) or real(rc, what)
-      try:
-        cache.set_lens(lens)
-        r = fn()
-      finally:
-        _lib.check = real
-      calls[k] = (len(seen), 1 + sum(LAUNCHES.get(w, 1) for w in seen), r)
-    same = (calls['U'][2].tokens == calls['F'][2].tokens).float().mean().item()
-    dlp = (calls['U'][2].logprob - calls['F'][2].logprob).abs().max().item()
-    dev, host = {k: [] for k in sides}, {k: [] for k in sides}
-    for i in range(a.warmup + a.runs):
-      for k, fn in sides.items():
-        cache.set_lens(lens)
-        torch.cuda.synchronize()
-        e = timed(fn)
-        cache.set_lens(lens)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        h = (time.perf_counter() - t0) * 1e3
-        torch.cuda.synchronize()
-        if i >= a.warmup:
-          dev[k].append(e), host[k].append(h)
+    dev, host, seen, ret = alternate(sides, lambda: cache.set_lens(lens), a)
+  calls = {k: (len(seen[k]), 1 + sum(LAUNCHES.get(w, 1) for w in seen[k])) for k in sides}
+  same = (ret['U'].tokens == ret['F'].tokens).float().mean().item()
+  dlp = (ret['U'].logprob - ret['F'].logprob).abs().max().item()
   name = {'U': 'decode step as it is (U)', 'F': 'fused decode step (F)   '}
   out = ['B = %d, context %d' % (batch, ctx)]
   for k in sides:
@@ -113,9 +235,12 @@ def main():
   ap.add_argument('--fused', action='store_true', help='compare the fused decode step with the decode step as it is')
   ap.add_argument('--batch', type=int, nargs='*', default=[], help='--fused: extra batch sizes at context %d' % CTX)
   ap.add_argument('--context', type=int, nargs='*', default=[], help='--fused: extra contexts at B = %d' % B)
+  ap.add_argument('--fused-extend', action='store_true', help='compare extend(fused=True) and a generate_lookup_fused round with the unfused ones')
   a = ap.parse_args()
   if a.fused:
     return main_fused(a)
+  if a.fused_extend:
+    return main_fused_extend(a)
   torch.manual_seed(0)
   cfg = ModelConfig(vocab_size=50280, seq_len=SEQ, dim=768, expand=8 / 3, n_layers=12, n_heads=12, mlp='glu')
   m = Transformer(cfg).cuda()
