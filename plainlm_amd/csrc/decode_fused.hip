@@ -1,19 +1,20 @@
-// The fused decode step for gfx950: a decode layer as six plain launches - three skinny-M stages around
-// plm_attn_decode's two - issued by ONE library call, plm_decode_layer_bf16.  No grid-wide barrier, no flag, no cooperative launch.
+// The fused layer for gfx950 (DESIGN.md sections 17 and 18): a layer over at most 32 token rows as six plain launches - three skinny-M
+// stages around the attention stage's two - issued by ONE library call.  No grid-wide barrier, no flag, no cooperative launch.
 //
-// The stages share one GEMM core, out[M, N] = A[M, K] W[N, K]^T with 1 <= M <= 32 rows (one decode token per sequence) against the bf16
-// weight shadows, and differ in prologue and epilogue:
-//   S1  plm_decode_norm_qkv_append_bf16   RMSNorm prologue | w_qkv | RoPE at pos[b], q to q_out, k | v into the cache row (b, pos[b])
+// The stages share one GEMM core, out[M, N] = A[M, K] W[N, K]^T with 1 <= M <= 32 rows against the bf16 weight shadows, and differ in
+// prologue and epilogue.  The rows are B sequences of n chunk rows each, M = B*n, row b*n + r being chunk row r of sequence b:
+//   S1r plm_extend_norm_qkv_append_bf16   RMSNorm prologue | w_qkv | RoPE at lens0[b] + r, q to q_out, k | v into the cache row
+//                                         (b, lens0[b] + r), under plm_kv_append_rope_rows's contract (ragged chunks by n_new,
+//                                         per-sequence refusal, zero q rows)
 //   S2  plm_decode_gemm_residual_bf16     bf16 A           | W     | x += float(bf16(.)) on the fp32 residual stream
 //   S3  plm_decode_norm_fc1_act_bf16      RMSNorm prologue | w_fc1 | SwiGLU / SiLU / ReLU^2 on the bf16 values
 // Every rounding point of the unfused step is kept (bf16 norm output, bf16 GEMM output, RoPE and activation on bf16 values, a bf16 branch
-// added to the fp32 stream); only the order of the fp32 sums differs.
+// added to the fp32 stream); only the order of the fp32 sums differs.  S2 and S3 never look at positions.
 //
-// The fused extend runs a chunk of n rows per sequence, M = B*n <= 32, on the same kernels.  S2 and S3 never look
-// at positions and serve chunk rows as they are; S1 gets a second epilogue that differs from the first only in where a row goes:
-//   S1r plm_extend_norm_qkv_append_bf16   as S1, with row b*n + r rotated at lens0[b] + r and its k | v in the cache row (b, lens0[b] + r),
-//                                         under plm_kv_append_rope_rows's contract (ragged chunks, per-sequence refusal, zero q rows)
-// and plm_extend_layer_bf16 is the layer call with S1r and plm_attn_extend where the decode layer has S1 and plm_attn_decode.
+// A decode step is the chunk of one row per sequence, as plm_kv_append_rope is plm_kv_append_rope_rows at n = 1 (attn_cache.hip):
+//   S1  plm_decode_norm_qkv_append_bf16   = S1r with n = 1, lens0 = pos, n_new = null: row b rotated at pos[b], its k | v in (b, pos[b])
+// the same kernel, the same checks, bit for bit.  So the two layer calls, plm_decode_layer_bf16 and plm_extend_layer_bf16, are one driver
+// and differ in their attention stage alone: plm_attn_decode and plm_attn_extend are two kernels, as attn_cache.hip says.
 //
 // The core.  Each launch streams 1 - 6 MB of weights once against at most 32 rows: a bandwidth and latency problem.  A workgroup of four
 // waves owns 16 weight rows (output columns): N / 16 workgroups cover the chip's 256 CUs at the sizes that matter (48 - 256 of them at
@@ -34,7 +35,7 @@
 #define DF_TILE_ELEMS 16640 // 16 x (1024 + 8) = 32 x (512 + 8)
 
 enum { DF_PRO_BF16 = 0, DF_PRO_NORM = 1 };
-enum { DF_EPI_QKV = 0, DF_EPI_RESIDUAL = 1, DF_EPI_GLU = 2, DF_EPI_SILU = 3, DF_EPI_RELU_SQ = 4, DF_EPI_QKV_ROWS = 5 };
+enum { DF_EPI_RESIDUAL = 1, DF_EPI_GLU = 2, DF_EPI_SILU = 3, DF_EPI_RELU_SQ = 4, DF_EPI_QKV_ROWS = 5 };
 
 struct DfArgs {
   // prologue
@@ -47,15 +48,14 @@ struct DfArgs {
   int M, N, K;
   // epilogues
   float* xio;            // RESIDUAL: x [M, N], in place
-  uint16_t* out;         // QKV: q_out [M, d]; activations: act [M, h]
-  uint16_t* kv;          // QKV
+  uint16_t* out;         // QKV_ROWS: q_out [M, d]; activations: act [M, h]
+  uint16_t* kv;          // QKV_ROWS
   int64_t ld_kv;
-  const int32_t* pos;
   const float* rcos;
   const float* rsin;
   int32_t* status;
   int rope_T, Tmax, hd, dm, h;
-  // QKV_ROWS: row b * n + r is chunk row r of sequence b
+  // QKV_ROWS: row b * n + r is chunk row r of sequence b (a decode step: n = 1, lens0 = the positions)
   int n;
   const int32_t* lens0;  // [M / n]: the cache lengths before the chunk
   const int32_t* n_new;  // [M / n] real rows per chunk, or null: n everywhere
@@ -175,23 +175,6 @@ __global__ __launch_bounds__(DF_THREADS) void decode_fused_kernel(const DfArgs p
     r.x += bf2f(f2bf(v0));
     r.y += bf2f(f2bf(v1));
     *reinterpret_cast<float2*>(xo) = r;
-  } else if (EPI == DF_EPI_QKV) {
-    const int col = blockIdx.x * DF_TILE_N + c2;  // of the 3 * dm qkv columns
-    const int dm = p.dm;
-    const int t = p.pos[m];
-    const int lim = p.Tmax < p.rope_T ? p.Tmax : p.rope_T;
-    if (t < 0 || t >= lim) {  // nothing of this sequence is stored; its q row is zeros
-      if (col == 0) p.status[0] = 1;
-      if (col < dm) df_st2(p.out + (int64_t)m * dm + col, f2bf(0.f), f2bf(0.f));
-      return;
-    }
-    bf16_t b0 = f2bf(v0), b1 = f2bf(v1);
-    if (col < 2 * dm) {
-      const int64_t ti = (int64_t)t * (p.hd / 2) + (col % p.hd) / 2;
-      df_rope2(b0, b1, p.rcos[ti], p.rsin[ti]);
-    }
-    if (col < dm) df_st2(p.out + (int64_t)m * dm + col, b0, b1);
-    else df_st2(p.kv + ((int64_t)m * p.Tmax + t) * p.ld_kv + (col - dm), b0, b1);
   } else if (EPI == DF_EPI_QKV_ROWS) {  // plm_kv_append_rope_rows's contract: row m is chunk row r of sequence b, at position lens0[b] + r
     const int col = blockIdx.x * DF_TILE_N + c2;
     const int dm = p.dm, n = p.n;
@@ -257,11 +240,13 @@ static int df_check_rows(const char* fn, int64_t M) {
   return PLM_OK;
 }
 
-static int df_check_qkv(const char* fn, const float* x, const float* nw, const uint16_t* w_qkv, const int32_t* pos, const float* rope_cos,
+// the qkv stage: B sequences of n rows, M = B*n (a decode step: n = 1, lens0 = the positions)
+static int df_check_qkv(const char* fn, const float* x, const float* nw, const uint16_t* w_qkv, const int32_t* lens0, const float* rope_cos,
                         const float* rope_sin, int64_t rope_T, const uint16_t* q_out, const uint16_t* kv, int64_t ld_kv, const int32_t* status,
-                        int64_t B, int64_t Tmax, int64_t nh, int64_t hd) {
-  PLM_REQUIRE(x && nw && w_qkv && pos && rope_cos && rope_sin && q_out && kv && status, "%s: null pointer", fn);
-  if (const int e = df_check_rows(fn, B)) return e;
+                        int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd) {
+  PLM_REQUIRE(x && nw && w_qkv && lens0 && rope_cos && rope_sin && q_out && kv && status, "%s: null pointer", fn);
+  PLM_REQUIRE(n >= 1 && n <= DF_MAX_ROWS && B >= 1 && B <= DF_MAX_ROWS && B * n <= DF_MAX_ROWS,
+              "%s: B=%ld chunks of n=%ld rows unsupported (n >= 1, 1 <= B*n <= %d rows)", fn, (long)B, (long)n, DF_MAX_ROWS);
   PLM_REQUIRE(hd == 32 || hd == 64 || hd == 128, "%s: head_dim %ld unsupported (32, 64, 128)", fn, (long)hd);
   PLM_REQUIRE(nh > 0 && nh * hd <= DF_MAX_DIM / 4 && Tmax > 0 && Tmax < (1 << 24) && rope_T > 0 && rope_T < (1 << 24),
               "%s: bad shape Tmax=%ld nh=%ld rope_T=%ld", fn, (long)Tmax, (long)nh, (long)rope_T);
@@ -269,16 +254,6 @@ static int df_check_qkv(const char* fn, const float* x, const float* nw, const u
   PLM_REQUIRE(ld_kv >= 2 * nh * hd && ld_kv % 8 == 0, "%s: the cache's row stride must be a multiple of 8 and at least 2*nh*hd", fn);
   PLM_REQUIRE(df_aligned(x, nw, w_qkv, q_out, kv), "%s: x, the norm weight, w_qkv, q_out and kv must be 16-byte aligned", fn);
   return PLM_OK;
-}
-
-// the chunk-rows qkv stage: B sequences of n rows, M = B*n; lens0 stands where df_check_qkv takes pos
-static int df_check_qkv_rows(const char* fn, const float* x, const float* nw, const uint16_t* w_qkv, const int32_t* lens0, const float* rope_cos,
-                             const float* rope_sin, int64_t rope_T, const uint16_t* q_out, const uint16_t* kv, int64_t ld_kv,
-                             const int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd) {
-  PLM_REQUIRE(lens0, "%s: null pointer", fn);
-  PLM_REQUIRE(n >= 1 && n <= DF_MAX_ROWS && B >= 1 && B <= DF_MAX_ROWS && B * n <= DF_MAX_ROWS,
-              "%s: B=%ld chunks of n=%ld rows unsupported (n >= 1, 1 <= B*n <= %d rows)", fn, (long)B, (long)n, DF_MAX_ROWS);
-  return df_check_qkv(fn, x, nw, w_qkv, lens0, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B * n, Tmax, nh, hd);
 }
 
 static int df_check_residual(const char* fn, const float* x, const uint16_t* a, const uint16_t* w, int64_t M, int64_t N, int64_t K) {
@@ -308,32 +283,16 @@ static void df_launch(const DfArgs& a, int64_t blocks, hipStream_t s) {
   else hipLaunchKernelGGL((decode_fused_kernel<PRO, EPI, false>), dim3((unsigned)blocks), dim3(DF_THREADS), 0, s, a);
 }
 
-// what the two qkv stages share of their arguments; M rows
-static DfArgs df_qkv_args(const float* x, const float* nw, float eps, const uint16_t* w_qkv, const float* rope_cos, const float* rope_sin,
-                          int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t M, int64_t Tmax, int64_t nh,
-                          int64_t hd) {
+static void df_launch_qkv(const float* x, const float* nw, float eps, const uint16_t* w_qkv, const int32_t* lens0, const int32_t* n_new,
+                          const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv,
+                          int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, hipStream_t s) {
   DfArgs a = {};
   const int64_t d = nh * hd;
-  a.x = x, a.nw = nw, a.eps = eps, a.w = w_qkv, a.M = (int)M, a.N = (int)(3 * d), a.K = (int)d;
+  a.x = x, a.nw = nw, a.eps = eps, a.w = w_qkv, a.M = (int)(B * n), a.N = (int)(3 * d), a.K = (int)d;
   a.out = q_out, a.kv = kv, a.ld_kv = ld_kv, a.rcos = rope_cos, a.rsin = rope_sin, a.status = status;
   a.rope_T = (int)rope_T, a.Tmax = (int)Tmax, a.hd = (int)hd, a.dm = (int)d;
-  return a;
-}
-
-static void df_launch_qkv(const float* x, const float* nw, float eps, const uint16_t* w_qkv, const int32_t* pos, const float* rope_cos,
-                          const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B,
-                          int64_t Tmax, int64_t nh, int64_t hd, hipStream_t s) {
-  DfArgs a = df_qkv_args(x, nw, eps, w_qkv, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, Tmax, nh, hd);
-  a.pos = pos;
-  df_launch<DF_PRO_NORM, DF_EPI_QKV>(a, 3 * nh * hd / DF_TILE_N, s);
-}
-
-static void df_launch_qkv_rows(const float* x, const float* nw, float eps, const uint16_t* w_qkv, const int32_t* lens0, const int32_t* n_new,
-                               const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv,
-                               int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, hipStream_t s) {
-  DfArgs a = df_qkv_args(x, nw, eps, w_qkv, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B * n, Tmax, nh, hd);
   a.n = (int)n, a.lens0 = lens0, a.n_new = n_new;
-  df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS>(a, 3 * nh * hd / DF_TILE_N, s);
+  df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS>(a, 3 * d / DF_TILE_N, s);
 }
 
 static void df_launch_residual(float* x, const uint16_t* A, const uint16_t* w, int64_t M, int64_t N, int64_t K, hipStream_t s) {
@@ -356,8 +315,9 @@ extern "C" int plm_decode_norm_qkv_append_bf16(const float* x, const float* norm
                                                const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv,
                                                int64_t ld_kv, int32_t* status, int64_t B, int64_t Tmax, int64_t nh, int64_t hd, void* stream) {
   const char* fn = "plm_decode_norm_qkv_append_bf16";
-  if (const int e = df_check_qkv(fn, x, norm_w, w_qkv, pos, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, Tmax, nh, hd)) return e;
-  df_launch_qkv(x, norm_w, eps, w_qkv, pos, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, Tmax, nh, hd, (hipStream_t)stream);
+  // one row per sequence at pos[b]: plm_kv_append_rope's way of calling the rows kernel
+  if (const int e = df_check_qkv(fn, x, norm_w, w_qkv, pos, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, 1, Tmax, nh, hd)) return e;
+  df_launch_qkv(x, norm_w, eps, w_qkv, pos, nullptr, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, 1, Tmax, nh, hd, (hipStream_t)stream);
   PLM_CHECK_LAUNCH(fn);
   return PLM_OK;
 }
@@ -379,92 +339,86 @@ extern "C" int plm_decode_norm_fc1_act_bf16(const float* x, const float* norm_w,
   return PLM_OK;
 }
 
-
 extern "C" int plm_extend_norm_qkv_append_bf16(const float* x, const float* norm_w, float eps, const uint16_t* w_qkv, const int32_t* lens0,
                                                const int32_t* n_new, const float* rope_cos, const float* rope_sin, int64_t rope_T,
                                                uint16_t* q_out, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t n, int64_t Tmax,
                                                int64_t nh, int64_t hd, void* stream) {
   const char* fn = "plm_extend_norm_qkv_append_bf16";
-  if (const int e = df_check_qkv_rows(fn, x, norm_w, w_qkv, lens0, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, n, Tmax, nh, hd))
-    return e;
-  df_launch_qkv_rows(x, norm_w, eps, w_qkv, lens0, n_new, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, n, Tmax, nh, hd,
-                     (hipStream_t)stream);
+  if (const int e = df_check_qkv(fn, x, norm_w, w_qkv, lens0, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, n, Tmax, nh, hd)) return e;
+  df_launch_qkv(x, norm_w, eps, w_qkv, lens0, n_new, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, n, Tmax, nh, hd, (hipStream_t)stream);
   PLM_CHECK_LAUNCH(fn);
   return PLM_OK;
 }
 
-// Workspace of a layer at M rows: q bf16 [M, d] | attention output bf16 [M, d] | activation bf16 [M, hidden] | the attention stage's
-// partials, every part a multiple of 16 bytes.  A function of the shapes and the splits argument alone.  n == 0 is the decode layer (M = B
-// rows, plm_attn_decode), n >= 1 the extend layer (M = B*n rows, plm_attn_extend).
+// The attention stage of a layer: what tells the two layer entry points apart.  The decode layer is n = 1 rows per sequence with
+// DF_ATTN_DECODE (its per-sequence operands: pos, lens); the extend layer any n with DF_ATTN_EXTEND (lens0, n_new - which may be null).
+enum DfAttn { DF_ATTN_DECODE, DF_ATTN_EXTEND };
+
+// Workspace of a layer at M = B*n rows: q bf16 [M, d] | attention output bf16 [M, d] | activation bf16 [M, hidden] | the attention stage's
+// partials, every part a multiple of 16 bytes.  A function of the shapes and the splits argument alone.
 static size_t df_round16(size_t n) { return (n + 15) / 16 * 16; }
 
-static size_t df_layer_workspace_bytes(int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t hidden, int64_t Tmax, int splits) {
-  if (B < 1 || B > DF_MAX_ROWS || n < 0 || n > DF_MAX_ROWS || B * n > DF_MAX_ROWS || nh < 1 || nh * hd > DF_MAX_DIM / 4 || (nh * hd) % 32 != 0 ||
+static size_t df_layer_workspace_bytes(DfAttn attn, int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t hidden, int64_t Tmax, int splits) {
+  if (B < 1 || B > DF_MAX_ROWS || n < 1 || n > DF_MAX_ROWS || B * n > DF_MAX_ROWS || nh < 1 || nh * hd > DF_MAX_DIM / 4 || (nh * hd) % 32 != 0 ||
       hidden < 1 || hidden > DF_MAX_DIM / 2 || hidden % 32 != 0)
     return 0;
   // 0 for a head_dim, Tmax or splits the attention stage refuses
-  const size_t att = n == 0 ? plm_attn_decode_workspace_bytes(B, nh, hd, Tmax, splits) : plm_attn_extend_workspace_bytes(B, n, nh, hd, Tmax, splits);
+  const size_t att = attn == DF_ATTN_DECODE ? plm_attn_decode_workspace_bytes(B, nh, hd, Tmax, splits)
+                                            : plm_attn_extend_workspace_bytes(B, n, nh, hd, Tmax, splits);
   if (att == 0) return 0;
-  const size_t M = (size_t)(n == 0 ? B : B * n), d = (size_t)(nh * hd);
+  const size_t M = (size_t)(B * n), d = (size_t)(nh * hd);
   return 2 * df_round16(M * d * 2) + df_round16(M * (size_t)hidden * 2) + att;
 }
 
 extern "C" size_t plm_decode_layer_workspace_bytes(int64_t B, int64_t nh, int64_t hd, int64_t hidden, int64_t Tmax, int splits) {
-  return df_layer_workspace_bytes(B, 0, nh, hd, hidden, Tmax, splits);
+  return df_layer_workspace_bytes(DF_ATTN_DECODE, B, 1, nh, hd, hidden, Tmax, splits);
 }
 
 extern "C" size_t plm_extend_layer_workspace_bytes(int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t hidden, int64_t Tmax, int splits) {
-  return n < 1 ? 0 : df_layer_workspace_bytes(B, n, nh, hd, hidden, Tmax, splits);
+  return df_layer_workspace_bytes(DF_ATTN_EXTEND, B, n, nh, hd, hidden, Tmax, splits);
 }
 
-// The layer driver of both entry points: they differ in their first and attention stages alone.  n == 0, the decode layer: p0 = pos,
-// p1 = lens (both required).  n >= 1, the extend layer: p0 = lens0, p1 = n_new (may be null).
-static int df_layer(const char* fn, float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+// The layer driver of both entry points: p0 = lens0, the position of every sequence's first row; p1 is the attention stage's own
+// per-sequence operand: lens (required) of DF_ATTN_DECODE; n_new (may be null), which the qkv stage takes too, of DF_ATTN_EXTEND.
+static int df_layer(const char* fn, DfAttn attn, float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
                     const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* p0, const int32_t* p1,
                     const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t n,
                     int64_t Tmax, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits, void* workspace, size_t workspace_bytes,
                     void* stream) {
-  const bool rows = n != 0;
-  PLM_REQUIRE(x && attn_norm_w && mlp_norm_w && w_qkv && w_out && w_fc1 && w_fc2 && p0 && (rows || p1) && rope_cos && rope_sin && kv && status &&
-                  workspace,
+  PLM_REQUIRE(x && attn_norm_w && mlp_norm_w && w_qkv && w_out && w_fc1 && w_fc2 && p0 && (attn == DF_ATTN_EXTEND || p1) && rope_cos && rope_sin &&
+                  kv && status && workspace,
               "%s: null pointer", fn);
   PLM_REQUIRE(df_aligned(workspace), "%s: the workspace must be 16-byte aligned", fn);
   const int64_t d = nh * hd;
   char* ws = static_cast<char*>(workspace);
   // every refusal of every stage before the first launch (the sub-buffers stand in for the stages' own operands)
   uint16_t* q = reinterpret_cast<uint16_t*>(ws);
-  if (rows) {
-    if (const int e = df_check_qkv_rows(fn, x, attn_norm_w, w_qkv, p0, rope_cos, rope_sin, rope_T, q, kv, ld_kv, status, B, n, Tmax, nh, hd)) return e;
-  } else {
-    if (const int e = df_check_qkv(fn, x, attn_norm_w, w_qkv, p0, rope_cos, rope_sin, rope_T, q, kv, ld_kv, status, B, Tmax, nh, hd)) return e;
-  }
-  const int64_t M = rows ? B * n : B;
+  if (const int e = df_check_qkv(fn, x, attn_norm_w, w_qkv, p0, rope_cos, rope_sin, rope_T, q, kv, ld_kv, status, B, n, Tmax, nh, hd)) return e;
+  const int64_t M = B * n;
   if (const int e = df_check_residual(fn, x, q, w_out, M, d, d)) return e;
   if (const int e = df_check_fc1(fn, x, mlp_norm_w, w_fc1, q, M, d, hidden, mlp_kind)) return e;
   if (const int e = df_check_residual(fn, x, q, w_fc2, M, d, hidden)) return e;
   PLM_REQUIRE(splits >= 0 && splits <= 64, "%s: splits=%d out of range (0 = automatic, 1..64 forced)", fn, splits);
   // the attention stage's own shape refusals are its workspace query's: 0 for anything plm_attn_decode / plm_attn_extend would refuse
-  const size_t need = df_layer_workspace_bytes(B, n, nh, hd, hidden, Tmax, splits);
-  PLM_REQUIRE(need != 0, "%s: bad shape B=%ld n=%ld Tmax=%ld nh=%ld hd=%ld hidden=%ld", fn, (long)B, (long)(rows ? n : 1), (long)Tmax, (long)nh,
-              (long)hd, (long)hidden);
+  const size_t need = df_layer_workspace_bytes(attn, B, n, nh, hd, hidden, Tmax, splits);
+  PLM_REQUIRE(need != 0, "%s: bad shape B=%ld n=%ld Tmax=%ld nh=%ld hd=%ld hidden=%ld", fn, (long)B, (long)n, (long)Tmax, (long)nh, (long)hd,
+              (long)hidden);
   if (workspace_bytes < need) {
     plm_set_error("%s: workspace of %zu bytes required, %zu given", fn, need, workspace_bytes);
     return PLM_E_WORKSPACE;
   }
   const size_t qb = df_round16((size_t)M * (size_t)d * 2), ab = df_round16((size_t)M * (size_t)hidden * 2);
-  uint16_t* attn = reinterpret_cast<uint16_t*>(ws + qb);
+  uint16_t* attn_out = reinterpret_cast<uint16_t*>(ws + qb);
   uint16_t* act = reinterpret_cast<uint16_t*>(ws + 2 * qb);
   void* att = ws + 2 * qb + ab;
   const size_t att_bytes = need - 2 * qb - ab;
   hipStream_t s = (hipStream_t)stream;
-  if (rows) {
-    df_launch_qkv_rows(x, attn_norm_w, eps, w_qkv, p0, p1, rope_cos, rope_sin, rope_T, q, kv, ld_kv, status, B, n, Tmax, nh, hd, s);
-    if (const int e = plm_attn_extend(q, kv, ld_kv, p0, p1, attn, nullptr, B, n, Tmax, nh, hd, splits, att, att_bytes, stream)) return e;
-  } else {
-    df_launch_qkv(x, attn_norm_w, eps, w_qkv, p0, rope_cos, rope_sin, rope_T, q, kv, ld_kv, status, B, Tmax, nh, hd, s);
-    if (const int e = plm_attn_decode(q, kv, ld_kv, p1, attn, nullptr, B, Tmax, nh, hd, splits, att, att_bytes, stream)) return e;
-  }
-  df_launch_residual(x, attn, w_out, M, d, d, s);
+  df_launch_qkv(x, attn_norm_w, eps, w_qkv, p0, attn == DF_ATTN_EXTEND ? p1 : nullptr, rope_cos, rope_sin, rope_T, q, kv, ld_kv, status, B, n, Tmax,
+                nh, hd, s);
+  if (const int e = attn == DF_ATTN_DECODE ? plm_attn_decode(q, kv, ld_kv, p1, attn_out, nullptr, B, Tmax, nh, hd, splits, att, att_bytes, stream)
+                                           : plm_attn_extend(q, kv, ld_kv, p0, p1, attn_out, nullptr, B, n, Tmax, nh, hd, splits, att, att_bytes, stream))
+    return e;
+  df_launch_residual(x, attn_out, w_out, M, d, d, s);
   df_launch_fc1(x, mlp_norm_w, eps, w_fc1, act, M, d, hidden, mlp_kind, s);
   df_launch_residual(x, act, w_fc2, M, d, hidden, s);
   PLM_CHECK_LAUNCH(fn);
@@ -476,8 +430,8 @@ extern "C" int plm_decode_layer_bf16(float* x, const float* attn_norm_w, const f
                                      const int32_t* lens, const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* kv,
                                      int64_t ld_kv, int32_t* status, int64_t B, int64_t Tmax, int64_t nh, int64_t hd, int64_t hidden,
                                      int mlp_kind, int splits, void* workspace, size_t workspace_bytes, void* stream) {
-  return df_layer("plm_decode_layer_bf16", x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, pos, lens, rope_cos, rope_sin, rope_T, kv,
-                  ld_kv, status, B, 0, Tmax, nh, hd, hidden, mlp_kind, splits, workspace, workspace_bytes, stream);
+  return df_layer("plm_decode_layer_bf16", DF_ATTN_DECODE, x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, pos, lens, rope_cos, rope_sin,
+                  rope_T, kv, ld_kv, status, B, 1, Tmax, nh, hd, hidden, mlp_kind, splits, workspace, workspace_bytes, stream);
 }
 
 extern "C" int plm_extend_layer_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
@@ -485,8 +439,6 @@ extern "C" int plm_extend_layer_bf16(float* x, const float* attn_norm_w, const f
                                      const int32_t* n_new, const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* kv,
                                      int64_t ld_kv, int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, int64_t hidden,
                                      int mlp_kind, int splits, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* fn = "plm_extend_layer_bf16";
-  PLM_REQUIRE(n >= 1, "%s: B=%ld chunks of n=%ld rows unsupported (n >= 1, 1 <= B*n <= %d rows)", fn, (long)B, (long)n, DF_MAX_ROWS);
-  return df_layer(fn, x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, lens0, n_new, rope_cos, rope_sin, rope_T, kv, ld_kv, status, B,
-                  n, Tmax, nh, hd, hidden, mlp_kind, splits, workspace, workspace_bytes, stream);
+  return df_layer("plm_extend_layer_bf16", DF_ATTN_EXTEND, x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, lens0, n_new, rope_cos,
+                  rope_sin, rope_T, kv, ld_kv, status, B, n, Tmax, nh, hd, hidden, mlp_kind, splits, workspace, workspace_bytes, stream);
 }

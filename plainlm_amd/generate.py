@@ -14,7 +14,8 @@ speculative decoding reuses that loop with ``_LookupSessi
 token history (check_lookup, lookup_uniforms, lookup_round_uniforms).  The fused decode step is a keyword of
 decode_step, ``fused=True``, which runs every layer as one ops.decode_layer call, and generate_fused is generate over it (check_fused holds
 its refusals).  The fused extend is the same keyword of extend, one ops.extend_layer call per layer, and
-generate_lookup_fused is generate_lookup over it (check_fused_rows).
+generate_lookup_fused is generate_lookup over it (check_fused_rows).  Both walk the layers with the host's one ``fused_layers``: a decode
+step is the chunk of one row per sequence, told apart by its ``chunk`` argument alone.
 """
 
 import math
@@ -121,20 +122,23 @@ def chunk_lens(token_lens, B, n, device):
   return t, t
 
 
+def check_fused_dim(who, dim):
+  if dim % 32 != 0:
+    raise ValueError(f'{who}: fused=True needs cfg.dim % 32 == 0, got {dim}: leave fused off')
+
+
 def check_fused(who, B, dim):
   """The refusals of fused=True that need no GPU: the skinny-M kernels take at most ops.FUSED_DECODE_MAX_ROWS rows and dim % 32 == 0."""
   if B > ops.FUSED_DECODE_MAX_ROWS:
     raise ValueError(f'{who}: fused=True serves at most {ops.FUSED_DECODE_MAX_ROWS} sequences, got {B}: leave fused off')
-  if dim % 32 != 0:
-    raise ValueError(f'{who}: fused=True needs cfg.dim % 32 == 0, got {dim}: leave fused off')
+  check_fused_dim(who, dim)
 
 
 def check_fused_rows(who, B, n, dim):
   """check_fused for a chunk of n rows per sequence: the skinny-M kernels take at most ops.FUSED_EXTEND_MAX_ROWS rows, B * n of them."""
   if B * n > ops.FUSED_EXTEND_MAX_ROWS:
     raise ValueError(f'{who}: fused=True serves at most {ops.FUSED_EXTEND_MAX_ROWS} chunk rows, got {B} sequences x {n} rows = {B * n}: leave fused off')
-  if dim % 32 != 0:
-    raise ValueError(f'{who}: fused=True needs cfg.dim % 32 == 0, got {dim}: leave fused off')
+  check_fused_dim(who, dim)
 
 
 def pad4(n):
@@ -576,10 +580,9 @@ class _LookupSession:
 class Generation:
   """KV-cached generation, mixed into ``Transformer`` (DESIGN.md sections 12 to 16).  What it asks of its host class:
     attributes  cfg (the ModelConfig), n_layers, head_dim, lm_head (its weight tells the model's device)
-    methods     _rope(device), trunk(x, attn_mask, cache), cached_layers(tokens, cache, attend), fused_layers(tokens, cache, rope),
-                fused_chunk_layers(tokens, cache, rope, lens0, n_new, n), head(y, logits, shape); the middle four call refresh_shadows()
-                themselves.  _rope keeps its underscore: tools and tests
-                from before the mixin call it by that name."""
+    methods     _rope(device), trunk(x, attn_mask, cache), cached_layers(tokens, cache, attend), fused_layers(tokens, cache, rope,
+                chunk=None | (lens0, n_new, n)), head(y, logits, shape); the middle three call refresh_shadows() themselves.  _rope
+                keeps its underscore: tools and tests from before the mixin call it by that name."""
 
   @torch.compiler.disable
   def prefill(self, x, prompt_lens=None, max_len=None, logits=False):
@@ -654,7 +657,7 @@ class Generation:
     The Block structure as decode_step runs it, through ops calls on the bf16 shadows at M = B * n: the same launches as one decode step,
     whatever n.  A chunk that does not fit the cache (or the RoPE table) stores nothing for that sequence and surfaces through
     ``cache.check()``.  Runs under no_grad.  fused=True runs every layer as one library call over the skinny-M
-    kernels (``fused_chunk_layers``: the same rounding points, other fp32 summation orders, so close to but not the bits of the default);
+    kernels (``fused_layers`` with the chunk: the same rounding points, other fp32 summation orders, so close to but not the bits of the default);
     it serves B * n <= ops.FUSED_EXTEND_MAX_ROWS chunk rows and raises ValueError otherwise, before anything is launched."""
     if isinstance(tokens, torch.Tensor) and (tokens.dim() != 2 or tokens.shape[0] != cache.B or tokens.shape[1] < 1):
       raise ValueError(f'extend: tokens {tuple(tokens.shape)} are not a [B, n] chunk for the cache\'s batch of {cache.B}')
@@ -674,7 +677,7 @@ class Generation:
         q, _ = ops.kv_append_rope_rows(qkv, lens0, rope[0], rope[1], cache.kv[i], nh, n_new=n_new, status=cache.status)
         return ops.attn_extend(q, cache.kv[i], lens0, nh, n_new=n_new)
       flat = tokens.reshape(-1).contiguous()
-      y = self.fused_chunk_layers(flat, cache, rope, lens0, n_new, n) if fused else self.cached_layers(flat, cache, attend)
+      y = self.fused_layers(flat, cache, rope, (lens0, n_new, n)) if fused else self.cached_layers(flat, cache, attend)
       cache.advance_by(adv)
       if all_rows:
         return self.head(y, logits, (B, n))

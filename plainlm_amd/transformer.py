@@ -543,31 +543,25 @@ class Transformer(nn.Module, G.Generation):
       branch = ops.gemm_nt(act, layer.mlp.fc2.shadow()[0])
     return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps, branch=branch)[1]
 
-  def fused_layers(self, tokens, cache, rope):
-    """``cached_layers`` for one decode token per sequence (tokens int64 [B], B <= ops.FUSED_DECODE_MAX_ROWS) through the skinny-M
-    kernels: the embedding, ONE library call per layer (ops.decode_layer: six launches, every intermediate in
-    the workspace arena), the out norm.  The fp32 residual stream is one buffer updated in place: a layer's MLP output is added by its
-    own fc2 launch, not by the next norm.  Returns the final normed rows [B, dim]."""
+  def fused_layers(self, tokens, cache, rope, chunk=None):
+    """``cached_layers`` through the skinny-M kernels (DESIGN.md sections 17 and 18): the embedding, ONE library call per layer (six
+    launches, every intermediate in the workspace arena), the out norm.  The fp32 residual stream is one buffer updated in place: a
+    layer's MLP output is added by its own fc2 launch, not by the next norm.  chunk None: a decode step, tokens int64 [B] with
+    B <= ops.FUSED_DECODE_MAX_ROWS, one per sequence at cache.pos (ops.decode_layer).  chunk (lens0, n_new, n): n tokens per sequence,
+    tokens int64 [B * n] with B * n <= ops.FUSED_EXTEND_MAX_ROWS (ops.extend_layer: row b * n + r is appended at lens0[b] + r, n_new
+    int32 [B] or None as ops.kv_append_rope_rows takes it).  Returns the final normed rows [B or B * n, dim]."""
+    if chunk is None:
+      layer_op, lengths = ops.decode_layer, (cache.pos, cache.lens)
+    else:
+      layer_op, lengths, n = ops.extend_layer, chunk[:2], chunk[2]
+      if tokens.shape[0] != cache.B * n:
+        raise ValueError(f'fused_layers: {tokens.shape[0]} tokens are not {cache.B} chunks of {n}')
     self.refresh_shadows()
     x = ops.embed_fwd(tokens, self.embed_tokens.weight)
     for i, layer in enumerate(self.layers):
-      ops.decode_layer(x, layer.attn_norm.weight, layer.mlp_norm.weight, layer.attn_norm.eps, layer.attn.w_qkv.shadow()[0],
-                       layer.attn.w_out.shadow()[0], layer.mlp.fc1.shadow()[0], layer.mlp.fc2.shadow()[0], cache.pos, cache.lens, rope[0],
-                       rope[1], cache.kv[i], self.cfg.n_heads, layer.mlp.kind, cache.status)
-    return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps)[1]
-
-  def fused_chunk_layers(self, tokens, cache, rope, lens0, n_new, n):
-    """``fused_layers`` for a chunk of n tokens per sequence (tokens int64 [B * n], B * n <= ops.FUSED_EXTEND_MAX_ROWS; DESIGN.md section
-    18): the embedding, ONE library call per layer (ops.extend_layer: row b * n + r is appended at lens0[b] + r, n_new int32 [B] or None
-    as ops.kv_append_rope_rows takes it), the out norm.  Returns the final normed rows [B * n, dim]."""
-    if tokens.shape[0] != cache.B * n:
-      raise ValueError(f'fused_chunk_layers: {tokens.shape[0]} tokens are not {cache.B} chunks of {n}')
-    self.refresh_shadows()
-    x = ops.embed_fwd(tokens, self.embed_tokens.weight)
-    for i, layer in enumerate(self.layers):
-      ops.extend_layer(x, layer.attn_norm.weight, layer.mlp_norm.weight, layer.attn_norm.eps, layer.attn.w_qkv.shadow()[0],
-                       layer.attn.w_out.shadow()[0], layer.mlp.fc1.shadow()[0], layer.mlp.fc2.shadow()[0], lens0, n_new, rope[0], rope[1],
-                       cache.kv[i], self.cfg.n_heads, layer.mlp.kind, cache.status)
+      layer_op(x, layer.attn_norm.weight, layer.mlp_norm.weight, layer.attn_norm.eps, layer.attn.w_qkv.shadow()[0],
+               layer.attn.w_out.shadow()[0], layer.mlp.fc1.shadow()[0], layer.mlp.fc2.shadow()[0], *lengths, rope[0], rope[1], cache.kv[i],
+               self.cfg.n_heads, layer.mlp.kind, cache.status)
     return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps)[1]
 
   def head(self, y, logits, shape, targets=None):
