@@ -592,6 +592,60 @@ int plm_optim_cast_multi(const plm_optim_hparams* h, const plm_optim_item* items
  * A NULL p or z or n <= 0 gives PLM_E_INVALID. */
 int plm_lerp_f32(float* p, const float* z, int64_t n, float w, void* stream);
 
+/* ---- Muon for the block matrices: torch.optim.Muon's arithmetic on whole 2-D weights
+ * Batched NT GEMM: one launch per PLM_NT_BATCH_GROUP problems, each
+ *   C[M,N] = bf16(alpha * (A[M,K] . B[N,K]^T) + beta * float(D[M,N]))     fp32 sums, one rounding per element:
+ *   fmaf(alpha, acc, beta * d) with D, alpha * acc without (D NULL; beta is then ignored)
+ * and, when Ct is not NULL, Ct[N, ldct] = C^T (the same bits).  Shapes and leading dimensions are per problem: M, N, K and every ld
+ * are positive multiples of 8 below 2^31, lda / ldb >= K, ldc / ldd >= N, ldct >= M; every base is 16-byte aligned.  Edge tiles are
+ * handled; nothing outside [M, N] of C / [N, M] of Ct is written and nothing outside the stated extents is read.  D may be C itself
+ * (each element is read before it is written, by the thread that writes it); A and B must not overlap C or Ct, nor D Ct.  EVERY item is
+ * validated before the first launch: a refused list (PLM_E_INVALID) leaves all outputs as they were. */
+#define PLM_NT_BATCH_GROUP 32
+typedef struct plm_nt_batch_item {
+  const uint16_t* A; int64_t lda;   /* bf16 [M, K] */
+  const uint16_t* B; int64_t ldb;   /* bf16 [N, K] */
+  uint16_t* C; int64_t ldc;         /* bf16 [M, N] */
+  const uint16_t* D; int64_t ldd;   /* bf16 [M, N] or NULL */
+  uint16_t* Ct; int64_t ldct;       /* bf16 [N, M] or NULL */
+  int64_t M, N, K;
+  float alpha, beta;
+} plm_nt_batch_item;
+int plm_gemm_bf16_nt_batched(const plm_nt_batch_item* items, int count, void* stream);
+
+/* The Muon tail of a list of weights W_i fp32 [rows_i, cols_i] (m_i = min, n_i = max of the two; X is always [m, n], the transpose
+ * of a tall weight).  The three calls share one caller-owned workspace of plm_muon_workspace_bytes(rows, cols, count) bytes, 16-byte
+ * aligned, laid out as: per matrix, in list order, the bf16 blocks X0 [m, n] | X0t [n, m] | X1 [m, n] | X1t [n, m] | A [m, m] |
+ * Bm [m, m], all contiguous; then one fp32 partial sum per 64 x 64 tile of every matrix (in list order).
+ *   plm_muon_prepare: g' = *clip_coef_dev * g (NULL = 1); buf = lerp(buf, g', 1 - momentum); U = nesterov ? lerp(g', buf, momentum) :
+ *     buf (torch.lerp's two-sided form); Ub = bf16(U); nrm[i] = max(bf16(sqrt(sum float(Ub)^2)), bf16(eps)) with the sum in fp32 in
+ *     a fixed order (one partial per 64 x 64 tile, then one ordered final sum: no atomics, two runs give the same bits);
+ *     X0 = bf16(float(Ub) / nrm[i]) in the wide orientation, X0t = X0^T.  Two launches per 56 matrices.
+ *   plm_muon_orthogonalize: `steps` Newton-Schulz steps on every X of the workspace, three plm_gemm_bf16_nt_batched launches per step
+ *     and PLM_NT_BATCH_GROUP matrices:  A = bf16(X X^T) ; Bm = bf16(b A + c (A A)) ; X' = bf16(a X + Bm X), X't = X'^T.
+ *     Step s reads X{s & 1} and writes X{(s + 1) & 1}: the result is X{steps & 1} and its transpose.
+ *   plm_muon_apply: W = fmaf(-lr_adj_i, float(O), W * decay) with O = the result of `steps` steps read in W's layout (X for a wide
+ *     weight, Xt for a tall one; steps = 0 reads X0); dst = bf16(W) and dst_t = bf16(W)^T [cols, ld_t] are written in the same pass.
+ * rows, cols, ld_t: positive multiples of 8 below 2^31 (rows * cols < 2^30), ld_t >= rows; all pointers 16-byte aligned; momentum in
+ * [0, 1); steps in 1..99 (plm_muon_apply: 0..99); at most 4096 matrices.  PLM_E_INVALID for a refused argument, PLM_E_WORKSPACE for a short or misaligned workspace, both before
+ * anything is launched.  plm_muon_workspace_bytes returns 0 for a list it refuses. */
+typedef struct plm_muon_item {
+  float* p;         /* fp32 [rows, cols], updated in place by plm_muon_apply */
+  const float* g;   /* fp32 gradient (plm_muon_prepare) */
+  float* buf;       /* fp32 momentum buffer, updated in place by plm_muon_prepare */
+  uint16_t* dst;    /* bf16 [rows, cols] (plm_muon_apply) */
+  uint16_t* dst_t;  /* bf16 [cols, ld_t] (plm_muon_apply) */
+  int64_t rows, cols, ld_t;
+  float lr_adj;     /* the shape-adjusted learning rate (plm_muon_apply) */
+} plm_muon_item;
+size_t plm_muon_workspace_bytes(const int64_t* rows, const int64_t* cols, int count);
+int plm_muon_prepare(const plm_muon_item* items, int count, float momentum, int nesterov, float eps, const float* clip_coef_dev,
+                     float* nrm, void* workspace, size_t workspace_bytes, void* stream);
+int plm_muon_orthogonalize(const int64_t* rows, const int64_t* cols, int count, int steps, float a, float b, float c, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int plm_muon_apply(const plm_muon_item* items, int count, float decay, int steps, const void* workspace, size_t workspace_bytes,
+                   void* stream);
+
 /* ---- MXFP8 (OCP MX: e4m3fn elements, one E8M0 scale byte per 32 elements)
  * Layout of a quantized operand blocked along its K: data uint8 [rows, Kp] and scales uint8 [rows, Kp/32], both row-major, Kp = roundup(K, 128);
  * padding elements are zero with scale byte 0.  Scale rule: amax = max |x| of the block, E = floor(log2 amax), e = E - 8 if amax <= 448 * 2^(E-8)

@@ -61,6 +61,19 @@ class MxQuantItem(C.Structure):
   _fields_ = [('x', _P), ('ld', _I64), ('rows', _I64), ('cols', _I64), ('q', _P), ('s', _P), ('qt', _P), ('st', _P)]
 
 
+class NtBatchItem(C.Structure):
+  """struct plm_nt_batch_item (include/plainlm_hip.h)."""
+  _fields_ = [('A', _P), ('lda', _I64), ('B', _P), ('ldb', _I64), ('C', _P), ('ldc', _I64), ('D', _P), ('ldd', _I64), ('Ct', _P), ('ldct', _I64),
+              ('M', _I64), ('N', _I64), ('K', _I64), ('alpha', _F), ('beta', _F)]
+
+
+class MuonItem(C.Structure):
+  """struct plm_muon_item (include/plainlm_hip.h)."""
+  _fields_ = [('p', _P), ('g', _P), ('buf', _P), ('dst', _P), ('dst_t', _P), ('rows', _I64), ('cols', _I64), ('ld_t', _I64), ('lr_adj', _F)]
+
+
+NT_BATCH_GROUP = 32  # PLM_NT_BATCH_GROUP
+
 MX_OUT_BF16, MX_OUT_F32, MX_OUT_F32_ACC = 0, 1, 2  # PLM_MX_OUT_*
 
 
@@ -138,6 +151,11 @@ SIGNATURES = {
   'plm_optim_f32': (_I, [C.POINTER(OptimHparams), _P, _P, _P, _P, _I64, _P, _P]),
   'plm_optim_cast_multi': (_I, [C.POINTER(OptimHparams), C.POINTER(OptimItem), _I, _P, _P]),
   'plm_lerp_f32': (_I, [_P, _P, _I64, _F, _P]),
+  'plm_gemm_bf16_nt_batched': (_I, [_P, _I, _P]),
+  'plm_muon_workspace_bytes': (_SZ, [C.POINTER(_I64), C.POINTER(_I64), _I]),
+  'plm_muon_prepare': (_I, [_P, _I, _F, _I, _F, _P, _P, _P, _SZ, _P]),
+  'plm_muon_orthogonalize': (_I, [C.POINTER(_I64), C.POINTER(_I64), _I, _I, _F, _F, _F, _P, _SZ, _P]),
+  'plm_muon_apply': (_I, [_P, _I, _F, _I, _P, _SZ, _P]),
   'plm_set_cu_reserve': (_I, [_I]),
   'plm_comm_unique_id': (_I, [_P]),
   'plm_comm_init': (_I, [C.POINTER(_P), _P, _I, _I, _I]),

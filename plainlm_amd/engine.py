@@ -147,15 +147,18 @@ class MissingOptimKey(ValueError, NotImplementedError):
 
 
 def intialize_optimizer(param_groups, cfg, model=None):
-  """(sic) optim/init_optim.py:7-70: adamw, nadamw, sgd, signSGD and sfo_adamw.
+  """(sic) optim/init_optim.py:7-70: adamw, nadamw, sgd, signSGD and sfo_adamw; and, not in the reference, muon.
   ``fused_optim: True`` (the shipped configs) with a model selects the flat optimizers of plainlm_amd.optim (clip + update on flat
   buffers with our kernels); ``False`` keeps the torch optimizers on the per-parameter views (for signSGD: optim.SignSGD, the
   reference's arithmetic; for sfo_adamw: optim.AdamWScheduleFree, schedulefree.AdamWScheduleFree restated).  The reference also
   passes ``fused=cfg.fused_optim`` to torch.optim.NAdam, which torch 2.10 does not accept; for NAdam ``fused_optim`` here selects
   only our flat path against torch's.  sfo_adamw takes the optimizer's own warm-up from ``warmup_steps`` (an int, or a fraction of
-  ``steps_budget``) and, like the reference, not ``cfg.eps`` (the package's default 1e-8); the scheduler still sets ``lr`` on top."""
+  ``steps_budget``) and, like the reference, not ``cfg.eps`` (the package's default 1e-8); the scheduler still sets ``lr`` on top.
+  muon (torch.optim.Muon's arithmetic) needs the model: the weights of the block linears take Muon
+  (``muon_momentum`` 0.95, ``muon_nesterov`` True, ``muon_ns_steps`` 5, ``muon_adjust_lr`` 'match_rms_adamw'), everything else AdamW from
+  ``lr`` / ``weight_decay`` / ``beta1`` / ``beta2`` / ``eps``; optim.FlatMuon with ``fused_optim``, optim.Muon without."""
   name = cfg.optim
-  if name not in ('adamw', 'nadamw', 'sgd', 'signSGD', 'sfo_adamw'):
+  if name not in ('adamw', 'nadamw', 'sgd', 'signSGD', 'sfo_adamw', 'muon'):
     raise NotImplementedError(f'Not implemented optim: {name}.')
   if name in ('sgd', 'signSGD') and not hasattr(cfg, 'dampening'):
     raise ValueError(f"optim '{name}' needs the config key 'dampening' (the reference reads cfg.dampening)")
@@ -174,6 +177,16 @@ def intialize_optimizer(param_groups, cfg, model=None):
       return O.FlatNAdamW(model, param_groups, lr=cfg.lr, betas=[cfg.beta1, cfg.beta2], eps=eps, weight_decay=cfg.weight_decay)
     return torch.optim.NAdam(param_groups, lr=cfg.lr, betas=[cfg.beta1, cfg.beta2], weight_decay=cfg.weight_decay,
                              decoupled_weight_decay=True, eps=eps)
+  if name == 'muon':
+    if model is None:
+      raise ValueError("optim 'muon' needs the model: its parameter groups are the block linears against everything else")
+    if getattr(getattr(model, 'cfg', None), 'linear_precision', 'bf16') == 'mxfp8':
+      raise NotImplementedError("optim 'muon' with linear_precision 'mxfp8' is not implemented")
+    kw = dict(lr=cfg.lr, betas=[cfg.beta1, cfg.beta2], eps=eps, weight_decay=cfg.weight_decay, momentum=getattr(cfg, 'muon_momentum', 0.95),
+              nesterov=getattr(cfg, 'muon_nesterov', True), ns_steps=getattr(cfg, 'muon_ns_steps', 5),
+              adjust_lr=getattr(cfg, 'muon_adjust_lr', 'match_rms_adamw'))
+    groups = O.muon_param_groups(model, param_groups)
+    return O.FlatMuon(model, groups, **kw) if flat else O.Muon(groups, **kw)
   if name == 'sfo_adamw':
     kw = dict(lr=cfg.lr, betas=[cfg.beta1, cfg.beta2], weight_decay=cfg.weight_decay,
               warmup_steps=_steps(cfg.warmup_steps, cfg.steps_budget))

@@ -1145,3 +1145,7 @@ from .ops_decode import (DECODE_MLP_KINDS, FUSED_DECODE_MAX_ROWS, decode_gemm_re
                          decode_norm_fc1_act, decode_norm_qkv_append)
 # ---- the fused extend: chunk rows on the same kernels, same module ------------------------------------------------------
 from .ops_decode import FUSED_EXTEND_MAX_ROWS, extend_layer, extend_layer_workspace, extend_norm_qkv_append  # noqa: E402,F401
+# ---- the Muon tail: batched NT GEMM, prepare / orthogonalize / apply; its wrappers live in ops_muon.py -------------------
+from .ops_muon import (MUON_ADJUST_LR, MUON_EPS, MUON_NS_COEFFICIENTS, NT_BATCH_GROUP, gemm_nt_batched, muon_adjusted_lr, muon_apply,  # noqa: E402,F401
+                       muon_arena, muon_blocks, muon_items, muon_layout, muon_ns_flops, muon_orthogonalize, muon_prepare, muon_set_lr,
+                       muon_workspace, muon_workspace_bytes)

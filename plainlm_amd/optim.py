@@ -22,6 +22,10 @@ package: ``AdamWScheduleFree`` in plain torch for ``fused_optim: False``, ``Flat
 package's state layout (group keys ``k`` / ``weight_sum`` / ``lr_max`` / ``scheduled_lr`` / ``train_mode`` / ...; per parameter ``z`` /
 ``exp_avg_sq``, created at a parameter's first step) and its ``train()`` / ``eval()`` swaps of the parameters between y (where gradients
 are taken) and the averaged iterate x (what is evaluated).
+
+Muon (``torch.optim.Muon``'s arithmetic) is ``Muon`` in plain torch and ``FlatMuon`` on the flat buffers: the weights
+of the block linears take the Newton-Schulz update (prepare -> orthogonalize -> apply on the batched NT GEMM), every other parameter
+takes AdamW in the same object, so the engine keeps one ``param_groups``.
 """
 
 import os
@@ -134,6 +138,105 @@ class AdamWScheduleFree(torch.optim.Optimizer):
     return loss
 
 
+def newton_schulz(u, steps=5, coefficients=ops.MUON_NS_COEFFICIENTS, eps=ops.MUON_EPS):
+  """torch.optim._muon._zeropower_via_newtonschulz restated: bf16(u), on the transpose when tall, divided by its (bf16) norm clamped at
+  eps, then ``steps`` times A = X X^T ; Bm = b A + c A A ; X = a X + Bm X in bf16 matmuls; transposed back."""
+  a, b, c = coefficients
+  x = u.bfloat16()
+  tall = u.size(0) > u.size(1)
+  if tall:
+    x = x.T
+  x = x / x.norm().clamp(min=eps)
+  for _ in range(steps):
+    gram = x @ x.T
+    upd = torch.addmm(gram, gram, gram, beta=b, alpha=c)
+    x = torch.addmm(x, upd, x, beta=a)
+  return x.T if tall else x
+
+
+def muon_param_groups(model, param_groups):
+  """[muon (decay), adamw decay, adamw no-decay] from the two groups of construct.get_param_groups: the Muon group holds the weight of
+  every HipLinear inside model.layers (the four block linears of a layer, whole: w_qkv and a GLU fc1 are not split); embed_tokens,
+  lm_head (tied or not) and the norm weights stay with AdamW."""
+  from .transformer import HipLinear
+  decay, no_decay = param_groups
+  ids = {id(m.weight) for layer in model.layers for m in layer.modules() if isinstance(m, HipLinear)}
+  outside = {id(m.weight) for n, m in model.named_modules() if isinstance(m, HipLinear) and not n.startswith('layers.')}
+  ids -= outside  # a weight shared with a module outside the blocks is not a block matrix
+  muon = [p for p in decay['params'] if id(p) in ids]
+  if len(muon) != len(ids):
+    raise ValueError('muon_param_groups: a block linear weight is missing from the weight-decay group')
+  rest = [p for p in decay['params'] if id(p) not in ids]
+  return [{'params': muon, 'weight_decay': decay['weight_decay'], 'use_muon': True},
+          {'params': rest, 'weight_decay': decay['weight_decay'], 'use_muon': False},
+          {'params': list(no_decay['params']), 'weight_decay': no_decay['weight_decay'], 'use_muon': False}]
+
+
+class Muon(torch.optim.Optimizer):
+  """Muon for the groups with ``use_muon=True`` (2-D parameters only), AdamW for the others, in one optimizer.  Per Muon parameter and
+  step, the arithmetic of torch.optim._muon._single_tensor_muon: ``buf.lerp_(g, 1 - momentum)``; ``u = g.lerp(buf, momentum)`` with
+  nesterov, else buf; ``o = newton_schulz(u)``; ``p *= 1 - lr*wd``; ``p -= lr_adj * o`` with lr_adj = lr * 0.2 sqrt(max(rows, cols))
+  ('match_rms_adamw', the default here: the schedule writes ONE lr into every group, and with this adjustment the matrices share
+  AdamW's lr and weight decay) or lr * sqrt(max(1, rows / cols)) ('original').  State: ``momentum_buffer``, created at the first step.
+  The other groups take torch.optim.AdamW's single-tensor arithmetic (state ``step`` / ``exp_avg`` / ``exp_avg_sq``)."""
+
+  def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.1, momentum=0.95, nesterov=True, ns_steps=5,
+               adjust_lr='match_rms_adamw', ns_coefficients=ops.MUON_NS_COEFFICIENTS, muon_eps=ops.MUON_EPS):
+    if not lr >= 0.0 or not eps >= 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or not weight_decay >= 0.0:
+      raise ValueError(f'Muon: invalid lr={lr} / eps={eps} / betas={betas} / weight_decay={weight_decay}')
+    if not 0.0 <= momentum < 1.0:
+      raise ValueError(f'Muon: momentum={momentum} must lie in [0, 1)')
+    if int(ns_steps) != ns_steps or not 1 <= ns_steps < 100:
+      raise ValueError(f'Muon: ns_steps={ns_steps} must be an integer in 1..99')
+    if adjust_lr not in ops.MUON_ADJUST_LR:
+      raise ValueError(f'Muon: muon_adjust_lr {adjust_lr!r} is not one of {ops.MUON_ADJUST_LR}')
+    if len(ns_coefficients) != 3:
+      raise ValueError('Muon: ns_coefficients must be three values')
+    super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, momentum=momentum, nesterov=bool(nesterov),
+                                  ns_steps=int(ns_steps), adjust_lr=adjust_lr, ns_coefficients=tuple(ns_coefficients), muon_eps=muon_eps,
+                                  use_muon=False))
+    for g in self.param_groups:
+      if g['use_muon'] and any(p.ndim != 2 for p in g['params']):
+        raise ValueError('Muon: a use_muon group holds a parameter that is not 2-D')
+
+  @torch.no_grad()
+  def step(self, closure=None):
+    loss = None
+    if closure is not None:
+      with torch.enable_grad():
+        loss = closure()
+    for group in self.param_groups:
+      lr, wd = group['lr'], group['weight_decay']
+      for p in group['params']:
+        if p.grad is None:
+          continue
+        st = self.state[p]
+        if group['use_muon']:
+          if 'momentum_buffer' not in st:
+            st['momentum_buffer'] = torch.zeros_like(p.grad)
+          buf, mom = st['momentum_buffer'], group['momentum']
+          buf.lerp_(p.grad, 1 - mom)
+          u = p.grad.lerp(buf, mom) if group['nesterov'] else buf
+          o = newton_schulz(u, group['ns_steps'], group['ns_coefficients'], group['muon_eps'])
+          p.mul_(1 - lr * wd)
+          p.add_(o, alpha=-ops.muon_adjusted_lr(lr, group['adjust_lr'], p.shape[0], p.shape[1]))
+          continue
+        if 'step' not in st:
+          st['step'] = torch.tensor(0.0)
+          st['exp_avg'] = torch.zeros_like(p)
+          st['exp_avg_sq'] = torch.zeros_like(p)
+        b1, b2 = group['betas']
+        st['step'] += 1
+        t = float(st['step'])
+        m, v = st['exp_avg'], st['exp_avg_sq']
+        p.mul_(1 - lr * wd)
+        m.lerp_(p.grad, 1 - b1)
+        v.mul_(b2).addcmul_(p.grad, p.grad, value=1 - b2)
+        denom = (v.sqrt() / (1 - b2 ** t) ** 0.5).add_(group['eps'])
+        p.addcdiv_(m, denom, value=-(lr / (1 - b1 ** t)))
+    return loss
+
+
 class _FlatTail:
   """What every flat optimizer shares, mixed in front of its torch class: the flat re-layout of parameters, gradients and state
   buffers (one span per parameter group), the model's gradient span table, the shadow-emitting launch plan, ``clip_and_step``,
@@ -224,6 +327,24 @@ class _FlatTail:
   def _check_step(self):
     pass
 
+  def _step_group(self, gi, g, lo, hi, clip, fresh):
+    """One group's update: the shadow-emitting launch over its Linear weights, the flat kernel over the rest of its span; the linears
+    whose shadows this step has written are appended to ``fresh``."""
+    hp = self._group_hparams(gi, g)
+    spans = [(lo, hi)]
+    if self._fused[gi] is not None:
+      lins, items, table, spans = self._fused[gi]
+      if any(lin._shadow[0] is not it[4] or lin.weight.data_ptr() != it[0].data_ptr() for lin, it in zip(lins, items)):
+        # a shadow buffer or a weight was re-allocated behind our back (model moved, weights re-laid): rebuild the cached table
+        items = [self._item(lin) for lin in lins]
+        table = None
+      table = ops.optim_cast_multi_(hp, items, clip, table)
+      self._fused[gi] = (lins, items, table, spans)
+      fresh.extend(lins)
+    for a, b in spans:
+      m, v = (t[a:b] if t is not None else None for t in self._state_bufs)
+      ops.optim_(hp, self.flat_p[a:b], self.flat_g[a:b], m, v, clip)
+
   @torch.no_grad()
   def clip_and_step(self, max_norm=None):
     self._check_step()
@@ -237,22 +358,8 @@ class _FlatTail:
       clip = torch.clamp(float(max_norm) / (self.last_grad_norm + 1e-6), max=1.0).reshape(1).contiguous()
     fresh = []
     for gi, (g, (lo, hi)) in enumerate(zip(self.param_groups, self.group_spans)):
-      if hi == lo:
-        continue
-      hp = self._group_hparams(gi, g)
-      spans = [(lo, hi)]
-      if self._fused[gi] is not None:
-        lins, items, table, spans = self._fused[gi]
-        if any(lin._shadow[0] is not it[4] or lin.weight.data_ptr() != it[0].data_ptr() for lin, it in zip(lins, items)):
-          # a shadow buffer or a weight was re-allocated behind our back (model moved, weights re-laid): rebuild the cached table
-          items = [self._item(lin) for lin in lins]
-          table = None
-        table = ops.optim_cast_multi_(hp, items, clip, table)
-        self._fused[gi] = (lins, items, table, spans)
-        fresh.extend(lins)
-      for a, b in spans:
-        m, v = (t[a:b] if t is not None else None for t in self._state_bufs)
-        ops.optim_(hp, self.flat_p[a:b], self.flat_g[a:b], m, v, clip)
+      if hi > lo:
+        self._step_group(gi, g, lo, hi, clip, fresh)
     self._after_step()
     self.model.invalidate_shadows()  # raw-pointer update: torch's version counters did not move
     for lin in fresh:                # ... except where this step has just written the shadows itself
@@ -276,7 +383,7 @@ class _FlatTail:
     for gi, g in enumerate(self.param_groups):
       states = [self.state.get(p) or {} for p in g['params']]
       for p, st in zip(g['params'], states):
-        for name, view in zip(self._state_names, self._views[id(p)]):
+        for name, view in zip(self._group_state_names(gi), self._views[id(p)]):
           if name in st:
             view.copy_(st[name])
         if 'step' in st:
@@ -287,6 +394,10 @@ class _FlatTail:
 
   def _restore_host_state(self, gi, states):
     pass
+
+  def _group_state_names(self, gi):
+    """torch's keys of group gi's state buffers (FlatMuon: its Muon group keeps momentum_buffer where the others keep exp_avg)."""
+    return self._state_names
 
 
 class FlatAdamW(_FlatTail, torch.optim.AdamW):
@@ -477,3 +588,68 @@ class FlatAdamWScheduleFree(_FlatTail, AdamWScheduleFree):
     if any(have) and not all(have):
       raise ValueError(f'FlatAdamWScheduleFree: the state dict holds z / exp_avg_sq for some parameters of group {gi} but not all')
     self._primed[gi] = bool(have) and all(have)
+
+
+class FlatMuon(_FlatTail, Muon):
+  """Muon on the flat buffers.  State buffer 0 is ``momentum_buffer`` on the Muon group's span and ``exp_avg`` elsewhere, buffer 1 is
+  ``exp_avg_sq`` (unused on the Muon span).  ``clip_and_step`` runs the AdamW groups exactly as FlatAdamW does (the PLM_OPTIM_ADAMW
+  kernels, the shadow-emitting launch for an untied lm_head), and the Muon group through ops.muon_prepare -> ops.muon_orthogonalize ->
+  ops.muon_apply on one workspace (the stream's arena); apply writes the block linears' bf16 shadows, which are marked fresh."""
+  _state_names = ('exp_avg', 'exp_avg_sq')
+
+  def __init__(self, model, param_groups, lr, betas, eps, weight_decay, momentum=0.95, nesterov=True, ns_steps=5,
+               adjust_lr='match_rms_adamw'):
+    Muon.__init__(self, param_groups, lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov,
+                  ns_steps=ns_steps, adjust_lr=adjust_lr)
+    self._lay_out(model)
+    self.flat_m, self.flat_v = self._state_bufs
+    by_weight = {id(m.weight): m for m in model.linear_modules()}
+    self._muon = {}  # group index -> [linears, ctypes item table, shapes, (weight, shadow) pointers the table was built from]
+    for gi, g in enumerate(self.param_groups):
+      if g['use_muon'] and g['params']:
+        lins = [by_weight[id(p)] for p in g['params']]
+        for lin in lins:
+          lin.stale_item()  # allocates the shadow buffers
+        self._muon[gi] = [lins, None, None, None]
+    self._muon_nrm = torch.zeros(max([len(v[0]) for v in self._muon.values()] + [1]), dtype=torch.float32, device=self.flat_p.device)
+    self._publish_state()
+
+  def _group_state_names(self, gi):
+    return ('momentum_buffer',) if self.param_groups[gi]['use_muon'] else self._state_names
+
+  def _publish_state(self):
+    for g in self.param_groups:
+      for p in g['params']:
+        m, v = self._views[id(p)]
+        if g['use_muon']:
+          self.state[p] = {'momentum_buffer': m}
+        else:
+          self.state[p] = {'step': torch.tensor(float(self._step_count)), 'exp_avg': m, 'exp_avg_sq': v}
+
+  def _after_step(self):
+    for st in self.state.values():
+      if 'step' in st:
+        st['step'].fill_(float(self._step_count))
+
+  def _group_hparams(self, gi, g):
+    b1, b2 = g['betas']
+    return ops.optim_hparams('adamw', float(g['lr']), g['weight_decay'], beta1=b1, beta2=b2, eps=g['eps'],
+                             bc1=1.0 - b1 ** self._step_count, bc2=1.0 - b2 ** self._step_count)
+
+  def _step_group(self, gi, g, lo, hi, clip, fresh):
+    if not g['use_muon']:
+      return super()._step_group(gi, g, lo, hi, clip, fresh)
+    lins, table, shapes, key = self._muon[gi]
+    now = [(lin.weight.data_ptr(), lin._shadow[0].data_ptr(), lin._shadow[1].data_ptr()) for lin in lins]
+    if table is None or now != key:  # first step, or a weight / shadow buffer was re-allocated behind our back
+      table, shapes = ops.muon_items([(lin.weight.data, lin.weight.main_grad, self._views[id(lin.weight)][0], lin._shadow[0], lin._shadow[1])
+                                      for lin in lins])
+      self._muon[gi] = [lins, table, shapes, now]
+    lr = float(g['lr'])
+    ops.muon_set_lr(table, [ops.muon_adjusted_lr(lr, g['adjust_lr'], r, c) for r, c in shapes])
+    dev = self.flat_p.device
+    ws = ops.muon_arena(shapes, dev)
+    ops.muon_prepare(table, shapes, g['momentum'], g['nesterov'], self._muon_nrm, clip, eps=g['muon_eps'], workspace=ws)
+    ops.muon_orthogonalize(shapes, g['ns_steps'], dev, g['ns_coefficients'], workspace=ws)
+    ops.muon_apply(table, shapes, 1.0 - lr * g['weight_decay'], g['ns_steps'], dev, workspace=ws)
+    fresh.extend(lins)
