@@ -378,6 +378,67 @@ int plm_extend_layer_bf16(float* x, const float* attn_norm_w, const float* mlp_n
                           int64_t Tmax, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* ---- the FP8 KV cache: block-scaled e4m3 rows for decode, extend and the fused layers -----
+ * Every argument check of these entry points comes before any HIP call.  An alternative to the bf16 cache above, chosen per cache; the
+ * entry points above are untouched.  head_dim is 32, 64 or 128, dm = nh*hd.
+ *
+ * Cache layout: one uint8 buffer per layer, kv8[B, Tmax, ld_kv8] with ld_kv8 in BYTES, a multiple of 16 and at least 2*dm + dm/8;
+ * sequence b starts at b * Tmax * ld_kv8.  Row (b, j) = [ k codes dm | v codes dm | k scales dm/16 | v scales dm/16 ]: OCP e4m3fn codes
+ * (not fnuz) and one E8M0 scale byte per 16 consecutive elements of a head.  Quantisation is of the bf16 values the bf16 cache would
+ * hold (k after RoPE), block by block: e = the smallest exponent with amax <= 448 * 2^e, clamped to [-127, 127]; scale byte e + 127; code
+ * = RNE-e4m3fn(x * 2^-e) with subnormals; amax = 0 gives scale byte 0 and zero codes; any non-finite value in the block gives scale byte
+ * 0xFF and codes 0x7F.  Dequantisation is code * 2^(s - 127), NaN for s = 0xFF: exact in fp32 (the decode kernel) and in bf16 (the extend
+ * kernel's LDS tile, plm_kv8_dequant_rows) unless the value lies below bf16's subnormal range (under 2^-133), where it rounds.  q, P,
+ * the softmax statistics and the partials are never quantised.  Because dequantisation is exact, plm_attn_decode_kv8 /
+ * plm_attn_extend_kv8 return, bit for bit, what plm_attn_decode / plm_attn_extend return on the plm_kv8_dequant_rows image of the cache.
+ *
+ * plm_kv8_quant_rows: src bf16 [B, T, ld_src] (k | v rows, 2*dm columns used; ld_src >= 2*dm, a multiple of 8) is quantised into cache
+ * rows 0 .. T-1 of every sequence (a prefill's write).  plm_kv8_dequant_rows: cache rows 0 .. T-1 of every sequence to dst bf16
+ * [B, T, ld_dst].  One launch each.  PLM_E_INVALID before anything is launched: NULL pointers, a head_dim other than 32 / 64 / 128,
+ * T < 1 or T > Tmax, B*T >= 2^31, a bf16 stride that is no multiple of 8 or shorter than 2*dm, an ld_kv8 that is no multiple of 16 or
+ * shorter than 2*dm + dm/8, bases that are not 16-byte aligned.
+ *
+ * plm_kv8_append_rope_rows: plm_kv_append_rope_rows's contract (lens0, n_new, c_b, the refusal on the device with status[0] = 1, zeroed
+ * q_out rows for rows without a cache row, the same rotation and the same q_out bits) with the rotated k | v quantised into kv8[b,
+ * lens0[b] + r].  A decode step is its n = 1 case (lens0 = the positions, n_new = NULL).  One launch.  Its refusals are
+ * plm_kv_append_rope_rows's, with the ld_kv8 rule above for the cache stride.
+ *
+ * plm_attn_decode_kv8 / plm_attn_extend_kv8: plm_attn_decode / plm_attn_extend over this cache.  Same arguments otherwise, same split
+ * rule, partial layout, combine launch and workspace (plm_attn_decode_workspace_bytes / plm_attn_extend_workspace_bytes), same refusals
+ * with the ld_kv8 rule above (PLM_E_INVALID; a short workspace PLM_E_WORKSPACE).  Rows at and beyond the valid length are never loaded.
+ *
+ * plm_extend_norm_qkv_append_kv8_bf16, plm_decode_layer_kv8_bf16, plm_extend_layer_kv8_bf16: the fused qkv stage and the two layer
+ * calls of the sections above over this cache (the decode qkv stage is the extend stage at n = 1, n_new = NULL).  The stage rounds to
+ * bf16 and rotates as plm_extend_norm_qkv_append_bf16 does, then quantises: q_out and the quantised values are that entry point's bits.
+ * The layers take plm_decode_layer_workspace_bytes / plm_extend_layer_workspace_bytes bytes.  Their refusals are those entry points',
+ * with the ld_kv8 rule above, all before the first launch. */
+int plm_kv8_quant_rows(const uint16_t* src, int64_t ld_src, uint8_t* kv8, int64_t ld_kv8, int64_t B, int64_t T, int64_t Tmax, int64_t nh,
+                       int64_t hd, void* stream);
+int plm_kv8_dequant_rows(const uint8_t* kv8, int64_t ld_kv8, uint16_t* dst, int64_t ld_dst, int64_t B, int64_t T, int64_t Tmax, int64_t nh,
+                         int64_t hd, void* stream);
+int plm_kv8_append_rope_rows(const uint16_t* qkv, int64_t ld_qkv, const int32_t* lens0, const int32_t* n_new, const float* rope_cos,
+                             const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint8_t* kv8, int64_t ld_kv8, int32_t* status, int64_t B,
+                             int64_t n, int64_t Tmax, int64_t nh, int64_t hd, void* stream);
+int plm_attn_decode_kv8(const uint16_t* q, const uint8_t* kv8, int64_t ld_kv8, const int32_t* lens, uint16_t* out, float* lse, int64_t B,
+                        int64_t Tmax, int64_t nh, int64_t hd, int splits, void* workspace, size_t workspace_bytes, void* stream);
+int plm_attn_extend_kv8(const uint16_t* q, const uint8_t* kv8, int64_t ld_kv8, const int32_t* lens0, const int32_t* n_new, uint16_t* out,
+                        float* lse, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, int splits, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int plm_extend_norm_qkv_append_kv8_bf16(const float* x, const float* norm_w, float eps, const uint16_t* w_qkv, const int32_t* lens0,
+                                        const int32_t* n_new, const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out,
+                                        uint8_t* kv8, int64_t ld_kv8, int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh,
+                                        int64_t hd, void* stream);
+int plm_decode_layer_kv8_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                              const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* pos, const int32_t* lens,
+                              const float* rope_cos, const float* rope_sin, int64_t rope_T, uint8_t* kv8, int64_t ld_kv8, int32_t* status,
+                              int64_t B, int64_t Tmax, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int plm_extend_layer_kv8_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                              const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* lens0, const int32_t* n_new,
+                              const float* rope_cos, const float* rope_sin, int64_t rope_T, uint8_t* kv8, int64_t ld_kv8, int32_t* status,
+                              int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- temperature / top-k / top-p sampling of one token per row -----
  * Every argument check comes before any HIP call.
  * logits bf16 [B, ld] (ld >= V; any 2-byte aligned base and any ld: columns >= V are never loaded); u fp32 [B], one uniform per row,

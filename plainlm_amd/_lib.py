@@ -135,6 +135,16 @@ SIGNATURES = {
   'plm_extend_layer_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I64, _I]),
   'plm_extend_layer_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I,
                                  _P, _SZ, _P]),
+  'plm_kv8_quant_rows': (_I, [_P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
+  'plm_kv8_dequant_rows': (_I, [_P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
+  'plm_kv8_append_rope_rows': (_I, [_P, _I64, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P]),
+  'plm_attn_decode_kv8': (_I, [_P, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
+  'plm_attn_extend_kv8': (_I, [_P, _P, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
+  'plm_extend_norm_qkv_append_kv8_bf16': (_I, [_P, _P, _F, _P, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P]),
+  'plm_decode_layer_kv8_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I, _I, _P,
+                                     _SZ, _P]),
+  'plm_extend_layer_kv8_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I,
+                                     _I, _P, _SZ, _P]),
   'plm_sample_logits_bf16': (_I, [_P, _I64, _P, _F, _I64, _F, _P, _P, _P, _P, _I64, _I64, _P]),
   'plm_spec_verify_bf16': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I64, _I64, _I64, _P]),
   'plm_lookup_draft_i64': (_I, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P]),

@@ -3,18 +3,21 @@
 
 from fractions import Fraction
 
+from .generate import check_kv_dtype
 from .transformer import ModelConfig, Transformer, check_attn_mask_mode, check_linear_precision
 
 
 def construct_model(cfg):
   """cfg: any object with the reference's YAML keys (model, vocab_size, d_model, expand,
   n_layers, n_heads, mlp_class, seq_len, tie_embeddings), plus the optional ``attn_mask_mode`` ('doc', the default, or 'dense') and
-  ``linear_precision`` ('bf16', the default, or 'mxfp8'): see ModelConfig.  Neither key is in the reference.  Returns (model, model_cfg)."""
+  ``linear_precision`` ('bf16', the default, or 'mxfp8') and ``kv_cache`` ('bf16', the default, or 'fp8'): see ModelConfig.  None of the three
+  keys is in the reference.  Returns (model, model_cfg)."""
   if cfg.model != 'transformer':
     raise NotImplementedError(
       f"model '{cfg.model}' is outside the accelerated hot path (only 'transformer'; the Pythia/HF branch is not built)")
   attn_mask_mode = check_attn_mask_mode(getattr(cfg, 'attn_mask_mode', 'doc'))
   linear_precision = check_linear_precision(getattr(cfg, 'linear_precision', 'bf16'))
+  kv_cache = check_kv_dtype(getattr(cfg, 'kv_cache', 'bf16'))
   model_cfg = ModelConfig(
     vocab_size=cfg.vocab_size,
     dim=cfg.d_model,
@@ -27,6 +30,7 @@ def construct_model(cfg):
     tie_embeddings=cfg.tie_embeddings,
     attn_mask_mode=attn_mask_mode,
     linear_precision=linear_precision,
+    kv_cache=kv_cache,
   )
   model = Transformer(model_cfg)
   print(f'Number of parameters: {model.count_params(non_embedding=False):_}')

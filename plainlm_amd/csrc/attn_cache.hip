@@ -79,15 +79,154 @@ __global__ __launch_bounds__(256) void kv_append_rope_rows_kernel(const uint16_t
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// the FP8 cache: kv8[B, Tmax, ld_kv8] bytes, row = k codes dm | v codes dm | k scales dm/16 | v scales dm/16,
+// e4m3fn codes under one E8M0 scale per 16 elements of a head (plm_fp8.h), quantised from the bf16 values the bf16 cache would hold
+// ---------------------------------------------------------------------------------------------------------------------------------
+// 16 bf16 values (two 16-byte chunks) -> 16 code bytes at dst and the block's scale byte at *sc: plain vector stores
+__device__ __forceinline__ void kv8_store_block(bf16x8_t v0, bf16x8_t v1, uint8_t* dst, uint8_t* sc) {
+  float f[16];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    f[e] = bf2f(v0[e]);
+    f[8 + e] = bf2f(v1[e]);
+  }
+  u32x4_t q;
+  const unsigned sb = kv8_block(f, q);
+  *reinterpret_cast<u32x4_t*>(dst) = q;
+  *sc = (uint8_t)sb;
+}
+
+// plm_kv8_append_rope_rows: kv_append_rope_rows_kernel with one thread per 16 columns (two of its chunks, one block of the cache);
+// the same refusals, the same table loads and rope8 calls, so q_out and the values that are quantised are its bits
+__global__ __launch_bounds__(256) void kv8_append_rope_rows_kernel(const uint16_t* __restrict__ qkv, int64_t ld_qkv,
+                                                                   const int32_t* __restrict__ lens0, const int32_t* __restrict__ n_new,
+                                                                   const float* __restrict__ rcos, const float* __restrict__ rsin, int rope_T,
+                                                                   uint16_t* __restrict__ q_out, uint8_t* __restrict__ kv8, int64_t ld_kv8,
+                                                                   int32_t* __restrict__ status, int B, int n, int Tmax, int nh, int hd,
+                                                                   float sgn) {
+  const int dm = nh * hd;
+  const int upr = 3 * dm / 16;  // 16-column units per qkv row
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * n * upr) return;
+  const int64_t row = i / upr;  // b * n + r
+  const int c = (int)(i - row * upr);
+  const int b = (int)(row / n), r = (int)(row - (int64_t)b * n);
+  const int col = c * 16;
+  const int l0 = lens0[b];
+  const int cb = ext_clamp(n_new != nullptr ? n_new[b] : n, 0, n);
+  const int lim = Tmax < rope_T ? Tmax : rope_T;
+  const bool refused = l0 < 0 || (int64_t)l0 + cb > lim;  // nothing of this sequence is stored
+  if (refused && r == 0 && c == 0) status[0] = 1;
+  if (refused || r >= cb) {  // no cache row: a q row of zeros
+    if (col < dm) {
+      st_bf16x8(q_out + row * dm + col, zero_bf16x8());
+      st_bf16x8(q_out + row * dm + col + 8, zero_bf16x8());
+    }
+    return;
+  }
+  const int t = l0 + r;
+  bf16x8_t v0 = ld_bf16x8(qkv + row * ld_qkv + col), v1 = ld_bf16x8(qkv + row * ld_qkv + col + 8);
+  if (col < 2 * dm) {
+    const float* cp = rcos + (int64_t)t * (hd / 2) + (col % hd) / 2;
+    const float* sp = rsin + (int64_t)t * (hd / 2) + (col % hd) / 2;
+    v0 = rope8(v0, *reinterpret_cast<const f32x4_t*>(cp), *reinterpret_cast<const f32x4_t*>(sp), sgn);
+    v1 = rope8(v1, *reinterpret_cast<const f32x4_t*>(cp + 4), *reinterpret_cast<const f32x4_t*>(sp + 4), sgn);
+  }
+  if (col < dm) {
+    st_bf16x8(q_out + row * dm + col, v0);
+    st_bf16x8(q_out + row * dm + col + 8, v1);
+  } else {
+    uint8_t* rowp = kv8 + ((int64_t)b * Tmax + t) * ld_kv8;
+    kv8_store_block(v0, v1, rowp + (col - dm), rowp + 2 * dm + (col - dm) / 16);
+  }
+}
+
+// plm_kv8_quant_rows / plm_kv8_dequant_rows: one thread per block of 16 of rows 0 .. T-1 of every sequence
+__global__ __launch_bounds__(256) void kv8_quant_rows_kernel(const uint16_t* __restrict__ src, int64_t ld_src, uint8_t* __restrict__ kv8,
+                                                             int64_t ld_kv8, int B, int T, int Tmax, int dm) {
+  const int upr = 2 * dm / 16;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * T * upr) return;
+  const int64_t row = i / upr;  // b * T + t
+  const int c = (int)(i - row * upr);
+  const int b = (int)(row / T), t = (int)(row - (int64_t)b * T);
+  const uint16_t* s = src + row * ld_src + c * 16;
+  uint8_t* rowp = kv8 + ((int64_t)b * Tmax + t) * ld_kv8;
+  kv8_store_block(ld_bf16x8(s), ld_bf16x8(s + 8), rowp + c * 16, rowp + 2 * dm + c);
+}
+
+__global__ __launch_bounds__(256) void kv8_dequant_rows_kernel(const uint8_t* __restrict__ kv8, int64_t ld_kv8, uint16_t* __restrict__ dst,
+                                                               int64_t ld_dst, int B, int T, int Tmax, int dm) {
+  const int upr = 2 * dm / 16;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * T * upr) return;
+  const int64_t row = i / upr;
+  const int c = (int)(i - row * upr);
+  const int b = (int)(row / T), t = (int)(row - (int64_t)b * T);
+  const uint8_t* rowp = kv8 + ((int64_t)b * Tmax + t) * ld_kv8;
+  const u32x4_t q = *reinterpret_cast<const u32x4_t*>(rowp + c * 16);
+  const unsigned sb = rowp[2 * dm + c];
+  uint16_t* d = dst + row * ld_dst + c * 16;
+  st_bf16x8(d, kv8_deq8_bf16(u32x2_t{q[0], q[1]}, sb));
+  st_bf16x8(d + 8, kv8_deq8_bf16(u32x2_t{q[2], q[3]}, sb));
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // plm_attn_decode
 // ---------------------------------------------------------------------------------------------------------------------------------
+// What a lane holds of one key row, by cache format: 8 elements of k and of v.  bf16: two 16-byte loads.  FP8: two 8-byte code loads
+// and the two scale bytes of the blocks they lie in, dequantised on use - code * 2^(s - 127) is exact in fp32, so the kernel computes,
+// bit for bit, what the bf16 instantiation computes on the dequantised cache.
+template <typename KV>
+struct DecRows;  // the DEC_UNROLL key rows a lane has in flight
+template <>
+struct DecRows<uint16_t> {
+  bf16x8_t kk[DEC_UNROLL], vv[DEC_UNROLL];
+  __device__ __forceinline__ void zero(int u) {
+    kk[u] = zero_bf16x8();
+    vv[u] = zero_bf16x8();
+  }
+  __device__ __forceinline__ void load(int u, const uint16_t* p, const uint16_t*, int dm) {
+    kk[u] = ld_bf16x8(p);
+    vv[u] = ld_bf16x8(p + dm);
+  }
+  __device__ __forceinline__ void prep(int) {}
+  __device__ __forceinline__ float kx(int u, int e) const { return bf2f(kk[u][e]); }
+  __device__ __forceinline__ float vx(int u, int e) const { return bf2f(vv[u][e]); }
+};
+template <>
+struct DecRows<uint8_t> {
+  u32x2_t kk[DEC_UNROLL], vv[DEC_UNROLL];
+  unsigned ks[DEC_UNROLL], vs[DEC_UNROLL];
+  float kf[8], vf[8];  // the row prep() dequantised last
+  __device__ __forceinline__ void zero(int u) {
+    kk[u] = u32x2_t{0u, 0u};
+    vv[u] = u32x2_t{0u, 0u};
+    ks[u] = vs[u] = 0u;
+  }
+  __device__ __forceinline__ void load(int u, const uint8_t* p, const uint8_t* sp, int dm) {  // sp: the k scale byte; + dm/16: the v scale byte
+    kk[u] = *reinterpret_cast<const u32x2_t*>(p);
+    vv[u] = *reinterpret_cast<const u32x2_t*>(p + dm);
+    ks[u] = sp[0];
+    vs[u] = sp[dm >> 4];
+  }
+  __device__ __forceinline__ void prep(int u) {
+    kv8_deq8(kk[u], ks[u], kf);
+    kv8_deq8(vv[u], vs[u], vf);
+  }
+  __device__ __forceinline__ float kx(int, int e) const { return kf[e]; }
+  __device__ __forceinline__ float vx(int, int e) const { return vf[e]; }
+};
+
 // exp2(x - m) with the one hazard of an online softmax taken out: when nothing has been seen yet m is -inf and x may be too
 // (-inf - -inf = NaN); subtracting 0 instead gives exp2(-inf) = 0, which is the right weight of an empty partial
 __device__ __forceinline__ float dec_base(float m) { return m == -INFINITY ? 0.f : m; }
 
 // Workspace: ml fp32 [B*nh, S, 2] (running maximum in log2 units, sum of 2^(s - m)) then acc fp32 [B*nh, S, hd] (sum of 2^(s - m) v).
-template <int HD>
-__global__ __launch_bounds__(DEC_THREADS) void attn_decode_split_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ kv,
+// KV = uint16_t: the bf16 cache, ld_kv in elements; uint8_t: the FP8 cache, ld_kv in bytes.  One body: the key -> (wave, lane group)
+// assignment, the loop and the order of every fp32 operation do not depend on the format.
+template <int HD, typename KV>
+__global__ __launch_bounds__(DEC_THREADS) void attn_decode_split_kernel(const uint16_t* __restrict__ q, const KV* __restrict__ kv,
                                                                         int64_t ld_kv, const int32_t* __restrict__ lens,
                                                                         float* __restrict__ ws_ml, float* __restrict__ ws_acc, int Tmax, int nh,
                                                                         int S, float c2) {
@@ -114,32 +253,31 @@ __global__ __launch_bounds__(DEC_THREADS) void attn_decode_split_kernel(const ui
 #pragma unroll
     for (int e = 0; e < 8; ++e) qf[e] = bf2f(qv[e]) * c2;
   }
-  const uint16_t* kbase = kv + (int64_t)b * Tmax * ld_kv + h * HD + sub * 8;  // + j * ld_kv: k of key j; + dm: its v
+  const KV* kbase = kv + (int64_t)b * Tmax * ld_kv + h * HD + sub * 8;  // + j * ld_kv: k of key j; + dm: its v
+  // FP8: the scale byte of this lane's k block (+ j * ld_kv; + dm / 16: of its v block); the bf16 rows have none
+  const KV* sbase = sizeof(KV) == 1 ? kv + (int64_t)b * Tmax * ld_kv + 2 * dm + ((h * HD + sub * 8) >> 4) : kbase;
 
   float m = -INFINITY, l = 0.f, acc[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = 0.f;
 
   for (int j0 = k0 + wave * (KPW * DEC_UNROLL); j0 < k1; j0 += DEC_WAVES * KPW * DEC_UNROLL) {
-    bf16x8_t kk[DEC_UNROLL], vv[DEC_UNROLL];
+    DecRows<KV> rows;
     bool ok[DEC_UNROLL];
 #pragma unroll
     for (int u = 0; u < DEC_UNROLL; ++u) {  // all loads first: the kernel lives on memory-level parallelism
       const int j = j0 + u * KPW + grp;
       ok[u] = j < k1;
-      kk[u] = zero_bf16x8();
-      vv[u] = zero_bf16x8();
-      if (ok[u]) {  // rows at and beyond lens[b] are never read (they may hold anything, and j may be past Tmax)
-        const uint16_t* p = kbase + (int64_t)j * ld_kv;
-        kk[u] = ld_bf16x8(p);
-        vv[u] = ld_bf16x8(p + dm);
-      }
+      rows.zero(u);
+      // rows at and beyond lens[b] are never read (they may hold anything, and j may be past Tmax)
+      if (ok[u]) rows.load(u, kbase + (int64_t)j * ld_kv, sbase + (int64_t)j * ld_kv, dm);
     }
 #pragma unroll
     for (int u = 0; u < DEC_UNROLL; ++u) {
+      rows.prep(u);
       float d = 0.f;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) d = fmaf(qf[e], bf2f(kk[u][e]), d);
+      for (int e = 0; e < 8; ++e) d = fmaf(qf[e], rows.kx(u, e), d);
 #pragma unroll
       for (int o = G / 2; o > 0; o >>= 1) d += __shfl_xor(d, o, PLM_WAVE);  // inside the lane group
       const float sc = ok[u] ? d : -INFINITY;
@@ -149,7 +287,7 @@ __global__ __launch_bounds__(DEC_THREADS) void attn_decode_split_kernel(const ui
       const float p = __builtin_amdgcn_exp2f(sc - base);
       l = l * alpha + p;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) acc[e] = acc[e] * alpha + p * bf2f(vv[u][e]);
+      for (int e = 0; e < 8; ++e) acc[e] = acc[e] * alpha + p * rows.vx(u, e);
       m = mn;
     }
   }
@@ -201,8 +339,9 @@ __global__ __launch_bounds__(DEC_THREADS) void attn_decode_split_kernel(const ui
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Workspace: acc fp32 [B*nh, S, n, hd] (sum of 2^(s - m) v) then ml fp32 [B*nh, S, n, 2] (running maximum in log2 units, sum of
 // 2^(s - m)); rows r >= c_b are neither written nor read.
-template <int HD>
-__global__ __launch_bounds__(256, 2) void attn_extend_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ kv, int64_t ld_kv,
+// KV as in attn_decode_split_kernel: the FP8 instantiation differs in the tile loads alone, which dequantise into the same LDS image.
+template <int HD, typename KV>
+__global__ __launch_bounds__(256, 2) void attn_extend_kernel(const uint16_t* __restrict__ q, const KV* __restrict__ kv, int64_t ld_kv,
                                                              const int32_t* __restrict__ lens0, const int32_t* __restrict__ n_new,
                                                              uint16_t* __restrict__ out, float* __restrict__ lse, float* __restrict__ ws_acc,
                                                              float* __restrict__ ws_ml, int n, int Tmax, int nh, int nqt, int S, float scale) {
@@ -227,7 +366,7 @@ __global__ __launch_bounds__(256, 2) void attn_extend_kernel(const uint16_t* __r
   const int rlast = min(q0 + 127, cb - 1);
   const int kend = rlast < q0 ? k0 : min(k1, min(l0 + min(rlast, Tmax), Tmax - 1) + 1);
 
-  const uint16_t* kbase = kv + (int64_t)b * Tmax * ld_kv + h * HD;  // + j * ld_kv: k of key j; + dm: its v
+  const KV* kbase = kv + (int64_t)b * Tmax * ld_kv + h * HD;  // + j * ld_kv: k of key j; + dm: its v
   const float c2 = scale * GLOG2E;
   bf16x8_t qf[NKS];
 #pragma unroll
@@ -241,8 +380,14 @@ __global__ __launch_bounds__(256, 2) void attn_extend_kernel(const uint16_t* __r
   char* sV = smem + TL::BYTES;
   for (int kv0 = k0; kv0 < kend; kv0 += 64) {  // (bounds uniform over the workgroup)
     __syncthreads();                           // everyone is done with the previous tile
-    TL::load(sK, kbase, ld_kv, kv0, L - 1, tid);
-    TL::load(sV, kbase + dm, ld_kv, kv0, L - 1, tid);
+    if constexpr (sizeof(KV) == 2) {
+      TL::load(sK, kbase, ld_kv, kv0, L - 1, tid);
+      TL::load(sV, kbase + dm, ld_kv, kv0, L - 1, tid);
+    } else {  // the scale bytes of this head: k's behind the 2 * dm code bytes of the row, v's dm / 16 further
+      const KV* sbase = kv + (int64_t)b * Tmax * ld_kv + 2 * dm + ((h * HD) >> 4);
+      TL::load(sK, kbase, sbase, ld_kv, kv0, L - 1, tid);
+      TL::load(sV, kbase + dm, sbase + (dm >> 4), ld_kv, kv0, L - 1, tid);
+    }
     __syncthreads();
     if (__ballot(kv0 <= lim) == 0) continue;            // none of this wave's 32 queries sees the tile (wave-uniform)
     const bool whole = __ballot(kv0 + 63 > lim) == 0;   // every query of the wave sees every key of it: the unmasked path
@@ -435,14 +580,75 @@ extern "C" int plm_kv_append_rope_rows(const uint16_t* qkv, int64_t ld_qkv, cons
                      hd, true, stream);
 }
 
-// the attention stage's refusals; *S is the resolved split count
-static int check_attend(const char* fn, const uint16_t* q, const uint16_t* kv, int64_t ld_kv, const int32_t* lens, const uint16_t* out, int64_t B,
+
+// the FP8 cache's stride rule: bytes, a multiple of 16 (the 16-byte code stores and 8-byte code loads stay aligned), at least the payload
+static bool kv8_stride_ok(int64_t ld_kv8, int64_t dm) { return ld_kv8 % 16 == 0 && ld_kv8 >= kv8_row_payload(dm); }
+#define KV8_STRIDE_MSG "%s: the FP8 cache's row stride must be a multiple of 16 bytes and at least 2*nh*hd + nh*hd/8"
+
+extern "C" int plm_kv8_append_rope_rows(const uint16_t* qkv, int64_t ld_qkv, const int32_t* lens0, const int32_t* n_new, const float* rope_cos,
+                                        const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint8_t* kv8, int64_t ld_kv8, int32_t* status,
+                                        int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, void* stream) {
+  const char* fn = "plm_kv8_append_rope_rows";
+  PLM_REQUIRE(qkv && lens0 && rope_cos && rope_sin && q_out && kv8 && status, "%s: null pointer", fn);
+  PLM_REQUIRE(hd == 32 || hd == 64 || hd == 128, "%s: head_dim %ld unsupported (32, 64, 128)", fn, (long)hd);
+  PLM_REQUIRE(shape_ok(B, n, nh, hd, Tmax) && rope_T > 0 && rope_T < (1 << 24),
+              "%s: bad shape B=%ld n=%ld Tmax=%ld nh=%ld rope_T=%ld (n >= 1, B*n < 2^31)", fn, (long)B, (long)n, (long)Tmax, (long)nh, (long)rope_T);
+  PLM_REQUIRE(ld_qkv >= 3 * nh * hd && ld_qkv % 8 == 0, "%s: the qkv row stride must be a multiple of 8 and at least 3*nh*hd", fn);
+  PLM_REQUIRE(kv8_stride_ok(ld_kv8, nh * hd), KV8_STRIDE_MSG, fn);
+  PLM_REQUIRE(((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(q_out) | reinterpret_cast<uintptr_t>(kv8) |
+                reinterpret_cast<uintptr_t>(rope_cos) | reinterpret_cast<uintptr_t>(rope_sin)) & 15) == 0,
+              "%s: qkv, q_out, kv8 and the RoPE tables must be 16-byte aligned", fn);
+  const int64_t blocks = plm_cdiv(B * n * (3 * nh * hd / 16), 256);
+  PLM_REQUIRE(blocks < ((int64_t)1 << 31), "%s: bad shape: B*n*nh*hd too large for one launch", fn);
+  hipLaunchKernelGGL(kv8_append_rope_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, qkv, ld_qkv, lens0, n_new, rope_cos,
+                     rope_sin, (int)rope_T, q_out, kv8, ld_kv8, status, (int)B, (int)n, (int)Tmax, (int)nh, (int)hd, 1.f);
+  PLM_CHECK_LAUNCH(fn);
+  return PLM_OK;
+}
+
+// rows 0 .. T-1 of every sequence between bf16 k | v rows [B, T, ld] and the FP8 cache: the shared refusals
+static int kv8_check_rows(const char* fn, const void* rows, int64_t ld, const void* kv8, int64_t ld_kv8, int64_t B, int64_t T, int64_t Tmax,
+                          int64_t nh, int64_t hd) {
+  PLM_REQUIRE(rows && kv8, "%s: null pointer", fn);
+  PLM_REQUIRE(hd == 32 || hd == 64 || hd == 128, "%s: head_dim %ld unsupported (32, 64, 128)", fn, (long)hd);
+  PLM_REQUIRE(shape_ok(B, T, nh, hd, Tmax) && T <= Tmax, "%s: bad shape B=%ld T=%ld Tmax=%ld nh=%ld (1 <= T <= Tmax, B*T < 2^31)", fn, (long)B,
+              (long)T, (long)Tmax, (long)nh);
+  PLM_REQUIRE(ld >= 2 * nh * hd && ld % 8 == 0, "%s: the bf16 row stride must be a multiple of 8 and at least 2*nh*hd", fn);
+  PLM_REQUIRE(kv8_stride_ok(ld_kv8, nh * hd), KV8_STRIDE_MSG, fn);
+  PLM_REQUIRE(((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(kv8)) & 15) == 0, "%s: the bf16 rows and kv8 must be 16-byte aligned",
+              fn);
+  PLM_REQUIRE(plm_cdiv(B * T * (nh * hd / 8), 256) < ((int64_t)1 << 31), "%s: bad shape: B*T*nh*hd too large for one launch", fn);
+  return PLM_OK;
+}
+
+extern "C" int plm_kv8_quant_rows(const uint16_t* src, int64_t ld_src, uint8_t* kv8, int64_t ld_kv8, int64_t B, int64_t T, int64_t Tmax,
+                                  int64_t nh, int64_t hd, void* stream) {
+  if (const int e = kv8_check_rows("plm_kv8_quant_rows", src, ld_src, kv8, ld_kv8, B, T, Tmax, nh, hd)) return e;
+  hipLaunchKernelGGL(kv8_quant_rows_kernel, dim3((unsigned)plm_cdiv(B * T * (nh * hd / 8), 256)), dim3(256), 0, (hipStream_t)stream, src, ld_src,
+                     kv8, ld_kv8, (int)B, (int)T, (int)Tmax, (int)(nh * hd));
+  PLM_CHECK_LAUNCH("plm_kv8_quant_rows");
+  return PLM_OK;
+}
+
+extern "C" int plm_kv8_dequant_rows(const uint8_t* kv8, int64_t ld_kv8, uint16_t* dst, int64_t ld_dst, int64_t B, int64_t T, int64_t Tmax,
+                                    int64_t nh, int64_t hd, void* stream) {
+  if (const int e = kv8_check_rows("plm_kv8_dequant_rows", dst, ld_dst, kv8, ld_kv8, B, T, Tmax, nh, hd)) return e;
+  hipLaunchKernelGGL(kv8_dequant_rows_kernel, dim3((unsigned)plm_cdiv(B * T * (nh * hd / 8), 256)), dim3(256), 0, (hipStream_t)stream, kv8, ld_kv8,
+                     dst, ld_dst, (int)B, (int)T, (int)Tmax, (int)(nh * hd));
+  PLM_CHECK_LAUNCH("plm_kv8_dequant_rows");
+  return PLM_OK;
+}
+
+// the attention stage's refusals; *S is the resolved split count.  KV picks the cache format's stride rule.
+template <typename KV>
+static int check_attend(const char* fn, const uint16_t* q, const KV* kv, int64_t ld_kv, const int32_t* lens, const uint16_t* out, int64_t B,
                         int64_t n, int64_t Tmax, int64_t nh, int64_t hd, int splits, const void* workspace, size_t workspace_bytes, int* S) {
   PLM_REQUIRE(q && kv && lens && out && workspace, "%s: null pointer", fn);
   PLM_REQUIRE(hd == 32 || hd == 64 || hd == 128, "%s: head_dim %ld unsupported (32, 64, 128)", fn, (long)hd);
   PLM_REQUIRE(shape_ok(B, n, nh, hd, Tmax), "%s: bad shape B=%ld n=%ld Tmax=%ld nh=%ld (n >= 1, B*n < 2^31)", fn, (long)B, (long)n, (long)Tmax,
               (long)nh);
-  PLM_REQUIRE(ld_kv >= 2 * nh * hd && ld_kv % 8 == 0, "%s: the cache's row stride must be a multiple of 8 and at least 2*nh*hd", fn);
+  if (sizeof(KV) == 2) PLM_REQUIRE(ld_kv >= 2 * nh * hd && ld_kv % 8 == 0, "%s: the cache's row stride must be a multiple of 8 and at least 2*nh*hd", fn);
+  else PLM_REQUIRE(kv8_stride_ok(ld_kv, nh * hd), KV8_STRIDE_MSG, fn);
   PLM_REQUIRE(((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kv) | reinterpret_cast<uintptr_t>(out) |
                 reinterpret_cast<uintptr_t>(workspace)) & 15) == 0,
               "%s: q, kv, out and the workspace must be 16-byte aligned", fn);
@@ -456,55 +662,80 @@ static int check_attend(const char* fn, const uint16_t* q, const uint16_t* kv, i
   return PLM_OK;
 }
 
-template <int HD>
-static void dec_launch(const uint16_t* q, const uint16_t* kv, int64_t ld_kv, const int32_t* lens, uint16_t* out, float* lse, int64_t B,
-                       int64_t Tmax, int64_t nh, int S, float* ws, hipStream_t s) {
+template <int HD, typename KV>
+static void dec_launch(const uint16_t* q, const KV* kv, int64_t ld_kv, const int32_t* lens, uint16_t* out, float* lse, int64_t B, int64_t Tmax,
+                       int64_t nh, int S, float* ws, hipStream_t s) {
   float* ws_ml = ws;
   float* ws_acc = ws + (size_t)B * nh * S * 2;
   const float c2 = (1.f / sqrtf((float)HD)) * GLOG2E;
-  hipLaunchKernelGGL(attn_decode_split_kernel<HD>, dim3((unsigned)(B * nh), (unsigned)S), dim3(DEC_THREADS), 0, s, q, kv, ld_kv, lens, ws_ml,
+  hipLaunchKernelGGL((attn_decode_split_kernel<HD, KV>), dim3((unsigned)(B * nh), (unsigned)S), dim3(DEC_THREADS), 0, s, q, kv, ld_kv, lens, ws_ml,
                      ws_acc, (int)Tmax, (int)nh, S, c2);
   hipLaunchKernelGGL(attn_cache_combine_kernel<HD>, dim3((unsigned)(B * nh)), dim3(HD), 0, s, ws_acc, ws_ml, (const int32_t*)nullptr, out, lse, 1,
                      (int)nh, S);
 }
 
-extern "C" int plm_attn_decode(const uint16_t* q, const uint16_t* kv, int64_t ld_kv, const int32_t* lens, uint16_t* out, float* lse, int64_t B,
-                               int64_t Tmax, int64_t nh, int64_t hd, int splits, void* workspace, size_t workspace_bytes, void* stream) {
+// plm_attn_decode and plm_attn_decode_kv8: `fn` is the entry point the caller sees
+template <typename KV>
+static int attn_decode(const char* fn, const uint16_t* q, const KV* kv, int64_t ld_kv, const int32_t* lens, uint16_t* out, float* lse, int64_t B,
+                       int64_t Tmax, int64_t nh, int64_t hd, int splits, void* workspace, size_t workspace_bytes, void* stream) {
   int S;
-  if (const int e = check_attend("plm_attn_decode", q, kv, ld_kv, lens, out, B, 1, Tmax, nh, hd, splits, workspace, workspace_bytes, &S)) return e;
+  if (const int e = check_attend(fn, q, kv, ld_kv, lens, out, B, 1, Tmax, nh, hd, splits, workspace, workspace_bytes, &S)) return e;
   hipStream_t s = (hipStream_t)stream;
   float* ws = static_cast<float*>(workspace);
   if (hd == 32) dec_launch<32>(q, kv, ld_kv, lens, out, lse, B, Tmax, nh, S, ws, s);
   else if (hd == 64) dec_launch<64>(q, kv, ld_kv, lens, out, lse, B, Tmax, nh, S, ws, s);
   else dec_launch<128>(q, kv, ld_kv, lens, out, lse, B, Tmax, nh, S, ws, s);
-  PLM_CHECK_LAUNCH("plm_attn_decode");
+  PLM_CHECK_LAUNCH(fn);
   return PLM_OK;
 }
 
-template <int HD>
-static void ext_launch(const uint16_t* q, const uint16_t* kv, int64_t ld_kv, const int32_t* lens0, const int32_t* n_new, uint16_t* out, float* lse,
+extern "C" int plm_attn_decode(const uint16_t* q, const uint16_t* kv, int64_t ld_kv, const int32_t* lens, uint16_t* out, float* lse, int64_t B,
+                               int64_t Tmax, int64_t nh, int64_t hd, int splits, void* workspace, size_t workspace_bytes, void* stream) {
+  return attn_decode("plm_attn_decode", q, kv, ld_kv, lens, out, lse, B, Tmax, nh, hd, splits, workspace, workspace_bytes, stream);
+}
+
+extern "C" int plm_attn_decode_kv8(const uint16_t* q, const uint8_t* kv8, int64_t ld_kv8, const int32_t* lens, uint16_t* out, float* lse, int64_t B,
+                                   int64_t Tmax, int64_t nh, int64_t hd, int splits, void* workspace, size_t workspace_bytes, void* stream) {
+  return attn_decode("plm_attn_decode_kv8", q, kv8, ld_kv8, lens, out, lse, B, Tmax, nh, hd, splits, workspace, workspace_bytes, stream);
+}
+
+template <int HD, typename KV>
+static void ext_launch(const uint16_t* q, const KV* kv, int64_t ld_kv, const int32_t* lens0, const int32_t* n_new, uint16_t* out, float* lse,
                        int64_t B, int64_t n, int64_t Tmax, int64_t nh, int S, float* ws, hipStream_t s) {
   float* ws_acc = ws;
   float* ws_ml = ws + (size_t)B * nh * S * n * HD;
   const int nqt = (int)plm_cdiv(n, 128);
   const float scale = 1.f / sqrtf((float)HD);
-  hipLaunchKernelGGL(attn_extend_kernel<HD>, dim3((unsigned)(B * nh * nqt), (unsigned)S), dim3(256), 0, s, q, kv, ld_kv, lens0, n_new, out, lse,
-                     ws_acc, ws_ml, (int)n, (int)Tmax, (int)nh, nqt, S, scale);
+  hipLaunchKernelGGL((attn_extend_kernel<HD, KV>), dim3((unsigned)(B * nh * nqt), (unsigned)S), dim3(256), 0, s, q, kv, ld_kv, lens0, n_new, out,
+                     lse, ws_acc, ws_ml, (int)n, (int)Tmax, (int)nh, nqt, S, scale);
   if (S > 1)
     hipLaunchKernelGGL(attn_cache_combine_kernel<HD>, dim3((unsigned)(B * nh * n)), dim3(HD), 0, s, ws_acc, ws_ml, n_new, out, lse, (int)n,
                        (int)nh, S);
 }
 
-extern "C" int plm_attn_extend(const uint16_t* q, const uint16_t* kv, int64_t ld_kv, const int32_t* lens0, const int32_t* n_new, uint16_t* out,
-                               float* lse, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, int splits, void* workspace,
-                               size_t workspace_bytes, void* stream) {
+template <typename KV>
+static int attn_extend(const char* fn, const uint16_t* q, const KV* kv, int64_t ld_kv, const int32_t* lens0, const int32_t* n_new, uint16_t* out,
+                       float* lse, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, int splits, void* workspace, size_t workspace_bytes,
+                       void* stream) {
   int S;
-  if (const int e = check_attend("plm_attn_extend", q, kv, ld_kv, lens0, out, B, n, Tmax, nh, hd, splits, workspace, workspace_bytes, &S)) return e;
+  if (const int e = check_attend(fn, q, kv, ld_kv, lens0, out, B, n, Tmax, nh, hd, splits, workspace, workspace_bytes, &S)) return e;
   hipStream_t s = (hipStream_t)stream;
   float* ws = static_cast<float*>(workspace);
   if (hd == 32) ext_launch<32>(q, kv, ld_kv, lens0, n_new, out, lse, B, n, Tmax, nh, S, ws, s);
   else if (hd == 64) ext_launch<64>(q, kv, ld_kv, lens0, n_new, out, lse, B, n, Tmax, nh, S, ws, s);
   else ext_launch<128>(q, kv, ld_kv, lens0, n_new, out, lse, B, n, Tmax, nh, S, ws, s);
-  PLM_CHECK_LAUNCH("plm_attn_extend");
+  PLM_CHECK_LAUNCH(fn);
   return PLM_OK;
+}
+
+extern "C" int plm_attn_extend(const uint16_t* q, const uint16_t* kv, int64_t ld_kv, const int32_t* lens0, const int32_t* n_new, uint16_t* out,
+                               float* lse, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, int splits, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  return attn_extend("plm_attn_extend", q, kv, ld_kv, lens0, n_new, out, lse, B, n, Tmax, nh, hd, splits, workspace, workspace_bytes, stream);
+}
+
+extern "C" int plm_attn_extend_kv8(const uint16_t* q, const uint8_t* kv8, int64_t ld_kv8, const int32_t* lens0, const int32_t* n_new,
+                                   uint16_t* out, float* lse, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, int splits,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+  return attn_extend("plm_attn_extend_kv8", q, kv8, ld_kv8, lens0, n_new, out, lse, B, n, Tmax, nh, hd, splits, workspace, workspace_bytes, stream);
 }

@@ -2,7 +2,7 @@
 // attn_masked.hip: head dims 32 / 64 / 128 with bit-packed dense masks).  A template on the head dim, so it does not include attn_common.h
 // (whose HD macro is the tuned family's 64).
 #pragma once
-#include "plm_device.h"
+#include "plm_fp8.h"
 
 #define GLOG2E 1.4426950408889634f
 
@@ -16,6 +16,19 @@ struct GenTile {
     for (int c = tid; c < 64 * CPR; c += 256) {
       const int r = c / CPR, k = c - r * CPR;
       *reinterpret_cast<bf16x8_t*>(tile + r * ROWB + k * 16) = ld_bf16x8(src + (int64_t)min(row0 + r, last_row) * ld + k * 8);
+    }
+  }
+  // the same image from an FP8 cache (plm_fp8.h): codes = the row's e4m3 bytes at this head's first column,
+  // scales = the row's E8M0 bytes at this head's first 16-block, both [*, ld] bytes.  A 16-byte LDS chunk is 8 codes times their block's
+  // scale, exact in bf16; the row clamp is load's.
+  static __device__ __forceinline__ void load(char* tile, const uint8_t* codes, const uint8_t* scales, int64_t ld, int row0, int last_row,
+                                              int tid) {
+    constexpr int CPR = HD / 8;
+    for (int c = tid; c < 64 * CPR; c += 256) {
+      const int r = c / CPR, k = c - r * CPR;
+      const int64_t ro = (int64_t)min(row0 + r, last_row) * ld;
+      const u32x2_t w = *reinterpret_cast<const u32x2_t*>(codes + ro + k * 8);
+      *reinterpret_cast<bf16x8_t*>(tile + r * ROWB + k * 16) = kv8_deq8_bf16(w, scales[ro + (k >> 1)]);
     }
   }
   // A operand, i = tile row (lane & 31), k = head dims ks*16 + hi*8 .. + 7

@@ -25,7 +25,7 @@
 // (the LDS tile); inside a chunk the four waves take contiguous runs of its 32-wide K steps, every wave loads all its weight fragments of
 // the chunk BEFORE the tile is built, so the prologue runs under the loads.  The four waves' partial tiles meet in LDS and are added in
 // wave order by the thread that owns the element: no float atomic, nothing depends on arrival order, two runs are bit-equal.
-#include "plm_device.h"
+#include "plm_fp8.h"
 
 #define DF_THREADS 256
 #define DF_WAVES 4
@@ -35,7 +35,7 @@
 #define DF_TILE_ELEMS 16640 // 16 x (1024 + 8) = 32 x (512 + 8)
 
 enum { DF_PRO_BF16 = 0, DF_PRO_NORM = 1 };
-enum { DF_EPI_RESIDUAL = 1, DF_EPI_GLU = 2, DF_EPI_SILU = 3, DF_EPI_RELU_SQ = 4, DF_EPI_QKV_ROWS = 5 };
+enum { DF_EPI_RESIDUAL = 1, DF_EPI_GLU = 2, DF_EPI_SILU = 3, DF_EPI_RELU_SQ = 4, DF_EPI_QKV_ROWS = 5, DF_EPI_QKV_ROWS_KV8 = 6 };
 
 struct DfArgs {
   // prologue
@@ -49,7 +49,7 @@ struct DfArgs {
   // epilogues
   float* xio;            // RESIDUAL: x [M, N], in place
   uint16_t* out;         // QKV_ROWS: q_out [M, d]; activations: act [M, h]
-  uint16_t* kv;          // QKV_ROWS
+  uint16_t* kv;          // QKV_ROWS; QKV_ROWS_KV8: the FP8 cache's bytes, ld_kv in bytes
   int64_t ld_kv;
   const float* rcos;
   const float* rsin;
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(DF_THREADS) void decode_fused_kernel(const DfArgs p
     r.x += bf2f(f2bf(v0));
     r.y += bf2f(f2bf(v1));
     *reinterpret_cast<float2*>(xo) = r;
-  } else if (EPI == DF_EPI_QKV_ROWS) {  // plm_kv_append_rope_rows's contract: row m is chunk row r of sequence b, at position lens0[b] + r
+  } else if (EPI == DF_EPI_QKV_ROWS || EPI == DF_EPI_QKV_ROWS_KV8) {  // plm_kv_append_rope_rows's contract: row m is chunk row r of sequence b, at position lens0[b] + r
     const int col = blockIdx.x * DF_TILE_N + c2;
     const int dm = p.dm, n = p.n;
     const int b = m / n, r = m - b * n;
@@ -198,8 +198,32 @@ __global__ __launch_bounds__(DF_THREADS) void decode_fused_kernel(const DfArgs p
       const int64_t ti = (int64_t)t * (p.hd / 2) + (col % p.hd) / 2;
       df_rope2(b0, b1, p.rcos[ti], p.rsin[ti]);
     }
-    if (col < dm) df_st2(p.out + (int64_t)m * dm + col, b0, b1);
-    else df_st2(p.kv + ((int64_t)b * p.Tmax + t) * p.ld_kv + (col - dm), b0, b1);
+    if (col < dm) {
+      df_st2(p.out + (int64_t)m * dm + col, b0, b1);
+    } else if (EPI == DF_EPI_QKV_ROWS) {
+      df_st2(p.kv + ((int64_t)b * p.Tmax + t) * p.ld_kv + (col - dm), b0, b1);
+    } else {
+      // The FP8 cache.  The 16 columns of this workgroup's tile are one block of the cache row, held as column pairs by the 8 adjacent
+      // lanes tid & 7 of this row; all 8 share m, b and r and col >= dm is uniform over the workgroup, so they are here together.  The
+      // block maximum is three butterfly steps; the 16 codes meet in the row's first lane, which stores them as one 16-byte vector.
+      const float x0 = bf2f(b0), x1 = bf2f(b1);
+      float amax = fmaxf(kv8_mag(x0), kv8_mag(x1));
+#pragma unroll
+      for (int o = 1; o < 8; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o, PLM_WAVE));
+      const unsigned sb = kv8_scale_byte(amax);
+      const unsigned pc = kv8_code(x0, amax, sb) | (kv8_code(x1, amax, sb) << 8);  // columns c2, c2 + 1
+      const unsigned w = pc | ((unsigned)__shfl_xor((int)pc, 1, PLM_WAVE) << 16);  // even lanes: columns c2 .. c2 + 3
+      const int l0g = (tid & 63) & ~7;
+      u32x4_t q;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) q[i] = (unsigned)__shfl((int)w, l0g + 2 * i, PLM_WAVE);
+      if ((tid & 7) == 0) {
+        uint8_t* rowp = reinterpret_cast<uint8_t*>(p.kv) + ((int64_t)b * p.Tmax + t) * p.ld_kv;
+        const int blk = col - dm;  // the block's first column among the 2 * dm k | v columns
+        *reinterpret_cast<u32x4_t*>(rowp + blk) = q;
+        rowp[2 * dm + (blk >> 4)] = (uint8_t)sb;
+      }
+    }
   } else if (EPI == DF_EPI_GLU) {
     if (c2 >= 8) return;  // columns 0..7 of the tile are the gates, 8..15 the ups of the same outputs
     float u0 = s_red[0][m][c2 + 8], u1 = s_red[0][m][c2 + 9];
@@ -243,7 +267,7 @@ static int df_check_rows(const char* fn, int64_t M) {
 // the qkv stage: B sequences of n rows, M = B*n (a decode step: n = 1, lens0 = the positions)
 static int df_check_qkv(const char* fn, const float* x, const float* nw, const uint16_t* w_qkv, const int32_t* lens0, const float* rope_cos,
                         const float* rope_sin, int64_t rope_T, const uint16_t* q_out, const uint16_t* kv, int64_t ld_kv, const int32_t* status,
-                        int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd) {
+                        int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, bool kv8 = false) {
   PLM_REQUIRE(x && nw && w_qkv && lens0 && rope_cos && rope_sin && q_out && kv && status, "%s: null pointer", fn);
   PLM_REQUIRE(n >= 1 && n <= DF_MAX_ROWS && B >= 1 && B <= DF_MAX_ROWS && B * n <= DF_MAX_ROWS,
               "%s: B=%ld chunks of n=%ld rows unsupported (n >= 1, 1 <= B*n <= %d rows)", fn, (long)B, (long)n, DF_MAX_ROWS);
@@ -251,7 +275,9 @@ static int df_check_qkv(const char* fn, const float* x, const float* nw, const u
   PLM_REQUIRE(nh > 0 && nh * hd <= DF_MAX_DIM / 4 && Tmax > 0 && Tmax < (1 << 24) && rope_T > 0 && rope_T < (1 << 24),
               "%s: bad shape Tmax=%ld nh=%ld rope_T=%ld", fn, (long)Tmax, (long)nh, (long)rope_T);
   PLM_REQUIRE((nh * hd) % 32 == 0, "%s: d = nh*hd = %ld unsupported (d %% 32 == 0)", fn, (long)(nh * hd));
-  PLM_REQUIRE(ld_kv >= 2 * nh * hd && ld_kv % 8 == 0, "%s: the cache's row stride must be a multiple of 8 and at least 2*nh*hd", fn);
+  if (kv8) PLM_REQUIRE(ld_kv >= kv8_row_payload(nh * hd) && ld_kv % 16 == 0,
+                       "%s: the FP8 cache's row stride must be a multiple of 16 bytes and at least 2*nh*hd + nh*hd/8", fn);
+  else PLM_REQUIRE(ld_kv >= 2 * nh * hd && ld_kv % 8 == 0, "%s: the cache's row stride must be a multiple of 8 and at least 2*nh*hd", fn);
   PLM_REQUIRE(df_aligned(x, nw, w_qkv, q_out, kv), "%s: x, the norm weight, w_qkv, q_out and kv must be 16-byte aligned", fn);
   return PLM_OK;
 }
@@ -285,14 +311,15 @@ static void df_launch(const DfArgs& a, int64_t blocks, hipStream_t s) {
 
 static void df_launch_qkv(const float* x, const float* nw, float eps, const uint16_t* w_qkv, const int32_t* lens0, const int32_t* n_new,
                           const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv,
-                          int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, hipStream_t s) {
+                          int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, hipStream_t s, bool kv8 = false) {
   DfArgs a = {};
   const int64_t d = nh * hd;
   a.x = x, a.nw = nw, a.eps = eps, a.w = w_qkv, a.M = (int)(B * n), a.N = (int)(3 * d), a.K = (int)d;
   a.out = q_out, a.kv = kv, a.ld_kv = ld_kv, a.rcos = rope_cos, a.rsin = rope_sin, a.status = status;
   a.rope_T = (int)rope_T, a.Tmax = (int)Tmax, a.hd = (int)hd, a.dm = (int)d;
   a.n = (int)n, a.lens0 = lens0, a.n_new = n_new;
-  df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS>(a, 3 * d / DF_TILE_N, s);
+  if (kv8) df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS_KV8>(a, 3 * d / DF_TILE_N, s);
+  else df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS>(a, 3 * d / DF_TILE_N, s);
 }
 
 static void df_launch_residual(float* x, const uint16_t* A, const uint16_t* w, int64_t M, int64_t N, int64_t K, hipStream_t s) {
@@ -384,7 +411,7 @@ static int df_layer(const char* fn, DfAttn attn, float* x, const float* attn_nor
                     const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* p0, const int32_t* p1,
                     const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t n,
                     int64_t Tmax, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits, void* workspace, size_t workspace_bytes,
-                    void* stream) {
+                    void* stream, bool kv8 = false) {
   PLM_REQUIRE(x && attn_norm_w && mlp_norm_w && w_qkv && w_out && w_fc1 && w_fc2 && p0 && (attn == DF_ATTN_EXTEND || p1) && rope_cos && rope_sin &&
                   kv && status && workspace,
               "%s: null pointer", fn);
@@ -393,7 +420,7 @@ static int df_layer(const char* fn, DfAttn attn, float* x, const float* attn_nor
   char* ws = static_cast<char*>(workspace);
   // every refusal of every stage before the first launch (the sub-buffers stand in for the stages' own operands)
   uint16_t* q = reinterpret_cast<uint16_t*>(ws);
-  if (const int e = df_check_qkv(fn, x, attn_norm_w, w_qkv, p0, rope_cos, rope_sin, rope_T, q, kv, ld_kv, status, B, n, Tmax, nh, hd)) return e;
+  if (const int e = df_check_qkv(fn, x, attn_norm_w, w_qkv, p0, rope_cos, rope_sin, rope_T, q, kv, ld_kv, status, B, n, Tmax, nh, hd, kv8)) return e;
   const int64_t M = B * n;
   if (const int e = df_check_residual(fn, x, q, w_out, M, d, d)) return e;
   if (const int e = df_check_fc1(fn, x, mlp_norm_w, w_fc1, q, M, d, hidden, mlp_kind)) return e;
@@ -414,10 +441,16 @@ static int df_layer(const char* fn, DfAttn attn, float* x, const float* attn_nor
   const size_t att_bytes = need - 2 * qb - ab;
   hipStream_t s = (hipStream_t)stream;
   df_launch_qkv(x, attn_norm_w, eps, w_qkv, p0, attn == DF_ATTN_EXTEND ? p1 : nullptr, rope_cos, rope_sin, rope_T, q, kv, ld_kv, status, B, n, Tmax,
-                nh, hd, s);
-  if (const int e = attn == DF_ATTN_DECODE ? plm_attn_decode(q, kv, ld_kv, p1, attn_out, nullptr, B, Tmax, nh, hd, splits, att, att_bytes, stream)
-                                           : plm_attn_extend(q, kv, ld_kv, p0, p1, attn_out, nullptr, B, n, Tmax, nh, hd, splits, att, att_bytes, stream))
-    return e;
+                nh, hd, s, kv8);
+  const uint8_t* c8 = reinterpret_cast<const uint8_t*>(kv);
+  int e;
+  if (attn == DF_ATTN_DECODE)
+    e = kv8 ? plm_attn_decode_kv8(q, c8, ld_kv, p1, attn_out, nullptr, B, Tmax, nh, hd, splits, att, att_bytes, stream)
+            : plm_attn_decode(q, kv, ld_kv, p1, attn_out, nullptr, B, Tmax, nh, hd, splits, att, att_bytes, stream);
+  else
+    e = kv8 ? plm_attn_extend_kv8(q, c8, ld_kv, p0, p1, attn_out, nullptr, B, n, Tmax, nh, hd, splits, att, att_bytes, stream)
+            : plm_attn_extend(q, kv, ld_kv, p0, p1, attn_out, nullptr, B, n, Tmax, nh, hd, splits, att, att_bytes, stream);
+  if (e) return e;
   df_launch_residual(x, attn_out, w_out, M, d, d, s);
   df_launch_fc1(x, mlp_norm_w, eps, w_fc1, act, M, d, hidden, mlp_kind, s);
   df_launch_residual(x, act, w_fc2, M, d, hidden, s);
@@ -441,4 +474,38 @@ extern "C" int plm_extend_layer_bf16(float* x, const float* attn_norm_w, const f
                                      int mlp_kind, int splits, void* workspace, size_t workspace_bytes, void* stream) {
   return df_layer("plm_extend_layer_bf16", DF_ATTN_EXTEND, x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, lens0, n_new, rope_cos,
                   rope_sin, rope_T, kv, ld_kv, status, B, n, Tmax, nh, hd, hidden, mlp_kind, splits, workspace, workspace_bytes, stream);
+}
+
+// ---- the same stage and layers over the FP8 cache: kv8 bytes, ld_kv8 in bytes; everything else as above ----
+extern "C" int plm_extend_norm_qkv_append_kv8_bf16(const float* x, const float* norm_w, float eps, const uint16_t* w_qkv, const int32_t* lens0,
+                                                   const int32_t* n_new, const float* rope_cos, const float* rope_sin, int64_t rope_T,
+                                                   uint16_t* q_out, uint8_t* kv8, int64_t ld_kv8, int32_t* status, int64_t B, int64_t n,
+                                                   int64_t Tmax, int64_t nh, int64_t hd, void* stream) {
+  const char* fn = "plm_extend_norm_qkv_append_kv8_bf16";
+  uint16_t* kv = reinterpret_cast<uint16_t*>(kv8);
+  if (const int e = df_check_qkv(fn, x, norm_w, w_qkv, lens0, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv8, status, B, n, Tmax, nh, hd, true)) return e;
+  df_launch_qkv(x, norm_w, eps, w_qkv, lens0, n_new, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv8, status, B, n, Tmax, nh, hd, (hipStream_t)stream,
+                true);
+  PLM_CHECK_LAUNCH(fn);
+  return PLM_OK;
+}
+
+extern "C" int plm_decode_layer_kv8_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                                         const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* pos,
+                                         const int32_t* lens, const float* rope_cos, const float* rope_sin, int64_t rope_T, uint8_t* kv8,
+                                         int64_t ld_kv8, int32_t* status, int64_t B, int64_t Tmax, int64_t nh, int64_t hd, int64_t hidden,
+                                         int mlp_kind, int splits, void* workspace, size_t workspace_bytes, void* stream) {
+  return df_layer("plm_decode_layer_kv8_bf16", DF_ATTN_DECODE, x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, pos, lens, rope_cos,
+                  rope_sin, rope_T, reinterpret_cast<uint16_t*>(kv8), ld_kv8, status, B, 1, Tmax, nh, hd, hidden, mlp_kind, splits, workspace,
+                  workspace_bytes, stream, true);
+}
+
+extern "C" int plm_extend_layer_kv8_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                                         const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* lens0,
+                                         const int32_t* n_new, const float* rope_cos, const float* rope_sin, int64_t rope_T, uint8_t* kv8,
+                                         int64_t ld_kv8, int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd,
+                                         int64_t hidden, int mlp_kind, int splits, void* workspace, size_t workspace_bytes, void* stream) {
+  return df_layer("plm_extend_layer_kv8_bf16", DF_ATTN_EXTEND, x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, lens0, n_new, rope_cos,
+                  rope_sin, rope_T, reinterpret_cast<uint16_t*>(kv8), ld_kv8, status, B, n, Tmax, nh, hd, hidden, mlp_kind, splits, workspace,
+                  workspace_bytes, stream, true);
 }

@@ -10,25 +10,13 @@
 // Scale rule (exact, shared with the CPU reference tests/mx_ref.py): amax = max |x| of the block, E = floor(log2 amax),
 // e = E - 8 if amax <= 448 * 2^(E-8) (= 1.75 * 2^E) else E - 7, clamped to [-127, 127]; scale byte e + 127; q = RNE_e4m3fn(x * 2^-e)
 // with subnormals.  amax = 0: scale byte 0, zero elements.  Any non-finite element: scale byte 0xFF and every element 0x7F (NaN).
-#include "plm_device.h"
+#include "plm_fp8.h"  // mx_e4m3, mx_scale_exp: shared with the FP8 KV cache
 
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
 
 // ---------------------------------------------------------------------------
 // quantizer
 // ---------------------------------------------------------------------------
-// RNE to e4m3fn of a finite |y| <= 448 (by construction of the scale): code = sign | exponent(4) | mantissa(3), bias 7, subnormal step 2^-9
-__device__ __forceinline__ unsigned mx_e4m3(float y) {
-  const unsigned u = __float_as_uint(y);
-  const unsigned sgn = (u >> 24) & 0x80u;
-  const float a = __builtin_fabsf(y);
-  const unsigned sub = (unsigned)__builtin_rintf(a * 512.f);  // |y| < 2^-6: multiples of 2^-9, v_rndne_f32 is RNE (8 = the smallest normal)
-  unsigned b = __float_as_uint(a);
-  b += 0x7FFFFu + ((b >> 20) & 1u);                             // RNE to 3 mantissa bits
-  const unsigned nrm = (b >> 20) - (120u << 3);                  // rebias 127 -> 7
-  return sgn | (a < 0.015625f ? sub : nrm);
-}
-
 // One block of 32 values: 8 packed dwords (element j in byte j & 3 of dword j >> 2) and the scale byte.
 __device__ __forceinline__ unsigned mx_block(const float (&v)[32], unsigned (&q)[8]) {
   float amax = 0.f;
@@ -48,19 +36,7 @@ __device__ __forceinline__ unsigned mx_block(const float (&v)[32], unsigned (&q)
     for (int j = 0; j < 8; ++j) q[j] = 0u;
     return 0u;
   }
-  const unsigned ab = __float_as_uint(amax);
-  const unsigned ex = ab >> 23;
-  int E, over;
-  if (ex != 0) {
-    E = (int)ex - 127;
-    over = (ab & 0x7FFFFFu) > 0x600000u;
-  } else {  // fp32 (= bf16) subnormal: amax = m * 2^-149
-    const int p = 31 - __builtin_clz(ab);
-    E = p - 149;
-    over = ab > (7u << (p - 2));
-  }
-  int e = E - 8 + over;
-  e = e < -127 ? -127 : (e > 127 ? 127 : e);
+  const int e = mx_scale_exp(amax);
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     unsigned w = 0;

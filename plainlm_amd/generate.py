@@ -15,7 +15,9 @@ token history (check_lookup, lookup_uniforms, lookup_round_uniforms).  The fused
 decode_step, ``fused=True``, which runs every layer as one ops.decode_layer call, and generate_fused is generate over it (check_fused holds
 its refusals).  The fused extend is the same keyword of extend, one ops.extend_layer call per layer, and
 generate_lookup_fused is generate_lookup over it (check_fused_rows).  Both walk the layers with the host's one ``fused_layers``: a decode
-step is the chunk of one row per sequence, told apart by its ``chunk`` argument alone.
+step is the chunk of one row per sequence, told apart by its ``chunk`` argument alone.  The FP8 KV cache is a
+format of ``KVCache`` (``kv_dtype='fp8'``, chosen by cfg.kv_cache or by prefill / new_cache's ``kv_dtype``): decode_step, extend and
+fused_layers dispatch on the cache to the ops.*_kv8 twins of the same calls, and nothing else here knows about it.
 """
 
 import math
@@ -24,18 +26,32 @@ import torch
 
 from . import ops
 
+KV_DTYPES = ('bf16', 'fp8')  # ModelConfig.kv_cache / KVCache.kv_dtype
+
+
+def check_kv_dtype(kv_dtype):
+  if kv_dtype not in KV_DTYPES:
+    raise ValueError(f'kv_cache: {kv_dtype!r} is not one of {KV_DTYPES}')
+  return kv_dtype
+
+
 FINISH_CHECK_EVERY = 16  # generate: the one device-to-host read of the loop (have all sequences emitted eos_id?) at most this often
 
 
 class KVCache:
   """Per-layer ``kv`` bf16 [B, Tmax, 2*dim] (row (b, j): the k | v columns of token j's rotated qkv row), ``lens`` int32 [B] on the
   device, and the status flag of the append kernel (checked by ``check``).  It owns no workspace: ops.attn_decode / ops.attn_extend take
-  theirs from the workspace arena of the current stream."""
+  theirs from the workspace arena of the current stream.  kv_dtype 'fp8' (DESIGN.md section 20): ``kv`` is uint8 [B, Tmax, row_bytes]
+  per layer, every row k codes | v codes | k scales | v scales (e4m3fn under one E8M0 scale per 16 elements of a head), 0.53 of the
+  bf16 bytes; ``to_bf16(layer)`` is its exact bf16 image."""
 
-  def __init__(self, n_layers, B, Tmax, n_heads, head_dim, device):
+  def __init__(self, n_layers, B, Tmax, n_heads, head_dim, device, kv_dtype='bf16'):
     dim = n_heads * head_dim
     self.B, self.Tmax, self.n_heads, self.head_dim = B, Tmax, n_heads, head_dim
-    self.kv = [torch.empty((B, Tmax, 2 * dim), dtype=torch.bfloat16, device=device) for _ in range(n_layers)]  # rows >= lens are never read
+    self.kv_dtype = check_kv_dtype(kv_dtype)
+    self.row_bytes = ops.kv8_row_bytes(dim) if kv_dtype == 'fp8' else 4 * dim  # bytes per token and layer
+    shape, dtype = ((B, Tmax, self.row_bytes), torch.uint8) if kv_dtype == 'fp8' else ((B, Tmax, 2 * dim), torch.bfloat16)
+    self.kv = [torch.empty(shape, dtype=dtype, device=device) for _ in range(n_layers)]  # rows >= lens are never read
     # [pos | lens] = [lens - 1 | lens] during a decode step: one in-place add per step moves both, every layer reads the same pair
     self._pl = torch.zeros((2, B), dtype=torch.int32, device=device)
     self._pl[0] -= 1
@@ -60,6 +76,13 @@ class KVCache:
   def advance_by(self, n_new):
     """Move [pos | lens] by n_new - an int32 [B] device tensor, or an int - with one in-place add (Transformer.extend, after its chunk)."""
     self._pl += n_new
+
+  def to_bf16(self, layer):
+    """Layer ``layer``'s cache as bf16 [B, Tmax, 2*dim]: the buffer itself, or the exact dequantised image of an fp8 cache (rows at and
+    beyond lens hold whatever the buffer holds there)."""
+    if self.kv_dtype == 'fp8':
+      return ops.kv8_dequant_rows(self.kv[layer], self.n_heads, self.head_dim)
+    return self.kv[layer]
 
   def check(self):
     """Raises if a decode step tried to append past the cache (or past the RoPE table); reads the device flag, so it waits for the GPU."""
@@ -98,6 +121,14 @@ def guard(what, tokens, model, *drafts, forward_only=False, rank2=False):
     refuse_mxfp8(what, d)
   if rank2 and tokens.dim() != 2:
     raise TypeError('inputs must be an int64 [B, T] tensor')
+
+
+def check_cache(who, cache, model):
+  """A cache made for another model shape is refused before any library call (its format is its own: every method dispatches on
+  cache.kv_dtype)."""
+  if len(cache.kv) != model.n_layers or cache.n_heads != model.cfg.n_heads or cache.head_dim != model.head_dim or \
+     getattr(cache, 'kv_dtype', None) not in KV_DTYPES:
+    raise ValueError(f'{who}: the cache was made for another model shape (layers, heads or head_dim differ)')
 
 
 def chunk_lens(token_lens, B, n, device):
@@ -585,14 +616,15 @@ class Generation:
                 keeps its underscore: tools and tests from before the mixin call it by that name."""
 
   @torch.compiler.disable
-  def prefill(self, x, prompt_lens=None, max_len=None, logits=False):
+  def prefill(self, x, prompt_lens=None, max_len=None, logits=False, kv_dtype=None):
     """Run the prompt x int64 [B, T] through the trunk once and keep every layer's rotated k | v: returns (KVCache, HeadPrediction [B]) -
     the greedy next token of every sequence, its log-probability and the entropy, from row prompt_lens[b] - 1 (host integers; default T).
     Prompts are right-padded to a multiple of 4 (the attention kernels' granularity), which under a causal mask changes no earlier row;
     with prompt_lens shorter rows hold padding the cache never reads (lens = prompt_lens).  max_len: cache rows per sequence (default
     cfg.seq_len).  logits=True returns the bf16 [B, V] logits of those rows in
-    place of the prediction.  Runs under no_grad."""
+    place of the prediction.  kv_dtype: 'bf16' | 'fp8' (DESIGN.md section 20), None: cfg.kv_cache.  Runs under no_grad."""
     guard('prefill', x, self, rank2=True)
+    kv_dtype = check_kv_dtype(self.cfg.kv_cache if kv_dtype is None else kv_dtype)
     B, T = x.shape
     lens = prompt_lens_list(prompt_lens, B, T)
     Tp = pad4(T)
@@ -602,7 +634,7 @@ class Generation:
     with torch.no_grad():
       if Tp != T:
         x = torch.nn.functional.pad(x, (0, Tp - T))
-      cache = KVCache(self.n_layers, B, Tmax, self.cfg.n_heads, self.head_dim, x.device)
+      cache = KVCache(self.n_layers, B, Tmax, self.cfg.n_heads, self.head_dim, x.device, kv_dtype)
       lens_dev = torch.tensor(lens, dtype=torch.int32).to(x.device)
       cache.set_lens(lens_dev)
       y, _, _ = self.trunk(x.contiguous(), None, cache)
@@ -621,6 +653,7 @@ class Generation:
       raise ValueError(f'decode_step: tokens {tuple(tokens.shape)} do not match the cache\'s batch of {B}')
     if fused:
       check_fused('decode_step', B, self.cfg.dim)
+    check_cache('decode_step', cache, self)
     nh = self.cfg.n_heads
     with torch.no_grad():
       rope = self._rope(tokens.device)
@@ -629,21 +662,25 @@ class Generation:
         return self.head(self.fused_layers(tokens.contiguous(), cache, rope), logits, (B,))
 
       def attend(i, qkv):
+        if cache.kv_dtype == 'fp8':  # the decode step is the chunk append at n = 1
+          q, _ = ops.kv8_append_rope_rows(qkv, cache.pos, rope[0], rope[1], cache.kv[i], nh, status=cache.status)
+          return ops.attn_decode_kv8(q, cache.kv[i], cache.lens, nh)
         q, _ = ops.kv_append_rope(qkv, cache.pos, rope[0], rope[1], cache.kv[i], nh, status=cache.status)
         return ops.attn_decode(q, cache.kv[i], cache.lens, nh)
       return self.head(self.cached_layers(tokens.contiguous(), cache, attend), logits, (B,))
 
-  def new_cache(self, B, max_len=None):
+  def new_cache(self, B, max_len=None, kv_dtype=None):
     """An empty KVCache for B sequences (lens 0) of max_len rows each (default and at most cfg.seq_len): the start of a chunked prefill
-    through ``extend``."""
+    through ``extend``.  kv_dtype: 'bf16' | 'fp8', None: cfg.kv_cache."""
     refuse_mxfp8('new_cache', self)
+    kv_dtype = check_kv_dtype(self.cfg.kv_cache if kv_dtype is None else kv_dtype)
     Tmax, fits = cache_rows(max_len, self.cfg.seq_len)
     if int(B) < 1 or not fits:
       raise ValueError(f'new_cache: need B >= 1 and 1 <= max_len <= cfg.seq_len {self.cfg.seq_len}, got B={B} max_len={Tmax}')
     device = self.lm_head.weight.device
     if device.type != 'cuda':
       raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (the model is on CPU; there is no CPU fallback)')
-    return KVCache(self.n_layers, int(B), Tmax, self.cfg.n_heads, self.head_dim, device)
+    return KVCache(self.n_layers, int(B), Tmax, self.cfg.n_heads, self.head_dim, device, kv_dtype)
 
   @torch.compiler.disable
   def extend(self, tokens, cache, token_lens=None, logits=False, all_rows=False, fused=False):
@@ -662,8 +699,7 @@ class Generation:
     if isinstance(tokens, torch.Tensor) and (tokens.dim() != 2 or tokens.shape[0] != cache.B or tokens.shape[1] < 1):
       raise ValueError(f'extend: tokens {tuple(tokens.shape)} are not a [B, n] chunk for the cache\'s batch of {cache.B}')
     guard('extend', tokens, self)
-    if len(cache.kv) != self.n_layers or cache.n_heads != self.cfg.n_heads or cache.head_dim != self.head_dim:
-      raise ValueError('extend: the cache was made for another model shape (layers, heads or head_dim differ)')
+    check_cache('extend', cache, self)
     B, n = tokens.shape
     if fused:
       check_fused_rows('extend', B, n, self.cfg.dim)
@@ -673,9 +709,11 @@ class Generation:
       rope = self._rope(tokens.device)
       lens0 = cache.lens  # the lengths before the chunk: what every layer's append and attention see; moved once, after the last layer
 
+      append, attn = (ops.kv8_append_rope_rows, ops.attn_extend_kv8) if cache.kv_dtype == 'fp8' else (ops.kv_append_rope_rows, ops.attn_extend)
+
       def attend(i, qkv):
-        q, _ = ops.kv_append_rope_rows(qkv, lens0, rope[0], rope[1], cache.kv[i], nh, n_new=n_new, status=cache.status)
-        return ops.attn_extend(q, cache.kv[i], lens0, nh, n_new=n_new)
+        q, _ = append(qkv, lens0, rope[0], rope[1], cache.kv[i], nh, n_new=n_new, status=cache.status)
+        return attn(q, cache.kv[i], lens0, nh, n_new=n_new)
       flat = tokens.reshape(-1).contiguous()
       y = self.fused_layers(flat, cache, rope, (lens0, n_new, n)) if fused else self.cached_layers(flat, cache, attend)
       cache.advance_by(adv)

@@ -739,10 +739,11 @@ def _need_kv(kv, nh, hd, name):
   return kv
 
 
-def _cached_operands(name, rows, width, kv, nh, lens, lens_name, chunk, n_new=None, rope=None):
+def _cached_operands(name, rows, width, kv, nh, lens, lens_name, chunk, n_new=None, rope=None, need_kv=None):
   """The operand checks of the four cached-step ops, returns (B, n, hd).  rows: bf16 [B*n, width*nh*hd] - width 3 the UN-rotated qkv
   (row stride free), width 1 the rotated q; kv: the cache; lens int32 [B]; n_new None | int32 [B]; rope None | (cos, sin) fp32
-  [rows, hd/2].  chunk False: one row per sequence (n = 1), the batch is the rows'; True: n = rows / the cache's batch."""
+  [rows, hd/2].  chunk False: one row per sequence (n = 1), the batch is the rows'; True: n = rows / the cache's batch.  need_kv: another
+  cache format's stand-in for _need_kv (ops_kv8.py)."""
   try:  # the per-tensor checks name the tensor; the op's name is put in front only when one fails (no string is built per call)
     if width == 3:
       if _need(rows, BF16, 'qkv', strided=True).shape[1] % (3 * nh) != 0:
@@ -750,7 +751,7 @@ def _cached_operands(name, rows, width, kv, nh, lens, lens_name, chunk, n_new=No
     else:
       _need(rows, BF16, 'q', 2)
     hd = rows.shape[1] // (width * nh)
-    _need_kv(kv, nh, hd, 'kv')
+    (need_kv or _need_kv)(kv, nh, hd, 'kv')
     _need(lens, torch.int32, lens_name, 1)
     if rope is not None:
       _need(rope[0], F32, 'rope_cos', 2)
@@ -1145,6 +1146,9 @@ from .ops_decode import (DECODE_MLP_KINDS, FUSED_DECODE_MAX_ROWS, decode_gemm_re
                          decode_norm_fc1_act, decode_norm_qkv_append)
 # ---- the fused extend: chunk rows on the same kernels, same module ------------------------------------------------------
 from .ops_decode import FUSED_EXTEND_MAX_ROWS, extend_layer, extend_layer_workspace, extend_norm_qkv_append  # noqa: E402,F401
+# ---- the FP8 KV cache: its wrappers live in ops_kv8.py, on this module's and ops_decode.py's contract ------------------
+from .ops_kv8 import (KV8_BLOCK, attn_decode_kv8, attn_extend_kv8, decode_layer_kv8, extend_layer_kv8,  # noqa: E402,F401
+                      extend_norm_qkv_append_kv8, kv8_append_rope_rows, kv8_dequant_rows, kv8_quant_rows, kv8_row_bytes)
 # ---- the Muon tail: batched NT GEMM, prepare / orthogonalize / apply; its wrappers live in ops_muon.py -------------------
 from .ops_muon import (MUON_ADJUST_LR, MUON_EPS, MUON_NS_COEFFICIENTS, NT_BATCH_GROUP, gemm_nt_batched, muon_adjusted_lr, muon_apply,  # noqa: E402,F401
                        muon_arena, muon_blocks, muon_items, muon_layout, muon_ns_flops, muon_orthogonalize, muon_prepare, muon_set_lr,

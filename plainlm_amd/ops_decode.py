@@ -43,13 +43,13 @@ def _decode_mlp_kind(name, kind):
   return DECODE_MLP_KINDS[kind]
 
 
-def _row_operands(name, M, hd, kv, lengths, rope_cos, rope_sin, nh, n):
+def _row_operands(name, M, hd, kv, lengths, rope_cos, rope_sin, nh, n, need_kv=None):
   """The operand checks of the ops that put M rows into a cache, beyond _decode_operands: the cache, the RoPE tables and ``lengths``, the
   op's per-sequence operands by name - int32 [B] each, None for one the caller left out (the library refuses a missing one it needs).
   n = 1: a decode op, one row per sequence, M = kv.shape[0]; n = None: a chunk op, M = kv.shape[0] * n.  Returns the row counts the op's
-  entry point takes: (B,) of a decode op, (B, n) of a chunk op."""
+  entry point takes: (B,) of a decode op, (B, n) of a chunk op.  need_kv: another cache format's stand-in for ops._need_kv (ops_kv8.py)."""
   try:
-    O._need_kv(kv, nh, hd, 'kv')
+    (need_kv or O._need_kv)(kv, nh, hd, 'kv')
     for what, t in lengths.items():
       if t is not None:
         O._need(t, torch.int32, what, 1)
@@ -66,13 +66,14 @@ def _row_operands(name, M, hd, kv, lengths, rope_cos, rope_sin, nh, n):
   return (B, M // B) if n is None else (B,)
 
 
-def _norm_qkv_append(name, entry, x, norm_w, eps, w_qkv, lengths, rope_cos, rope_sin, kv, nh, q_out, status, n):
-  """Both qkv stages.  ``entry`` takes lengths' pointers where its row positions stand and, a chunk entry point (n = None), n after B."""
+def _norm_qkv_append(name, entry, x, norm_w, eps, w_qkv, lengths, rope_cos, rope_sin, kv, nh, q_out, status, n, need_kv=None):
+  """Both qkv stages.  ``entry`` takes lengths' pointers where its row positions stand and, a chunk entry point (n = None), n after B.
+  need_kv: as _row_operands takes it."""
   M, d = _decode_operands(name, x, (norm_w,), (w_qkv,))
   if d % nh != 0 or tuple(w_qkv.shape) != (3 * d, d):
     raise ValueError(f'{name}: x {tuple(x.shape)}, w_qkv {tuple(w_qkv.shape)} do not fit nh={nh}')
   hd = d // nh
-  rows = _row_operands(name, M, hd, kv, lengths, rope_cos, rope_sin, nh, n)
+  rows = _row_operands(name, M, hd, kv, lengths, rope_cos, rope_sin, nh, n, need_kv)
   q_out, status = O._append_outputs(name, x, M, d, q_out, status)
   with O._Launch('hbm:decode_fused', 2.0 * w_qkv.numel()):
     _lib.check(getattr(_lib.load(), entry)(O._p(x), O._p(norm_w), float(eps), O._p(w_qkv), *map(O._p, lengths.values()), O._p(rope_cos),
@@ -133,8 +134,9 @@ def _layer_workspace(name, query, rows, nh, hd, hidden, Tmax, splits, device):
 
 
 def _layer(name, entry, query, x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, lengths, rope_cos, rope_sin, kv, nh, kind, status,
-           splits, workspace, n):
-  """Both layers.  ``entry`` and ``query``, its workspace query, take what _norm_qkv_append's entry points take of lengths and n."""
+           splits, workspace, n, need_kv=None):
+  """Both layers.  ``entry`` and ``query``, its workspace query, take what _norm_qkv_append's entry points take of lengths and n;
+  need_kv as there."""
   M, d = _decode_operands(name, x, (attn_norm_w, mlp_norm_w), (w_qkv, w_out, w_fc1, w_fc2))
   k = _decode_mlp_kind(name, kind)
   hidden = w_fc2.shape[1]
@@ -143,7 +145,7 @@ def _layer(name, entry, query, x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_
     raise ValueError(f'{name}: the weights {tuple(w_qkv.shape)}, {tuple(w_out.shape)}, {tuple(w_fc1.shape)}, {tuple(w_fc2.shape)} do not fit '
                      f'x {tuple(x.shape)}, nh={nh}, kind {kind!r}')
   hd = d // nh
-  rows = _row_operands(name, M, hd, kv, lengths, rope_cos, rope_sin, nh, n)
+  rows = _row_operands(name, M, hd, kv, lengths, rope_cos, rope_sin, nh, n, need_kv)
   try:
     O._need(status, torch.int32, 'status')
   except (RuntimeError, TypeError, ValueError) as e:

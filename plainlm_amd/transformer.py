@@ -42,6 +42,9 @@ class ModelConfig:
   # not in the reference: 'bf16' (default) | 'mxfp8': the four linears of every block run their forward, dX and dW GEMMs on MX (e4m3fn,
   # one E8M0 scale per 32 elements) operands; lm_head, attention, norms, loss and optimizer are unchanged
   linear_precision: str = 'bf16'
+  # not in the reference: 'bf16' (default) | 'fp8': the format of the KV caches prefill / new_cache make for generation - bf16 rows, or
+  # e4m3fn codes under one E8M0 scale per 16 elements of a head, 0.53 of the bytes; training never looks at it
+  kv_cache: str = 'bf16'
 
 
 ATTN_MASK_MODES = ('doc', 'dense')
@@ -226,7 +229,12 @@ class Attention(nn.Module):
     qkv = Fn.QKVRopeFn.apply(x2d, self.w_qkv.weight, self.w_qkv, rope[0], rope[1], B, T, self.n_heads)
     if cache is not None:  # prefill: this layer's kv [B, Tmax, 2*dim] takes the k | v columns of the rotated qkv, as they are
       d = self.n_heads * self.head_dim
-      cache[:, :T].copy_(qkv.detach().view(B, T, 3 * d)[:, :, d:])
+      kvrows = qkv.detach().view(B, T, 3 * d)[:, :, d:]
+      if cache.dtype == torch.uint8:  # an FP8 cache: the same rows, quantised by one launch - and read back, so
+        ops.kv8_quant_rows(kvrows, cache, self.n_heads)  # that the prompt attends the k | v every later step will find in the cache
+        ops.kv8_dequant_rows(cache, self.n_heads, self.head_dim, out=kvrows)
+      else:
+        cache[:, :T].copy_(kvrows)
     a = Fn.AttnFn.apply(qkv, rope[0], rope[1], doc_start, B, T, self.n_heads)
     return self.w_out(a)
 
@@ -264,6 +272,7 @@ class Transformer(nn.Module, G.Generation):
     self.n_layers = cfg.n_layers
     check_attn_mask_mode(cfg.attn_mask_mode)
     check_linear_precision(cfg.linear_precision)
+    G.check_kv_dtype(cfg.kv_cache)
     if cfg.dim % cfg.n_heads != 0:
       raise ValueError('dim must be divisible by n_heads')
     self.head_dim = cfg.dim // cfg.n_heads
@@ -550,10 +559,11 @@ class Transformer(nn.Module, G.Generation):
     B <= ops.FUSED_DECODE_MAX_ROWS, one per sequence at cache.pos (ops.decode_layer).  chunk (lens0, n_new, n): n tokens per sequence,
     tokens int64 [B * n] with B * n <= ops.FUSED_EXTEND_MAX_ROWS (ops.extend_layer: row b * n + r is appended at lens0[b] + r, n_new
     int32 [B] or None as ops.kv_append_rope_rows takes it).  Returns the final normed rows [B or B * n, dim]."""
+    fp8 = cache.kv_dtype == 'fp8'  # DESIGN.md section 20: the same calls over the FP8 cache
     if chunk is None:
-      layer_op, lengths = ops.decode_layer, (cache.pos, cache.lens)
+      layer_op, lengths = ops.decode_layer_kv8 if fp8 else ops.decode_layer, (cache.pos, cache.lens)
     else:
-      layer_op, lengths, n = ops.extend_layer, chunk[:2], chunk[2]
+      layer_op, lengths, n = ops.extend_layer_kv8 if fp8 else ops.extend_layer, chunk[:2], chunk[2]
       if tokens.shape[0] != cache.B * n:
         raise ValueError(f'fused_layers: {tokens.shape[0]} tokens are not {cache.B} chunks of {n}')
     self.refresh_shadows()

@@ -13,9 +13,14 @@ With --fused-extend the sides are ``extend`` as it is and
 (1, 32) on 1024 cached tokens, then one generate_lookup round against one generate_lookup_fused round at B = 4, n_draft = 7 (the round
 of tools/lookup_bench.py: draft launch, the extend of n_draft + 1 rows, acceptance, commit_round and the cache move, on a periodic prompt
 so that every round carries n_draft proposals), with the fused decode step at B = 8 beside them for scale: the same columns.
+With --kv fp8 the sides are the two cache formats: one model, a bf16 cache and an FP8 cache prefilled with the same
+tokens, the unfused and the fused decode step over each alternating in one process at (B, context) = (8, 1024), (8, 4096), (32, 1024),
+(32, 4096), then extend(fused=True) at (B, n) = (8, 4) on 1024 cached tokens: device ms, median of --runs [min max], and per row whether the
+FP8 side's [min max] lies wholly below the bf16 side's.
 Usage: python tools/gen_bench.py [--runs 20] [--out profiles/generate_bench.txt]
        python tools/gen_bench.py --fused [--batch 1 32] [--context 4096] --out profiles/fused_decode_bench.txt
-       python tools/gen_bench.py --fused-extend --out profiles/fused_extend_bench.txt"""
+       python tools/gen_bench.py --fused-extend --out profiles/fused_extend_bench.txt
+       python tools/gen_bench.py --kv fp8 --out profiles/kv8_bench.txt"""
 import argparse
 import os
 import statistics
@@ -227,6 +232,47 @@ def main_fused(a):
       f.write(text)
 
 
+def main_kv(a):
+  torch.manual_seed(0)
+  shapes = [(8, 1024), (8, 4096), (32, 1024), (32, 4096)]
+  room = 8
+  cfg = ModelConfig(vocab_size=50280, seq_len=max(c for _, c in shapes) + room, dim=768, expand=8 / 3, n_layers=12, n_heads=12, mlp='glu')
+  m = Transformer(cfg).cuda()
+  lines = ['# tools/gen_bench.py --kv %s: 160M (12 layers, d 768, 12 heads, V 50280); one model, a bf16 and an %s KV cache prefilled with the '
+           'same tokens; one process, sides alternating; device ms per call, HIP events, median of %d [min max]; "below": the %s side\'s '
+           '[min max] lies wholly below the bf16 side\'s' % (a.kv, a.kv, a.runs, a.kv)]
+
+  def row(name, dev, b, f):
+    below = max(dev[f]) < min(dev[b])
+    return '  %-22s bf16 %s   %s %s   bf16 / %s (medians) %.2f; %s' % (name, med(dev[b]), a.kv, med(dev[f]), a.kv,
+                                                                     statistics.median(dev[b]) / statistics.median(dev[f]),
+                                                                     'below' if below else 'NOT below')
+  with torch.no_grad():
+    for batch, ctx in shapes:
+      tok = torch.randint(0, cfg.vocab_size, (batch, ctx + 4), device='cuda')
+      lens = torch.full((batch,), ctx, dtype=torch.int32, device='cuda')
+      caches = {kv: m.prefill(tok[:, :ctx].contiguous(), max_len=ctx + room, kv_dtype=kv)[0] for kv in ('bf16', a.kv)}
+      nxt = tok[:, ctx].contiguous()
+      sides = {(kv, fused): (lambda kv=kv, fused=fused: m.decode_step(nxt, caches[kv], fused=fused)) for fused in (False, True) for kv in caches}
+      dev, _, _, ret = alternate(sides, lambda: [c.set_lens(lens) for c in caches.values()], a)
+      lines.append('B = %d, context %d: cache bytes per layer bf16 %d, %s %d' % (batch, ctx, caches['bf16'].kv[0].numel() * 2, a.kv,
+                                                                                 caches[a.kv].kv[0].numel()))
+      for fused, name in ((False, 'decode step'), (True, 'fused decode step')):
+        same = (ret[('bf16', fused)].tokens == ret[(a.kv, fused)].tokens).float().mean().item()
+        lines.append(row(name, dev, ('bf16', fused), (a.kv, fused)) + '; same greedy token %.3f of %d' % (same, batch))
+      if (batch, ctx) == (8, 1024):
+        chunk = tok[:, ctx:ctx + 4].contiguous()
+        sides = {kv: (lambda kv=kv: m.extend(chunk, caches[kv], fused=True)) for kv in caches}
+        dev, _, _, _ = alternate(sides, lambda: [c.set_lens(lens) for c in caches.values()], a)
+        lines.append(row('extend(fused), n = 4', dev, 'bf16', a.kv))
+      del caches
+  text = '\n'.join(lines) + '\n'
+  print(text, end='')
+  if a.out:
+    with open(a.out, 'w') as f:
+      f.write(text)
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--runs', type=int, default=20)
@@ -236,7 +282,10 @@ def main():
   ap.add_argument('--batch', type=int, nargs='*', default=[], help='--fused: extra batch sizes at context %d' % CTX)
   ap.add_argument('--context', type=int, nargs='*', default=[], help='--fused: extra contexts at B = %d' % B)
   ap.add_argument('--fused-extend', action='store_true', help='compare extend(fused=True) and a generate_lookup_fused round with the unfused ones')
+  ap.add_argument('--kv', choices=['fp8'], default=None, help='compare the decode steps over an FP8 KV cache with those over the bf16 cache')
   a = ap.parse_args()
+  if a.kv:
+    return main_kv(a)
   if a.fused:
     return main_fused(a)
   if a.fused_extend:
