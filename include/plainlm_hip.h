@@ -439,6 +439,58 @@ int plm_extend_layer_kv8_bf16(float* x, const float* attn_norm_w, const float* m
                               int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- parallel sampling from one prompt: shared-prefix decode attention -----
+ * Every argument check of these entry points comes before any HIP call.  P prompts, G samples per prompt; row i = p*G + g of every
+ * [P*G, ...] operand is sample g of prompt p.  Two bf16 caches in the layout above: the prefix cache kv_p[P, Tp_max, ld_kv_p] with lens_p
+ * int32[P], held once per prompt, and the suffix cache kv_s[P*G, Ts_max, ld_kv_s] with lens_s int32[P*G], one sequence per sample.  Both
+ * lens arrays are read on the device only and clamped to [0, T*_max]; rows at and beyond them are never loaded.
+ *
+ * plm_attn_decode_shared: q bf16 [P*G, nh*hd], rotated.  Sample i attends keys 0 .. lens_p[p]-1 of prompt p's prefix followed by keys
+ * 0 .. lens_s[i]-1 of its own suffix; writes out bf16 [P*G, nh*hd] and, unless NULL, lse fp32 [P*G, nh] (base 2, plm_attn_fwd's
+ * convention).  lens_p[p] == 0 attends the suffix only, lens_s[i] == 0 the prefix only, both 0 give out = 0 and lse = +INFINITY.
+ * Three launches.  Prefix: a (P*nh*ceil(G/32)) x S_p grid of MFMA workgroups; a workgroup takes one prompt, one head, up to 32 samples
+ * and one contiguous range of the prefix keys, so every prefix k | v row is fetched once per 32 samples.  Suffix: plm_attn_decode's
+ * split kernel over kv_s / lens_s with S_s splits.  Both leave fp32 partials (max, sum, acc[hd]) per (sample, head, split) in the
+ * workspace - the S_p prefix partials of a (sample, head) first, its S_s suffix partials behind them - and plm_attn_decode's combine
+ * walks the S_p + S_s partials in that order, skipping empty ones.  No atomics: bit-reproducible, and for fixed split counts a sample's
+ * bits do not depend on the other samples or prompts.  splits_p: 0 = automatic (two workgroups per CU, no split shorter than 256 keys
+ * of Tp_max, at most 64: a function of P, G, nh, Tp_max and the CU count alone), 1..64 forced.  splits_s: plm_attn_decode's rule on
+ * (P*G, nh, Ts_max).  workspace: plm_attn_decode_shared_workspace_bytes(...) bytes for the same splits arguments, 16-byte aligned,
+ * caller-owned (the query returns 0 for arguments the launch refuses).  Refusals as plm_attn_decode's (PLM_E_INVALID, a short workspace
+ * PLM_E_WORKSPACE).
+ *
+ * plm_kv_append_rope_at: plm_kv_append_rope with the cache row and the RoPE position told apart: row int32[B], rot0 int32[B]; sequence
+ * b's token is rotated at position rot0[b] + row[b] and stored in kv[b, row[b]] (a suffix cache: row = lens_s, rot0 = the prompt's
+ * length).  A row outside [0, Tmax) or a position outside [0, rope_T) stores nothing for that sequence, leaves a q_out row of zeros and
+ * sets status[0] = 1.  With rot0 all zero the stored and returned bits are plm_kv_append_rope's.
+ *
+ * plm_decode_norm_qkv_append_at_bf16: plm_decode_norm_qkv_append_bf16 under plm_kv_append_rope_at's contract (row, rot0).
+ * plm_decode_layer_shared_bf16: plm_decode_layer_bf16 for P*G <= 32 samples with that qkv stage (the suffix cache kv_s takes the new row
+ * at row[i], rotated at rot0[i] + row[i]) and plm_attn_decode_shared's three launches as its attention stage (lens_s = row + 1 during a
+ * step).  Workspace: plm_decode_layer_shared_workspace_bytes(...), same splits arguments.  Refusals as plm_decode_layer_bf16's, all
+ * before the first launch. */
+size_t plm_attn_decode_shared_workspace_bytes(int64_t P, int64_t G, int64_t nh, int64_t hd, int64_t Tp_max, int64_t Ts_max, int splits_p,
+                                              int splits_s);
+int plm_attn_decode_shared(const uint16_t* q, const uint16_t* kv_p, int64_t ld_kv_p, const int32_t* lens_p, const uint16_t* kv_s,
+                           int64_t ld_kv_s, const int32_t* lens_s, uint16_t* out, float* lse, int64_t P, int64_t G, int64_t Tp_max,
+                           int64_t Ts_max, int64_t nh, int64_t hd, int splits_p, int splits_s, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int plm_kv_append_rope_at(const uint16_t* qkv, int64_t ld_qkv, const int32_t* row, const int32_t* rot0, const float* rope_cos,
+                          const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B,
+                          int64_t Tmax, int64_t nh, int64_t hd, void* stream);
+int plm_decode_norm_qkv_append_at_bf16(const float* x, const float* norm_w, float eps, const uint16_t* w_qkv, const int32_t* row,
+                                       const int32_t* rot0, const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out,
+                                       uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t Tmax, int64_t nh, int64_t hd,
+                                       void* stream);
+size_t plm_decode_layer_shared_workspace_bytes(int64_t P, int64_t G, int64_t nh, int64_t hd, int64_t hidden, int64_t Tp_max, int64_t Ts_max,
+                                               int splits_p, int splits_s);
+int plm_decode_layer_shared_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                                 const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* row, const int32_t* lens_s,
+                                 const int32_t* rot0, const int32_t* lens_p, const float* rope_cos, const float* rope_sin, int64_t rope_T,
+                                 const uint16_t* kv_p, int64_t ld_kv_p, uint16_t* kv_s, int64_t ld_kv_s, int32_t* status, int64_t P, int64_t G,
+                                 int64_t Tp_max, int64_t Ts_max, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits_p,
+                                 int splits_s, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- temperature / top-k / top-p sampling of one token per row -----
  * Every argument check comes before any HIP call.
  * logits bf16 [B, ld] (ld >= V; any 2-byte aligned base and any ld: columns >= V are never loaded); u fp32 [B], one uniform per row,

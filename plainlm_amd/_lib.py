@@ -145,6 +145,13 @@ SIGNATURES = {
                                      _SZ, _P]),
   'plm_extend_layer_kv8_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I,
                                      _I, _P, _SZ, _P]),
+  'plm_attn_decode_shared_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I64, _I, _I]),
+  'plm_attn_decode_shared': (_I, [_P, _P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _P, _SZ, _P]),
+  'plm_kv_append_rope_at': (_I, [_P, _I64, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
+  'plm_decode_norm_qkv_append_at_bf16': (_I, [_P, _P, _F, _P, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
+  'plm_decode_layer_shared_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I]),
+  'plm_decode_layer_shared_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64,
+                                        _I64, _I64, _I64, _I64, _I, _I, _I, _P, _SZ, _P]),
   'plm_sample_logits_bf16': (_I, [_P, _I64, _P, _F, _I64, _F, _P, _P, _P, _P, _I64, _I64, _P]),
   'plm_spec_verify_bf16': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I64, _I64, _I64, _P]),
   'plm_lookup_draft_i64': (_I, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P]),

@@ -24,15 +24,13 @@
 // With n <= 32 only wave 0 of a workgroup holds query rows: the four waves load the tiles together and one computes; the parallelism of
 // a short chunk comes from the splits, as in the decode kernel.
 #include "attn_gen_tile.h"
+#include "attn_cache.h"
 
 #include "../../include/plainlm_hip.h"
 
 #define DEC_THREADS 256
 #define DEC_WAVES (DEC_THREADS / PLM_WAVE)
 #define DEC_UNROLL 4
-#define CACHE_MAX_SPLITS 64
-// the automatic split rule knows the device by this one number (MI355X: 256 CUs); nothing is queried, nothing is read back
-#define CACHE_CUS 256
 
 __device__ __forceinline__ int ext_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -43,10 +41,10 @@ __device__ __forceinline__ int ext_clamp(int v, int lo, int hi) { return v < lo 
 // a row writes nothing at all (the decode contract: q_out stays as the caller left it).
 __global__ __launch_bounds__(256) void kv_append_rope_rows_kernel(const uint16_t* __restrict__ qkv, int64_t ld_qkv,
                                                                   const int32_t* __restrict__ lens0, const int32_t* __restrict__ n_new,
-                                                                  const float* __restrict__ rcos, const float* __restrict__ rsin, int rope_T,
-                                                                  uint16_t* __restrict__ q_out, uint16_t* __restrict__ kv, int64_t ld_kv,
-                                                                  int32_t* __restrict__ status, int B, int n, int Tmax, int nh, int hd,
-                                                                  float sgn, int zero_q) {
+                                                                  const int32_t* __restrict__ rot0, const float* __restrict__ rcos,
+                                                                  const float* __restrict__ rsin, int rope_T, uint16_t* __restrict__ q_out,
+                                                                  uint16_t* __restrict__ kv, int64_t ld_kv, int32_t* __restrict__ status, int B,
+                                                                  int n, int Tmax, int nh, int hd, float sgn, int zero_q) {
   const int dm = nh * hd;
   const int cpr = 3 * dm / 8;  // 16-byte chunks per qkv row
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -57,8 +55,9 @@ __global__ __launch_bounds__(256) void kv_append_rope_rows_kernel(const uint16_t
   const int col = c * 8;
   const int l0 = lens0[b];
   const int cb = ext_clamp(n_new != nullptr ? n_new[b] : n, 0, n);
-  const int lim = Tmax < rope_T ? Tmax : rope_T;
-  const bool refused = l0 < 0 || (int64_t)l0 + cb > lim;  // nothing of this sequence is stored
+  // rot0 (plm_kv_append_rope_at): the rows go to l0 + r as ever but are rotated at rot0[b] + l0 + r; null: position = row
+  const int r0 = rot0 != nullptr ? rot0[b] : 0;
+  const bool refused = l0 < 0 || r0 < 0 || (int64_t)l0 + cb > Tmax || (int64_t)r0 + l0 + cb > rope_T;  // nothing of this sequence is stored
   if (refused && r == 0 && c == 0) status[0] = 1;
   if (refused || r >= cb) {  // no cache row
     if (zero_q && col < dm) st_bf16x8(q_out + row * dm + col, zero_bf16x8());
@@ -68,8 +67,8 @@ __global__ __launch_bounds__(256) void kv_append_rope_rows_kernel(const uint16_t
   bf16x8_t v = ld_bf16x8(qkv + row * ld_qkv + col);
   if (col < 2 * dm) {  // q | k: the rotation of rope_qk_kernel (attn.hip), same table loads, same rope8
     const int pair0 = (col % hd) / 2;
-    const f32x4_t cs = *reinterpret_cast<const f32x4_t*>(rcos + (int64_t)t * (hd / 2) + pair0);
-    const f32x4_t sn = *reinterpret_cast<const f32x4_t*>(rsin + (int64_t)t * (hd / 2) + pair0);
+    const f32x4_t cs = *reinterpret_cast<const f32x4_t*>(rcos + (int64_t)(r0 + t) * (hd / 2) + pair0);
+    const f32x4_t sn = *reinterpret_cast<const f32x4_t*>(rsin + (int64_t)(r0 + t) * (hd / 2) + pair0);
     v = rope8(v, cs, sn, sgn);
   }
   if (col < dm)
@@ -229,7 +228,7 @@ template <int HD, typename KV>
 __global__ __launch_bounds__(DEC_THREADS) void attn_decode_split_kernel(const uint16_t* __restrict__ q, const KV* __restrict__ kv,
                                                                         int64_t ld_kv, const int32_t* __restrict__ lens,
                                                                         float* __restrict__ ws_ml, float* __restrict__ ws_acc, int Tmax, int nh,
-                                                                        int S, float c2) {
+                                                                        int S, float c2, int part_stride, int part_off) {
   constexpr int G = HD / 8;          // lanes per key row
   constexpr int KPW = PLM_WAVE / G;  // key rows per wave and load instruction
   __shared__ float s_ml[DEC_WAVES][2];
@@ -325,7 +324,7 @@ __global__ __launch_bounds__(DEC_THREADS) void attn_decode_split_kernel(const ui
       ll += s_ml[w][1] * sc;
       a += s_acc[w][tid] * sc;
     }
-    const int64_t part = (int64_t)bh * S + s;
+    const int64_t part = (int64_t)bh * part_stride + part_off + s;  // plm_attn_decode: stride S, offset 0
     if (tid == 0) {
       ws_ml[part * 2] = mm;
       ws_ml[part * 2 + 1] = ll;
@@ -516,7 +515,7 @@ __global__ __launch_bounds__(HD) void attn_cache_combine_kernel(const float* __r
 // ---------------------------------------------------------------------------------------------------------------------------------
 // splits == 0: enough workgroups for two per CU, but no split shorter than 64 keys of the longest possible sequence.  A function of
 // B, n, nh, Tmax and the CU count alone: what lens / n_new hold on the device is never consulted.
-static int resolve_splits(int64_t B, int64_t n, int64_t nh, int64_t Tmax, int splits) {
+int cache_resolve_splits(int64_t B, int64_t n, int64_t nh, int64_t Tmax, int splits) {
   if (splits != 0) return splits;
   int64_t s = plm_cdiv(2 * CACHE_CUS, B * nh * plm_cdiv(n, 128));
   const int64_t cap = plm_cdiv(Tmax, 64);
@@ -525,20 +524,20 @@ static int resolve_splits(int64_t B, int64_t n, int64_t nh, int64_t Tmax, int sp
   return s < 1 ? 1 : (int)s;
 }
 
-static bool shape_ok(int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t Tmax) {
+bool cache_shape_ok(int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t Tmax) {
   const int64_t lim = (int64_t)1 << 31;
   return B > 0 && nh > 0 && Tmax > 0 && n > 0 && B < 65536 && nh < 65536 && Tmax < (1 << 24) && n < lim && B * n < lim && B * n * nh < lim &&
          (hd == 32 || hd == 64 || hd == 128);
 }
 
-static size_t ws_bytes(int64_t B, int64_t n, int64_t nh, int64_t hd, int S) {
+size_t cache_ws_bytes(int64_t B, int64_t n, int64_t nh, int64_t hd, int S) {
   const size_t parts = (size_t)B * (size_t)nh * (size_t)S * (size_t)n;
   return (parts * (2 + (size_t)hd) * sizeof(float) + 15) / 16 * 16;
 }
 
 extern "C" size_t plm_attn_extend_workspace_bytes(int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t Tmax, int splits) {
-  if (!shape_ok(B, n, nh, hd, Tmax) || splits < 0 || splits > CACHE_MAX_SPLITS) return 0;
-  return ws_bytes(B, n, nh, hd, resolve_splits(B, n, nh, Tmax, splits));
+  if (!cache_shape_ok(B, n, nh, hd, Tmax) || splits < 0 || splits > CACHE_MAX_SPLITS) return 0;
+  return cache_ws_bytes(B, n, nh, hd, cache_resolve_splits(B, n, nh, Tmax, splits));
 }
 
 extern "C" size_t plm_attn_decode_workspace_bytes(int64_t B, int64_t nh, int64_t hd, int64_t Tmax, int splits) {
@@ -546,12 +545,13 @@ extern "C" size_t plm_attn_decode_workspace_bytes(int64_t B, int64_t nh, int64_t
 }
 
 // the append stage: every refusal, then the one launch.  `fn` is the entry point the caller sees.
-static int append_rows(const char* fn, const uint16_t* qkv, int64_t ld_qkv, const int32_t* lens0, const int32_t* n_new, const float* rope_cos,
+static int append_rows(const char* fn, const uint16_t* qkv, int64_t ld_qkv, const int32_t* lens0, const int32_t* n_new, const int32_t* rot0,
+                       const float* rope_cos,
                        const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t n,
                        int64_t Tmax, int64_t nh, int64_t hd, bool zero_q, void* stream) {
   PLM_REQUIRE(qkv && lens0 && rope_cos && rope_sin && q_out && kv && status, "%s: null pointer", fn);
   PLM_REQUIRE(hd == 32 || hd == 64 || hd == 128, "%s: head_dim %ld unsupported (32, 64, 128)", fn, (long)hd);
-  PLM_REQUIRE(shape_ok(B, n, nh, hd, Tmax) && rope_T > 0 && rope_T < (1 << 24),
+  PLM_REQUIRE(cache_shape_ok(B, n, nh, hd, Tmax) && rope_T > 0 && rope_T < (1 << 24),
               "%s: bad shape B=%ld n=%ld Tmax=%ld nh=%ld rope_T=%ld (n >= 1, B*n < 2^31)", fn, (long)B, (long)n, (long)Tmax, (long)nh, (long)rope_T);
   PLM_REQUIRE(ld_qkv >= 3 * nh * hd && ld_qkv % 8 == 0 && ld_kv >= 2 * nh * hd && ld_kv % 8 == 0,
               "%s: row strides must be multiples of 8 and at least 3*nh*hd (qkv) / 2*nh*hd (kv)", fn);
@@ -560,8 +560,8 @@ static int append_rows(const char* fn, const uint16_t* qkv, int64_t ld_qkv, cons
               "%s: qkv, q_out, kv and the RoPE tables must be 16-byte aligned", fn);
   const int64_t blocks = plm_cdiv(B * n * (3 * nh * hd / 8), 256);
   PLM_REQUIRE(blocks < ((int64_t)1 << 31), "%s: bad shape: B*n*nh*hd too large for one launch", fn);
-  hipLaunchKernelGGL(kv_append_rope_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, qkv, ld_qkv, lens0, n_new, rope_cos,
-                     rope_sin, (int)rope_T, q_out, kv, ld_kv, status, (int)B, (int)n, (int)Tmax, (int)nh, (int)hd, 1.f, (int)zero_q);
+  hipLaunchKernelGGL(kv_append_rope_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, qkv, ld_qkv, lens0, n_new, rot0,
+                     rope_cos, rope_sin, (int)rope_T, q_out, kv, ld_kv, status, (int)B, (int)n, (int)Tmax, (int)nh, (int)hd, 1.f, (int)zero_q);
   PLM_CHECK_LAUNCH(fn);
   return PLM_OK;
 }
@@ -569,17 +569,24 @@ static int append_rows(const char* fn, const uint16_t* qkv, int64_t ld_qkv, cons
 extern "C" int plm_kv_append_rope(const uint16_t* qkv, int64_t ld_qkv, const int32_t* pos, const float* rope_cos, const float* rope_sin,
                                   int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t Tmax,
                                   int64_t nh, int64_t hd, void* stream) {
-  return append_rows("plm_kv_append_rope", qkv, ld_qkv, pos, nullptr, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, 1, Tmax, nh, hd,
+  return append_rows("plm_kv_append_rope", qkv, ld_qkv, pos, nullptr, nullptr, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, 1, Tmax, nh, hd,
                      false, stream);
 }
 
 extern "C" int plm_kv_append_rope_rows(const uint16_t* qkv, int64_t ld_qkv, const int32_t* lens0, const int32_t* n_new, const float* rope_cos,
                                        const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv, int32_t* status,
                                        int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, void* stream) {
-  return append_rows("plm_kv_append_rope_rows", qkv, ld_qkv, lens0, n_new, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, n, Tmax, nh,
+  return append_rows("plm_kv_append_rope_rows", qkv, ld_qkv, lens0, n_new, nullptr, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, n, Tmax, nh,
                      hd, true, stream);
 }
-
+// one token per sequence at row[b], rotated at rot0[b] + row[b] (a suffix cache); a refused row leaves zeros in q_out
+extern "C" int plm_kv_append_rope_at(const uint16_t* qkv, int64_t ld_qkv, const int32_t* row, const int32_t* rot0, const float* rope_cos,
+                                     const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B,
+                                     int64_t Tmax, int64_t nh, int64_t hd, void* stream) {
+  PLM_REQUIRE(rot0, "plm_kv_append_rope_at: null pointer");
+  return append_rows("plm_kv_append_rope_at", qkv, ld_qkv, row, nullptr, rot0, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, 1, Tmax, nh,
+                     hd, true, stream);
+}
 
 // the FP8 cache's stride rule: bytes, a multiple of 16 (the 16-byte code stores and 8-byte code loads stay aligned), at least the payload
 static bool kv8_stride_ok(int64_t ld_kv8, int64_t dm) { return ld_kv8 % 16 == 0 && ld_kv8 >= kv8_row_payload(dm); }
@@ -591,7 +598,7 @@ extern "C" int plm_kv8_append_rope_rows(const uint16_t* qkv, int64_t ld_qkv, con
   const char* fn = "plm_kv8_append_rope_rows";
   PLM_REQUIRE(qkv && lens0 && rope_cos && rope_sin && q_out && kv8 && status, "%s: null pointer", fn);
   PLM_REQUIRE(hd == 32 || hd == 64 || hd == 128, "%s: head_dim %ld unsupported (32, 64, 128)", fn, (long)hd);
-  PLM_REQUIRE(shape_ok(B, n, nh, hd, Tmax) && rope_T > 0 && rope_T < (1 << 24),
+  PLM_REQUIRE(cache_shape_ok(B, n, nh, hd, Tmax) && rope_T > 0 && rope_T < (1 << 24),
               "%s: bad shape B=%ld n=%ld Tmax=%ld nh=%ld rope_T=%ld (n >= 1, B*n < 2^31)", fn, (long)B, (long)n, (long)Tmax, (long)nh, (long)rope_T);
   PLM_REQUIRE(ld_qkv >= 3 * nh * hd && ld_qkv % 8 == 0, "%s: the qkv row stride must be a multiple of 8 and at least 3*nh*hd", fn);
   PLM_REQUIRE(kv8_stride_ok(ld_kv8, nh * hd), KV8_STRIDE_MSG, fn);
@@ -611,7 +618,7 @@ static int kv8_check_rows(const char* fn, const void* rows, int64_t ld, const vo
                           int64_t nh, int64_t hd) {
   PLM_REQUIRE(rows && kv8, "%s: null pointer", fn);
   PLM_REQUIRE(hd == 32 || hd == 64 || hd == 128, "%s: head_dim %ld unsupported (32, 64, 128)", fn, (long)hd);
-  PLM_REQUIRE(shape_ok(B, T, nh, hd, Tmax) && T <= Tmax, "%s: bad shape B=%ld T=%ld Tmax=%ld nh=%ld (1 <= T <= Tmax, B*T < 2^31)", fn, (long)B,
+  PLM_REQUIRE(cache_shape_ok(B, T, nh, hd, Tmax) && T <= Tmax, "%s: bad shape B=%ld T=%ld Tmax=%ld nh=%ld (1 <= T <= Tmax, B*T < 2^31)", fn, (long)B,
               (long)T, (long)Tmax, (long)nh);
   PLM_REQUIRE(ld >= 2 * nh * hd && ld % 8 == 0, "%s: the bf16 row stride must be a multiple of 8 and at least 2*nh*hd", fn);
   PLM_REQUIRE(kv8_stride_ok(ld_kv8, nh * hd), KV8_STRIDE_MSG, fn);
@@ -645,7 +652,7 @@ static int check_attend(const char* fn, const uint16_t* q, const KV* kv, int64_t
                         int64_t n, int64_t Tmax, int64_t nh, int64_t hd, int splits, const void* workspace, size_t workspace_bytes, int* S) {
   PLM_REQUIRE(q && kv && lens && out && workspace, "%s: null pointer", fn);
   PLM_REQUIRE(hd == 32 || hd == 64 || hd == 128, "%s: head_dim %ld unsupported (32, 64, 128)", fn, (long)hd);
-  PLM_REQUIRE(shape_ok(B, n, nh, hd, Tmax), "%s: bad shape B=%ld n=%ld Tmax=%ld nh=%ld (n >= 1, B*n < 2^31)", fn, (long)B, (long)n, (long)Tmax,
+  PLM_REQUIRE(cache_shape_ok(B, n, nh, hd, Tmax), "%s: bad shape B=%ld n=%ld Tmax=%ld nh=%ld (n >= 1, B*n < 2^31)", fn, (long)B, (long)n, (long)Tmax,
               (long)nh);
   if (sizeof(KV) == 2) PLM_REQUIRE(ld_kv >= 2 * nh * hd && ld_kv % 8 == 0, "%s: the cache's row stride must be a multiple of 8 and at least 2*nh*hd", fn);
   else PLM_REQUIRE(kv8_stride_ok(ld_kv, nh * hd), KV8_STRIDE_MSG, fn);
@@ -653,8 +660,8 @@ static int check_attend(const char* fn, const uint16_t* q, const KV* kv, int64_t
                 reinterpret_cast<uintptr_t>(workspace)) & 15) == 0,
               "%s: q, kv, out and the workspace must be 16-byte aligned", fn);
   PLM_REQUIRE(splits >= 0 && splits <= CACHE_MAX_SPLITS, "%s: splits=%d out of range (0 = automatic, 1..%d forced)", fn, splits, CACHE_MAX_SPLITS);
-  *S = resolve_splits(B, n, nh, Tmax, splits);
-  const size_t need = ws_bytes(B, n, nh, hd, *S);
+  *S = cache_resolve_splits(B, n, nh, Tmax, splits);
+  const size_t need = cache_ws_bytes(B, n, nh, hd, *S);
   if (workspace_bytes < need) {
     plm_set_error("%s: workspace of %zu bytes required, %zu given", fn, need, workspace_bytes);
     return PLM_E_WORKSPACE;
@@ -669,9 +676,33 @@ static void dec_launch(const uint16_t* q, const KV* kv, int64_t ld_kv, const int
   float* ws_acc = ws + (size_t)B * nh * S * 2;
   const float c2 = (1.f / sqrtf((float)HD)) * GLOG2E;
   hipLaunchKernelGGL((attn_decode_split_kernel<HD, KV>), dim3((unsigned)(B * nh), (unsigned)S), dim3(DEC_THREADS), 0, s, q, kv, ld_kv, lens, ws_ml,
-                     ws_acc, (int)Tmax, (int)nh, S, c2);
+                     ws_acc, (int)Tmax, (int)nh, S, c2, S, 0);
   hipLaunchKernelGGL(attn_cache_combine_kernel<HD>, dim3((unsigned)(B * nh)), dim3(HD), 0, s, ws_acc, ws_ml, (const int32_t*)nullptr, out, lse, 1,
                      (int)nh, S);
+}
+
+// what attn_shared.hip borrows (attn_cache.h): the split kernel into a wider partial layout, and the combine over all of it
+template <int HD>
+static void dec_partials(const uint16_t* q, const uint16_t* kv, int64_t ld_kv, const int32_t* lens, float* ws_ml, float* ws_acc, int64_t B,
+                         int64_t Tmax, int64_t nh, int S, int part_stride, int part_off, hipStream_t s) {
+  const float c2 = (1.f / sqrtf((float)HD)) * GLOG2E;
+  hipLaunchKernelGGL((attn_decode_split_kernel<HD, uint16_t>), dim3((unsigned)(B * nh), (unsigned)S), dim3(DEC_THREADS), 0, s, q, kv, ld_kv, lens,
+                     ws_ml, ws_acc, (int)Tmax, (int)nh, S, c2, part_stride, part_off);
+}
+
+void cache_decode_partials_launch(const uint16_t* q, const uint16_t* kv, int64_t ld_kv, const int32_t* lens, float* ws_ml, float* ws_acc, int64_t B,
+                                  int64_t Tmax, int64_t nh, int64_t hd, int S, int part_stride, int part_off, hipStream_t s) {
+  if (hd == 32) dec_partials<32>(q, kv, ld_kv, lens, ws_ml, ws_acc, B, Tmax, nh, S, part_stride, part_off, s);
+  else if (hd == 64) dec_partials<64>(q, kv, ld_kv, lens, ws_ml, ws_acc, B, Tmax, nh, S, part_stride, part_off, s);
+  else dec_partials<128>(q, kv, ld_kv, lens, ws_ml, ws_acc, B, Tmax, nh, S, part_stride, part_off, s);
+}
+
+void cache_combine_launch(const float* ws_acc, const float* ws_ml, uint16_t* out, float* lse, int64_t B, int64_t nh, int64_t hd, int S, hipStream_t s) {
+  const dim3 grid((unsigned)(B * nh));
+  const int32_t* none = nullptr;
+  if (hd == 32) hipLaunchKernelGGL(attn_cache_combine_kernel<32>, grid, dim3(32), 0, s, ws_acc, ws_ml, none, out, lse, 1, (int)nh, S);
+  else if (hd == 64) hipLaunchKernelGGL(attn_cache_combine_kernel<64>, grid, dim3(64), 0, s, ws_acc, ws_ml, none, out, lse, 1, (int)nh, S);
+  else hipLaunchKernelGGL(attn_cache_combine_kernel<128>, grid, dim3(128), 0, s, ws_acc, ws_ml, none, out, lse, 1, (int)nh, S);
 }
 
 // plm_attn_decode and plm_attn_decode_kv8: `fn` is the entry point the caller sees

@@ -59,6 +59,7 @@ struct DfArgs {
   int n;
   const int32_t* lens0;  // [M / n]: the cache lengths before the chunk
   const int32_t* n_new;  // [M / n] real rows per chunk, or null: n everywhere
+  const int32_t* rot0;   // [M / n] or null: the rows are rotated at rot0[b] + lens0[b] + r (a suffix cache); null: at their row
 };
 
 // (a, b) -> (a cos - b sin, b cos + a sin): the pair arithmetic of rope8 (plm_device.h) at sgn = +1
@@ -185,17 +186,17 @@ __global__ __launch_bounds__(DF_THREADS) void decode_fused_kernel(const DfArgs p
       cb = cb < 0 ? 0 : (cb > n ? n : cb);
     }
     const int l0 = p.lens0[b];
-    const int lim = p.Tmax < p.rope_T ? p.Tmax : p.rope_T;
-    const bool refused = l0 < 0 || (int64_t)l0 + cb > lim;  // nothing of this sequence is stored
+    const int r0 = p.rot0 != nullptr ? p.rot0[b] : 0;
+    const bool refused = l0 < 0 || r0 < 0 || (int64_t)l0 + cb > p.Tmax || (int64_t)r0 + l0 + cb > p.rope_T;  // nothing of this sequence is stored
     if (refused && col == 0) p.status[0] = 1;
     if (refused || r >= cb) {  // no cache row; the q row is zeros, so that every byte of q_out is defined
       if (col < dm) df_st2(p.out + (int64_t)m * dm + col, f2bf(0.f), f2bf(0.f));
       return;
     }
-    const int t = l0 + r;  // 0 <= t < lim
+    const int t = l0 + r;  // 0 <= t < Tmax, 0 <= r0 + t < rope_T
     bf16_t b0 = f2bf(v0), b1 = f2bf(v1);
     if (col < 2 * dm) {
-      const int64_t ti = (int64_t)t * (p.hd / 2) + (col % p.hd) / 2;
+      const int64_t ti = (int64_t)(r0 + t) * (p.hd / 2) + (col % p.hd) / 2;
       df_rope2(b0, b1, p.rcos[ti], p.rsin[ti]);
     }
     if (col < dm) {
@@ -311,13 +312,14 @@ static void df_launch(const DfArgs& a, int64_t blocks, hipStream_t s) {
 
 static void df_launch_qkv(const float* x, const float* nw, float eps, const uint16_t* w_qkv, const int32_t* lens0, const int32_t* n_new,
                           const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv,
-                          int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, hipStream_t s, bool kv8 = false) {
+                          int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, hipStream_t s, bool kv8 = false,
+                          const int32_t* rot0 = nullptr) {
   DfArgs a = {};
   const int64_t d = nh * hd;
   a.x = x, a.nw = nw, a.eps = eps, a.w = w_qkv, a.M = (int)(B * n), a.N = (int)(3 * d), a.K = (int)d;
   a.out = q_out, a.kv = kv, a.ld_kv = ld_kv, a.rcos = rope_cos, a.rsin = rope_sin, a.status = status;
   a.rope_T = (int)rope_T, a.Tmax = (int)Tmax, a.hd = (int)hd, a.dm = (int)d;
-  a.n = (int)n, a.lens0 = lens0, a.n_new = n_new;
+  a.n = (int)n, a.lens0 = lens0, a.n_new = n_new, a.rot0 = rot0;
   if (kv8) df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS_KV8>(a, 3 * d / DF_TILE_N, s);
   else df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS>(a, 3 * d / DF_TILE_N, s);
 }
@@ -345,6 +347,20 @@ extern "C" int plm_decode_norm_qkv_append_bf16(const float* x, const float* norm
   // one row per sequence at pos[b]: plm_kv_append_rope's way of calling the rows kernel
   if (const int e = df_check_qkv(fn, x, norm_w, w_qkv, pos, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, 1, Tmax, nh, hd)) return e;
   df_launch_qkv(x, norm_w, eps, w_qkv, pos, nullptr, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, 1, Tmax, nh, hd, (hipStream_t)stream);
+  PLM_CHECK_LAUNCH(fn);
+  return PLM_OK;
+}
+
+extern "C" int plm_decode_norm_qkv_append_at_bf16(const float* x, const float* norm_w, float eps, const uint16_t* w_qkv, const int32_t* row,
+                                                  const int32_t* rot0, const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out,
+                                                  uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t Tmax, int64_t nh, int64_t hd,
+                                                  void* stream) {
+  const char* fn = "plm_decode_norm_qkv_append_at_bf16";
+  // one row per sequence in cache row row[b], rotated at rot0[b] + row[b]: plm_kv_append_rope_at's contract
+  PLM_REQUIRE(rot0, "%s: null pointer", fn);
+  if (const int e = df_check_qkv(fn, x, norm_w, w_qkv, row, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, 1, Tmax, nh, hd)) return e;
+  df_launch_qkv(x, norm_w, eps, w_qkv, row, nullptr, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, 1, Tmax, nh, hd, (hipStream_t)stream, false,
+                rot0);
   PLM_CHECK_LAUNCH(fn);
   return PLM_OK;
 }
@@ -474,6 +490,71 @@ extern "C" int plm_extend_layer_bf16(float* x, const float* attn_norm_w, const f
                                      int mlp_kind, int splits, void* workspace, size_t workspace_bytes, void* stream) {
   return df_layer("plm_extend_layer_bf16", DF_ATTN_EXTEND, x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, lens0, n_new, rope_cos,
                   rope_sin, rope_T, kv, ld_kv, status, B, n, Tmax, nh, hd, hidden, mlp_kind, splits, workspace, workspace_bytes, stream);
+}
+
+// ---- the decode layer over a shared prefix: P prompts x G samples, M = P*G rows; the qkv stage appends to the suffix
+// cache at row[i] and rotates at rot0[i] + row[i], the attention stage is plm_attn_decode_shared's three launches, the rest is df_layer's ----
+extern "C" size_t plm_decode_layer_shared_workspace_bytes(int64_t P, int64_t G, int64_t nh, int64_t hd, int64_t hidden, int64_t Tp_max,
+                                                          int64_t Ts_max, int splits_p, int splits_s) {
+  const int64_t M = P * G;
+  if (P < 1 || G < 1 || P > DF_MAX_ROWS || G > DF_MAX_ROWS || M > DF_MAX_ROWS || nh < 1 || nh * hd > DF_MAX_DIM / 4 || (nh * hd) % 32 != 0 ||
+      hidden < 1 || hidden > DF_MAX_DIM / 2 || hidden % 32 != 0)
+    return 0;
+  const size_t att = plm_attn_decode_shared_workspace_bytes(P, G, nh, hd, Tp_max, Ts_max, splits_p, splits_s);
+  if (att == 0) return 0;
+  const size_t d = (size_t)(nh * hd);
+  return 2 * df_round16((size_t)M * d * 2) + df_round16((size_t)M * (size_t)hidden * 2) + att;
+}
+
+extern "C" int plm_decode_layer_shared_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                                            const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* row,
+                                            const int32_t* lens_s, const int32_t* rot0, const int32_t* lens_p, const float* rope_cos,
+                                            const float* rope_sin, int64_t rope_T, const uint16_t* kv_p, int64_t ld_kv_p, uint16_t* kv_s,
+                                            int64_t ld_kv_s, int32_t* status, int64_t P, int64_t G, int64_t Tp_max, int64_t Ts_max, int64_t nh,
+                                            int64_t hd, int64_t hidden, int mlp_kind, int splits_p, int splits_s, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  const char* fn = "plm_decode_layer_shared_bf16";
+  PLM_REQUIRE(x && attn_norm_w && mlp_norm_w && w_qkv && w_out && w_fc1 && w_fc2 && row && lens_s && rot0 && lens_p && rope_cos && rope_sin && kv_p &&
+                  kv_s && status && workspace,
+              "%s: null pointer", fn);
+  PLM_REQUIRE(df_aligned(workspace, kv_p), "%s: the workspace and kv_p must be 16-byte aligned", fn);
+  PLM_REQUIRE(P >= 1 && G >= 1 && P <= DF_MAX_ROWS && G <= DF_MAX_ROWS && P * G <= DF_MAX_ROWS,
+              "%s: P=%ld prompts x G=%ld samples unsupported (1 <= P*G <= %d rows)", fn, (long)P, (long)G, DF_MAX_ROWS);
+  const int64_t d = nh * hd, M = P * G;
+  char* ws = static_cast<char*>(workspace);
+  uint16_t* q = reinterpret_cast<uint16_t*>(ws);
+  if (const int e = df_check_qkv(fn, x, attn_norm_w, w_qkv, row, rope_cos, rope_sin, rope_T, q, kv_s, ld_kv_s, status, M, 1, Ts_max, nh, hd)) return e;
+  if (const int e = df_check_residual(fn, x, q, w_out, M, d, d)) return e;
+  if (const int e = df_check_fc1(fn, x, mlp_norm_w, w_fc1, q, M, d, hidden, mlp_kind)) return e;
+  if (const int e = df_check_residual(fn, x, q, w_fc2, M, d, hidden)) return e;
+  PLM_REQUIRE(splits_p >= 0 && splits_p <= 64 && splits_s >= 0 && splits_s <= 64, "%s: splits_p=%d / splits_s=%d out of range (0 = automatic, 1..64 forced)",
+              fn, splits_p, splits_s);
+  PLM_REQUIRE(ld_kv_p >= 2 * d && ld_kv_p % 8 == 0, "%s: the prefix cache's row stride must be a multiple of 8 and at least 2*nh*hd", fn);
+  const size_t need = plm_decode_layer_shared_workspace_bytes(P, G, nh, hd, hidden, Tp_max, Ts_max, splits_p, splits_s);
+  PLM_REQUIRE(need != 0, "%s: bad shape P=%ld G=%ld Tp_max=%ld Ts_max=%ld nh=%ld hd=%ld hidden=%ld", fn, (long)P, (long)G, (long)Tp_max, (long)Ts_max,
+              (long)nh, (long)hd, (long)hidden);
+  if (workspace_bytes < need) {
+    plm_set_error("%s: workspace of %zu bytes required, %zu given", fn, need, workspace_bytes);
+    return PLM_E_WORKSPACE;
+  }
+  const size_t qb = df_round16((size_t)M * (size_t)d * 2), ab = df_round16((size_t)M * (size_t)hidden * 2);
+  uint16_t* attn_out = reinterpret_cast<uint16_t*>(ws + qb);
+  uint16_t* act = reinterpret_cast<uint16_t*>(ws + 2 * qb);
+  hipStream_t s = (hipStream_t)stream;
+  df_launch_qkv(x, attn_norm_w, eps, w_qkv, row, nullptr, rope_cos, rope_sin, rope_T, q, kv_s, ld_kv_s, status, M, 1, Ts_max, nh, hd, s, false, rot0);
+  // plm_attn_decode_shared checks its arguments again, after the launch above.  "Every refusal before the first launch" holds because each of
+  // them was already made here: null pointers and the workspace's / kv_p's alignment (above; q, attn_out and the partials are 16-byte offsets
+  // into the workspace, kv_s's alignment is df_check_qkv's), head_dim and ld_kv_s (df_check_qkv), ld_kv_p and both splits (above), its shape
+  // limits and its workspace size (need != 0 asks plm_attn_decode_shared_workspace_bytes, and the bytes handed on are that query's answer).  A refusal
+  // added there must be added here.
+  if (const int e = plm_attn_decode_shared(q, kv_p, ld_kv_p, lens_p, kv_s, ld_kv_s, lens_s, attn_out, nullptr, P, G, Tp_max, Ts_max, nh, hd, splits_p,
+                                           splits_s, ws + 2 * qb + ab, need - 2 * qb - ab, stream))
+    return e;
+  df_launch_residual(x, attn_out, w_out, M, d, d, s);
+  df_launch_fc1(x, mlp_norm_w, eps, w_fc1, act, M, d, hidden, mlp_kind, s);
+  df_launch_residual(x, act, w_fc2, M, d, hidden, s);
+  PLM_CHECK_LAUNCH(fn);
+  return PLM_OK;
 }
 
 // ---- the same stage and layers over the FP8 cache: kv8 bytes, ld_kv8 in bytes; everything else as above ----

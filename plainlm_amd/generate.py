@@ -17,7 +17,10 @@ its refusals).  The fused extend is the same keyword of e
 generate_lookup_fused is generate_lookup over it (check_fused_rows).  Both walk the layers with the host's one ``fused_layers``: a decode
 step is the chunk of one row per sequence, told apart by its ``chunk`` argument alone.  The FP8 KV cache is a
 format of ``KVCache`` (``kv_dtype='fp8'``, chosen by cfg.kv_cache or by prefill / new_cache's ``kv_dtype``): decode_step, extend and
-fused_layers dispatch on the cache to the ops.*_kv8 twins of the same calls, and nothing else here knows about it.
+fused_layers dispatch on the cache to the ops.*_kv8 twins of the same calls, and nothing else here knows about it.  Parallel sampling from
+one prompt is ``SharedPrefixCache`` - a prefilled KVCache held once per prompt plus one suffix cache per sample -
+made by ``fork``; decode_step dispatches on it to ops.kv_append_rope_at / ops.attn_decode_shared (fused: ops.decode_layer_shared), and
+``generate_samples`` is generate over it (check_fork holds its refusals).
 """
 
 import math
@@ -89,6 +92,66 @@ class KVCache:
     if int(self.status.item()) != 0:
       raise RuntimeError(f'KVCache: a decode step appended at a position outside [0, {self.Tmax}): that token was not stored '
                          '(prefill with a larger max_len)')
+
+
+class SharedPrefixCache:
+  """G continuations per prompt on top of ONE copy of the prompts' cache.  ``prefix``: the prefilled bf16 KVCache
+  of the P prompts, read-only from here on; ``kv``: per layer the suffix buffer bf16 [P*G, Ts_max, 2*dim], sequence p*G + g = sample g of
+  prompt p, row j = the sample's j-th own token; ``[pos | lens]`` of the suffix as KVCache keeps them (one in-place add per step);
+  ``rot0`` int32 [P*G] = the prompts' lengths repeated G times, on the device: suffix row j of sample i is rotated at rot0[i] + j.
+  ``status`` / ``check()`` as KVCache's: a step past Ts_max (or past the RoPE table) stores nothing and raises the flag."""
+  kv_dtype = 'bf16'
+
+  def __init__(self, prefix, n_samples, max_new_tokens):
+    G, Ts = check_fork(prefix, n_samples, max_new_tokens)
+    self.prefix, self.G, self.P, self.B, self.Tmax = prefix, G, prefix.B, prefix.B * G, Ts
+    self.n_heads, self.head_dim = prefix.n_heads, prefix.head_dim
+    dev = prefix.status.device
+    self.kv = [torch.empty((self.B, Ts, 2 * self.n_heads * self.head_dim), dtype=torch.bfloat16, device=dev) for _ in prefix.kv]
+    self._pl = torch.zeros((2, self.B), dtype=torch.int32, device=dev)
+    self._pl[0] -= 1
+    self.rot0 = prefix.lens.repeat_interleave(G).contiguous()
+    self.status = torch.zeros((1,), dtype=torch.int32, device=dev)
+
+  lens = KVCache.lens
+  pos = KVCache.pos
+  advance = KVCache.advance
+
+  def cache_bytes(self):
+    """Bytes of cache held for all layers: the prefix once, (Tp_max + G * Ts_max) rows per prompt."""
+    return sum(t.numel() * t.element_size() for t in self.prefix.kv + self.kv)
+
+  def check(self):
+    if int(self.status.item()) != 0:
+      raise RuntimeError(f'SharedPrefixCache: a decode step appended at a row outside [0, {self.Tmax}) or past the RoPE table: that token was '
+                         'not stored (fork with a larger max_new_tokens)')
+
+
+def check_fork(cache, n_samples, max_new_tokens):
+  """The refusals of Transformer.fork that need no GPU; returns (G, suffix rows per sample)."""
+  if isinstance(cache, SharedPrefixCache):
+    raise TypeError('fork: the cache is already a fork (a SharedPrefixCache cannot be forked again: fork its prefix)')
+  if not isinstance(cache, KVCache):
+    raise TypeError(f'fork: cache must be a prefilled KVCache, got {type(cache).__name__}')
+  if cache.kv_dtype != 'bf16':
+    raise ValueError(f"fork: a {cache.kv_dtype!r} cache cannot be shared (the shared-prefix kernels read bf16 prefix and suffix rows): prefill "
+                     "with kv_dtype='bf16'")
+  if isinstance(n_samples, bool) or not isinstance(n_samples, int) or n_samples < 1:
+    raise ValueError(f'fork: n_samples must be an int >= 1, got {n_samples!r}')
+  if int(max_new_tokens) < 1:
+    raise ValueError(f'fork: max_new_tokens must be at least 1, got {max_new_tokens}')
+  return n_samples, int(max_new_tokens)
+
+
+def refuse_shared(what, cache):
+  if isinstance(cache, SharedPrefixCache):
+    raise TypeError(f'Transformer.{what}: a SharedPrefixCache takes decode steps only (decode_step, generate_samples): no chunks, no '
+                    'speculative or lookup rounds')
+
+
+def refuse_shared_mxfp8(what, model):
+  if model.cfg.linear_precision == 'mxfp8':
+    raise ValueError(f'Transformer.{what}: linear_precision: mxfp8 has no shared-prefix decode path (the decode step runs the bf16 shadows)')
 
 
 def refuse_cpu(tokens):
@@ -647,6 +710,8 @@ class Generation:
     is (``cached_layers``), with ops.kv_append_rope / ops.attn_decode as the attention stage.  fused=True runs
     every layer as one library call over the skinny-M kernels (``fused_layers``: the same rounding points, other fp32 summation orders,
     so close to but not the bits of the default); it serves B <= ops.FUSED_DECODE_MAX_ROWS and raises ValueError otherwise."""
+    if isinstance(cache, SharedPrefixCache):
+      refuse_shared_mxfp8('decode_step', self)
     guard('decode_step', tokens, self)
     B = cache.B
     if tuple(tokens.shape) != (B,):
@@ -662,6 +727,9 @@ class Generation:
         return self.head(self.fused_layers(tokens.contiguous(), cache, rope), logits, (B,))
 
       def attend(i, qkv):
+        if isinstance(cache, SharedPrefixCache):  # row pos of the suffix, rotated at rot0 + pos; prefix, then suffix
+          q, _ = ops.kv_append_rope_at(qkv, cache.pos, cache.rot0, rope[0], rope[1], cache.kv[i], nh, status=cache.status)
+          return ops.attn_decode_shared(q, cache.prefix.kv[i], cache.prefix.lens, cache.kv[i], cache.lens, nh)
         if cache.kv_dtype == 'fp8':  # the decode step is the chunk append at n = 1
           q, _ = ops.kv8_append_rope_rows(qkv, cache.pos, rope[0], rope[1], cache.kv[i], nh, status=cache.status)
           return ops.attn_decode_kv8(q, cache.kv[i], cache.lens, nh)
@@ -696,6 +764,7 @@ class Generation:
     ``cache.check()``.  Runs under no_grad.  fused=True runs every layer as one library call over the skinny-M
     kernels (``fused_layers`` with the chunk: the same rounding points, other fp32 summation orders, so close to but not the bits of the default);
     it serves B * n <= ops.FUSED_EXTEND_MAX_ROWS chunk rows and raises ValueError otherwise, before anything is launched."""
+    refuse_shared('extend', cache)
     if isinstance(tokens, torch.Tensor) and (tokens.dim() != 2 or tokens.shape[0] != cache.B or tokens.shape[1] < 1):
       raise ValueError(f'extend: tokens {tuple(tokens.shape)} are not a [B, n] chunk for the cache\'s batch of {cache.B}')
     guard('extend', tokens, self)
@@ -724,6 +793,52 @@ class Generation:
       else:
         y = last_rows(y, B, n, n_new.clamp(min=1))
       return self.head(y, logits, (B,))
+
+  def fork(self, cache, n_samples, max_new_tokens):
+    """A SharedPrefixCache for n_samples continuations of every prompt of the prefilled bf16 ``cache``, max_new_tokens suffix rows each.
+    The prompts' rows stay where they are, once; ``cache`` must not be appended to afterwards.  Refused: an FP8 cache (ValueError), a
+    SharedPrefixCache (TypeError), an mxfp8 model (ValueError)."""
+    refuse_shared_mxfp8('fork', self)
+    check_fork(cache, n_samples, max_new_tokens)
+    check_cache('fork', cache, self)
+    return SharedPrefixCache(cache, n_samples, max_new_tokens)
+
+  @torch.compiler.disable
+  def generate_samples(self, prompt, n_samples, max_new_tokens, prompt_lens=None, eos_id=None, temperature=None, top_k=None, top_p=None,
+                       seed=None, return_logprobs=False, fused=False):
+    """n_samples continuations of every prompt of prompt int64 [P, T] (best-of-n, self-consistency, policy-gradient rollouts): returns the
+    new tokens int64 [P, n_samples, max_new_tokens], with return_logprobs also their log-probabilities fp32 of that shape.  ONE prefill of
+    the P prompts; their k | v rows are stored once (``fork``) and every decode step reads them once per 32 samples (DESIGN.md section
+    21).  The first token of all samples is drawn from the prompt's one last-row logits (the row repeated, one ops.sample_logits launch),
+    the rest are decode steps on the SharedPrefixCache.  temperature / top_k / top_p / seed / eos_id / prompt_lens as ``generate`` takes
+    them; the uniforms of the whole call are drawn once for P * n_samples rows, so a seed reproduces it bit for bit.  Without sampling
+    arguments the call is greedy and the samples of a prompt are identical.  fused=True runs the decode steps through
+    ops.decode_layer_shared and serves P * n_samples <= ops.FUSED_DECODE_MAX_ROWS, ValueError beyond."""
+    who = 'generate_samples'
+    refuse_shared_mxfp8(who, self)
+    guard(who, prompt, self, forward_only=True, rank2=True)
+    if isinstance(n_samples, bool) or not isinstance(n_samples, int) or n_samples < 1:
+      raise ValueError(f'{who}: n_samples must be an int >= 1, got {n_samples!r}')
+    P, T = prompt.shape
+    G, N = n_samples, int(max_new_tokens)
+    check_lengths(T, max_new_tokens, self.cfg.seq_len)
+    on_device = check_sampling(temperature, top_k, top_p, None, seed)
+    if fused:
+      check_fused(who, P * G, self.cfg.dim)
+    want_logits = on_device is not None
+    cache, r = self.prefill(prompt, prompt_lens, max_len=pad4(T), logits=want_logits, kv_dtype='bf16')
+    shared = self.fork(cache, G, N)
+    with torch.no_grad():
+      if want_logits:
+        pick = sampling_pick(draw_uniforms(N, P * G, prompt.device, seed), *on_device)
+        first = pick(r.repeat_interleave(G, dim=0))
+      else:
+        pick = lambda o: (o.tokens, o.logprob)  # noqa: E731
+        first = (r.tokens.repeat_interleave(G), r.logprob.repeat_interleave(G))
+      toks, lps = generate_loop(first, lambda t: pick(self.decode_step(t, shared, logits=want_logits, fused=fused)), N, eos_id)
+    shared.check()
+    toks, lps = toks.view(P, G, N), lps.view(P, G, N)
+    return (toks, lps) if return_logprobs else toks
 
   @torch.compiler.disable
   def generate(self, prompt, max_new_tokens, prompt_lens=None, eos_id=None, sample=None, return_logprobs=False, temperature=None,

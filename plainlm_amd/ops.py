@@ -1149,6 +1149,9 @@ from .ops_decode import FUSED_EXTEND_MAX_ROWS, extend_layer, extend_layer_worksp
 # ---- the FP8 KV cache: its wrappers live in ops_kv8.py, on this module's and ops_decode.py's contract ------------------
 from .ops_kv8 import (KV8_BLOCK, attn_decode_kv8, attn_extend_kv8, decode_layer_kv8, extend_layer_kv8,  # noqa: E402,F401
                       extend_norm_qkv_append_kv8, kv8_append_rope_rows, kv8_dequant_rows, kv8_quant_rows, kv8_row_bytes)
+# ---- parallel sampling from one prompt: shared-prefix decode attention; its wrappers live in ops_shared.py ------------
+from .ops_shared import (attn_decode_shared, attn_decode_shared_workspace_bytes, decode_layer_shared, decode_norm_qkv_append_at,  # noqa: E402,F401
+                         kv_append_rope_at)
 # ---- the Muon tail: batched NT GEMM, prepare / orthogonalize / apply; its wrappers live in ops_muon.py -------------------
 from .ops_muon import (MUON_ADJUST_LR, MUON_EPS, MUON_NS_COEFFICIENTS, NT_BATCH_GROUP, gemm_nt_batched, muon_adjusted_lr, muon_apply,  # noqa: E402,F401
                        muon_arena, muon_blocks, muon_items, muon_layout, muon_ns_flops, muon_orthogonalize, muon_prepare, muon_set_lr,

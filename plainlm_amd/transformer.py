@@ -560,6 +560,17 @@ class Transformer(nn.Module, G.Generation):
     tokens int64 [B * n] with B * n <= ops.FUSED_EXTEND_MAX_ROWS (ops.extend_layer: row b * n + r is appended at lens0[b] + r, n_new
     int32 [B] or None as ops.kv_append_rope_rows takes it).  Returns the final normed rows [B or B * n, dim]."""
     fp8 = cache.kv_dtype == 'fp8'  # DESIGN.md section 20: the same calls over the FP8 cache
+    if isinstance(cache, G.SharedPrefixCache):  # a SharedPrefixCache (DESIGN.md section 21): decode steps only, ops.decode_layer_shared per layer
+      if chunk is not None:
+        raise TypeError('fused_layers: a SharedPrefixCache takes decode steps only')
+      self.refresh_shadows()
+      x = ops.embed_fwd(tokens, self.embed_tokens.weight)
+      for i, layer in enumerate(self.layers):
+        ops.decode_layer_shared(x, layer.attn_norm.weight, layer.mlp_norm.weight, layer.attn_norm.eps, layer.attn.w_qkv.shadow()[0],
+                                layer.attn.w_out.shadow()[0], layer.mlp.fc1.shadow()[0], layer.mlp.fc2.shadow()[0], cache.pos, cache.lens,
+                                cache.rot0, cache.prefix.lens, rope[0], rope[1], cache.prefix.kv[i], cache.kv[i], self.cfg.n_heads,
+                                layer.mlp.kind, cache.status)
+      return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps)[1]
     if chunk is None:
       layer_op, lengths = ops.decode_layer_kv8 if fp8 else ops.decode_layer, (cache.pos, cache.lens)
     else:

@@ -17,10 +17,15 @@ With --kv fp8 the sides are the two cache formats: one mo
 tokens, the unfused and the fused decode step over each alternating in one process at (B, context) = (8, 1024), (8, 4096), (32, 1024),
 (32, 4096), then extend(fused=True) at (B, n) = (8, 4) on 1024 cached tokens: device ms, median of --runs [min max], and per row whether the
 FP8 side's [min max] lies wholly below the bf16 side's.
+With --samples G [G ...] the sides are the two ways to decode G continuations of ONE prompt: decode_step on a KVCache
+that holds the prompt G times (R, all there was before) and decode_step on a SharedPrefixCache (S: the prompt once, every step reads it once
+per 32 samples), unfused and fused, all four alternating in one process at prompt 1024 and 4096 (--context), after 64 generated tokens:
+device ms median [min max], host enqueue, library calls and kernel launches, and the cache bytes of both forms.
 Usage: python tools/gen_bench.py [--runs 20] [--out profiles/generate_bench.txt]
        python tools/gen_bench.py --fused [--batch 1 32] [--context 4096] --out profiles/fused_decode_bench.txt
        python tools/gen_bench.py --fused-extend --out profiles/fused_extend_bench.txt
-       python tools/gen_bench.py --kv fp8 --out profiles/kv8_bench.txt"""
+       python tools/gen_bench.py --kv fp8 --out profiles/kv8_bench.txt
+       python tools/gen_bench.py --samples 8 32 --context 1024 4096 --out profiles/shared_prefix_bench.txt"""
 import argparse
 import os
 import statistics
@@ -50,7 +55,8 @@ def med(v):
 
 
 # kernel launches behind one call of an entry point at the decode shapes (include/plainlm_hip.h)
-LAUNCHES = {'plm_attn_decode': 2, 'plm_head_predict_bf16': 2, 'plm_decode_layer_bf16': 6}
+LAUNCHES = {'plm_attn_decode': 2, 'plm_head_predict_bf16': 2, 'plm_decode_layer_bf16': 6, 'plm_attn_decode_shared': 3,
+            'plm_decode_layer_shared_bf16': 7}
 
 
 def alternate(sides, reset, a):
@@ -273,6 +279,59 @@ def main_kv(a):
       f.write(text)
 
 
+def main_samples(a):
+  torch.manual_seed(0)
+  done, room = 64, 68  # tokens every sample has generated before the timed step; suffix rows per sample
+  ctxs = a.context or [1024, 4096]
+  cfg = ModelConfig(vocab_size=50280, seq_len=max(ctxs) + room, dim=768, expand=8 / 3, n_layers=12, n_heads=12, mlp='glu')
+  m = Transformer(cfg).cuda()
+  lines = ['# tools/gen_bench.py --samples: 160M (12 layers, d 768, 12 heads, V 50280), P = 1 prompt, G samples, after %d generated tokens; R = '
+           'decode_step on a KVCache holding the prompt G times, S = decode_step on a SharedPrefixCache (the prompt once); one process, the four '
+           'sides alternating; ms per step, HIP events, median of %d [min max]; host enqueue = wall time of the call, not waited for' % (done, a.runs)]
+  with torch.no_grad():
+    for ctx in ctxs:
+      prompt = torch.randint(0, cfg.vocab_size, (1, ctx), device='cuda')
+      pcache, _ = m.prefill(prompt, max_len=ctx)
+      for Gs in a.samples:
+        shared = m.fork(pcache, Gs, room)
+        repl = G.KVCache(cfg.n_layers, Gs, ctx + room, cfg.n_heads, m.head_dim, prompt.device)
+        for i in range(cfg.n_layers):  # the same keys on both sides: the prompt's rows, then every sample's own
+          shared.kv[i].copy_(torch.randn(shared.kv[i].shape, device='cuda') * 0.5)
+          repl.kv[i][:, :ctx] = pcache.kv[i][0, :ctx]
+          repl.kv[i][:, ctx:] = shared.kv[i]
+        l_s = torch.full((Gs,), done, dtype=torch.int32, device='cuda')
+        l_r = l_s + ctx
+        nxt = torch.randint(0, cfg.vocab_size, (Gs,), device='cuda')
+        sides = {(c, f): (lambda c=c, f=f: m.decode_step(nxt, c, fused=f)) for f in (False, True) for c in (repl, shared)}
+
+        def reset():
+          repl.set_lens(l_r)
+          shared._pl[1].copy_(l_s)
+          shared._pl[0].copy_(l_s - 1)
+        dev, host, calls, ret = alternate(sides, reset, a)
+        rb, sb = sum(t.numel() * 2 for t in repl.kv), shared.cache_bytes()
+        lines.append('G = %d, prompt %d: cache bytes replicated %d, shared %d (%.1f x); per step and layer the replicated step streams %d B of '
+                     'k | v, the shared step %d B' % (Gs, ctx, rb, sb, rb / sb, Gs * (ctx + done + 1) * 4 * cfg.dim,
+                                                      (-(-Gs // 32) * ctx + Gs * (done + 1)) * 4 * cfg.dim))
+        for f, what in ((False, 'decode step'), (True, 'fused decode step')):
+          for c, name in ((repl, 'replicated (R)'), (shared, 'shared (S)    ')):
+            k = (c, f)
+            lines.append('  %-17s %s  device %s   host enqueue %s   library calls %3d   kernel launches %3d'
+                         % (what, name, med(dev[k]), med(host[k]), len(calls[k]), 1 + sum(LAUNCHES.get(w, 1) for w in calls[k])))
+          r, sh = (repl, f), (shared, f)
+          below = max(dev[sh]) < min(dev[r])
+          lines.append('    R / S (medians) %.2f; S\'s [min max] lies %s R\'s; same greedy token %.3f of %d samples, max |dlogp| %.2e'
+                       % (statistics.median(dev[r]) / statistics.median(dev[sh]), 'wholly below' if below else 'NOT wholly below',
+                          (ret[r].tokens == ret[sh].tokens).float().mean().item(), Gs, (ret[r].logprob - ret[sh].logprob).abs().max().item()))
+        del shared, repl, sides
+      del pcache
+  text = '\n'.join(lines) + '\n'
+  print(text, end='')
+  if a.out:
+    with open(a.out, 'w') as f:
+      f.write(text)
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--runs', type=int, default=20)
@@ -283,7 +342,11 @@ def main():
   ap.add_argument('--context', type=int, nargs='*', default=[], help='--fused: extra contexts at B = %d' % B)
   ap.add_argument('--fused-extend', action='store_true', help='compare extend(fused=True) and a generate_lookup_fused round with the unfused ones')
   ap.add_argument('--kv', choices=['fp8'], default=None, help='compare the decode steps over an FP8 KV cache with those over the bf16 cache')
+  ap.add_argument('--samples', type=int, nargs='+', default=None, help='compare decode steps on a SharedPrefixCache of G samples of one prompt '
+                  'with those on a cache that holds the prompt G times (prompt lengths: --context, default 1024 4096)')
   a = ap.parse_args()
+  if a.samples:
+    return main_samples(a)
   if a.kv:
     return main_kv(a)
   if a.fused:
