@@ -491,6 +491,75 @@ int plm_decode_layer_shared_bf16(float* x, const float* attn_norm_w, const float
                                  int64_t Tp_max, int64_t Ts_max, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits_p,
                                  int splits_s, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- tree verification for lookup decoding: one extend over a trie of drafts -----
+ * Every argument check of these entry points comes before any HIP call.  A chunk is n rows per sequence, 1 <= n <= 32; row 0 is the root
+ * (the newest committed token, not yet in the cache); parent int32 [B, n]: parent[b, 0] = -1 and 0 <= parent[b, r] < r (or -1: another
+ * root); n_new int32 [B] (NULL: n) the real rows, clamped to [0, n] on the device.  depth[r] = depth[parent[r]] + 1; anc[r] has bit j set
+ * iff j == r or row j is an ancestor of r.  Row r of sequence b is STORED at cache row lens0[b] + r and ROTATED at lens0[b] + depth[b, r].
+ * bf16 caches only.
+ *
+ * plm_tree_plan: parent, n_new -> depth int32 [B, n], anc uint32 [B, n]; one launch.  Rows at and beyond n_new[b] get depth 0, anc 0.
+ * A real row whose parent lies outside [-1, r) refuses its sequence: status[0] = 1, depth = -1 and anc = 0 for all its rows, and the
+ * append stages below store nothing for it.
+ *
+ * plm_kv_append_rope_tree: plm_kv_append_rope_rows with the RoPE table row lens0[b] + depth[b, r] in place of lens0[b] + r; the storage
+ * row, the refusal predicate (applied to lens0 + n_new, which bounds the deepest position) and the zero q rows are unchanged; a sequence
+ * with depth[b, 0] < 0 is refused too.  depth may be NULL: position = row, the stored and returned bits of
+ * plm_kv_append_rope_rows (as they are with depth[b, r] = r).
+ *
+ * plm_attn_extend_tree: q bf16 [B*n, nh*hd] rotated, the cache with the chunk appended, lens0 (clamped to [0, Tmax]), n_new, anc.  Row
+ * r < n_new[b] attends keys 0 .. lens0[b]-1 and the chunk keys lens0[b] + j with bit j of anc[b, r] set; writes out bf16 [B*n, nh*hd] and,
+ * unless NULL, lse fp32 [B*n, nh] (base 2).  Rows at and beyond n_new[b] get out = 0, lse = +INFINITY.  Three launches over
+ * plm_attn_decode_shared's partial layout with one suffix partial: its prefix kernel at P = B, G = n, lens_p = lens0 (S_p splits by its
+ * rule: a function of B, n, nh, Tmax and the CU count alone; splits 0 = automatic, 1..64 forced), one wave per (sequence, head) over
+ * the chunk keys under the ancestor mask, and plm_attn_decode's combine over the S_p + 1 partials in key order.  No atomics:
+ * bit-reproducible, and a row's bits do not depend on chunk rows outside its ancestor set.  workspace:
+ * plm_attn_extend_tree_workspace_bytes(...) bytes, 16-byte aligned (0 for arguments the launch refuses).
+ *
+ * plm_tree_accept_greedy: tok int64 [B, n] the rows' tokens, pred int64 [B, n] / logp fp32 [B, n] the target's greedy prediction after
+ * every row and its log-probability.  From row 0, descend to the smallest-index real child of the current row whose token equals the
+ * current row's prediction; stop when there is none.  n_accept int32 [B] = the depth reached; path int32 [B, n] = the row at every
+ * accepted depth (path[0] = 0, -1 beyond n_accept); acc_tok int64 [B, n-1] = the accepted tokens in path order, 0 beyond; next_tok
+ * int64 [B] = the prediction of the last accepted row; logp_out fp32 [B, n] = the log-probabilities of the accepted tokens followed by
+ * next_tok's, 0 beyond.  One launch, one wave per sequence, integers and copies only.
+ *
+ * plm_kv_tree_commit: for d = 1 .. n_accept[b], cache row lens0[b] + path[b, d] is copied to row lens0[b] + d, in every layer's cache.
+ * kv_layers: a HOST array of n_layers device pointers, each a cache [B, Tmax, ld_kv] (passed to the kernel by value, one launch per 64
+ * layers).  Rows with path[d] == d and rows beyond lens0 + n_accept are left as they are; a path that is not strictly increasing with
+ * path[d] >= d, or that leaves the chunk or the cache, ends the sequence's copy there.
+ *
+ * plm_lookup_draft_tree_i64: plm_lookup_draft_i64's history handling and match rule, keeping the up to n_branch (<= 8) most recent ends
+ * of the longest match; their continuations, k tokens each, are merged into a trie of at most n rows in creation order (the most
+ * recent match first; equal tokens under one parent share a row).  Writes tok int64 [B, n] (row 0 = the sequence's newest token),
+ * parent int32 [B, n] (-1 in row 0 and in unused rows), n_new int32 [B] = rows used (1 without a match), and, unless NULL, match_len.
+ * A refused sequence (its append does not fit ld, or its history is empty) gets n_new = 0 and status[0] = 1.  With n_branch = 1 and
+ * n > k rows 1 .. k are plm_lookup_draft_i64's proposal.
+ *
+ * plm_extend_layer_tree_bf16: plm_extend_layer_bf16 for B*n <= 32 tree rows: the qkv stage under plm_kv_append_rope_tree's contract and
+ * plm_attn_extend_tree's three launches as its attention stage.  Workspace: plm_extend_layer_tree_workspace_bytes(...). */
+int plm_tree_plan(const int32_t* parent, const int32_t* n_new, int32_t* depth, uint32_t* anc, int32_t* status, int64_t B, int64_t n, void* stream);
+int plm_kv_append_rope_tree(const uint16_t* qkv, int64_t ld_qkv, const int32_t* lens0, const int32_t* n_new, const int32_t* depth,
+                            const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv,
+                            int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, void* stream);
+size_t plm_attn_extend_tree_workspace_bytes(int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t Tmax, int splits);
+int plm_attn_extend_tree(const uint16_t* q, const uint16_t* kv, int64_t ld_kv, const int32_t* lens0, const int32_t* n_new, const uint32_t* anc,
+                         uint16_t* out, float* lse, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, int splits, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int plm_tree_accept_greedy(const int64_t* tok, const int32_t* parent, const int32_t* n_new, const int64_t* pred, const float* logp,
+                           int32_t* n_accept, int32_t* path, int64_t* acc_tok, int64_t* next_tok, float* logp_out, int64_t B, int64_t n,
+                           void* stream);
+int plm_kv_tree_commit(uint16_t** kv_layers, int64_t n_layers, int64_t ld_kv, const int32_t* lens0, const int32_t* path,
+                       const int32_t* n_accept, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, void* stream);
+int plm_lookup_draft_tree_i64(int64_t* hist, int64_t ld, int32_t* lens, const int64_t* add_tok, int64_t ld_add, const int32_t* n_add,
+                              int64_t* tok, int32_t* parent, int32_t* n_new, int32_t* match_len, int32_t* status, int64_t B, int64_t n, int64_t k,
+                              int64_t n_branch, int64_t g_min, int64_t g_max, void* stream);
+size_t plm_extend_layer_tree_workspace_bytes(int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t hidden, int64_t Tmax, int splits);
+int plm_extend_layer_tree_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                               const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* lens0, const int32_t* n_new,
+                               const int32_t* depth, const uint32_t* anc, const float* rope_cos, const float* rope_sin, int64_t rope_T,
+                               uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd,
+                               int64_t hidden, int mlp_kind, int splits, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- temperature / top-k / top-p sampling of one token per row -----
  * Every argument check comes before any HIP call.
  * logits bf16 [B, ld] (ld >= V; any 2-byte aligned base and any ld: columns >= V are never loaded); u fp32 [B], one uniform per row,

@@ -152,6 +152,16 @@ SIGNATURES = {
   'plm_decode_layer_shared_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I]),
   'plm_decode_layer_shared_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64,
                                         _I64, _I64, _I64, _I64, _I, _I, _I, _P, _SZ, _P]),
+  'plm_tree_plan': (_I, [_P, _P, _P, _P, _P, _I64, _I64, _P]),
+  'plm_kv_append_rope_tree': (_I, [_P, _I64, _P, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P]),
+  'plm_attn_extend_tree_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I]),
+  'plm_attn_extend_tree': (_I, [_P, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
+  'plm_tree_accept_greedy': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P]),
+  'plm_kv_tree_commit': (_I, [C.POINTER(_P), _I64, _I64, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P]),
+  'plm_lookup_draft_tree_i64': (_I, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
+  'plm_extend_layer_tree_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I64, _I]),
+  'plm_extend_layer_tree_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64,
+                                      _I, _I, _P, _SZ, _P]),
   'plm_sample_logits_bf16': (_I, [_P, _I64, _P, _F, _I64, _F, _P, _P, _P, _P, _I64, _I64, _P]),
   'plm_spec_verify_bf16': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I64, _I64, _I64, _P]),
   'plm_lookup_draft_i64': (_I, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P]),

@@ -41,8 +41,9 @@ __device__ __forceinline__ int ext_clamp(int v, int lo, int hi) { return v < lo 
 // a row writes nothing at all (the decode contract: q_out stays as the caller left it).
 __global__ __launch_bounds__(256) void kv_append_rope_rows_kernel(const uint16_t* __restrict__ qkv, int64_t ld_qkv,
                                                                   const int32_t* __restrict__ lens0, const int32_t* __restrict__ n_new,
-                                                                  const int32_t* __restrict__ rot0, const float* __restrict__ rcos,
-                                                                  const float* __restrict__ rsin, int rope_T, uint16_t* __restrict__ q_out,
+                                                                  const int32_t* __restrict__ rot0, const int32_t* __restrict__ depth,
+                                                                  const float* __restrict__ rcos, const float* __restrict__ rsin, int rope_T,
+                                                                  uint16_t* __restrict__ q_out,
                                                                   uint16_t* __restrict__ kv, int64_t ld_kv, int32_t* __restrict__ status, int B,
                                                                   int n, int Tmax, int nh, int hd, float sgn, int zero_q) {
   const int dm = nh * hd;
@@ -57,18 +58,23 @@ __global__ __launch_bounds__(256) void kv_append_rope_rows_kernel(const uint16_t
   const int cb = ext_clamp(n_new != nullptr ? n_new[b] : n, 0, n);
   // rot0 (plm_kv_append_rope_at): the rows go to l0 + r as ever but are rotated at rot0[b] + l0 + r; null: position = row
   const int r0 = rot0 != nullptr ? rot0[b] : 0;
-  const bool refused = l0 < 0 || r0 < 0 || (int64_t)l0 + cb > Tmax || (int64_t)r0 + l0 + cb > rope_T;  // nothing of this sequence is stored
+  // depth (plm_kv_append_rope_tree): row r is a tree node, stored at l0 + r as ever but rotated at l0 + depth[b, r]
+  // (0 <= depth <= r, so the deepest position is below l0 + cb and the predicate covers it); plm_tree_plan marks a sequence whose
+  // parents it refused with depth[b, 0] < 0, and nothing of it is stored.  null: position = row, today's bits
+  const bool refused = l0 < 0 || r0 < 0 || (int64_t)l0 + cb > Tmax || (int64_t)r0 + l0 + cb > rope_T ||
+                       (depth != nullptr && depth[(int64_t)b * n] < 0);  // nothing of this sequence is stored
   if (refused && r == 0 && c == 0) status[0] = 1;
   if (refused || r >= cb) {  // no cache row
     if (zero_q && col < dm) st_bf16x8(q_out + row * dm + col, zero_bf16x8());
     return;
   }
   const int t = l0 + r;
+  const int tr = depth != nullptr ? l0 + ext_clamp(depth[row], 0, r) : t;  // the RoPE table row before rot0
   bf16x8_t v = ld_bf16x8(qkv + row * ld_qkv + col);
   if (col < 2 * dm) {  // q | k: the rotation of rope_qk_kernel (attn.hip), same table loads, same rope8
     const int pair0 = (col % hd) / 2;
-    const f32x4_t cs = *reinterpret_cast<const f32x4_t*>(rcos + (int64_t)(r0 + t) * (hd / 2) + pair0);
-    const f32x4_t sn = *reinterpret_cast<const f32x4_t*>(rsin + (int64_t)(r0 + t) * (hd / 2) + pair0);
+    const f32x4_t cs = *reinterpret_cast<const f32x4_t*>(rcos + (int64_t)(r0 + tr) * (hd / 2) + pair0);
+    const f32x4_t sn = *reinterpret_cast<const f32x4_t*>(rsin + (int64_t)(r0 + tr) * (hd / 2) + pair0);
     v = rope8(v, cs, sn, sgn);
   }
   if (col < dm)
@@ -482,14 +488,17 @@ __global__ __launch_bounds__(256, 2) void attn_extend_kernel(const uint16_t* __r
 template <int HD>
 __global__ __launch_bounds__(HD) void attn_cache_combine_kernel(const float* __restrict__ ws_acc, const float* __restrict__ ws_ml,
                                                                 const int32_t* __restrict__ n_new, uint16_t* __restrict__ out,
-                                                                float* __restrict__ lse, int n, int nh, int S) {
+                                                                float* __restrict__ lse, int n, int nh, int S, int grp) {
   const int r = (int)(blockIdx.x % n), bh = (int)(blockIdx.x / n), h = bh % nh, b = bh / nh, d = threadIdx.x;
-  const int cb = ext_clamp(n_new != nullptr ? n_new[b] : n, 0, n);
+  // grp > 0 (n == 1; plm_attn_extend_tree): `b` counts query rows in the shared-prefix layout, grp of them per n_new entry - row b is
+  // chunk row b % grp of sequence b / grp.  grp == 0: one n_new entry per b, as ever
+  const int rr = grp > 0 ? b % grp : r, nn = grp > 0 ? grp : n;
+  const int cb = ext_clamp(n_new != nullptr ? n_new[grp > 0 ? b / grp : b] : nn, 0, nn);
   bf16_t o = f2bf(0.f);
   // a row at or beyond c_b (its partials, never written, are not read) and a row without any key (lens[b] == 0): the masked kernels'
   // rule for such a row, out = 0 and lse = +inf
   float Lq = INFINITY;
-  if (r < cb) {
+  if (rr < cb) {
     float mm = -INFINITY;
     for (int s = 0; s < S; ++s) mm = fmaxf(mm, ws_ml[(((int64_t)bh * S + s) * n + r) * 2]);
     if (mm != -INFINITY) {
@@ -546,8 +555,7 @@ extern "C" size_t plm_attn_decode_workspace_bytes(int64_t B, int64_t nh, int64_t
 
 // the append stage: every refusal, then the one launch.  `fn` is the entry point the caller sees.
 static int append_rows(const char* fn, const uint16_t* qkv, int64_t ld_qkv, const int32_t* lens0, const int32_t* n_new, const int32_t* rot0,
-                       const float* rope_cos,
-                       const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t n,
+                       const int32_t* depth, const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t n,
                        int64_t Tmax, int64_t nh, int64_t hd, bool zero_q, void* stream) {
   PLM_REQUIRE(qkv && lens0 && rope_cos && rope_sin && q_out && kv && status, "%s: null pointer", fn);
   PLM_REQUIRE(hd == 32 || hd == 64 || hd == 128, "%s: head_dim %ld unsupported (32, 64, 128)", fn, (long)hd);
@@ -561,7 +569,7 @@ static int append_rows(const char* fn, const uint16_t* qkv, int64_t ld_qkv, cons
   const int64_t blocks = plm_cdiv(B * n * (3 * nh * hd / 8), 256);
   PLM_REQUIRE(blocks < ((int64_t)1 << 31), "%s: bad shape: B*n*nh*hd too large for one launch", fn);
   hipLaunchKernelGGL(kv_append_rope_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, qkv, ld_qkv, lens0, n_new, rot0,
-                     rope_cos, rope_sin, (int)rope_T, q_out, kv, ld_kv, status, (int)B, (int)n, (int)Tmax, (int)nh, (int)hd, 1.f, (int)zero_q);
+                     depth, rope_cos, rope_sin, (int)rope_T, q_out, kv, ld_kv, status, (int)B, (int)n, (int)Tmax, (int)nh, (int)hd, 1.f, (int)zero_q);
   PLM_CHECK_LAUNCH(fn);
   return PLM_OK;
 }
@@ -569,23 +577,32 @@ static int append_rows(const char* fn, const uint16_t* qkv, int64_t ld_qkv, cons
 extern "C" int plm_kv_append_rope(const uint16_t* qkv, int64_t ld_qkv, const int32_t* pos, const float* rope_cos, const float* rope_sin,
                                   int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t Tmax,
                                   int64_t nh, int64_t hd, void* stream) {
-  return append_rows("plm_kv_append_rope", qkv, ld_qkv, pos, nullptr, nullptr, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, 1, Tmax, nh, hd,
+  return append_rows("plm_kv_append_rope", qkv, ld_qkv, pos, nullptr, nullptr, nullptr, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, 1, Tmax, nh, hd,
                      false, stream);
 }
 
 extern "C" int plm_kv_append_rope_rows(const uint16_t* qkv, int64_t ld_qkv, const int32_t* lens0, const int32_t* n_new, const float* rope_cos,
                                        const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv, int32_t* status,
                                        int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, void* stream) {
-  return append_rows("plm_kv_append_rope_rows", qkv, ld_qkv, lens0, n_new, nullptr, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, n, Tmax, nh,
-                     hd, true, stream);
+  return append_rows("plm_kv_append_rope_rows", qkv, ld_qkv, lens0, n_new, nullptr, nullptr, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, n, Tmax,
+                     nh, hd, true, stream);
 }
 // one token per sequence at row[b], rotated at rot0[b] + row[b] (a suffix cache); a refused row leaves zeros in q_out
 extern "C" int plm_kv_append_rope_at(const uint16_t* qkv, int64_t ld_qkv, const int32_t* row, const int32_t* rot0, const float* rope_cos,
                                      const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B,
                                      int64_t Tmax, int64_t nh, int64_t hd, void* stream) {
   PLM_REQUIRE(rot0, "plm_kv_append_rope_at: null pointer");
-  return append_rows("plm_kv_append_rope_at", qkv, ld_qkv, row, nullptr, rot0, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, 1, Tmax, nh,
-                     hd, true, stream);
+  return append_rows("plm_kv_append_rope_at", qkv, ld_qkv, row, nullptr, rot0, nullptr, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B, 1, Tmax,
+                     nh, hd, true, stream);
+}
+// a chunk of tree nodes: row r of sequence b is stored at lens0[b] + r and rotated at lens0[b] + depth[b, r]; a NULL
+// depth is plm_kv_append_rope_rows at n <= 32, bit for bit
+extern "C" int plm_kv_append_rope_tree(const uint16_t* qkv, int64_t ld_qkv, const int32_t* lens0, const int32_t* n_new, const int32_t* depth,
+                                       const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv,
+                                       int64_t ld_kv, int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, void* stream) {
+  PLM_REQUIRE(n >= 1 && n <= 32, "plm_kv_append_rope_tree: n=%ld tree rows (need 1 <= n <= 32)", (long)n);
+  return append_rows("plm_kv_append_rope_tree", qkv, ld_qkv, lens0, n_new, nullptr, depth, rope_cos, rope_sin, rope_T, q_out, kv, ld_kv, status, B,
+                     n, Tmax, nh, hd, true, stream);
 }
 
 // the FP8 cache's stride rule: bytes, a multiple of 16 (the 16-byte code stores and 8-byte code loads stay aligned), at least the payload
@@ -678,7 +695,7 @@ static void dec_launch(const uint16_t* q, const KV* kv, int64_t ld_kv, const int
   hipLaunchKernelGGL((attn_decode_split_kernel<HD, KV>), dim3((unsigned)(B * nh), (unsigned)S), dim3(DEC_THREADS), 0, s, q, kv, ld_kv, lens, ws_ml,
                      ws_acc, (int)Tmax, (int)nh, S, c2, S, 0);
   hipLaunchKernelGGL(attn_cache_combine_kernel<HD>, dim3((unsigned)(B * nh)), dim3(HD), 0, s, ws_acc, ws_ml, (const int32_t*)nullptr, out, lse, 1,
-                     (int)nh, S);
+                     (int)nh, S, 0);
 }
 
 // what attn_shared.hip borrows (attn_cache.h): the split kernel into a wider partial layout, and the combine over all of it
@@ -697,12 +714,12 @@ void cache_decode_partials_launch(const uint16_t* q, const uint16_t* kv, int64_t
   else dec_partials<128>(q, kv, ld_kv, lens, ws_ml, ws_acc, B, Tmax, nh, S, part_stride, part_off, s);
 }
 
-void cache_combine_launch(const float* ws_acc, const float* ws_ml, uint16_t* out, float* lse, int64_t B, int64_t nh, int64_t hd, int S, hipStream_t s) {
+void cache_combine_launch(const float* ws_acc, const float* ws_ml, uint16_t* out, float* lse, int64_t B, int64_t nh, int64_t hd, int S, hipStream_t s,
+                          const int32_t* n_new, int grp) {
   const dim3 grid((unsigned)(B * nh));
-  const int32_t* none = nullptr;
-  if (hd == 32) hipLaunchKernelGGL(attn_cache_combine_kernel<32>, grid, dim3(32), 0, s, ws_acc, ws_ml, none, out, lse, 1, (int)nh, S);
-  else if (hd == 64) hipLaunchKernelGGL(attn_cache_combine_kernel<64>, grid, dim3(64), 0, s, ws_acc, ws_ml, none, out, lse, 1, (int)nh, S);
-  else hipLaunchKernelGGL(attn_cache_combine_kernel<128>, grid, dim3(128), 0, s, ws_acc, ws_ml, none, out, lse, 1, (int)nh, S);
+  if (hd == 32) hipLaunchKernelGGL(attn_cache_combine_kernel<32>, grid, dim3(32), 0, s, ws_acc, ws_ml, n_new, out, lse, 1, (int)nh, S, grp);
+  else if (hd == 64) hipLaunchKernelGGL(attn_cache_combine_kernel<64>, grid, dim3(64), 0, s, ws_acc, ws_ml, n_new, out, lse, 1, (int)nh, S, grp);
+  else hipLaunchKernelGGL(attn_cache_combine_kernel<128>, grid, dim3(128), 0, s, ws_acc, ws_ml, n_new, out, lse, 1, (int)nh, S, grp);
 }
 
 // plm_attn_decode and plm_attn_decode_kv8: `fn` is the entry point the caller sees
@@ -741,7 +758,7 @@ static void ext_launch(const uint16_t* q, const KV* kv, int64_t ld_kv, const int
                      lse, ws_acc, ws_ml, (int)n, (int)Tmax, (int)nh, nqt, S, scale);
   if (S > 1)
     hipLaunchKernelGGL(attn_cache_combine_kernel<HD>, dim3((unsigned)(B * nh * n)), dim3(HD), 0, s, ws_acc, ws_ml, n_new, out, lse, (int)n,
-                       (int)nh, S);
+                       (int)nh, S, 0);
 }
 
 template <typename KV>

@@ -203,7 +203,7 @@ __global__ __launch_bounds__(SHP_THREADS) void attn_shared_prefix_kernel(const u
 // ---------------------------------------------------------------------------------------------------------------------------------
 // splits_p == 0: enough workgroups for two per CU, but no split shorter than 256 keys (one step of a workgroup) of the longest possible
 // prefix.  A function of P, G, nh, Tp_max and the CU count alone.
-static int shared_resolve_splits_p(int64_t P, int64_t G, int64_t nh, int64_t Tp_max, int splits_p) {
+int shared_resolve_splits_p(int64_t P, int64_t G, int64_t nh, int64_t Tp_max, int splits_p) {
   if (splits_p != 0) return splits_p;
   int64_t s = plm_cdiv(2 * CACHE_CUS, P * nh * plm_cdiv(G, SHP_Q));
   const int64_t cap = plm_cdiv(Tp_max, SHP_STEP);
@@ -233,6 +233,13 @@ static void shp_launch(const uint16_t* q, const uint16_t* kv_p, int64_t ld_kv_p,
                      ws_ml, ws_acc, (int)G, (int)Tp_max, (int)nh, ngt, Sp, Stot, 1.f / sqrtf((float)HD));
 }
 
+void shared_prefix_launch(const uint16_t* q, const uint16_t* kv_p, int64_t ld_kv_p, const int32_t* lens_p, float* ws_ml, float* ws_acc, int64_t P,
+                          int64_t G, int64_t Tp_max, int64_t nh, int64_t hd, int Sp, int Stot, hipStream_t s) {
+  if (hd == 32) shp_launch<32>(q, kv_p, ld_kv_p, lens_p, ws_ml, ws_acc, P, G, Tp_max, nh, Sp, Stot, s);
+  else if (hd == 64) shp_launch<64>(q, kv_p, ld_kv_p, lens_p, ws_ml, ws_acc, P, G, Tp_max, nh, Sp, Stot, s);
+  else shp_launch<128>(q, kv_p, ld_kv_p, lens_p, ws_ml, ws_acc, P, G, Tp_max, nh, Sp, Stot, s);
+}
+
 extern "C" int plm_attn_decode_shared(const uint16_t* q, const uint16_t* kv_p, int64_t ld_kv_p, const int32_t* lens_p, const uint16_t* kv_s,
                                       int64_t ld_kv_s, const int32_t* lens_s, uint16_t* out, float* lse, int64_t P, int64_t G, int64_t Tp_max,
                                       int64_t Ts_max, int64_t nh, int64_t hd, int splits_p, int splits_s, void* workspace,
@@ -259,9 +266,7 @@ extern "C" int plm_attn_decode_shared(const uint16_t* q, const uint16_t* kv_p, i
   hipStream_t s = (hipStream_t)stream;
   float* ws_ml = static_cast<float*>(workspace);
   float* ws_acc = ws_ml + (size_t)P * G * nh * Stot * 2;
-  if (hd == 32) shp_launch<32>(q, kv_p, ld_kv_p, lens_p, ws_ml, ws_acc, P, G, Tp_max, nh, Sp, Stot, s);
-  else if (hd == 64) shp_launch<64>(q, kv_p, ld_kv_p, lens_p, ws_ml, ws_acc, P, G, Tp_max, nh, Sp, Stot, s);
-  else shp_launch<128>(q, kv_p, ld_kv_p, lens_p, ws_ml, ws_acc, P, G, Tp_max, nh, Sp, Stot, s);
+  shared_prefix_launch(q, kv_p, ld_kv_p, lens_p, ws_ml, ws_acc, P, G, Tp_max, nh, hd, Sp, Stot, s);
   cache_decode_partials_launch(q, kv_s, ld_kv_s, lens_s, ws_ml, ws_acc, P * G, Ts_max, nh, hd, Ss, Stot, Sp, s);
   cache_combine_launch(ws_acc, ws_ml, out, lse, P * G, nh, hd, Stot, s);
   PLM_CHECK_LAUNCH(fn);

@@ -60,6 +60,8 @@ struct DfArgs {
   const int32_t* lens0;  // [M / n]: the cache lengths before the chunk
   const int32_t* n_new;  // [M / n] real rows per chunk, or null: n everywhere
   const int32_t* rot0;   // [M / n] or null: the rows are rotated at rot0[b] + lens0[b] + r (a suffix cache); null: at their row
+  const int32_t* depth;  // [M] or null: row r is a tree node rotated at lens0[b] + depth[b, r], stored at lens0[b] + r as ever (DESIGN.md section
+                         // 22; depth[b, 0] < 0: plm_tree_plan refused the sequence, nothing of it is stored); null: at their row
 };
 
 // (a, b) -> (a cos - b sin, b cos + a sin): the pair arithmetic of rope8 (plm_device.h) at sgn = +1
@@ -187,16 +189,22 @@ __global__ __launch_bounds__(DF_THREADS) void decode_fused_kernel(const DfArgs p
     }
     const int l0 = p.lens0[b];
     const int r0 = p.rot0 != nullptr ? p.rot0[b] : 0;
-    const bool refused = l0 < 0 || r0 < 0 || (int64_t)l0 + cb > p.Tmax || (int64_t)r0 + l0 + cb > p.rope_T;  // nothing of this sequence is stored
+    const bool refused = l0 < 0 || r0 < 0 || (int64_t)l0 + cb > p.Tmax || (int64_t)r0 + l0 + cb > p.rope_T ||
+                         (p.depth != nullptr && p.depth[b * n] < 0);  // nothing of this sequence is stored
     if (refused && col == 0) p.status[0] = 1;
     if (refused || r >= cb) {  // no cache row; the q row is zeros, so that every byte of q_out is defined
       if (col < dm) df_st2(p.out + (int64_t)m * dm + col, f2bf(0.f), f2bf(0.f));
       return;
     }
     const int t = l0 + r;  // 0 <= t < Tmax, 0 <= r0 + t < rope_T
+    int tr = t;            // the RoPE table row before r0: a tree node's is l0 + its depth, 0 <= depth <= r
+    if (p.depth != nullptr) {
+      const int dr = p.depth[m];
+      tr = l0 + (dr < 0 ? 0 : (dr > r ? r : dr));
+    }
     bf16_t b0 = f2bf(v0), b1 = f2bf(v1);
     if (col < 2 * dm) {
-      const int64_t ti = (int64_t)(r0 + t) * (p.hd / 2) + (col % p.hd) / 2;
+      const int64_t ti = (int64_t)(r0 + tr) * (p.hd / 2) + (col % p.hd) / 2;
       df_rope2(b0, b1, p.rcos[ti], p.rsin[ti]);
     }
     if (col < dm) {
@@ -313,13 +321,13 @@ static void df_launch(const DfArgs& a, int64_t blocks, hipStream_t s) {
 static void df_launch_qkv(const float* x, const float* nw, float eps, const uint16_t* w_qkv, const int32_t* lens0, const int32_t* n_new,
                           const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv,
                           int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, hipStream_t s, bool kv8 = false,
-                          const int32_t* rot0 = nullptr) {
+                          const int32_t* rot0 = nullptr, const int32_t* depth = nullptr) {
   DfArgs a = {};
   const int64_t d = nh * hd;
   a.x = x, a.nw = nw, a.eps = eps, a.w = w_qkv, a.M = (int)(B * n), a.N = (int)(3 * d), a.K = (int)d;
   a.out = q_out, a.kv = kv, a.ld_kv = ld_kv, a.rcos = rope_cos, a.rsin = rope_sin, a.status = status;
   a.rope_T = (int)rope_T, a.Tmax = (int)Tmax, a.hd = (int)hd, a.dm = (int)d;
-  a.n = (int)n, a.lens0 = lens0, a.n_new = n_new, a.rot0 = rot0;
+  a.n = (int)n, a.lens0 = lens0, a.n_new = n_new, a.rot0 = rot0, a.depth = depth;
   if (kv8) df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS_KV8>(a, 3 * d / DF_TILE_N, s);
   else df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS>(a, 3 * d / DF_TILE_N, s);
 }
@@ -549,6 +557,61 @@ extern "C" int plm_decode_layer_shared_bf16(float* x, const float* attn_norm_w, 
   // added there must be added here.
   if (const int e = plm_attn_decode_shared(q, kv_p, ld_kv_p, lens_p, kv_s, ld_kv_s, lens_s, attn_out, nullptr, P, G, Tp_max, Ts_max, nh, hd, splits_p,
                                            splits_s, ws + 2 * qb + ab, need - 2 * qb - ab, stream))
+    return e;
+  df_launch_residual(x, attn_out, w_out, M, d, d, s);
+  df_launch_fc1(x, mlp_norm_w, eps, w_fc1, act, M, d, hidden, mlp_kind, s);
+  df_launch_residual(x, act, w_fc2, M, d, hidden, s);
+  PLM_CHECK_LAUNCH(fn);
+  return PLM_OK;
+}
+
+// ---- the extend layer over a token tree: B sequences of n <= 32 tree rows, M = B*n <= 32; the qkv stage stores row r at
+// lens0[b] + r and rotates it at lens0[b] + depth[b, r], the attention stage is plm_attn_extend_tree's three launches, the rest is df_layer's ----
+extern "C" size_t plm_extend_layer_tree_workspace_bytes(int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t hidden, int64_t Tmax, int splits) {
+  if (B < 1 || B > DF_MAX_ROWS || n < 1 || n > DF_MAX_ROWS || B * n > DF_MAX_ROWS || nh < 1 || nh * hd > DF_MAX_DIM / 4 || (nh * hd) % 32 != 0 ||
+      hidden < 1 || hidden > DF_MAX_DIM / 2 || hidden % 32 != 0)
+    return 0;
+  const size_t att = plm_attn_extend_tree_workspace_bytes(B, n, nh, hd, Tmax, splits);
+  if (att == 0) return 0;
+  const size_t M = (size_t)(B * n), d = (size_t)(nh * hd);
+  return 2 * df_round16(M * d * 2) + df_round16(M * (size_t)hidden * 2) + att;
+}
+
+extern "C" int plm_extend_layer_tree_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                                          const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* lens0,
+                                          const int32_t* n_new, const int32_t* depth, const uint32_t* anc, const float* rope_cos,
+                                          const float* rope_sin, int64_t rope_T, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t n,
+                                          int64_t Tmax, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  const char* fn = "plm_extend_layer_tree_bf16";
+  PLM_REQUIRE(x && attn_norm_w && mlp_norm_w && w_qkv && w_out && w_fc1 && w_fc2 && lens0 && depth && anc && rope_cos && rope_sin && kv && status &&
+                  workspace,
+              "%s: null pointer", fn);
+  PLM_REQUIRE(df_aligned(workspace), "%s: the workspace must be 16-byte aligned", fn);
+  const int64_t d = nh * hd, M = B * n;
+  char* ws = static_cast<char*>(workspace);
+  uint16_t* q = reinterpret_cast<uint16_t*>(ws);
+  if (const int e = df_check_qkv(fn, x, attn_norm_w, w_qkv, lens0, rope_cos, rope_sin, rope_T, q, kv, ld_kv, status, B, n, Tmax, nh, hd)) return e;
+  if (const int e = df_check_residual(fn, x, q, w_out, M, d, d)) return e;
+  if (const int e = df_check_fc1(fn, x, mlp_norm_w, w_fc1, q, M, d, hidden, mlp_kind)) return e;
+  if (const int e = df_check_residual(fn, x, q, w_fc2, M, d, hidden)) return e;
+  PLM_REQUIRE(splits >= 0 && splits <= 64, "%s: splits=%d out of range (0 = automatic, 1..64 forced)", fn, splits);
+  const size_t need = plm_extend_layer_tree_workspace_bytes(B, n, nh, hd, hidden, Tmax, splits);
+  PLM_REQUIRE(need != 0, "%s: bad shape B=%ld n=%ld Tmax=%ld nh=%ld hd=%ld hidden=%ld", fn, (long)B, (long)n, (long)Tmax, (long)nh, (long)hd,
+              (long)hidden);
+  if (workspace_bytes < need) {
+    plm_set_error("%s: workspace of %zu bytes required, %zu given", fn, need, workspace_bytes);
+    return PLM_E_WORKSPACE;
+  }
+  const size_t qb = df_round16((size_t)M * (size_t)d * 2), ab = df_round16((size_t)M * (size_t)hidden * 2);
+  uint16_t* attn_out = reinterpret_cast<uint16_t*>(ws + qb);
+  uint16_t* act = reinterpret_cast<uint16_t*>(ws + 2 * qb);
+  hipStream_t s = (hipStream_t)stream;
+  df_launch_qkv(x, attn_norm_w, eps, w_qkv, lens0, n_new, rope_cos, rope_sin, rope_T, q, kv, ld_kv, status, B, n, Tmax, nh, hd, s, false, nullptr, depth);
+  // every refusal of plm_attn_extend_tree was made above (null pointers, head_dim, the stride and kv's alignment in df_check_qkv, the splits,
+  // its shape limits and workspace size through need != 0; q, attn_out and the partials are 16-byte offsets into the workspace)
+  if (const int e = plm_attn_extend_tree(q, kv, ld_kv, lens0, n_new, anc, attn_out, nullptr, B, n, Tmax, nh, hd, splits, ws + 2 * qb + ab,
+                                         need - 2 * qb - ab, stream))
     return e;
   df_launch_residual(x, attn_out, w_out, M, d, d, s);
   df_launch_fc1(x, mlp_norm_w, eps, w_fc1, act, M, d, hidden, mlp_kind, s);

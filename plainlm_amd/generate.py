@@ -80,6 +80,15 @@ class KVCache:
     """Move [pos | lens] by n_new - an int32 [B] device tensor, or an int - with one in-place add (Transformer.extend, after its chunk)."""
     self._pl += n_new
 
+  def commit_tree(self, path, n_accept):
+    """After Transformer.extend_tree: keep the accepted root-to-leaf path (ops.tree_accept's path int32 [B, n] and n_accept int32 [B]) -
+    every layer's rows lens + path[d] move to lens + d in one ops.kv_tree_commit launch - and move the lengths by n_accept + 1, the root
+    included, on the device.  bf16 caches only."""
+    if self.kv_dtype != 'bf16':
+      raise ValueError(f"KVCache.commit_tree: a {self.kv_dtype!r} cache has no tree path (bf16 caches only)")
+    ops.kv_tree_commit(self.kv, self.lens, path, n_accept, self.n_heads)
+    self.advance_by(n_accept + 1)
+
   def to_bf16(self, layer):
     """Layer ``layer``'s cache as bf16 [B, Tmax, 2*dim]: the buffer itself, or the exact dequantised image of an fp8 cache (rows at and
     beyond lens hold whatever the buffer holds there)."""
@@ -671,6 +680,84 @@ class _LookupSession:
       raise RuntimeError('generate_lookup: a round\'s tokens did not fit the token history: they were not stored')
 
 
+# ---- tree verification for lookup decoding -------------------------------------------------------------------------------
+def refuse_tree_cache(what, cache):
+  """The cache refusals of the tree methods: a SharedPrefixCache (TypeError) and an FP8 cache (ValueError) - the tree kernels read and move
+  bf16 rows."""
+  refuse_shared(what, cache)
+  if getattr(cache, 'kv_dtype', 'bf16') != 'bf16':
+    raise ValueError(f"Transformer.{what}: a {cache.kv_dtype!r} cache has no tree path (the tree kernels read and move bf16 rows): prefill with "
+                     "kv_dtype='bf16'")
+
+
+def check_tree_rows(who, n):
+  if not 1 <= n <= ops.TREE_MAX_ROWS:
+    raise ValueError(f'{who}: a tree chunk holds 1 to {ops.TREE_MAX_ROWS} rows per sequence (one bit of the ancestor mask each), got {n}')
+
+
+def tree_rows(n_draft, n_branch, max_rows=None):
+  """Rows of generate_lookup_tree's chunk: the root and up to n_branch continuations of n_draft tokens, at most ops.TREE_MAX_ROWS and at
+  most max_rows (the caller's cap, e.g. 32 // B to fit the fused path); the trie is filled most recent match first."""
+  return min(1 + int(n_draft) * int(n_branch), ops.TREE_MAX_ROWS if max_rows is None else int(max_rows))
+
+
+def check_lookup_tree(T, max_new_tokens, n_draft, n_branch, ngram, cfg, max_rows=None):
+  """The refusals of generate_lookup_tree that need no GPU; returns (cache rows per sequence, rows per chunk).  A round may write a whole
+  chunk past the last token a sequence keeps, hence the longer cache."""
+  who = 'generate_lookup_tree'
+  for name, v in (('n_draft', n_draft), ('n_branch', n_branch)):
+    if isinstance(v, bool) or not isinstance(v, int):
+      raise TypeError(f'{who}: {name} must be an int, got {type(v).__name__}')
+  if n_draft < 1 or n_draft > MAX_DRAFT:
+    raise ValueError(f'{who}: n_draft must be in [1, {MAX_DRAFT}], got {n_draft}')
+  if n_branch < 1 or n_branch > ops.TREE_MAX_BRANCH:
+    raise ValueError(f'{who}: n_branch must be in [1, {ops.TREE_MAX_BRANCH}], got {n_branch}')
+  if not isinstance(ngram, (tuple, list)) or len(ngram) != 2 or any(isinstance(g, bool) or not isinstance(g, int) for g in ngram):
+    raise TypeError(f'{who}: ngram must be two ints (g_min, g_max), got {ngram!r}')
+  if not 1 <= ngram[0] <= ngram[1] <= MAX_NGRAM:
+    raise ValueError(f'{who}: ngram must satisfy 1 <= g_min <= g_max <= {MAX_NGRAM}, got {tuple(ngram)}')
+  if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, int) or not 2 <= max_rows <= ops.TREE_MAX_ROWS):
+    raise ValueError(f'{who}: max_rows must be an int in [2, {ops.TREE_MAX_ROWS}] (the root and at least one node), got {max_rows!r}')
+  n = tree_rows(n_draft, n_branch, max_rows)
+  return _check_new_tokens(who, T, max_new_tokens, n, f' + a chunk of {n} tree rows', [('', cfg.seq_len)]), n
+
+
+class _TreeSession(_LookupSession):
+  """_LookupSession whose draft is a trie (ops.lookup_draft_tree) verified by one ``extend_tree``: greedy only.  The loop's "draft tokens"
+  are the ACCEPTED tokens in path order, which exist only after the verify step: draft_round hands the loop a buffer and accept has
+  ops.tree_accept write into it, before commit_round reads it.  ``self.k`` = n - 1, the buffer's width; n_draft is the length of one
+  continuation.  advance keeps the accepted path's cache rows (ops.kv_tree_commit) before the lengths move."""
+
+  def __init__(self, model, cache, prompt, first_tok, n_draft, n_branch, n, ngram, max_new_tokens, fused=False):
+    super().__init__(model, cache, prompt, first_tok, n - 1, ngram, max_new_tokens, None, None, fused=fused)
+    self.n, self.n_draft, self.n_branch = n, n_draft, n_branch
+    self.acc = torch.zeros((prompt.shape[0], n - 1), dtype=torch.int64, device=prompt.device)
+    self.nodes = torch.zeros((prompt.shape[0],), dtype=torch.int64, device=prompt.device)  # rows verified, the roots included
+
+  def draft_round(self, last, carry_tok, carry, live):
+    self.tree = ops.lookup_draft_tree(self.hist, self.hlen, self.add, self.n_add, n=self.n, k=self.n_draft, n_branch=self.n_branch, ngram=self.ngram,
+                                      status=self.status)
+    self.tree.tokens[:, 0] = last  # the root: the history's newest token (a refused history has none to read)
+    self.n_new = live.to(torch.int32) * self.tree.n_new.clamp(min=1)
+    self.nodes += self.n_new
+    return self.acc, None
+
+  def target_round(self, last, draft_tok, live):
+    return self.model.extend_tree(self.tree.tokens, self.tree.parent, self.cache, token_lens=self.n_new, **self.extend_kw)
+
+  def accept(self, draft_tok, draft_out, out):
+    a = ops.tree_accept(self.tree.tokens, self.tree.parent, out.tokens, out.logprob, n_new=self.n_new, tokens_out=draft_tok)
+    self.n_accept, self.next_tok, self.path, self.draft_tok = a.n_accept, a.next_token, a.path, draft_tok
+    return a.n_accept, a.next_token, a.logprob
+
+  def drafted(self):
+    return (self.n_new - 1).clamp(min=0)
+
+  def advance(self, moved, live):
+    ops.kv_tree_commit(self.cache.kv, self.tlen, self.path, self.n_accept, self.cache.n_heads)  # tlen: the lengths before the chunk
+    super().advance(moved, live)
+
+
 class Generation:
   """KV-cached generation, mixed into ``Transformer`` (DESIGN.md sections 12 to 16).  What it asks of its host class:
     attributes  cfg (the ModelConfig), n_layers, head_dim, lm_head (its weight tells the model's device)
@@ -954,6 +1041,76 @@ class Generation:
     with torch.no_grad():
       s = _LookupSession(self, cache, prompt, first[0], k, ngram, N, sampling, u, fused=fused)
       toks, lps, stats = speculative_loop(first, s.draft_round, s.target_round, s.accept, N, k, eos_id, s.advance, drafted_in_round=s.drafted)
+    cache.check()
+    s.check()
+    res = (toks,) + ((lps,) if return_logprobs else ()) + ((stats,) if return_stats else ())
+    return res[0] if len(res) == 1 else res
+
+  @torch.compiler.disable
+  def extend_tree(self, tokens, parent, cache, token_lens=None, logits=False, fused=False):
+    """``extend`` over a token TREE: tokens int64 [B, n], n <= ops.TREE_MAX_ROWS; row 0 is the root (the newest
+    committed token, not yet in the cache) and parent int32 [B, n] on the device names every other row's parent (parent[b, 0] = -1,
+    0 <= parent[b, r] < r).  Row r is stored at cache row lens[b] + r, rotated at position lens[b] + depth(r), and attends the cache and
+    its own ancestors only, so its output is what ``extend`` gives it on its root-to-node path run as a chain.  token_lens: the real
+    rows per sequence, as ``extend`` takes them.  Returns the [B, n] predictions - with logits=True the [B, n, V] logits - of ALL rows
+    (rows at and beyond token_lens[b] mean nothing).  It advances nothing: the caller picks a path (ops.tree_accept) and commits it with
+    ``cache.commit_tree(path, n_accept)``.  A tree whose parents break the rule stores nothing for its sequence and surfaces through
+    ``cache.check()``.  fused=True runs every layer as one ops.extend_layer_tree call and serves B * n <= ops.FUSED_EXTEND_MAX_ROWS.
+    Refused before any launch: a SharedPrefixCache (TypeError), an FP8 cache, n > 32, fused with too many rows (ValueError), an mxfp8 model."""
+    who = 'extend_tree'
+    refuse_tree_cache(who, cache)
+    if isinstance(tokens, torch.Tensor) and (tokens.dim() != 2 or tokens.shape[0] != cache.B or tokens.shape[1] < 1):
+      raise ValueError(f'{who}: tokens {tuple(tokens.shape)} are not a [B, n] chunk for the cache\'s batch of {cache.B}')
+    guard(who, tokens, self)
+    check_cache(who, cache, self)
+    B, n = tokens.shape
+    check_tree_rows(who, n)
+    if not isinstance(parent, torch.Tensor) or parent.dtype != torch.int32 or tuple(parent.shape) != (B, n) or parent.device != tokens.device:
+      raise TypeError(f'{who}: parent must be an int32 [{B}, {n}] tensor on the tokens\' device')
+    if fused:
+      check_fused_rows(who, B, n, self.cfg.dim)
+    nh = self.cfg.n_heads
+    with torch.no_grad():
+      _, n_new = chunk_lens(token_lens, B, n, tokens.device)
+      rope = self._rope(tokens.device)
+      lens0 = cache.lens
+      plan = ops.tree_plan(parent.contiguous(), n_new, status=cache.status)
+
+      def attend(i, qkv):
+        q, _ = ops.kv_append_rope_tree(qkv, lens0, plan.depth, rope[0], rope[1], cache.kv[i], nh, n_new=n_new, status=cache.status)
+        return ops.attn_extend_tree(q, cache.kv[i], lens0, plan.anc, nh, n_new=n_new)
+      flat = tokens.reshape(-1).contiguous()
+      y = self.fused_layers(flat, cache, rope, (lens0, n_new, n, plan.depth, plan.anc)) if fused else self.cached_layers(flat, cache, attend)
+      return self.head(y, logits, (B, n))
+
+  @torch.compiler.disable
+  def generate_lookup_tree(self, prompt, max_new_tokens, n_draft=8, n_branch=3, ngram=(1, 4), prompt_lens=None, eos_id=None, return_logprobs=False,
+                           return_stats=False, fused=False, max_rows=None):
+    """``generate_lookup`` that verifies several continuations per round: one ops.lookup_draft_tree launch keeps the
+    up to n_branch most recent occurrences of the longest n-gram match and merges the n_draft tokens that followed each into a trie of at
+    most min(1 + n_draft * n_branch, 32) rows; one ``extend_tree`` checks every node, ops.tree_accept takes the longest root-to-leaf path
+    this model's greedy predictions follow, and ops.kv_tree_commit keeps that path's cache rows.  Greedy only: the tokens are what
+    ``generate`` decodes greedily.  Sampled acceptance over a tree (sibling rejection sampling) is deliberately not built - there are no
+    sampling arguments; use ``generate_lookup`` to sample.  Returns the tokens int64 [B, N]; with return_logprobs also this model's
+    log-probabilities, with return_stats also dict(rounds, drafted int64 [B] = the nodes proposed below the roots, accepted int64 [B],
+    nodes int64 [B] = the tree rows verified, the roots included).  One int32 is read from the device per round.  fused=True runs the
+    rounds' chunks through ops.extend_layer_tree and serves B * rows <= ops.FUSED_EXTEND_MAX_ROWS, ValueError beyond: at the default width that
+    is one sequence of n_draft 8, n_branch 3 - max_rows caps the rows per sequence (32 // B fits any B <= 16), the trie then keeps what the most
+    recent matches fill first.  Refused before any
+    launch: an mxfp8 model; cfg.kv_cache = 'fp8' does not apply (the call prefills a bf16 cache)."""
+    who = 'generate_lookup_tree'
+    guard(who, prompt, self, forward_only=True, rank2=True)
+    B, T = prompt.shape
+    N = int(max_new_tokens)
+    max_len, n = check_lookup_tree(T, max_new_tokens, n_draft, n_branch, ngram, self.cfg, max_rows)
+    if fused:
+      check_fused_rows(who, B, n, self.cfg.dim)
+    cache, r = self.prefill(prompt, prompt_lens, max_len=max_len, kv_dtype='bf16')
+    first = (r.tokens, r.logprob)
+    with torch.no_grad():
+      s = _TreeSession(self, cache, prompt, first[0], n_draft, n_branch, n, ngram, N, fused=fused)
+      toks, lps, stats = speculative_loop(first, s.draft_round, s.target_round, s.accept, N, n - 1, eos_id, s.advance, drafted_in_round=s.drafted)
+    stats['nodes'] = s.nodes
     cache.check()
     s.check()
     res = (toks,) + ((lps,) if return_logprobs else ()) + ((stats,) if return_stats else ())

@@ -1152,6 +1152,10 @@ from .ops_kv8 import (KV8_BLOCK, attn_decode_kv8, attn_extend_kv8, decode_layer_
 # ---- parallel sampling from one prompt: shared-prefix decode attention; its wrappers live in ops_shared.py ------------
 from .ops_shared import (attn_decode_shared, attn_decode_shared_workspace_bytes, decode_layer_shared, decode_norm_qkv_append_at,  # noqa: E402,F401
                          kv_append_rope_at)
+# ---- tree verification for lookup decoding: its wrappers live in ops_tree.py ------------------------------------------
+from .ops_tree import (TREE_MAX_BRANCH, TREE_MAX_ROWS, LookupTree, TreeAccept, TreePlan, attn_extend_tree,  # noqa: E402,F401
+                       attn_extend_tree_workspace_bytes, extend_layer_tree, kv_append_rope_tree, kv_tree_commit, lookup_draft_tree, tree_accept,
+                       tree_plan)
 # ---- the Muon tail: batched NT GEMM, prepare / orthogonalize / apply; its wrappers live in ops_muon.py -------------------
 from .ops_muon import (MUON_ADJUST_LR, MUON_EPS, MUON_NS_COEFFICIENTS, NT_BATCH_GROUP, gemm_nt_batched, muon_adjusted_lr, muon_apply,  # noqa: E402,F401
                        muon_arena, muon_blocks, muon_items, muon_layout, muon_ns_flops, muon_orthogonalize, muon_prepare, muon_set_lr,

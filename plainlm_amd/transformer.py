@@ -575,6 +575,8 @@ class Transformer(nn.Module, G.Generation):
       layer_op, lengths = ops.decode_layer_kv8 if fp8 else ops.decode_layer, (cache.pos, cache.lens)
     else:
       layer_op, lengths, n = ops.extend_layer_kv8 if fp8 else ops.extend_layer, chunk[:2], chunk[2]
+      if len(chunk) == 5:  # (lens0, n_new, n, depth, anc): tree rows, ops.extend_layer_tree; bf16 caches only
+        layer_op, lengths = ops.extend_layer_tree, chunk[:2] + chunk[3:]
       if tokens.shape[0] != cache.B * n:
         raise ValueError(f'fused_layers: {tokens.shape[0]} tokens are not {cache.B} chunks of {n}')
     self.refresh_shadows()

@@ -21,11 +21,17 @@ With --samples G [G ...] the sides are the two ways to de
 that holds the prompt G times (R, all there was before) and decode_step on a SharedPrefixCache (S: the prompt once, every step reads it once
 per 32 samples), unfused and fused, all four alternating in one process at prompt 1024 and 4096 (--context), after 64 generated tokens:
 device ms median [min max], host enqueue, library calls and kernel launches, and the cache bytes of both forms.
+With --tree the sides are one generate_lookup round (L) and one generate_lookup_tree round at n_branch 1 and 3 (T1, T3),
+unfused and fused, B = 4 (and fused at B = 1), n_draft = 7, context 1024, the sides of a row alternating in one process on one cache.  The prompt is built so that the longest
+n-gram match occurs many times with DIFFERENT continuations (a shared 8-token block followed by random tails), so T3 verifies three branches.
+Unfused trees hold 1 + n_draft * n_branch rows; fused at B = 4 they are capped at 8 rows (max_rows: B * rows <= 32), so T3 repeats T1 there;
+fused at B = 1 the 22-row trie fits.
 Usage: python tools/gen_bench.py [--runs 20] [--out profiles/generate_bench.txt]
        python tools/gen_bench.py --fused [--batch 1 32] [--context 4096] --out profiles/fused_decode_bench.txt
        python tools/gen_bench.py --fused-extend --out profiles/fused_extend_bench.txt
        python tools/gen_bench.py --kv fp8 --out profiles/kv8_bench.txt
-       python tools/gen_bench.py --samples 8 32 --context 1024 4096 --out profiles/shared_prefix_bench.txt"""
+       python tools/gen_bench.py --samples 8 32 --context 1024 4096 --out profiles/shared_prefix_bench.txt
+       python tools/gen_bench.py --tree --out profiles/tree_bench.txt"""
 import argparse
 import os
 import statistics
@@ -97,7 +103,8 @@ def extend_launches(seen, nh, hd, n, B, Tmax):
   from plainlm_amd import _lib
   one = (B * n * nh * (2 + hd) * 4 + 15) // 16 * 16
   ext = 1 if _lib.load().plm_attn_extend_workspace_bytes(B, n, nh, hd, Tmax, 0) == one else 2
-  per = {'plm_attn_extend': ext, 'plm_extend_layer_bf16': 4 + ext, 'plm_head_predict_bf16': 2, 'plm_decode_layer_bf16': 6}
+  per = {'plm_attn_extend': ext, 'plm_extend_layer_bf16': 4 + ext, 'plm_head_predict_bf16': 2, 'plm_decode_layer_bf16': 6,
+         'plm_attn_extend_tree': 3, 'plm_extend_layer_tree_bf16': 7}
   return sum(per.get(w, 1) for w in seen)
 
 
@@ -140,6 +147,69 @@ class LookupRound:
     _, _, moved = G.commit_round(self.out_tok, self.out_lp, self.count, self.done, d, *res)
     s.advance(moved, self.live)
     return s.n_prop.clone(), res[1]
+
+
+class TreeRound(LookupRound):
+  """LookupRound over a _TreeSession: returns (rows verified, next token, accepted depth) of the round."""
+
+  def __call__(self):
+    s = self.s
+    d, _ = s.draft_round(self.first, self.first, self.carry, self.live)
+    res = s.accept(d, None, s.target_round(self.first, d, self.live))
+    _, _, moved = G.commit_round(self.out_tok, self.out_lp, self.count, self.done, d, *res)
+    s.advance(moved, self.live)
+    return s.n_new.clone(), res[1], res[0].clone()
+
+
+def main_tree(a):
+  torch.manual_seed(0)
+  Bx, k, new, room, blk, seg = 4, 7, 64, 64, 8, 37
+  cfg = ModelConfig(vocab_size=50280, seq_len=CTX + room, dim=768, expand=8 / 3, n_layers=12, n_heads=12, mlp='glu')
+  m = Transformer(cfg).cuda()
+  nh = cfg.n_heads
+  # every segment is the shared block followed by its own random tail; the prompt ends inside the block, `first` is the block's last token
+  prompt = torch.randint(0, cfg.vocab_size, (Bx, CTX), device='cuda')
+  block = torch.randint(0, cfg.vocab_size, (Bx, blk), device='cuda')
+  for at in range(0, CTX - seg, seg):
+    prompt[:, at:at + blk] = block
+  prompt[:, CTX - (blk - 1):] = block[:, :blk - 1]
+  first = block[:, blk - 1].contiguous()
+  lens0 = torch.full((Bx,), CTX, dtype=torch.int32, device='cuda')
+  lines = ['# tools/gen_bench.py --tree: 160M (12 layers, d 768, 12 heads, V 50280), B = %d (fused also B = 1), n_draft = %d, %d cached tokens; L = a generate_lookup '
+           'round, T1 / T3 = a generate_lookup_tree round at n_branch 1 / 3; one process, one cache per row group, sides '
+           'alternating; ms per round, HIP events, median of %d [min max]; host enqueue = wall time of the call, not waited for; kernel launches '
+           'from the documented counts of the entry points, torch\'s own bookkeeping launches not counted' % (Bx, k, CTX, a.runs)]
+  with torch.no_grad():
+    # unfused and fused at B = 4 (fused: B * rows <= 32 caps the trie at 8 rows, so T3 repeats T1's chain), then fused at B = 1, where the
+    # 22-row trie fits and T3 is a branched tree on the fused path
+    for Bx, fused, cap in ((4, False, None), (4, True, 8), (1, True, None)):
+      prompt, first, lens0 = (t[:Bx].contiguous() for t in (prompt, first, lens0))
+      cache, _ = m.prefill(prompt)
+      rows = {nb: G.tree_rows(k, nb, cap) for nb in (1, 3)}
+      rounds = {'L': LookupRound(G._LookupSession(m, cache, prompt, first, k, (1, 4), new, None, None, fused=fused), cache, first, lens0, new)}
+      for nb in (1, 3):
+        rounds['T%d' % nb] = TreeRound(G._TreeSession(m, cache, prompt, first, k, nb, rows[nb], (1, 4), new, fused=fused), cache, first, lens0, new)
+      dev, host, calls, ret = alternate(rounds, lambda: [r.reset() for r in rounds.values()], a)
+      lines.append('%s rounds, B = %d%s' % ('fused' if fused else 'unfused', Bx, ', max_rows %d' % cap if cap else ''))
+      width = {'L': k + 1, 'T1': rows[1], 'T3': rows[3]}
+      for key in rounds:
+        name = 'lookup round (L)' if key == 'L' else 'tree round, n_branch %s, %d rows (%s)' % (key[1], width[key], key)
+        lines.append(report(name, key, dev, host, calls, '%3d' % extend_launches(calls[key], nh, m.head_dim, width[key], Bx, cache.Tmax)))
+      lines.append('  L: proposals per sequence %s' % ret['L'][0].tolist())
+      for key in ('T1', 'T3'):
+        below, above = max(dev[key]) < min(dev['L']), min(dev[key]) > max(dev['L'])
+        lines.append('  %s: nodes drafted per sequence %s, tokens per round %s; %s / L (medians) %.2f; its [min max] %s L\'s; same next token as L '
+                     '%.3f of %d' % (key, (ret[key][0] - 1).tolist(), (ret[key][2] + 1).tolist(), key,
+                                    statistics.median(dev[key]) / statistics.median(dev['L']),
+                                    'lies wholly below' if below else ('lies wholly above' if above else 'overlaps'),
+                                    (ret[key][1] == ret['L'][1]).float().mean().item(), Bx))
+      del rounds, cache
+  lines.append('random-init weights: near-uniform logits, so the acceptance figures say nothing about text')
+  text = '\n'.join(lines) + '\n'
+  print(text, end='')
+  if a.out:
+    with open(a.out, 'w') as f:
+      f.write(text)
 
 
 def main_fused_extend(a):
@@ -344,7 +414,10 @@ def main():
   ap.add_argument('--kv', choices=['fp8'], default=None, help='compare the decode steps over an FP8 KV cache with those over the bf16 cache')
   ap.add_argument('--samples', type=int, nargs='+', default=None, help='compare decode steps on a SharedPrefixCache of G samples of one prompt '
                   'with those on a cache that holds the prompt G times (prompt lengths: --context, default 1024 4096)')
+  ap.add_argument('--tree', action='store_true', help='compare a generate_lookup_tree round (n_branch 1 and 3) with a generate_lookup round')
   a = ap.parse_args()
+  if a.tree:
+    return main_tree(a)
   if a.samples:
     return main_samples(a)
   if a.kv:
