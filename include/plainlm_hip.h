@@ -491,6 +491,76 @@ int plm_decode_layer_shared_bf16(float* x, const float* attn_norm_w, const float
                                  int64_t Tp_max, int64_t Ts_max, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits_p,
                                  int splits_s, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- beam search on the shared-prefix cache: ancestor-table attention, selection, bookkeeping -----
+ * Every argument check of these entry points comes before any HIP call.  P prompts, G <= 32 beams per prompt; row i = p*G + g of every
+ * [P*G, ...] operand is beam (or suffix slot) g of prompt p.  The caches are plm_attn_decode_shared's; beam search re-parents the beams at
+ * every step and copies no cache row: anc uint8 [P*G, Ts_max] names, for beam g and generated token j, the slot (0 .. G-1) of the same
+ * prompt whose suffix row j holds that token.  All slots of a prompt hold the same number of rows: lens_s[p*G] is the prompt's.
+ *
+ * plm_attn_decode_beam: q bf16 [P*G, nh*hd], rotated.  Beam g of prompt p attends keys 0 .. lens_p[p]-1 of the prefix and then, for
+ * j < lens_s[p*G], row j of slot anc[p*G+g][j]; an entry >= G names no slot (the key is skipped), entries at and beyond lens_s are never
+ * read.  out bf16 [P*G, nh*hd] and, unless NULL, lse fp32 [P*G, nh] (base 2).  lens_s == 0 gives the prefix-only result.  Three launches
+ * over plm_attn_decode_shared's partial layout: its prefix kernel; a (P*nh) x S_s grid of MFMA workgroups over the suffix - a key tile is 32
+ * consecutive rows of one slot, the beams are the MFMA's columns under a one-word mask per lane, and a (slot, tile) pair no beam attends
+ * is skipped before any of its bytes is fetched; plm_attn_decode's combine over the S_p + S_s partials.  No atomics: bit-reproducible,
+ * and a beam's bits depend on its own query, its own table row and the rows that row names alone.  splits_p: plm_attn_decode_shared's
+ * rule; splits_s: 0 = automatic (two workgroups per CU, no split shorter than 64 rows of Ts_max, at most 64: a function of P, nh, Ts_max
+ * and the CU count alone), 1..64 forced.  workspace: plm_attn_decode_beam_workspace_bytes(...) bytes, 16-byte aligned (0 for arguments
+ * the launch refuses).  Refusals as plm_attn_decode_shared's, and G > 32.
+ *
+ * plm_decode_layer_beam_bf16: plm_decode_layer_shared_bf16 with plm_attn_decode_beam as its attention stage (anc as above); workspace
+ * plm_decode_layer_beam_workspace_bytes(...).
+ *
+ * plm_beam_select_bf16: logits bf16 [P*rows_per_prompt, ld] with V valid columns (2-byte aligned base, ld >= V; columns >= V are never
+ * loaded), score fp32 [P*rows_per_prompt]; rows_per_prompt is 1 for the first step (the prompt's one row) and G afterwards.  Per prompt
+ * the 2G best candidates (score[g] + logp[g][v], g, v), sorted by score descending, then beam ascending, then token ascending:
+ * cand_score fp32 / cand_beam int32 / cand_tok int32, each [P, 2G].  logp is the row's log-softmax at temperature 1 from
+ * plm_sample_logits_bf16's integers: x_max the largest finite logit, Z the 64-bit sum of the fixed-point weights of all finite logits,
+ * logp = (x - x_max) - ln(Z / scale) in fp32 - a function of the row's multiset of logits, so the result is bit-reproducible.  A NaN or
+ * infinite logit is never a candidate, a beam whose score is not finite has none; missing candidates are (-inf, -1, -1) at the end.
+ * Two launches (one workgroup per row: radix select of the row's 2G best keys; one per prompt: scoring and an LDS sort on a 64-bit key).
+ * workspace: plm_beam_select_workspace_bytes(rows, G) bytes, 16-byte aligned.  PLM_E_INVALID for: a NULL pointer, G outside [1, 32],
+ * rows_per_prompt outside [1, G], V < 2G or V > 2^26, ld < V, misaligned logits or workspace.
+ *
+ * plm_beam_advance: step t (0 <= t < N) of the search, one launch.  Walks a prompt's 2G candidates in order: a candidate whose token is
+ * eos_id (-1: none) and whose rank is below G enters the prompt's finished pool with length t + 1 (EOS counted) - the pool keeps the G
+ * best by score / length ** length_penalty, an equal newcomer does not displace; every other candidate becomes the next live beam
+ * n = 0, 1, .. until G are filled.  A beam left without a candidate is dead: score -inf, token eos_id (0 without one), parent 0.
+ * Outputs: tok_next int64 [P*G], score_out fp32 [P*G], parent int32 [P*G], row t of tok_hist / par_hist int32 [P, N, G], and the next
+ * ancestor table anc_out[n][0..t-1] = anc_in[parent[n]][0..t-1], anc_out[n][t] = n (both uint8 [P*G, N], two different buffers).
+ * done[p] int32 is set once the pool holds G hypotheses and either early_stopping or best live score / (t+1) ** length_penalty is no
+ * better than the pool's worst; a done prompt's pool is frozen, its beams keep stepping.  The pool: pool_f fp32 [P, G, 2] (normalised,
+ * raw score), pool_i int32 [P, G, 3] (length, the step and the beam its backtrack starts at), pool_n int32 [P]; zero before step 0.
+ *
+ * plm_beam_finalize: after n_steps <= N steps; one launch, changes no state.  For a prompt that is not done the live beams of finite
+ * score enter (a copy of) the pool at length n_steps.  The best R = num_return <= G hypotheses, best first (among equals the earlier
+ * entry), are backtracked through par_hist: tokens int64 [P, R, N] padded with pad_id, lengths int32 [P, R], scores fp32 [P, R]
+ * (normalised); a missing hypothesis has length 0 and score -inf. */
+size_t plm_attn_decode_beam_workspace_bytes(int64_t P, int64_t G, int64_t nh, int64_t hd, int64_t Tp_max, int64_t Ts_max, int splits_p,
+                                            int splits_s);
+int plm_attn_decode_beam(const uint16_t* q, const uint16_t* kv_p, int64_t ld_kv_p, const int32_t* lens_p, const uint16_t* kv_s,
+                         int64_t ld_kv_s, const int32_t* lens_s, const uint8_t* anc, uint16_t* out, float* lse, int64_t P, int64_t G,
+                         int64_t Tp_max, int64_t Ts_max, int64_t nh, int64_t hd, int splits_p, int splits_s, void* workspace,
+                         size_t workspace_bytes, void* stream);
+size_t plm_decode_layer_beam_workspace_bytes(int64_t P, int64_t G, int64_t nh, int64_t hd, int64_t hidden, int64_t Tp_max, int64_t Ts_max,
+                                             int splits_p, int splits_s);
+int plm_decode_layer_beam_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                               const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* row, const int32_t* lens_s,
+                               const int32_t* rot0, const int32_t* lens_p, const uint8_t* anc, const float* rope_cos, const float* rope_sin,
+                               int64_t rope_T, const uint16_t* kv_p, int64_t ld_kv_p, uint16_t* kv_s, int64_t ld_kv_s, int32_t* status,
+                               int64_t P, int64_t G, int64_t Tp_max, int64_t Ts_max, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind,
+                               int splits_p, int splits_s, void* workspace, size_t workspace_bytes, void* stream);
+size_t plm_beam_select_workspace_bytes(int64_t rows, int64_t G);
+int plm_beam_select_bf16(const uint16_t* logits, int64_t ld, const float* score, float* cand_score, int32_t* cand_beam, int32_t* cand_tok,
+                         int64_t P, int64_t rows_per_prompt, int64_t G, int64_t V, void* workspace, size_t workspace_bytes, void* stream);
+int plm_beam_advance(const float* cand_score, const int32_t* cand_beam, const int32_t* cand_tok, const uint8_t* anc_in, uint8_t* anc_out,
+                     int64_t* tok_next, float* score_out, int32_t* parent, int32_t* tok_hist, int32_t* par_hist, float* pool_f,
+                     int32_t* pool_i, int32_t* pool_n, int32_t* done, int64_t P, int64_t G, int64_t N, int64_t t, int64_t eos_id,
+                     float length_penalty, int early_stopping, void* stream);
+int plm_beam_finalize(const float* score, const int32_t* tok_hist, const int32_t* par_hist, const float* pool_f, const int32_t* pool_i,
+                      const int32_t* pool_n, const int32_t* done, int64_t* tokens, int32_t* lengths, float* scores, int64_t P, int64_t G,
+                      int64_t N, int64_t n_steps, int64_t R, int64_t eos_id, int64_t pad_id, float length_penalty, void* stream);
+
 /* ---- tree verification for lookup decoding: one extend over a trie of drafts -----
  * Every argument check of these entry points comes before any HIP call.  A chunk is n rows per sequence, 1 <= n <= 32; row 0 is the root
  * (the newest committed token, not yet in the cache); parent int32 [B, n]: parent[b, 0] = -1 and 0 <= parent[b, r] < r (or -1: another

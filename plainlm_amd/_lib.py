@@ -152,6 +152,15 @@ SIGNATURES = {
   'plm_decode_layer_shared_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I]),
   'plm_decode_layer_shared_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64,
                                         _I64, _I64, _I64, _I64, _I, _I, _I, _P, _SZ, _P]),
+  'plm_attn_decode_beam_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I64, _I, _I]),
+  'plm_attn_decode_beam': (_I, [_P, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _P, _SZ, _P]),
+  'plm_decode_layer_beam_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I]),
+  'plm_decode_layer_beam_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64,
+                                      _I64, _I64, _I64, _I64, _I, _I, _I, _P, _SZ, _P]),
+  'plm_beam_select_workspace_bytes': (_SZ, [_I64, _I64]),
+  'plm_beam_select_bf16': (_I, [_P, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _SZ, _P]),
+  'plm_beam_advance': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _F, _I, _P]),
+  'plm_beam_finalize': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _F, _P]),
   'plm_tree_plan': (_I, [_P, _P, _P, _P, _P, _I64, _I64, _P]),
   'plm_kv_append_rope_tree': (_I, [_P, _I64, _P, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P]),
   'plm_attn_extend_tree_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I]),

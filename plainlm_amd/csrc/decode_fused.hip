@@ -565,6 +565,71 @@ extern "C" int plm_decode_layer_shared_bf16(float* x, const float* attn_norm_w, 
   return PLM_OK;
 }
 
+// ---- the decode layer of beam search: plm_decode_layer_beam_bf16 with plm_attn_decode_beam's three launches as the
+// attention stage - the G <= 32 beams of a prompt attend the suffix rows their ancestor table anc names; every other stage and refusal is that layer's ----
+extern "C" size_t plm_decode_layer_beam_workspace_bytes(int64_t P, int64_t G, int64_t nh, int64_t hd, int64_t hidden, int64_t Tp_max,
+                                                          int64_t Ts_max, int splits_p, int splits_s) {
+  const int64_t M = P * G;
+  if (P < 1 || G < 1 || P > DF_MAX_ROWS || G > DF_MAX_ROWS || M > DF_MAX_ROWS || nh < 1 || nh * hd > DF_MAX_DIM / 4 || (nh * hd) % 32 != 0 ||
+      hidden < 1 || hidden > DF_MAX_DIM / 2 || hidden % 32 != 0)
+    return 0;
+  const size_t att = plm_attn_decode_beam_workspace_bytes(P, G, nh, hd, Tp_max, Ts_max, splits_p, splits_s);
+  if (att == 0) return 0;
+  const size_t d = (size_t)(nh * hd);
+  return 2 * df_round16((size_t)M * d * 2) + df_round16((size_t)M * (size_t)hidden * 2) + att;
+}
+
+extern "C" int plm_decode_layer_beam_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                                            const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* row,
+                                            const int32_t* lens_s, const int32_t* rot0, const int32_t* lens_p, const uint8_t* anc, const float* rope_cos,
+                                            const float* rope_sin, int64_t rope_T, const uint16_t* kv_p, int64_t ld_kv_p, uint16_t* kv_s,
+                                            int64_t ld_kv_s, int32_t* status, int64_t P, int64_t G, int64_t Tp_max, int64_t Ts_max, int64_t nh,
+                                            int64_t hd, int64_t hidden, int mlp_kind, int splits_p, int splits_s, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  const char* fn = "plm_decode_layer_beam_bf16";
+  PLM_REQUIRE(x && attn_norm_w && mlp_norm_w && w_qkv && w_out && w_fc1 && w_fc2 && row && lens_s && rot0 && lens_p && anc && rope_cos && rope_sin && kv_p &&
+                  kv_s && status && workspace,
+              "%s: null pointer", fn);
+  PLM_REQUIRE(df_aligned(workspace, kv_p), "%s: the workspace and kv_p must be 16-byte aligned", fn);
+  PLM_REQUIRE(P >= 1 && G >= 1 && P <= DF_MAX_ROWS && G <= DF_MAX_ROWS && P * G <= DF_MAX_ROWS,
+              "%s: P=%ld prompts x G=%ld samples unsupported (1 <= P*G <= %d rows)", fn, (long)P, (long)G, DF_MAX_ROWS);
+  const int64_t d = nh * hd, M = P * G;
+  char* ws = static_cast<char*>(workspace);
+  uint16_t* q = reinterpret_cast<uint16_t*>(ws);
+  if (const int e = df_check_qkv(fn, x, attn_norm_w, w_qkv, row, rope_cos, rope_sin, rope_T, q, kv_s, ld_kv_s, status, M, 1, Ts_max, nh, hd)) return e;
+  if (const int e = df_check_residual(fn, x, q, w_out, M, d, d)) return e;
+  if (const int e = df_check_fc1(fn, x, mlp_norm_w, w_fc1, q, M, d, hidden, mlp_kind)) return e;
+  if (const int e = df_check_residual(fn, x, q, w_fc2, M, d, hidden)) return e;
+  PLM_REQUIRE(splits_p >= 0 && splits_p <= 64 && splits_s >= 0 && splits_s <= 64, "%s: splits_p=%d / splits_s=%d out of range (0 = automatic, 1..64 forced)",
+              fn, splits_p, splits_s);
+  PLM_REQUIRE(ld_kv_p >= 2 * d && ld_kv_p % 8 == 0, "%s: the prefix cache's row stride must be a multiple of 8 and at least 2*nh*hd", fn);
+  const size_t need = plm_decode_layer_beam_workspace_bytes(P, G, nh, hd, hidden, Tp_max, Ts_max, splits_p, splits_s);
+  PLM_REQUIRE(need != 0, "%s: bad shape P=%ld G=%ld Tp_max=%ld Ts_max=%ld nh=%ld hd=%ld hidden=%ld", fn, (long)P, (long)G, (long)Tp_max, (long)Ts_max,
+              (long)nh, (long)hd, (long)hidden);
+  if (workspace_bytes < need) {
+    plm_set_error("%s: workspace of %zu bytes required, %zu given", fn, need, workspace_bytes);
+    return PLM_E_WORKSPACE;
+  }
+  const size_t qb = df_round16((size_t)M * (size_t)d * 2), ab = df_round16((size_t)M * (size_t)hidden * 2);
+  uint16_t* attn_out = reinterpret_cast<uint16_t*>(ws + qb);
+  uint16_t* act = reinterpret_cast<uint16_t*>(ws + 2 * qb);
+  hipStream_t s = (hipStream_t)stream;
+  df_launch_qkv(x, attn_norm_w, eps, w_qkv, row, nullptr, rope_cos, rope_sin, rope_T, q, kv_s, ld_kv_s, status, M, 1, Ts_max, nh, hd, s, false, rot0);
+  // plm_attn_decode_beam checks its arguments again, after the launch above.  "Every refusal before the first launch" holds because each of
+  // them was already made here: null pointers and the workspace's / kv_p's alignment (above; q, attn_out and the partials are 16-byte offsets
+  // into the workspace, kv_s's alignment is df_check_qkv's), head_dim and ld_kv_s (df_check_qkv), ld_kv_p and both splits (above), its shape
+  // limits and its workspace size (need != 0 asks plm_attn_decode_beam_workspace_bytes, and the bytes handed on are that query's answer).  A refusal
+  // added there must be added here.
+  if (const int e = plm_attn_decode_beam(q, kv_p, ld_kv_p, lens_p, kv_s, ld_kv_s, lens_s, anc, attn_out, nullptr, P, G, Tp_max, Ts_max, nh, hd, splits_p,
+                                           splits_s, ws + 2 * qb + ab, need - 2 * qb - ab, stream))
+    return e;
+  df_launch_residual(x, attn_out, w_out, M, d, d, s);
+  df_launch_fc1(x, mlp_norm_w, eps, w_fc1, act, M, d, hidden, mlp_kind, s);
+  df_launch_residual(x, act, w_fc2, M, d, hidden, s);
+  PLM_CHECK_LAUNCH(fn);
+  return PLM_OK;
+}
+
 // ---- the extend layer over a token tree: B sequences of n <= 32 tree rows, M = B*n <= 32; the qkv stage stores row r at
 // lens0[b] + r and rotates it at lens0[b] + depth[b, r], the attention stage is plm_attn_extend_tree's three launches, the rest is df_layer's ----
 extern "C" size_t plm_extend_layer_tree_workspace_bytes(int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t hidden, int64_t Tmax, int splits) {

@@ -20,7 +20,10 @@ format of ``KVCache`` (``kv_dtype='fp8'``, chosen by cfg.kv_cache or by prefill 
 fused_layers dispatch on the cache to the ops.*_kv8 twins of the same calls, and nothing else here knows about it.  Parallel sampling from
 one prompt is ``SharedPrefixCache`` - a prefilled KVCache held once per prompt plus one suffix cache per sample -
 made by ``fork``; decode_step dispatches on it to ops.kv_append_rope_at / ops.attn_decode_shared (fused: ops.decode_layer_shared), and
-``generate_samples`` is generate over it (check_fork holds its refusals).
+``generate_samples`` is generate over it (check_fork holds its refusals).  Beam search rides the same cache: ``fork_beam``
+attaches ops.BeamBuffers to a fork (``cache.beam``), decode_step then attends the suffix through the buffers' ancestor table
+(ops.attn_decode_beam, fused: ops.decode_layer_beam) and no cache row is copied when beams are re-parented; ``beam_loop`` is the host loop over
+ops.beam_select / ops.beam_advance / ops.beam_finalize, ``generate_beam`` the public call (check_beam holds its refusals).
 """
 
 import math
@@ -108,8 +111,11 @@ class SharedPrefixCache:
   of the P prompts, read-only from here on; ``kv``: per layer the suffix buffer bf16 [P*G, Ts_max, 2*dim], sequence p*G + g = sample g of
   prompt p, row j = the sample's j-th own token; ``[pos | lens]`` of the suffix as KVCache keeps them (one in-place add per step);
   ``rot0`` int32 [P*G] = the prompts' lengths repeated G times, on the device: suffix row j of sample i is rotated at rot0[i] + j.
-  ``status`` / ``check()`` as KVCache's: a step past Ts_max (or past the RoPE table) stores nothing and raises the flag."""
+  ``status`` / ``check()`` as KVCache's: a step past Ts_max (or past the RoPE table) stores nothing and raises the flag.  ``beam``: None, or
+  the ops.BeamBuffers of a beam search (``fork_beam``): suffix slot g then holds the rows beam g WROTE, and a beam attends the rows its
+  ancestor table names."""
   kv_dtype = 'bf16'
+  beam = None
 
   def __init__(self, prefix, n_samples, max_new_tokens):
     G, Ts = check_fork(prefix, n_samples, max_new_tokens)
@@ -680,6 +686,55 @@ class _LookupSession:
       raise RuntimeError('generate_lookup: a round\'s tokens did not fit the token history: they were not stored')
 
 
+# ---- beam search ---------------------------------------------------------------------------------------------------
+def check_beam(num_beams, num_return=1, length_penalty=1.0, vocab_size=None, eos_id=None, pad_id=None, temperature=None, top_k=None, top_p=None,
+               seed=None, sample=None):
+  """The refusals of generate_beam / beam_loop that need no GPU; returns (G, R, length_penalty, pad_id) - pad_id defaults to eos_id, then 0."""
+  who = 'generate_beam'
+  given = [n for n, v in (('temperature', temperature), ('top_k', top_k), ('top_p', top_p), ('seed', seed), ('sample', sample)) if v is not None]
+  if given:
+    raise ValueError(f'{who}: beam search is deterministic and takes no sampling arguments ({", ".join(given)}): use generate_samples to sample')
+  for name, v in (('num_beams', num_beams), ('num_return', num_return)):
+    if isinstance(v, bool) or not isinstance(v, int):
+      raise TypeError(f'{who}: {name} must be an int, got {type(v).__name__}')
+  if not 1 <= num_beams <= ops.BEAM_MAX:
+    raise ValueError(f'{who}: num_beams must be in [1, {ops.BEAM_MAX}] (the beams of a prompt are one MFMA tile of queries), got {num_beams}')
+  if not 1 <= num_return <= num_beams:
+    raise ValueError(f'{who}: num_return must be in [1, num_beams={num_beams}], got {num_return}')
+  if vocab_size is not None and vocab_size < 2 * num_beams:
+    raise ValueError(f'{who}: a vocabulary of {vocab_size} is too small for {num_beams} beams (a step keeps 2 * num_beams candidates per prompt)')
+  lp = float(length_penalty)
+  if not math.isfinite(lp):
+    raise ValueError(f'{who}: length_penalty must be finite, got {length_penalty}')
+  for name, v in (('eos_id', eos_id), ('pad_id', pad_id)):
+    if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 0 or (vocab_size is not None and v >= vocab_size)):
+      raise ValueError(f'{who}: {name} must be a token id, got {v!r}')
+  return num_beams, num_return, lp, (pad_id if pad_id is not None else (eos_id if eos_id is not None else 0))
+
+
+def beam_loop(first_logits, step, max_new_tokens, num_beams, num_return=1, length_penalty=1.0, early_stopping=False, eos_id=None, pad_id=None,
+              buffers=None, check_every=FINISH_CHECK_EVERY):
+  """The beam-search loop over a callable.  first_logits bf16 [P, V]: the prompts' last-row logits; ``step(tokens int64 [P*G]) -> logits
+  bf16 [P*G, V]`` is one decode step of all beams, row p*G + n = live beam n of prompt p.  Every token costs one ops.beam_select and one
+  ops.beam_advance on ``buffers`` (ops.BeamBuffers; made here when None - a ``step`` that attends through ``buffers.anc`` brings its own);
+  ``buffers.done`` - the one device-to-host read - is looked at once every ``check_every`` steps and ends the loop when every prompt is
+  done.  Returns ops.beam_finalize's (tokens int64 [P, R, N], lengths int32 [P, R], scores fp32 [P, R])."""
+  N = int(max_new_tokens)
+  if N < 1:
+    raise ValueError(f'generate_beam: max_new_tokens must be at least 1, got {max_new_tokens}')
+  G, R, lp, pad = check_beam(num_beams, num_return, length_penalty, first_logits.shape[-1], eos_id, pad_id)
+  buf = ops.BeamBuffers(first_logits.shape[0], G, N, first_logits.device) if buffers is None else buffers
+  if (buf.P, buf.G, buf.N, buf.steps) != (first_logits.shape[0], G, N, 0):
+    raise ValueError(f'generate_beam: the buffers (P={buf.P}, G={buf.G}, N={buf.N}, steps={buf.steps}) are not fresh ones for P={first_logits.shape[0]}, '
+                     f'G={G}, N={N}')
+  tok = ops.beam_advance(buf, ops.beam_select(first_logits, buf.score0, G, 1), eos_id, lp, early_stopping)
+  for t in range(1, N):
+    if t % check_every == 0 and bool(buf.done.all()):
+      break
+    tok = ops.beam_advance(buf, ops.beam_select(step(tok), buf.score, G, G), eos_id, lp, early_stopping)
+  return ops.beam_finalize(buf, R, lp, eos_id, pad)
+
+
 # ---- tree verification for lookup decoding (DESIGN.md section 22) -------------------------------------------------------------------------------
 def refuse_tree_cache(what, cache):
   """The cache refusals of the tree methods: a SharedPrefixCache (TypeError) and an FP8 cache (ValueError) - the tree kernels read and move
@@ -816,6 +871,8 @@ class Generation:
       def attend(i, qkv):
         if isinstance(cache, SharedPrefixCache):  # row pos of the suffix, rotated at rot0 + pos; prefix, then suffix
           q, _ = ops.kv_append_rope_at(qkv, cache.pos, cache.rot0, rope[0], rope[1], cache.kv[i], nh, status=cache.status)
+          if cache.beam is not None:  # the suffix rows the beam's ancestor table names
+            return ops.attn_decode_beam(q, cache.prefix.kv[i], cache.prefix.lens, cache.kv[i], cache.lens, cache.beam.anc, nh)
           return ops.attn_decode_shared(q, cache.prefix.kv[i], cache.prefix.lens, cache.kv[i], cache.lens, nh)
         if cache.kv_dtype == 'fp8':  # the decode step is the chunk append at n = 1
           q, _ = ops.kv8_append_rope_rows(qkv, cache.pos, rope[0], rope[1], cache.kv[i], nh, status=cache.status)
@@ -926,6 +983,46 @@ class Generation:
     shared.check()
     toks, lps = toks.view(P, G, N), lps.view(P, G, N)
     return (toks, lps) if return_logprobs else toks
+
+  def fork_beam(self, cache, num_beams, max_new_tokens):
+    """``fork`` for beam search: a SharedPrefixCache of num_beams suffix slots per prompt with fresh ops.BeamBuffers
+    as its ``beam``.  decode_step on it stores beam n's row in slot n and attends the rows ``beam.anc`` names; ops.beam_advance moves the
+    table.  Refused: what ``fork`` refuses (an FP8 cache, a fork, an mxfp8 model) and num_beams outside [1, ops.BEAM_MAX]."""
+    G = check_beam(num_beams)[0]
+    shared = self.fork(cache, G, max_new_tokens)
+    shared.beam = ops.BeamBuffers(shared.P, G, shared.Tmax, shared.status.device)
+    return shared
+
+  @torch.compiler.disable
+  def generate_beam(self, prompt, max_new_tokens, num_beams, num_return=1, length_penalty=1.0, early_stopping=False, eos_id=None, pad_id=None,
+                    prompt_lens=None, fused=False, temperature=None, top_k=None, top_p=None, seed=None, sample=None):
+    """Beam search: the num_return <= num_beams best continuations of every prompt of prompt int64 [P, T] by score / length **
+    length_penalty, score = the sum of the tokens' log-probabilities.  Returns (tokens int64 [P, num_return, max_new_tokens] padded with
+    pad_id - default eos_id, then 0 - after a hypothesis's length, lengths int32 [P, num_return] with EOS counted, scores fp32 [P,
+    num_return], best first).  ONE prefill; the prompts' k | v rows are stored once (``fork_beam``) and the beams' own rows are never copied
+    when beams are re-parented: a decode step attends them through an ancestor table (ops.attn_decode_beam).  Every token is one decode
+    step of P * num_beams rows with logits, one ops.beam_select (the 2 * num_beams best continuations per prompt; ties by beam, then
+    token) and one ops.beam_advance.  A hypothesis ends at eos_id; a prompt is done when it holds num_beams finished hypotheses and
+    (early_stopping, or no live beam can still beat the worst of them at the current length); the call ends when all are, looked at every
+    FINISH_CHECK_EVERY steps.  Deterministic and bit-reproducible.  fused=True runs the decode steps through ops.decode_layer_beam and
+    serves P * num_beams <= ops.FUSED_DECODE_MAX_ROWS.  Refused before any launch (ValueError / TypeError): num_beams outside [1, 32],
+    num_return > num_beams, a vocabulary below 2 * num_beams, sampling arguments, an mxfp8 model, fused with too many rows;
+    cfg.kv_cache = 'fp8' does not apply (the call prefills a bf16 cache, and ``fork_beam`` refuses an FP8 one)."""
+    who = 'generate_beam'
+    refuse_shared_mxfp8(who, self)
+    guard(who, prompt, self, forward_only=True, rank2=True)
+    G, R, lp, pad = check_beam(num_beams, num_return, length_penalty, self.cfg.vocab_size, eos_id, pad_id, temperature, top_k, top_p, seed, sample)
+    P, T = prompt.shape
+    check_lengths(T, max_new_tokens, self.cfg.seq_len)
+    if fused:
+      check_fused(who, P * G, self.cfg.dim)
+    cache, first = self.prefill(prompt, prompt_lens, max_len=pad4(T), logits=True, kv_dtype='bf16')
+    shared = self.fork_beam(cache, G, int(max_new_tokens))
+    with torch.no_grad():
+      out = beam_loop(first, lambda t: self.decode_step(t, shared, logits=True, fused=fused), max_new_tokens, G, R, lp, early_stopping, eos_id, pad,
+                      buffers=shared.beam)
+    shared.check()
+    return out
 
   @torch.compiler.disable
   def generate(self, prompt, max_new_tokens, prompt_lens=None, eos_id=None, sample=None, return_logprobs=False, temperature=None,

@@ -1156,6 +1156,8 @@ from .ops_shared import (attn_decode_shared, attn_decode_shared_workspace_bytes,
 from .ops_tree import (TREE_MAX_BRANCH, TREE_MAX_ROWS, LookupTree, TreeAccept, TreePlan, attn_extend_tree,  # noqa: E402,F401
                        attn_extend_tree_workspace_bytes, extend_layer_tree, kv_append_rope_tree, kv_tree_commit, lookup_draft_tree, tree_accept,
                        tree_plan)
+# ---- beam search on the shared-prefix cache: its wrappers live in ops_beam.py ------------------------------------------
+from .ops_beam import (BEAM_MAX, BeamBuffers, attn_decode_beam, beam_advance, beam_finalize, beam_select, decode_layer_beam)  # noqa: E402,F401
 # ---- the Muon tail: batched NT GEMM, prepare / orthogonalize / apply; its wrappers live in ops_muon.py -------------------
 from .ops_muon import (MUON_ADJUST_LR, MUON_EPS, MUON_NS_COEFFICIENTS, NT_BATCH_GROUP, gemm_nt_batched, muon_adjusted_lr, muon_apply,  # noqa: E402,F401
                        muon_arena, muon_blocks, muon_items, muon_layout, muon_ns_flops, muon_orthogonalize, muon_prepare, muon_set_lr,

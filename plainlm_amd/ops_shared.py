@@ -105,7 +105,14 @@ def decode_layer_shared(x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_
   """ops.decode_layer for P*G <= FUSED_DECODE_MAX_ROWS samples over a shared prefix, one library call (seven launches):
   decode_norm_qkv_append_at into the suffix cache (row, rot0), attn_decode_shared (lens_p; lens_s = row + 1 during a step),
   decode_gemm_residual with w_out, decode_norm_fc1_act, decode_gemm_residual with w_fc2.  x fp32 [P*G, d] is updated in place and returned."""
-  name = 'decode_layer_shared'
+  return _layer_two_caches('decode_layer_shared', 'plm_decode_layer_shared', x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, row, lens_s,
+                           rot0, lens_p, (), rope_cos, rope_sin, kv_p, kv_s, nh, kind, status, splits_p, splits_s)
+
+
+def _layer_two_caches(name, sym, x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, row, lens_s, rot0, lens_p, anc, rope_cos, rope_sin, kv_p,
+                      kv_s, nh, kind, status, splits_p, splits_s):
+  """decode_layer_shared and ops_beam.decode_layer_beam: the entry points ``sym``_bf16 / ``sym``_workspace_bytes differ by the operands ``anc``
+  (none, or the beam layer's ancestor table) behind lens_p."""
   M, d = D._decode_operands(name, x, (attn_norm_w, mlp_norm_w), (w_qkv, w_out, w_fc1, w_fc2))
   k = D._decode_mlp_kind(name, kind)
   hidden = w_fc2.shape[1]
@@ -121,15 +128,15 @@ def decode_layer_shared(x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_
   except (RuntimeError, TypeError, ValueError) as e:
     raise type(e)(f'{name}.{e}') from None
   Tp, Ts = kv_p.shape[1], kv_s.shape[1]
-  nbytes = O._ws_bytes('plm_decode_layer_shared_workspace_bytes', P, G, nh, hd, hidden, Tp, Ts, int(splits_p), int(splits_s))
+  nbytes = O._ws_bytes(sym + '_workspace_bytes', P, G, nh, hd, hidden, Tp, Ts, int(splits_p), int(splits_s))
   if nbytes == 0:
     raise ValueError(f'{name}: unsupported shape P={P} G={G} nh={nh} hd={hd} hidden={hidden} Tp_max={Tp} Ts_max={Ts} or splits_p={splits_p} / '
                      f'splits_s={splits_s}')
   stream = O._stream()
   ws = O._workspace(x.device, nbytes, stream)
   with O._Launch('hbm:decode_fused', 2.0 * (w_qkv.numel() + w_out.numel() + w_fc1.numel() + w_fc2.numel())):
-    _lib.check(_lib.load().plm_decode_layer_shared_bf16(
+    _lib.check(getattr(_lib.load(), sym + '_bf16')(
         O._p(x), O._p(attn_norm_w), O._p(mlp_norm_w), float(eps), O._p(w_qkv), O._p(w_out), O._p(w_fc1), O._p(w_fc2), O._p(row), O._p(lens_s),
-        O._p(rot0), O._p(lens_p), O._p(rope_cos), O._p(rope_sin), rope_cos.shape[0], O._p(kv_p), kv_p.stride(1), O._p(kv_s), kv_s.stride(1),
-        O._p(status), P, G, Tp, Ts, nh, hd, hidden, k, int(splits_p), int(splits_s), O._p(ws), nbytes, stream), 'plm_decode_layer_shared_bf16')
+        O._p(rot0), O._p(lens_p), *[O._p(a) for a in anc], O._p(rope_cos), O._p(rope_sin), rope_cos.shape[0], O._p(kv_p), kv_p.stride(1), O._p(kv_s),
+        kv_s.stride(1), O._p(status), P, G, Tp, Ts, nh, hd, hidden, k, int(splits_p), int(splits_s), O._p(ws), nbytes, stream), sym + '_bf16')
   return x

@@ -566,10 +566,13 @@ class Transformer(nn.Module, G.Generation):
       self.refresh_shadows()
       x = ops.embed_fwd(tokens, self.embed_tokens.weight)
       for i, layer in enumerate(self.layers):
-        ops.decode_layer_shared(x, layer.attn_norm.weight, layer.mlp_norm.weight, layer.attn_norm.eps, layer.attn.w_qkv.shadow()[0],
-                                layer.attn.w_out.shadow()[0], layer.mlp.fc1.shadow()[0], layer.mlp.fc2.shadow()[0], cache.pos, cache.lens,
-                                cache.rot0, cache.prefix.lens, rope[0], rope[1], cache.prefix.kv[i], cache.kv[i], self.cfg.n_heads,
-                                layer.mlp.kind, cache.status)
+        w = (layer.attn_norm.weight, layer.mlp_norm.weight, layer.attn_norm.eps, layer.attn.w_qkv.shadow()[0], layer.attn.w_out.shadow()[0],
+             layer.mlp.fc1.shadow()[0], layer.mlp.fc2.shadow()[0], cache.pos, cache.lens, cache.rot0, cache.prefix.lens)
+        tail = (rope[0], rope[1], cache.prefix.kv[i], cache.kv[i], self.cfg.n_heads, layer.mlp.kind, cache.status)
+        if cache.beam is not None:  # beam search: the suffix is attended through the ancestor table
+          ops.decode_layer_beam(x, *w, cache.beam.anc, *tail)
+        else:
+          ops.decode_layer_shared(x, *w, *tail)
       return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps)[1]
     if chunk is None:
       layer_op, lengths = ops.decode_layer_kv8 if fp8 else ops.decode_layer, (cache.pos, cache.lens)
