@@ -630,6 +630,88 @@ int plm_extend_layer_tree_bf16(float* x, const float* attn_norm_w, const float* 
                                uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd,
                                int64_t hidden, int mlp_kind, int splits, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the paged KV cache: a pool of 64-row pages behind a block table -----
+ * Every argument check of these entry points comes before any HIP call.  bf16 only.
+ * pool bf16 [n_pages, PLM_KV_PAGE_ROWS, ld_kv]: one layer's pages, every row the k | v columns of plm_kv_append_rope's cache row (k
+ * rotated), ld_kv >= 2*nh*hd and a multiple of 8.  table int32 [B, max_pages]: entry (b, i) is the page that holds tokens 64*i .. 64*i+63
+ * of sequence b, or -1; token j of sequence b lives in row (table[b, j / 64] * 64 + j % 64) of the pool.  An entry outside [0, n_pages)
+ * is never turned into an address.  plm_kv_page_rows() is PLM_KV_PAGE_ROWS; plm_kv_paged_chunk_rows() the keys one workgroup of
+ * plm_attn_decode_paged owns (a compile-time constant of the library: it decides the bits).
+ *
+ * plm_kv_paged_append_rope_rows: plm_kv_append_rope_rows's contract (ragged n_new clamped to [0, n], c_b, zero q_out rows for rows
+ * without a cache row, the same RoPE table loads and rotation: q_out and the stored values are its bits) with row lens0[b] + r stored in
+ * its page.  A sequence is refused on the device - nothing of it is stored, its q_out rows are zeros, status[0] = 1 - when lens0[b] < 0,
+ * lens0[b] + c_b > min(max_pages * 64, rope_T), or a page that one of its rows lens0[b] .. lens0[b] + c_b - 1 needs is outside
+ * [0, n_pages).  n = 1 is the decode step's append.  One launch.
+ *
+ * plm_kv_paged_store_rows: rows bf16 [B, T, ld_rows] (2*nh*hd columns: a prompt's rotated k | v); row t < lens[b] is copied to its page,
+ * 16 bytes per lane.  Rows at or beyond lens[b] are not read and need no page; a row t < lens[b] whose page is outside [0, n_pages)
+ * (or beyond max_pages) is not stored and sets status[0] = 1.  One launch.
+ *
+ * plm_attn_decode_paged: q bf16 [B, nh*hd] rotated; lens int32 [B], clamped to [0, Lcap]; Lcap: the keys of the table the caller wants
+ * walked, 1 <= Lcap <= max_pages * 64.  Sequence b attends keys 0 .. lens[b]-1 (lens[b] == 0: out = 0, lse = +INFINITY); a page outside
+ * [0, n_pages) contributes no key.  Writes out bf16 [B, nh*hd] and, unless NULL, lse fp32 [B, nh] (base 2).  Two launches: a grid of
+ * (B*nh) x ceil(Lcap / chunk) workgroups, each over one chunk of plm_kv_paged_chunk_rows() keys of one (sequence, head) - a workgroup
+ * whose chunk starts at or beyond lens[b] writes an empty partial and reads nothing else - then plm_attn_decode's combine.  No atomics:
+ * bit-reproducible, and a sequence's bits depend on its own length and rows alone - not on B, the other sequences, Lcap or where its
+ * pages lie in the pool.  ceil(Lcap / chunk) > 64 is refused.  workspace: plm_attn_decode_paged_workspace_bytes(...) bytes, 16-byte
+ * aligned (0 for a shape the launch refuses).
+ *
+ * plm_attn_extend_paged: plm_attn_extend (q bf16 [B*n, nh*hd] rotated, the chunk already appended, lens0 clamped to [0, Lcap], n_new
+ * clamped to [0, n], out / lse as there) over the pool.  The S split ranges are whole pages - ceil(ceil(L / 64) / S) of them, L the
+ * sequence's keys - so every 64-key tile is one page.  splits: 0 automatic (plm_attn_extend's rule with Lcap for Tmax) | 1..64 forced;
+ * S == 1 is one launch, else two.  Bit-reproducible and independent of page placement.  workspace:
+ * plm_attn_extend_paged_workspace_bytes(...) bytes.
+ *
+ * PLM_E_INVALID before anything is launched: NULL pointers (n_new, lse excepted), a head_dim other than 32 / 64 / 128, row strides
+ * that are not multiples of 8 or too short, bases that are not 16-byte aligned, max_pages outside [1, 2^18), n_pages outside
+ * [1, 2^24), Lcap outside [1, max_pages * 64], splits outside 0..64; a short workspace gives PLM_E_WORKSPACE. */
+#define PLM_KV_PAGE_ROWS 64
+int plm_kv_page_rows(void);
+int plm_kv_paged_chunk_rows(void);
+int plm_kv_paged_append_rope_rows(const uint16_t* qkv, int64_t ld_qkv, const int32_t* lens0, const int32_t* n_new, const float* rope_cos,
+                                  const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* pool, int64_t ld_kv, const int32_t* table,
+                                  int32_t* status, int64_t B, int64_t n, int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd,
+                                  void* stream);
+int plm_kv_paged_store_rows(const uint16_t* rows, int64_t ld_rows, const int32_t* lens, uint16_t* pool, int64_t ld_kv, const int32_t* table,
+                            int32_t* status, int64_t B, int64_t T, int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd, void* stream);
+size_t plm_attn_decode_paged_workspace_bytes(int64_t B, int64_t nh, int64_t hd, int64_t Lcap);
+int plm_attn_decode_paged(const uint16_t* q, const uint16_t* pool, int64_t ld_kv, const int32_t* table, const int32_t* lens, uint16_t* out,
+                          float* lse, int64_t B, int64_t Lcap, int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd, void* workspace,
+                          size_t workspace_bytes, void* stream);
+size_t plm_attn_extend_paged_workspace_bytes(int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t Lcap, int splits);
+int plm_attn_extend_paged(const uint16_t* q, const uint16_t* pool, int64_t ld_kv, const int32_t* table, const int32_t* lens0,
+                          const int32_t* n_new, uint16_t* out, float* lse, int64_t B, int64_t n, int64_t Lcap, int64_t max_pages,
+                          int64_t n_pages, int64_t nh, int64_t hd, int splits, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The fused layer (see plm_decode_layer_bf16 / plm_extend_layer_bf16) over a paged cache: pool and table in kv's place, Lcap as the
+ * attention stage takes it.
+ * plm_extend_norm_qkv_append_paged_bf16: plm_extend_norm_qkv_append_bf16 with plm_kv_paged_append_rope_rows's addresses and refusal
+ * predicate (Tmax = max_pages * 64, every page of the chunk's rows inside [0, n_pages)): q_out and the stored rows are its contiguous
+ * sibling's bits.  One launch.
+ * plm_decode_layer_paged_bf16: that stage at n = 1 with lens0 = pos and n_new = live (int32 [B] or NULL: 0 marks an idle slot, which
+ * appends nothing), plm_attn_decode_paged over lens, then the out, fc1 and fc2 stages of plm_decode_layer_bf16 unchanged.
+ * plm_extend_layer_paged_bf16: the stage, plm_attn_extend_paged, the same three stages.  1 <= B*n <= 32 rows as ever.
+ * Every refusal of every stage comes before the first launch; workspace: the _workspace_bytes query (0 for a refused shape). */
+int plm_extend_norm_qkv_append_paged_bf16(const float* x, const float* norm_w, float eps, const uint16_t* w_qkv, const int32_t* lens0,
+                                          const int32_t* n_new, const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out,
+                                          uint16_t* pool, int64_t ld_kv, const int32_t* table, int32_t* status, int64_t B, int64_t n,
+                                          int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd, void* stream);
+size_t plm_decode_layer_paged_workspace_bytes(int64_t B, int64_t nh, int64_t hd, int64_t hidden, int64_t Lcap);
+size_t plm_extend_layer_paged_workspace_bytes(int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t hidden, int64_t Lcap, int splits);
+int plm_decode_layer_paged_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                                const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* pos, const int32_t* lens,
+                                const int32_t* live, const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* pool,
+                                int64_t ld_kv, const int32_t* table, int32_t* status, int64_t B, int64_t Lcap, int64_t max_pages,
+                                int64_t n_pages, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, void* workspace,
+                                size_t workspace_bytes, void* stream);
+int plm_extend_layer_paged_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                                const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* lens0,
+                                const int32_t* n_new, const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* pool,
+                                int64_t ld_kv, const int32_t* table, int32_t* status, int64_t B, int64_t n, int64_t Lcap, int64_t max_pages,
+                                int64_t n_pages, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
 /* ---- temperature / top-k / top-p sampling of one token per row -----
  * Every argument check comes before any HIP call.
  * logits bf16 [B, ld] (ld >= V; any 2-byte aligned base and any ld: columns >= V are never loaded); u fp32 [B], one uniform per row,

@@ -171,6 +171,22 @@ SIGNATURES = {
   'plm_extend_layer_tree_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I64, _I]),
   'plm_extend_layer_tree_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64,
                                       _I, _I, _P, _SZ, _P]),
+  'plm_kv_page_rows': (_I, []),
+  'plm_kv_paged_chunk_rows': (_I, []),
+  'plm_kv_paged_append_rope_rows': (_I, [_P, _I64, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
+  'plm_kv_paged_store_rows': (_I, [_P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
+  'plm_attn_decode_paged_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64]),
+  'plm_attn_decode_paged': (_I, [_P, _P, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _SZ, _P]),
+  'plm_attn_extend_paged_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I]),
+  'plm_attn_extend_paged': (_I, [_P, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
+  'plm_extend_norm_qkv_append_paged_bf16': (_I, [_P, _P, _F, _P, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64,
+                                                 _P]),
+  'plm_decode_layer_paged_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64]),
+  'plm_extend_layer_paged_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I64, _I]),
+  'plm_decode_layer_paged_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64,
+                                       _I64, _I64, _I, _P, _SZ, _P]),
+  'plm_extend_layer_paged_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64,
+                                       _I64, _I64, _I64, _I, _I, _P, _SZ, _P]),
   'plm_sample_logits_bf16': (_I, [_P, _I64, _P, _F, _I64, _F, _P, _P, _P, _P, _I64, _I64, _P]),
   'plm_spec_verify_bf16': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I64, _I64, _I64, _P]),
   'plm_lookup_draft_i64': (_I, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P]),

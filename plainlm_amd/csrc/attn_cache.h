@@ -19,9 +19,10 @@ size_t cache_ws_bytes(int64_t B, int64_t n, int64_t nh, int64_t hd, int S);
 void cache_decode_partials_launch(const uint16_t* q, const uint16_t* kv, int64_t ld_kv, const int32_t* lens, float* ws_ml, float* ws_acc, int64_t B,
                                   int64_t Tmax, int64_t nh, int64_t hd, int S, int part_stride, int part_off, hipStream_t s);
 // attn_cache_combine_kernel at n = 1 over S partials per (b, h).  n_new / grp (attn_tree.hip): the B rows are grp chunk rows per n_new entry,
-// and a row at or beyond its entry reads no partial (out = 0, lse = +inf); without them every row is combined
+// and a row at or beyond its entry reads no partial (out = 0, lse = +inf); without them every row is combined.  n > 1 (attn_paged.hip, grp
+// == 0): the chunk form, partials [B*nh, S, n], row r of sequence b combined when r < n_new[b]
 void cache_combine_launch(const float* ws_acc, const float* ws_ml, uint16_t* out, float* lse, int64_t B, int64_t nh, int64_t hd, int S, hipStream_t s,
-                          const int32_t* n_new = nullptr, int grp = 0);
+                          const int32_t* n_new = nullptr, int grp = 0, int64_t n = 1);
 
 // What attn_shared.hip lends to attn_tree.hip: its split rule and the launch of attn_shared_prefix_kernel - P prompts,
 // G query rows each (row p*G + g of q), Sp splits into a partial layout of Stot per (query row, head), ml [., 2] then acc [., hd]

@@ -715,11 +715,11 @@ void cache_decode_partials_launch(const uint16_t* q, const uint16_t* kv, int64_t
 }
 
 void cache_combine_launch(const float* ws_acc, const float* ws_ml, uint16_t* out, float* lse, int64_t B, int64_t nh, int64_t hd, int S, hipStream_t s,
-                          const int32_t* n_new, int grp) {
-  const dim3 grid((unsigned)(B * nh));
-  if (hd == 32) hipLaunchKernelGGL(attn_cache_combine_kernel<32>, grid, dim3(32), 0, s, ws_acc, ws_ml, n_new, out, lse, 1, (int)nh, S, grp);
-  else if (hd == 64) hipLaunchKernelGGL(attn_cache_combine_kernel<64>, grid, dim3(64), 0, s, ws_acc, ws_ml, n_new, out, lse, 1, (int)nh, S, grp);
-  else hipLaunchKernelGGL(attn_cache_combine_kernel<128>, grid, dim3(128), 0, s, ws_acc, ws_ml, n_new, out, lse, 1, (int)nh, S, grp);
+                          const int32_t* n_new, int grp, int64_t n) {
+  const dim3 grid((unsigned)(B * nh * n));
+  if (hd == 32) hipLaunchKernelGGL(attn_cache_combine_kernel<32>, grid, dim3(32), 0, s, ws_acc, ws_ml, n_new, out, lse, (int)n, (int)nh, S, grp);
+  else if (hd == 64) hipLaunchKernelGGL(attn_cache_combine_kernel<64>, grid, dim3(64), 0, s, ws_acc, ws_ml, n_new, out, lse, (int)n, (int)nh, S, grp);
+  else hipLaunchKernelGGL(attn_cache_combine_kernel<128>, grid, dim3(128), 0, s, ws_acc, ws_ml, n_new, out, lse, (int)n, (int)nh, S, grp);
 }
 
 // plm_attn_decode and plm_attn_decode_kv8: `fn` is the entry point the caller sees

@@ -35,7 +35,7 @@
 #define DF_TILE_ELEMS 16640 // 16 x (1024 + 8) = 32 x (512 + 8)
 
 enum { DF_PRO_BF16 = 0, DF_PRO_NORM = 1 };
-enum { DF_EPI_RESIDUAL = 1, DF_EPI_GLU = 2, DF_EPI_SILU = 3, DF_EPI_RELU_SQ = 4, DF_EPI_QKV_ROWS = 5, DF_EPI_QKV_ROWS_KV8 = 6 };
+enum { DF_EPI_RESIDUAL = 1, DF_EPI_GLU = 2, DF_EPI_SILU = 3, DF_EPI_RELU_SQ = 4, DF_EPI_QKV_ROWS = 5, DF_EPI_QKV_ROWS_KV8 = 6, DF_EPI_QKV_ROWS_PAGED = 7 };
 
 struct DfArgs {
   // prologue
@@ -62,6 +62,10 @@ struct DfArgs {
   const int32_t* rot0;   // [M / n] or null: the rows are rotated at rot0[b] + lens0[b] + r (a suffix cache); null: at their row
   const int32_t* depth;  // [M] or null: row r is a tree node rotated at lens0[b] + depth[b, r], stored at lens0[b] + r as ever (DESIGN.md section
                          // 22; depth[b, 0] < 0: plm_tree_plan refused the sequence, nothing of it is stored); null: at their row
+  // QKV_ROWS_PAGED: kv is a pool [n_pages, PLM_KV_PAGE_ROWS, ld_kv], row t of sequence b lives in page
+  // table[b, t / 64]; Tmax = max_pages * 64
+  const int32_t* table;  // [M / n, max_pages]
+  int max_pages, n_pages;
 };
 
 // (a, b) -> (a cos - b sin, b cos + a sin): the pair arithmetic of rope8 (plm_device.h) at sgn = +1
@@ -178,7 +182,7 @@ __global__ __launch_bounds__(DF_THREADS) void decode_fused_kernel(const DfArgs p
     r.x += bf2f(f2bf(v0));
     r.y += bf2f(f2bf(v1));
     *reinterpret_cast<float2*>(xo) = r;
-  } else if (EPI == DF_EPI_QKV_ROWS || EPI == DF_EPI_QKV_ROWS_KV8) {  // plm_kv_append_rope_rows's contract: row m is chunk row r of sequence b, at position lens0[b] + r
+  } else if (EPI == DF_EPI_QKV_ROWS || EPI == DF_EPI_QKV_ROWS_KV8 || EPI == DF_EPI_QKV_ROWS_PAGED) {  // plm_kv_append_rope_rows's contract: row m is chunk row r of sequence b, at position lens0[b] + r
     const int col = blockIdx.x * DF_TILE_N + c2;
     const int dm = p.dm, n = p.n;
     const int b = m / n, r = m - b * n;
@@ -189,8 +193,12 @@ __global__ __launch_bounds__(DF_THREADS) void decode_fused_kernel(const DfArgs p
     }
     const int l0 = p.lens0[b];
     const int r0 = p.rot0 != nullptr ? p.rot0[b] : 0;
-    const bool refused = l0 < 0 || r0 < 0 || (int64_t)l0 + cb > p.Tmax || (int64_t)r0 + l0 + cb > p.rope_T ||
-                         (p.depth != nullptr && p.depth[b * n] < 0);  // nothing of this sequence is stored
+    bool refused = l0 < 0 || r0 < 0 || (int64_t)l0 + cb > p.Tmax || (int64_t)r0 + l0 + cb > p.rope_T ||
+                   (p.depth != nullptr && p.depth[b * n] < 0);  // nothing of this sequence is stored
+    if (EPI == DF_EPI_QKV_ROWS_PAGED && !refused && cb > 0) {  // plm_kv_paged_append_rope_rows's page checks: every page the chunk's rows lie in
+      const int32_t* trow = p.table + (int64_t)b * p.max_pages;  // (l0 + cb <= Tmax = max_pages * 64: the entries exist)
+      for (int pi = l0 / PLM_KV_PAGE_ROWS; pi <= (l0 + cb - 1) / PLM_KV_PAGE_ROWS; ++pi) refused = refused || (unsigned)trow[pi] >= (unsigned)p.n_pages;
+    }
     if (refused && col == 0) p.status[0] = 1;
     if (refused || r >= cb) {  // no cache row; the q row is zeros, so that every byte of q_out is defined
       if (col < dm) df_st2(p.out + (int64_t)m * dm + col, f2bf(0.f), f2bf(0.f));
@@ -211,6 +219,9 @@ __global__ __launch_bounds__(DF_THREADS) void decode_fused_kernel(const DfArgs p
       df_st2(p.out + (int64_t)m * dm + col, b0, b1);
     } else if (EPI == DF_EPI_QKV_ROWS) {
       df_st2(p.kv + ((int64_t)b * p.Tmax + t) * p.ld_kv + (col - dm), b0, b1);
+    } else if (EPI == DF_EPI_QKV_ROWS_PAGED) {  // the same values at the page's address
+      const int page = p.table[(int64_t)b * p.max_pages + t / PLM_KV_PAGE_ROWS];  // checked above: 0 <= page < n_pages
+      df_st2(p.kv + ((int64_t)page * PLM_KV_PAGE_ROWS + t % PLM_KV_PAGE_ROWS) * p.ld_kv + (col - dm), b0, b1);
     } else {
       // The FP8 cache.  The 16 columns of this workgroup's tile are one block of the cache row, held as column pairs by the 8 adjacent
       // lanes tid & 7 of this row; all 8 share m, b and r and col >= dm is uniform over the workgroup, so they are here together.  The
@@ -312,6 +323,24 @@ static int df_check_fc1(const char* fn, const float* x, const float* nw, const u
   return PLM_OK;
 }
 
+// A paged cache's operands: the qkv stage stores through the table into the pool that stands in kv's place, the
+// attention stage walks Lcap keys of the table.  live: the decode layer's n_new (0: an idle slot appends nothing), may be null.
+struct DfPaged {
+  const int32_t* table;
+  const int32_t* live;
+  int64_t max_pages, n_pages, Lcap;
+};
+
+static int df_check_paged(const char* fn, const DfPaged& pg, bool attend) {
+  PLM_REQUIRE(pg.table, "%s: null pointer", fn);
+  PLM_REQUIRE((reinterpret_cast<uintptr_t>(pg.table) & 3) == 0, "%s: the table must be 4-byte aligned", fn);
+  PLM_REQUIRE(pg.max_pages > 0 && pg.max_pages < (1 << 18) && pg.n_pages > 0 && pg.n_pages < (1 << 24),
+              "%s: bad shape max_pages=%ld n_pages=%ld (max_pages < 2^18, n_pages < 2^24)", fn, (long)pg.max_pages, (long)pg.n_pages);
+  PLM_REQUIRE(!attend || (pg.Lcap >= 1 && pg.Lcap <= pg.max_pages * PLM_KV_PAGE_ROWS), "%s: Lcap=%ld outside [1, max_pages * %d = %ld]", fn,
+              (long)pg.Lcap, PLM_KV_PAGE_ROWS, (long)(pg.max_pages * PLM_KV_PAGE_ROWS));
+  return PLM_OK;
+}
+
 template <int PRO, int EPI>
 static void df_launch(const DfArgs& a, int64_t blocks, hipStream_t s) {
   if (a.M > 16) hipLaunchKernelGGL((decode_fused_kernel<PRO, EPI, true>), dim3((unsigned)blocks), dim3(DF_THREADS), 0, s, a);
@@ -321,14 +350,17 @@ static void df_launch(const DfArgs& a, int64_t blocks, hipStream_t s) {
 static void df_launch_qkv(const float* x, const float* nw, float eps, const uint16_t* w_qkv, const int32_t* lens0, const int32_t* n_new,
                           const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* kv, int64_t ld_kv,
                           int32_t* status, int64_t B, int64_t n, int64_t Tmax, int64_t nh, int64_t hd, hipStream_t s, bool kv8 = false,
-                          const int32_t* rot0 = nullptr, const int32_t* depth = nullptr) {
+                          const int32_t* rot0 = nullptr, const int32_t* depth = nullptr, const DfPaged* pg = nullptr) {
   DfArgs a = {};
   const int64_t d = nh * hd;
   a.x = x, a.nw = nw, a.eps = eps, a.w = w_qkv, a.M = (int)(B * n), a.N = (int)(3 * d), a.K = (int)d;
   a.out = q_out, a.kv = kv, a.ld_kv = ld_kv, a.rcos = rope_cos, a.rsin = rope_sin, a.status = status;
   a.rope_T = (int)rope_T, a.Tmax = (int)Tmax, a.hd = (int)hd, a.dm = (int)d;
   a.n = (int)n, a.lens0 = lens0, a.n_new = n_new, a.rot0 = rot0, a.depth = depth;
-  if (kv8) df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS_KV8>(a, 3 * d / DF_TILE_N, s);
+  if (pg != nullptr) {  // Tmax is max_pages * 64 here
+    a.table = pg->table, a.max_pages = (int)pg->max_pages, a.n_pages = (int)pg->n_pages;
+    df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS_PAGED>(a, 3 * d / DF_TILE_N, s);
+  } else if (kv8) df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS_KV8>(a, 3 * d / DF_TILE_N, s);
   else df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS>(a, 3 * d / DF_TILE_N, s);
 }
 
@@ -409,13 +441,18 @@ enum DfAttn { DF_ATTN_DECODE, DF_ATTN_EXTEND };
 // partials, every part a multiple of 16 bytes.  A function of the shapes and the splits argument alone.
 static size_t df_round16(size_t n) { return (n + 15) / 16 * 16; }
 
-static size_t df_layer_workspace_bytes(DfAttn attn, int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t hidden, int64_t Tmax, int splits) {
+// paged: Tmax is Lcap, the attention stage plm_attn_decode_paged / plm_attn_extend_paged
+static size_t df_layer_workspace_bytes(DfAttn attn, int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t hidden, int64_t Tmax, int splits,
+                                       bool paged = false) {
   if (B < 1 || B > DF_MAX_ROWS || n < 1 || n > DF_MAX_ROWS || B * n > DF_MAX_ROWS || nh < 1 || nh * hd > DF_MAX_DIM / 4 || (nh * hd) % 32 != 0 ||
       hidden < 1 || hidden > DF_MAX_DIM / 2 || hidden % 32 != 0)
     return 0;
   // 0 for a head_dim, Tmax or splits the attention stage refuses
-  const size_t att = attn == DF_ATTN_DECODE ? plm_attn_decode_workspace_bytes(B, nh, hd, Tmax, splits)
-                                            : plm_attn_extend_workspace_bytes(B, n, nh, hd, Tmax, splits);
+  size_t att;
+  if (paged) att = attn == DF_ATTN_DECODE ? plm_attn_decode_paged_workspace_bytes(B, nh, hd, Tmax)
+                                          : plm_attn_extend_paged_workspace_bytes(B, n, nh, hd, Tmax, splits);
+  else att = attn == DF_ATTN_DECODE ? plm_attn_decode_workspace_bytes(B, nh, hd, Tmax, splits)
+                                    : plm_attn_extend_workspace_bytes(B, n, nh, hd, Tmax, splits);
   if (att == 0) return 0;
   const size_t M = (size_t)(B * n), d = (size_t)(nh * hd);
   return 2 * df_round16(M * d * 2) + df_round16(M * (size_t)hidden * 2) + att;
@@ -435,7 +472,7 @@ static int df_layer(const char* fn, DfAttn attn, float* x, const float* attn_nor
                     const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* p0, const int32_t* p1,
                     const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t n,
                     int64_t Tmax, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits, void* workspace, size_t workspace_bytes,
-                    void* stream, bool kv8 = false) {
+                    void* stream, bool kv8 = false, const DfPaged* pg = nullptr) {
   PLM_REQUIRE(x && attn_norm_w && mlp_norm_w && w_qkv && w_out && w_fc1 && w_fc2 && p0 && (attn == DF_ATTN_EXTEND || p1) && rope_cos && rope_sin &&
                   kv && status && workspace,
               "%s: null pointer", fn);
@@ -444,14 +481,18 @@ static int df_layer(const char* fn, DfAttn attn, float* x, const float* attn_nor
   char* ws = static_cast<char*>(workspace);
   // every refusal of every stage before the first launch (the sub-buffers stand in for the stages' own operands)
   uint16_t* q = reinterpret_cast<uint16_t*>(ws);
-  if (const int e = df_check_qkv(fn, x, attn_norm_w, w_qkv, p0, rope_cos, rope_sin, rope_T, q, kv, ld_kv, status, B, n, Tmax, nh, hd, kv8)) return e;
+  // a paged cache (kv: the pool): the qkv stage's rows per sequence are the table's, Tmax is the attention stage's Lcap
+  if (pg != nullptr)
+    if (const int e = df_check_paged(fn, *pg, true)) return e;
+  const int64_t Tq = pg != nullptr ? pg->max_pages * PLM_KV_PAGE_ROWS : Tmax;
+  if (const int e = df_check_qkv(fn, x, attn_norm_w, w_qkv, p0, rope_cos, rope_sin, rope_T, q, kv, ld_kv, status, B, n, Tq, nh, hd, kv8)) return e;
   const int64_t M = B * n;
   if (const int e = df_check_residual(fn, x, q, w_out, M, d, d)) return e;
   if (const int e = df_check_fc1(fn, x, mlp_norm_w, w_fc1, q, M, d, hidden, mlp_kind)) return e;
   if (const int e = df_check_residual(fn, x, q, w_fc2, M, d, hidden)) return e;
   PLM_REQUIRE(splits >= 0 && splits <= 64, "%s: splits=%d out of range (0 = automatic, 1..64 forced)", fn, splits);
   // the attention stage's own shape refusals are its workspace query's: 0 for anything plm_attn_decode / plm_attn_extend would refuse
-  const size_t need = df_layer_workspace_bytes(attn, B, n, nh, hd, hidden, Tmax, splits);
+  const size_t need = df_layer_workspace_bytes(attn, B, n, nh, hd, hidden, Tmax, splits, pg != nullptr);
   PLM_REQUIRE(need != 0, "%s: bad shape B=%ld n=%ld Tmax=%ld nh=%ld hd=%ld hidden=%ld", fn, (long)B, (long)n, (long)Tmax, (long)nh, (long)hd,
               (long)hidden);
   if (workspace_bytes < need) {
@@ -464,11 +505,16 @@ static int df_layer(const char* fn, DfAttn attn, float* x, const float* attn_nor
   void* att = ws + 2 * qb + ab;
   const size_t att_bytes = need - 2 * qb - ab;
   hipStream_t s = (hipStream_t)stream;
-  df_launch_qkv(x, attn_norm_w, eps, w_qkv, p0, attn == DF_ATTN_EXTEND ? p1 : nullptr, rope_cos, rope_sin, rope_T, q, kv, ld_kv, status, B, n, Tmax,
-                nh, hd, s, kv8);
+  df_launch_qkv(x, attn_norm_w, eps, w_qkv, p0, attn == DF_ATTN_EXTEND ? p1 : (pg != nullptr ? pg->live : nullptr), rope_cos, rope_sin, rope_T, q, kv,
+                ld_kv, status, B, n, Tq, nh, hd, s, kv8, nullptr, nullptr, pg);
   const uint8_t* c8 = reinterpret_cast<const uint8_t*>(kv);
   int e;
-  if (attn == DF_ATTN_DECODE)
+  if (pg != nullptr)
+    e = attn == DF_ATTN_DECODE
+            ? plm_attn_decode_paged(q, kv, ld_kv, pg->table, p1, attn_out, nullptr, B, Tmax, pg->max_pages, pg->n_pages, nh, hd, att, att_bytes, stream)
+            : plm_attn_extend_paged(q, kv, ld_kv, pg->table, p0, p1, attn_out, nullptr, B, n, Tmax, pg->max_pages, pg->n_pages, nh, hd, splits, att,
+                                    att_bytes, stream);
+  else if (attn == DF_ATTN_DECODE)
     e = kv8 ? plm_attn_decode_kv8(q, c8, ld_kv, p1, attn_out, nullptr, B, Tmax, nh, hd, splits, att, att_bytes, stream)
             : plm_attn_decode(q, kv, ld_kv, p1, attn_out, nullptr, B, Tmax, nh, hd, splits, att, att_bytes, stream);
   else
@@ -717,4 +763,52 @@ extern "C" int plm_extend_layer_kv8_bf16(float* x, const float* attn_norm_w, con
   return df_layer("plm_extend_layer_kv8_bf16", DF_ATTN_EXTEND, x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, lens0, n_new, rope_cos,
                   rope_sin, rope_T, reinterpret_cast<uint16_t*>(kv8), ld_kv8, status, B, n, Tmax, nh, hd, hidden, mlp_kind, splits, workspace,
                   workspace_bytes, stream, true);
+}
+
+// ---- the same stage and layers over a paged cache: pool [n_pages, 64, ld_kv] and table [B, max_pages] in kv's place;
+// the qkv stage's epilogue is DF_EPI_QKV_ROWS_PAGED, the attention stage plm_attn_decode_paged / plm_attn_extend_paged over Lcap keys ----
+extern "C" int plm_extend_norm_qkv_append_paged_bf16(const float* x, const float* norm_w, float eps, const uint16_t* w_qkv, const int32_t* lens0,
+                                                     const int32_t* n_new, const float* rope_cos, const float* rope_sin, int64_t rope_T,
+                                                     uint16_t* q_out, uint16_t* pool, int64_t ld_kv, const int32_t* table, int32_t* status, int64_t B,
+                                                     int64_t n, int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd, void* stream) {
+  const char* fn = "plm_extend_norm_qkv_append_paged_bf16";
+  const DfPaged pg = {table, nullptr, max_pages, n_pages, 0};
+  if (const int e = df_check_paged(fn, pg, false)) return e;
+  const int64_t Tq = max_pages * PLM_KV_PAGE_ROWS;
+  if (const int e = df_check_qkv(fn, x, norm_w, w_qkv, lens0, rope_cos, rope_sin, rope_T, q_out, pool, ld_kv, status, B, n, Tq, nh, hd)) return e;
+  df_launch_qkv(x, norm_w, eps, w_qkv, lens0, n_new, rope_cos, rope_sin, rope_T, q_out, pool, ld_kv, status, B, n, Tq, nh, hd, (hipStream_t)stream,
+                false, nullptr, nullptr, &pg);
+  PLM_CHECK_LAUNCH(fn);
+  return PLM_OK;
+}
+
+extern "C" size_t plm_decode_layer_paged_workspace_bytes(int64_t B, int64_t nh, int64_t hd, int64_t hidden, int64_t Lcap) {
+  return df_layer_workspace_bytes(DF_ATTN_DECODE, B, 1, nh, hd, hidden, Lcap, 0, true);
+}
+
+extern "C" size_t plm_extend_layer_paged_workspace_bytes(int64_t B, int64_t n, int64_t nh, int64_t hd, int64_t hidden, int64_t Lcap, int splits) {
+  return df_layer_workspace_bytes(DF_ATTN_EXTEND, B, n, nh, hd, hidden, Lcap, splits, true);
+}
+
+extern "C" int plm_decode_layer_paged_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                                           const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* pos,
+                                           const int32_t* lens, const int32_t* live, const float* rope_cos, const float* rope_sin, int64_t rope_T,
+                                           uint16_t* pool, int64_t ld_kv, const int32_t* table, int32_t* status, int64_t B, int64_t Lcap,
+                                           int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+  const DfPaged pg = {table, live, max_pages, n_pages, Lcap};
+  return df_layer("plm_decode_layer_paged_bf16", DF_ATTN_DECODE, x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, pos, lens, rope_cos,
+                  rope_sin, rope_T, pool, ld_kv, status, B, 1, Lcap, nh, hd, hidden, mlp_kind, 0, workspace, workspace_bytes, stream, false, &pg);
+}
+
+extern "C" int plm_extend_layer_paged_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                                           const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* lens0,
+                                           const int32_t* n_new, const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* pool,
+                                           int64_t ld_kv, const int32_t* table, int32_t* status, int64_t B, int64_t n, int64_t Lcap,
+                                           int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+  const DfPaged pg = {table, nullptr, max_pages, n_pages, Lcap};
+  return df_layer("plm_extend_layer_paged_bf16", DF_ATTN_EXTEND, x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, lens0, n_new, rope_cos,
+                  rope_sin, rope_T, pool, ld_kv, status, B, n, Lcap, nh, hd, hidden, mlp_kind, splits, workspace, workspace_bytes, stream, false,
+                  &pg);
 }

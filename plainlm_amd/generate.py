@@ -23,7 +23,12 @@ made by ``fork``; decode_step dispatches on it to ops.kv_append_rope_at / ops.at
 ``generate_samples`` is generate over it (check_fork holds its refusals).  Beam search rides the same cache: ``fork_beam``
 attaches ops.BeamBuffers to a fork (``cache.beam``), decode_step then attends the suffix through the buffers' ancestor table
 (ops.attn_decode_beam, fused: ops.decode_layer_beam) and no cache row is copied when beams are re-parented; ``beam_loop`` is the host loop over
-ops.beam_select / ops.beam_advance / ops.beam_finalize, ``generate_beam`` the public call (check_beam holds its refusals).
+ops.beam_select / ops.beam_advance / ops.beam_finalize, ``generate_beam`` the public call (check_beam holds its refusals).  The paged KV
+cache is ``PagePool`` - per-layer pages of ops.KV_PAGE_ROWS token rows and a host free list - and ``PagedKVCache`` - a
+device block table with a host mirror, host upper bounds of the lengths, release / adopt; ``prefill_paged`` / ``new_cache_paged`` make one,
+decode_step and extend dispatch on it to ops.kv_paged_append_rope_rows / ops.attn_decode_paged / ops.attn_extend_paged, and ``serve`` is
+continuous batching over it (refuse_paged and refuse_paged_model hold its refusals); fused=True runs ops.decode_layer_paged /
+ops.extend_layer_paged per layer.
 """
 
 import math
@@ -142,8 +147,210 @@ class SharedPrefixCache:
                          'not stored (fork with a larger max_new_tokens)')
 
 
+class PagePool:
+  """The pages of a paged KV cache: per layer ``kv`` bf16 [n_pages, ops.KV_PAGE_ROWS, 2*dim] in KVCache's row
+  layout, and a host free list.  One page id means the same page in every layer.  ``alloc(k)`` hands out k page ids and raises
+  RuntimeError when fewer are free - on the host, before anything is launched; ``free(ids)`` takes them back.  bf16 pages only."""
+
+  def __init__(self, n_layers, n_pages, n_heads, head_dim, device, kv_dtype='bf16'):
+    if check_kv_dtype(kv_dtype) != 'bf16':
+      raise ValueError(f'PagePool: {kv_dtype!r} pages are not served (the paged kernels read bf16 pages)')
+    if int(n_pages) < 1:
+      raise ValueError(f'PagePool: n_pages must be at least 1, got {n_pages}')
+    self.n_pages, self.n_heads, self.head_dim = int(n_pages), n_heads, head_dim
+    shape = (self.n_pages, ops.KV_PAGE_ROWS, 2 * n_heads * head_dim)
+    self.kv = [torch.empty(shape, dtype=torch.bfloat16, device=device) for _ in range(n_layers)]  # rows >= a sequence's length are never read
+    self._free = list(range(self.n_pages - 1, -1, -1))  # a stack: page 0 goes out first, a freed page is reused first
+    self._used = [False] * self.n_pages
+
+  @property
+  def n_free(self):
+    return len(self._free)
+
+  def alloc(self, k):
+    if k > len(self._free):
+      raise RuntimeError(f'PagePool: {k} pages asked for, {len(self._free)} of {self.n_pages} free (nothing was launched): release sequences or '
+                         'make a larger pool')
+    ids = [self._free.pop() for _ in range(k)]
+    for p in ids:
+      self._used[p] = True
+    return ids
+
+  def free(self, ids):
+    ids = list(ids)
+    if any(not 0 <= p < self.n_pages or not self._used[p] for p in ids) or len(set(ids)) != len(ids):
+      raise ValueError(f'PagePool.free: {ids} are not all pages in use')
+    for p in ids:
+      self._used[p] = False
+    self._free.extend(reversed(ids))
+
+  def bytes_in_use(self):
+    """Bytes of the pages handed out, all layers."""
+    return (self.n_pages - len(self._free)) * sum(t[0].numel() * t.element_size() for t in self.kv)
+
+
+class PagedKVCache:
+  """B sequences over a PagePool: ``table`` int32 [B, max_pages] on the device (entry (b, i): the page of tokens
+  64*i .. 64*i + 63 of sequence b, -1 for none) with a host mirror, ``[pos | lens]`` and ``status`` as KVCache keeps them, ``live`` int32
+  [B] (1: the slot holds a sequence, 0: idle - an idle slot keeps pos = lens = 0, appends nothing and attends nothing), and per sequence
+  a HOST upper bound of its length.  Pages are taken on the host, before a step, whenever a bound crosses a page boundary (``reserve``);
+  the changed table rows go to the device as one copy when ``table`` is next read, and nothing is ever read back from the device."""
+  kv_dtype = 'bf16'
+
+  def __init__(self, pool, B, max_len):
+    if not isinstance(pool, PagePool):
+      raise TypeError(f'PagedKVCache: pool must be a PagePool, got {type(pool).__name__}')
+    if int(B) < 1 or int(max_len) < 1:
+      raise ValueError(f'PagedKVCache: need B >= 1 and max_len >= 1, got B={B} max_len={max_len}')
+    self.pool, self.B, self.Tmax = pool, int(B), int(max_len)
+    self.n_heads, self.head_dim = pool.n_heads, pool.head_dim
+    self.max_pages = -(-self.Tmax // ops.KV_PAGE_ROWS)
+    dev = pool.kv[0].device
+    self._table = torch.full((self.B, self.max_pages), -1, dtype=torch.int32, device=dev)
+    self._mirror = torch.full((self.B, self.max_pages), -1, dtype=torch.int32)
+    self._dirty = None  # (first, last) changed row of the mirror
+    self.pages = [[] for _ in range(self.B)]
+    self.bound = [0] * self.B
+    self._live = [False] * self.B
+    self._pl = torch.zeros((2, self.B), dtype=torch.int32, device=dev)
+    self.live = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+    self.status = torch.zeros((1,), dtype=torch.int32, device=dev)
+
+  lens = KVCache.lens
+  pos = KVCache.pos
+
+  @property
+  def kv(self):
+    return self.pool.kv
+
+  @property
+  def table(self):
+    if self._dirty is not None:
+      lo, hi = self._dirty
+      src = self._mirror[lo:hi + 1].clone()  # a snapshot: the mirror may change again before the copy has run
+      self._table[lo:hi + 1].copy_(src.pin_memory() if self._table.is_cuda else src, non_blocking=True)
+      self._dirty = None
+    return self._table
+
+  def _touch(self, b):
+    self._dirty = (b, b) if self._dirty is None else (min(b, self._dirty[0]), max(b, self._dirty[1]))
+
+  def lcap(self):
+    """The keys of the table worth walking: the largest host bound, rounded up to whole chunks of ops.KV_PAGED_CHUNK."""
+    c = ops.KV_PAGED_CHUNK
+    return min(self.max_pages * ops.KV_PAGE_ROWS, max(1, -(-max(self.bound) // c)) * c)
+
+  def reserve(self, extra):
+    """Move the host bounds by ``extra`` (an int for every live sequence, or B ints) and take the pages the new bounds need - all of
+    them or, when the pool is short, none (RuntimeError).  A bound beyond max_len takes no page: the append refuses that sequence."""
+    extra = [int(extra) if live else 0 for live in self._live] if isinstance(extra, int) else [int(v) for v in extra]
+    want = [min(-(-(self.bound[b] + extra[b]) // ops.KV_PAGE_ROWS), self.max_pages) - len(self.pages[b]) if extra[b] > 0 else 0
+            for b in range(self.B)]
+    want = [max(w, 0) for w in want]
+    ids = self.pool.alloc(sum(want))
+    for b, w in enumerate(want):
+      for _ in range(w):
+        self._mirror[b, len(self.pages[b])] = ids[0]
+        self.pages[b].append(ids.pop(0))
+      if w:
+        self._touch(b)
+      self.bound[b] += extra[b]
+
+  def set_lens(self, lens):
+    """Host integers (B ints or a CPU tensor): every sequence becomes live with that length; pages are taken or returned to match."""
+    if isinstance(lens, torch.Tensor) and lens.is_cuda:
+      raise TypeError('PagedKVCache.set_lens: pass host integers (they size the page lists before anything is launched)')
+    vals = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    if len(vals) != self.B or any(v < 0 or v > self.Tmax for v in vals):
+      raise ValueError(f'PagedKVCache.set_lens: need {self.B} lengths in [0, {self.Tmax}], got {vals}')
+    for b, v in enumerate(vals):
+      keep = -(-v // ops.KV_PAGE_ROWS)
+      if len(self.pages[b]) > keep:
+        self.pool.free(self.pages[b][keep:])
+        del self.pages[b][keep:]
+        self._mirror[b, keep:] = -1
+        self._touch(b)
+      self.bound[b] = min(self.bound[b], v)
+    self._live = [True] * self.B
+    self.reserve([v - self.bound[b] for b, v in enumerate(vals)])
+    t = torch.tensor([[v - 1 for v in vals], vals], dtype=torch.int32)
+    self._pl.copy_(t.to(self._pl.device))
+    self.live.fill_(1)
+
+  def advance(self):
+    """One token per live sequence: its page when the bound crosses a page edge, then one in-place add of ``live``."""
+    self.reserve(1)
+    self._pl += self.live
+
+  def advance_by(self, n_new, bound=None):
+    """Move [pos | lens] by n_new (an int, or an int32 [B] device tensor) after ``reserve`` has moved the host bounds; or pass
+    ``bound`` (host ints) to do both here."""
+    if bound is not None:
+      self.reserve(bound)
+    self._pl += n_new * self.live if isinstance(n_new, int) else n_new
+
+  def release(self, b):
+    """Sequence b leaves: its pages go back to the pool, its table row to -1, its length to 0; the slot is idle."""
+    self.pool.free(self.pages[b])
+    self.pages[b] = []
+    self._mirror[b] = -1
+    self._touch(b)
+    self.bound[b], self._live[b] = 0, False
+    self._pl[:, b] = 0
+    self.live[b] = 0
+
+  def adopt(self, b, other, j):
+    """Sequence j of ``other`` (a cache on the same pool) moves into the idle slot b: page ids move, no row is copied."""
+    if not isinstance(other, PagedKVCache) or other.pool is not self.pool:
+      raise ValueError('PagedKVCache.adopt: the other cache must be a PagedKVCache on the same pool')
+    if self._live[b] or self.pages[b]:
+      raise ValueError(f'PagedKVCache.adopt: slot {b} holds a sequence (release it first)')
+    if len(other.pages[j]) > self.max_pages or other.bound[j] > self.Tmax:
+      raise ValueError(f'PagedKVCache.adopt: the sequence holds {other.bound[j]} tokens, this cache {self.Tmax} per sequence')
+    self.pages[b], other.pages[j] = other.pages[j], []
+    self._mirror[b, :len(self.pages[b])] = torch.tensor(self.pages[b], dtype=torch.int32)
+    other._mirror[j] = -1
+    self._touch(b)
+    other._touch(j)
+    self.bound[b], self._live[b] = other.bound[j], True
+    other.bound[j], other._live[j] = 0, False
+    self._pl[:, b].copy_(other._pl[:, j])
+    self.live[b] = 1
+    other._pl[:, j] = 0
+    other.live[j] = 0
+
+  def prefill_sink(self, layer):
+    """What the trunk hands layer ``layer``'s rotated k | v rows [B, T, 2*dim] to: one ops.kv_paged_store_rows launch."""
+    return lambda rows: ops.kv_paged_store_rows(rows, self.lens, self.pool.kv[layer], self.table, self.n_heads, status=self.status)
+
+  def gather(self, layer):
+    """Layer ``layer`` as the contiguous image bf16 [B, max_pages * 64, 2*dim], by torch indexing (rows of missing pages and rows at and
+    beyond lens hold whatever page 0 / the page holds).  For tests and debugging only."""
+    t = self.table.clamp(min=0).long()
+    return self.pool.kv[layer][t].reshape(self.B, self.max_pages * ops.KV_PAGE_ROWS, -1)
+
+  def check(self):
+    if int(self.status.item()) != 0:
+      raise RuntimeError(f'PagedKVCache: a step appended past max_len {self.Tmax} (or the RoPE table) or into a missing page: those tokens '
+                         'were not stored')
+
+
+def refuse_paged(what, cache):
+  if isinstance(cache, PagedKVCache):
+    raise TypeError(f'Transformer.{what}: a PagedKVCache takes prefill_paged, decode_step, extend and serve only (no fork, no tree rows, no '
+                    'speculative or lookup rounds)')
+
+
+def refuse_paged_model(what, model):
+  if model.cfg.linear_precision == 'mxfp8':
+    raise ValueError(f'Transformer.{what}: linear_precision: mxfp8 has no paged cache path (the cached step runs the bf16 shadows)')
+  if model.cfg.kv_cache != 'bf16':
+    raise ValueError(f"Transformer.{what}: cfg.kv_cache = {model.cfg.kv_cache!r}: FP8 pages are not served (the paged kernels read bf16 pages)")
+
+
 def check_fork(cache, n_samples, max_new_tokens):
   """The refusals of Transformer.fork that need no GPU; returns (G, suffix rows per sample)."""
+  refuse_paged('fork', cache)
   if isinstance(cache, SharedPrefixCache):
     raise TypeError('fork: the cache is already a fork (a SharedPrefixCache cannot be forked again: fork its prefix)')
   if not isinstance(cache, KVCache):
@@ -740,6 +947,7 @@ def refuse_tree_cache(what, cache):
   """The cache refusals of the tree methods: a SharedPrefixCache (TypeError) and an FP8 cache (ValueError) - the tree kernels read and move
   bf16 rows."""
   refuse_shared(what, cache)
+  refuse_paged(what, cache)
   if getattr(cache, 'kv_dtype', 'bf16') != 'bf16':
     raise ValueError(f"Transformer.{what}: a {cache.kv_dtype!r} cache has no tree path (the tree kernels read and move bf16 rows): prefill with "
                      "kv_dtype='bf16'")
@@ -869,6 +1077,10 @@ class Generation:
         return self.head(self.fused_layers(tokens.contiguous(), cache, rope), logits, (B,))
 
       def attend(i, qkv):
+        if isinstance(cache, PagedKVCache):  # the chunk append at n = 1 into the sequence's page, chunks of its own keys
+          q, _ = ops.kv_paged_append_rope_rows(qkv, cache.pos, rope[0], rope[1], cache.kv[i], cache.table, nh, n_new=cache.live,
+                                               status=cache.status)
+          return ops.attn_decode_paged(q, cache.kv[i], cache.table, cache.lens, nh, Lcap=cache.lcap())
         if isinstance(cache, SharedPrefixCache):  # row pos of the suffix, rotated at rot0 + pos; prefix, then suffix
           q, _ = ops.kv_append_rope_at(qkv, cache.pos, cache.rot0, rope[0], rope[1], cache.kv[i], nh, status=cache.status)
           if cache.beam is not None:  # the suffix rows the beam's ancestor table names
@@ -917,14 +1129,24 @@ class Generation:
     if fused:
       check_fused_rows('extend', B, n, self.cfg.dim)
     nh = self.cfg.n_heads
+    paged = isinstance(cache, PagedKVCache)
     with torch.no_grad():
       adv, n_new = chunk_lens(token_lens, B, n, tokens.device)
       rope = self._rope(tokens.device)
       lens0 = cache.lens  # the lengths before the chunk: what every layer's append and attention see; moved once, after the last layer
+      if paged:  # the chunk's pages, on the host: by the token_lens the host knows, else by the chunk's width - a device token_lens is
+        # never read back, so every live bound then moves by the full n and the pages it took beyond the real length stay until release
+        host = token_lens is not None and not (isinstance(token_lens, torch.Tensor) and token_lens.is_cuda)
+        cache.reserve([int(v) if live else 0 for v, live in zip(token_lens, cache._live)] if host else int(n))
+        n_new = cache.live * n if n_new is None else n_new * cache.live  # an idle slot appends nothing, whatever its entry says
+        adv = n_new
 
       append, attn = (ops.kv8_append_rope_rows, ops.attn_extend_kv8) if cache.kv_dtype == 'fp8' else (ops.kv_append_rope_rows, ops.attn_extend)
 
       def attend(i, qkv):
+        if paged:
+          q, _ = ops.kv_paged_append_rope_rows(qkv, lens0, rope[0], rope[1], cache.kv[i], cache.table, nh, n_new=n_new, status=cache.status)
+          return ops.attn_extend_paged(q, cache.kv[i], cache.table, lens0, nh, n_new=n_new)  # Lcap = the table's width: S from the shape alone
         q, _ = append(qkv, lens0, rope[0], rope[1], cache.kv[i], nh, n_new=n_new, status=cache.status)
         return attn(q, cache.kv[i], lens0, nh, n_new=n_new)
       flat = tokens.reshape(-1).contiguous()
@@ -937,6 +1159,154 @@ class Generation:
       else:
         y = last_rows(y, B, n, n_new.clamp(min=1))
       return self.head(y, logits, (B,))
+
+  # ---- the paged KV cache.  prefill / new_cache keep their pinned parameter lists: the paged forms are methods of
+  # their own, as generate_fused is
+  def new_page_pool(self, n_pages, kv_dtype=None):
+    """A PagePool of n_pages pages of ops.KV_PAGE_ROWS token rows for this model, on its device.  bf16 pages only: kv_dtype 'fp8', a
+    model with cfg.kv_cache = 'fp8' and an mxfp8 model raise ValueError."""
+    refuse_paged_model('new_page_pool', self)
+    device = self.lm_head.weight.device
+    if device.type != 'cuda':
+      raise RuntimeError('plainlm_amd.Transformer runs on MI355X only (the model is on CPU; there is no CPU fallback)')
+    return PagePool(self.n_layers, n_pages, self.cfg.n_heads, self.head_dim, device, 'bf16' if kv_dtype is None else kv_dtype)
+
+  def new_cache_paged(self, B, pool, max_len=None):
+    """``new_cache`` over a PagePool: an empty PagedKVCache of B idle slots, max_len tokens each at most (default and at most
+    cfg.seq_len).  It holds no page until a sequence is adopted or its lengths are set."""
+    refuse_paged_model('new_cache_paged', self)
+    Tmax, fits = cache_rows(max_len, self.cfg.seq_len)
+    if int(B) < 1 or not fits:
+      raise ValueError(f'new_cache_paged: need B >= 1 and 1 <= max_len <= cfg.seq_len {self.cfg.seq_len}, got B={B} max_len={Tmax}')
+    cache = PagedKVCache(pool, int(B), Tmax)
+    check_cache('new_cache_paged', cache, self)
+    return cache
+
+  @torch.compiler.disable
+  def prefill_paged(self, x, pool, prompt_lens=None, max_len=None, logits=False):
+    """``prefill`` into a PagedKVCache on ``pool``: the trunk as it is, every layer's rotated k | v rows scattered into the sequences'
+    pages by one ops.kv_paged_store_rows launch.  Pages are taken for prompt_lens[b] tokens, not for the padded width; max_len (default
+    cfg.seq_len) bounds what a sequence may grow to and costs nothing until it does.  Returns (PagedKVCache, HeadPrediction [B]) as
+    ``prefill`` does.  A pool that is short of pages raises RuntimeError before anything is launched."""
+    refuse_paged_model('prefill_paged', self)
+    guard('prefill_paged', x, self, rank2=True)
+    B, T = x.shape
+    lens = prompt_lens_list(prompt_lens, B, T)
+    Tp = pad4(T)
+    Tmax, fits = cache_rows(max_len, self.cfg.seq_len, least=max(lens))
+    if not fits or Tp > self.cfg.seq_len:
+      raise ValueError(f'prefill_paged: the prompts ({max(lens)} tokens, {Tp} padded rows) must fit max_len {Tmax} and cfg.seq_len {self.cfg.seq_len}')
+    cache = PagedKVCache(pool, B, Tmax)
+    check_cache('prefill_paged', cache, self)
+    with torch.no_grad():
+      if Tp != T:
+        x = torch.nn.functional.pad(x, (0, Tp - T))
+      try:
+        cache.set_lens(lens)
+        y, _, _ = self.trunk(x.contiguous(), None, cache)
+      except Exception:
+        for b in range(B):
+          cache.release(b)
+        raise
+      return cache, self.head(last_rows(y, B, Tp, cache.lens), logits, (B,))
+
+  @torch.compiler.disable
+  def serve(self, prompts, max_new_tokens, max_batch, pool=None, eos_id=None, fused=False, temperature=None, top_k=None, top_p=None,
+            sample=None, seed=None):
+    """Continuous batching: continue every prompt of ``prompts`` - a list of 1-D int64 token tensors of any
+    lengths - by up to max_new_tokens tokens (an int, or one int per prompt), greedily, with at most max_batch sequences in flight.
+    Returns a list of int64 tensors, the new tokens of every prompt, ended by eos_id when the sequence emitted it.  A waiting prompt is
+    prefilled as a one-sequence PagedKVCache on ``pool`` (default: a pool made here, large enough for max_batch full sequences) and
+    adopted into a free slot of the batch; a sequence that reaches its budget - or, as seen by the one device-to-host read every
+    FINISH_CHECK_EVERY steps, emitted eos_id - is released and its slot refilled; idle slots step with length 0.  A prompt is admitted
+    only when the pool can hold it to the end of its budget, so a step never runs out of pages; a pool too small for one sequence raises
+    RuntimeError.  Greedy only: the on-device sampler's per-call uniforms do not map onto sequences that start at different steps, so
+    sampling arguments raise ValueError.  fused=True runs the steps through ops.decode_layer_paged and serves max_batch <=
+    ops.FUSED_DECODE_MAX_ROWS, ValueError beyond."""
+    who = 'serve'
+    refuse_paged_model(who, self)
+    if any(a is not None for a in (temperature, top_k, top_p, sample, seed)):
+      raise ValueError(f'{who}: greedy only - the sampler\'s uniforms are drawn per call for a fixed batch and do not map onto sequences that '
+                       'join at different steps: drop temperature / top_k / top_p / sample / seed')
+    if fused:
+      check_fused(who, int(max_batch), self.cfg.dim)
+    prompts = list(prompts)
+    if not prompts or int(max_batch) < 1:
+      raise ValueError(f'{who}: need at least one prompt and max_batch >= 1')
+    for t in prompts:
+      if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or t.numel() < 1:
+        raise TypeError(f'{who}: every prompt must be a non-empty 1-D int64 tensor')
+    guard(who, prompts[0], self, forward_only=True)
+    N, S = len(prompts), int(max_batch)
+    budget = [int(max_new_tokens)] * N if isinstance(max_new_tokens, int) else [int(v) for v in max_new_tokens]
+    if len(budget) != N:
+      raise ValueError(f'{who}: {len(budget)} budgets for {N} prompts')
+    total = [_check_new_tokens(who, prompts[i].numel(), budget[i], 0, '', [('', self.cfg.seq_len)]) for i in range(N)]
+    pages = [-(-t // ops.KV_PAGE_ROWS) for t in total]  # what sequence i holds at the end of its budget
+    if pool is None:
+      pool = self.new_page_pool(min(S, N) * max(pages))
+    if max(pages) > pool.n_free:
+      raise RuntimeError(f'{who}: the pool has {pool.n_free} free pages, one sequence needs {max(pages)}')
+    dev = prompts[0].device
+    with torch.no_grad():
+      slots = self.new_cache_paged(S, pool, max(total))
+      owner, left, promised = [None] * S, [0] * S, [0] * S  # per slot: its prompt, the tokens it may still emit, the pages it may still take
+      first, steps, where = [None] * N, [], [[] for _ in range(N)]  # where[i]: (step, slot) of sequence i's decode tokens
+      cur = torch.zeros((S,), dtype=torch.int64, device=dev)
+      done = torch.zeros((S,), dtype=torch.bool, device=dev)
+      waiting = list(range(N))
+
+      def leave(b):
+        slots.release(b)
+        owner[b], promised[b] = None, 0
+
+      while waiting or any(o is not None for o in owner):
+        for b in range(S):  # admission: in prompt order, into the lowest free slot, while the pool can hold the sequence to its end
+          while owner[b] is None and waiting and pool.n_free - sum(promised) >= pages[waiting[0]]:
+            i = waiting.pop(0)
+            one, r = self.prefill_paged(prompts[i].view(1, -1), pool, max_len=total[i])
+            first[i] = r.tokens
+            if budget[i] == 1:
+              one.release(0)
+              continue
+            slots.adopt(b, one, 0)
+            owner[b], left[b], promised[b] = i, budget[i] - 1, pages[i] - len(slots.pages[b])
+            cur[b:b + 1] = r.tokens
+            done[b:b + 1] = (r.tokens == eos_id) if eos_id is not None else False
+        if all(o is None for o in owner):
+          if waiting:
+            raise RuntimeError(f'{who}: the pool cannot hold prompt {waiting[0]} ({pages[waiting[0]]} pages, {pool.n_free} free)')
+          break
+        held = [len(p) for p in slots.pages]
+        steps.append(self.decode_step(cur, slots, fused=fused).tokens)
+        cur = steps[-1].clone()  # admission writes a new sequence's first token into its slot: not into the recorded step
+        if eos_id is not None:
+          done = done | (cur == eos_id)
+        for b in range(S):
+          if owner[b] is not None:
+            promised[b] -= len(slots.pages[b]) - held[b]
+            where[owner[b]].append((len(steps) - 1, b))
+            left[b] -= 1
+            if left[b] == 0:
+              leave(b)
+        if eos_id is not None and len(steps) % FINISH_CHECK_EVERY == 0:  # the one device-to-host read
+          for b, d in enumerate(done.tolist()):
+            if d and owner[b] is not None:
+              leave(b)
+      slots.check()
+      out = []
+      grid = torch.stack(steps) if steps else None
+      for i in range(N):
+        t = first[i]
+        if where[i]:
+          st, sl = zip(*where[i])
+          t = torch.cat([t, grid[torch.tensor(st, device=dev), torch.tensor(sl, device=dev)]])
+        if eos_id is not None:
+          hit = (t == eos_id).nonzero()
+          if hit.numel():
+            t = t[:int(hit[0]) + 1]
+        out.append(t)
+      return out
 
   def fork(self, cache, n_samples, max_new_tokens):
     """A SharedPrefixCache for n_samples continuations of every prompt of the prefilled bf16 ``cache``, max_new_tokens suffix rows each.

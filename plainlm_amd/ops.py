@@ -1158,6 +1158,9 @@ from .ops_tree import (TREE_MAX_BRANCH, TREE_MAX_ROWS, LookupTree, TreeAccept, T
                        tree_plan)
 # ---- beam search on the shared-prefix cache: its wrappers live in ops_beam.py ------------------------------------------
 from .ops_beam import (BEAM_MAX, BeamBuffers, attn_decode_beam, beam_advance, beam_finalize, beam_select, decode_layer_beam)  # noqa: E402,F401
+# ---- the paged KV cache: pages behind a block table; its wrappers live in ops_paged.py ---------------------------------
+from .ops_paged import (KV_PAGE_ROWS, KV_PAGED_CHUNK, attn_decode_paged, attn_decode_paged_workspace_bytes, attn_extend_paged,  # noqa: E402,F401
+                        decode_layer_paged, extend_layer_paged, extend_norm_qkv_append_paged, kv_paged_append_rope_rows, kv_paged_store_rows)
 # ---- the Muon tail: batched NT GEMM, prepare / orthogonalize / apply; its wrappers live in ops_muon.py -------------------
 from .ops_muon import (MUON_ADJUST_LR, MUON_EPS, MUON_NS_COEFFICIENTS, NT_BATCH_GROUP, gemm_nt_batched, muon_adjusted_lr, muon_apply,  # noqa: E402,F401
                        muon_arena, muon_blocks, muon_items, muon_layout, muon_ns_flops, muon_orthogonalize, muon_prepare, muon_set_lr,

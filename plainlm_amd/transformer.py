@@ -230,7 +230,9 @@ class Attention(nn.Module):
     if cache is not None:  # prefill: this layer's kv [B, Tmax, 2*dim] takes the k | v columns of the rotated qkv, as they are
       d = self.n_heads * self.head_dim
       kvrows = qkv.detach().view(B, T, 3 * d)[:, :, d:]
-      if cache.dtype == torch.uint8:  # an FP8 cache: the same rows, quantised by one launch - and read back, so
+      if callable(cache):  # a paged cache: the rows < lens are scattered into the sequences' pages by one launch
+        cache(kvrows)
+      elif cache.dtype == torch.uint8:  # an FP8 cache: the same rows, quantised by one launch - and read back, so
         ops.kv8_quant_rows(kvrows, cache, self.n_heads)  # that the prompt attends the k | v every later step will find in the cache
         ops.kv8_dequant_rows(cache, self.n_heads, self.head_dim, out=kvrows)
       else:
@@ -477,7 +479,8 @@ class Transformer(nn.Module, G.Generation):
     h = self.embed_tokens(x).view(B * T, self.cfg.dim)
     branch = None
     for i, layer in enumerate(self.layers):
-      h, branch = layer(h, branch, rope, doc_start, B, T, None if cache is None else cache.kv[i])
+      sink = None if cache is None else (cache.prefill_sink(i) if hasattr(cache, 'prefill_sink') else cache.kv[i])
+      h, branch = layer(h, branch, rope, doc_start, B, T, sink)
     _, y = Fn.AddNormFn.apply(h, branch, self.out_norm.weight, self.out_norm)
     return y, B, T
 
@@ -573,6 +576,21 @@ class Transformer(nn.Module, G.Generation):
           ops.decode_layer_beam(x, *w, cache.beam.anc, *tail)
         else:
           ops.decode_layer_shared(x, *w, *tail)
+      return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps)[1]
+    if isinstance(cache, G.PagedKVCache):  # the pool and the table in the cache's place, ops.*_layer_paged per layer
+      if chunk is not None and (len(chunk) != 3 or tokens.shape[0] != cache.B * chunk[2]):
+        raise ValueError(f'fused_layers: {tokens.shape[0]} tokens are not {cache.B} plain chunks on a PagedKVCache')
+      self.refresh_shadows()
+      x = ops.embed_fwd(tokens, self.embed_tokens.weight)
+      table = cache.table
+      for i, layer in enumerate(self.layers):
+        w = (layer.attn_norm.weight, layer.mlp_norm.weight, layer.attn_norm.eps, layer.attn.w_qkv.shadow()[0], layer.attn.w_out.shadow()[0],
+             layer.mlp.fc1.shadow()[0], layer.mlp.fc2.shadow()[0])
+        tail = (rope[0], rope[1], cache.kv[i], table, self.cfg.n_heads, layer.mlp.kind, cache.status)
+        if chunk is None:
+          ops.decode_layer_paged(x, *w, cache.pos, cache.lens, *tail, live=cache.live, Lcap=cache.lcap())
+        else:
+          ops.extend_layer_paged(x, *w, chunk[0], chunk[1], *tail)
       return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps)[1]
     if chunk is None:
       layer_op, lengths = ops.decode_layer_kv8 if fp8 else ops.decode_layer, (cache.pos, cache.lens)
