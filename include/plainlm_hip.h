@@ -853,6 +853,29 @@ int plm_head_predict_bf16(const uint16_t* Y, int64_t ldy, const uint16_t* W, int
                           float* logp, float* entropy, float* nll, float* lse, int64_t M, int64_t V, int64_t K, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* ---- top-k head -----
+ * Per row of l = bf16(Y[M,K] W[V,K]^T) - the logits plm_gemm_bf16_nt would store, never held for more than a chunk of rows - the k
+ * (1 <= k <= 64, k <= V) most likely columns:
+ *   tok   int64[M, k]  columns by logit descending, equal logits by column ascending (+0 == -0); -1 past the row's finite logits
+ *   logp  fp32[M, k]   l[tok] - lse; -inf where tok is -1
+ *   lse   fp32[M]      log-sum-exp of the row's finite logits, -inf for a row without one                (may be NULL)
+ *   rank  int32[M]     0-based place of targets[m] in that order over the whole row: the columns with a larger logit plus the
+ *                      lower columns with an equal one; -1 for a target outside [0, V), V for a target whose logit is not finite
+ *                                                                                                       (may be NULL; needs targets)
+ * NaN and +-inf logits are treated as absent: never in tok, not in lse, not counted by rank.  targets int64[M] may be NULL.
+ * The NT GEMM (the kernel plm_gemm_bf16_nt picks for the whole shape, so the same bf16 values) writes plm_head_topk_chunk_rows() rows
+ * of logits at a time into the workspace and a row kernel (one workgroup per row: the row staged in LDS once, radix select, a sort of
+ * the k candidates) reads them back from cache; 2 launches per chunk.  No gradient is produced.
+ * workspace: plm_head_topk_workspace_bytes(M, V, K, k) bytes (min(M, chunk rows) * ceil(V / 8) * 16; 0 = k out of range), 16-byte
+ * aligned, caller-owned.  NULL pointers, k outside [1, min(64, V)], K % 64 != 0, row strides that are not multiples of 8, Y / W that
+ * are not 16-byte aligned give PLM_E_INVALID and a short workspace PLM_E_WORKSPACE before anything is launched.
+ * Deterministic (no global atomics, integer selection, fixed summation order). */
+int64_t plm_head_topk_chunk_rows(void);
+size_t plm_head_topk_workspace_bytes(int64_t M, int64_t V, int64_t K, int64_t k);
+int plm_head_topk_bf16(const uint16_t* Y, int64_t ldy, const uint16_t* W, int64_t ldw, const int64_t* targets, int64_t k, int64_t* tok,
+                       float* logp, float* lse, int32_t* rank, int64_t M, int64_t V, int64_t K, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 /* ---- device-scalar scaling (chunked lm_head + cross-entropy, models/transformer.py:114 + engine/engine.py:111,118)
  * The chunked head runs its dX / dW GEMMs inside forward, before autograd hands over the upstream gradient g
  * (engine.py:118 `(loss / accum).backward()`); backward applies g with

@@ -197,6 +197,9 @@ SIGNATURES = {
   'plm_head_score_bf16': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
   'plm_head_predict_workspace_bytes': (_SZ, [_I64, _I64, _I64]),
   'plm_head_predict_bf16': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
+  'plm_head_topk_chunk_rows': (_I64, []),
+  'plm_head_topk_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64]),
+  'plm_head_topk_bf16': (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
   'plm_scale_bf16': (_I, [_P, _I64, _P, _P]),
   'plm_axpy_f32': (_I, [_P, _P, _I64, _P, _I, _P]),
   'plm_sumsq_f32': (_I, [_P, _I64, _P, _P, _P]),

@@ -390,3 +390,58 @@ extern "C" int plm_head_predict_bf16(const uint16_t* Y, int64_t ldy, const uint1
   PLM_CHECK_LAUNCH("plm_head_predict_bf16");
   return PLM_OK;
 }
+
+// =============================================================================================
+// Top-k head (include/plainlm_hip.h):  the k best columns of every row of  bf16(Y W^T)  with their log-probabilities
+// =============================================================================================
+// plm_head_predict_bf16's chunk loop as the only path: the NT GEMM writes a chunk of rows of logits into the workspace - small enough to stay
+// in the 256 MB Infinity Cache (1024 rows of V = 50280: 103 MB) - and head_topk.hip's row kernel reads them back from there.  The kernel
+// is the one plm_gemm_bf16_nt plans for the WHOLE matrix, named explicitly, so that a chunk gets the accumulators the whole matrix would.
+// Workspace: the chunk of logits, nothing else.  PLM_HT_CHUNK: profiles/head_topk_bench.txt.
+#define PLM_HT_CHUNK 1024
+static int64_t ht_chunk_rows() { return plm_env().ht_chunk ? plm_env().ht_chunk : PLM_HT_CHUNK; }
+
+extern "C" int64_t plm_head_topk_chunk_rows(void) { return ht_chunk_rows(); }
+
+extern "C" size_t plm_head_topk_workspace_bytes(int64_t M, int64_t V, int64_t K, int64_t k) {
+  if (M <= 0 || V <= 0 || K <= 0 || k < 1 || k > 64 || k > V) return 0;
+  const int64_t rows = M < ht_chunk_rows() ? M : ht_chunk_rows();
+  return hs_align((size_t)rows * (size_t)(plm_cdiv(V, 8) * 8) * sizeof(uint16_t));
+}
+
+extern "C" int plm_head_topk_bf16(const uint16_t* Y, int64_t ldy, const uint16_t* W, int64_t ldw, const int64_t* targets, int64_t k, int64_t* tok,
+                                  float* logp, float* lse, int32_t* rank, int64_t M, int64_t V, int64_t K, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  PLM_REQUIRE(Y && W && tok && logp && workspace, "plm_head_topk_bf16: null pointer");
+  PLM_REQUIRE(targets || !rank, "plm_head_topk_bf16: null pointer (rank needs targets)");
+  PLM_REQUIRE(M > 0 && V > 0 && K > 0 && M < (1 << 30) && V < (1 << 30) && K < (1 << 30), "plm_head_topk_bf16: bad shape M=%ld V=%ld K=%ld",
+              (long)M, (long)V, (long)K);
+  PLM_REQUIRE(k >= 1 && k <= 64 && k <= V, "plm_head_topk_bf16: k=%ld must be in [1, min(64, V=%ld)]", (long)k, (long)V);
+  PLM_REQUIRE(K % 64 == 0, "plm_head_topk_bf16: K %% 64 == 0 required (K=%ld)", (long)K);
+  PLM_REQUIRE(ldy % 8 == 0 && ldw % 8 == 0 && ldy >= K && ldw >= K, "plm_head_topk_bf16: row strides must be multiples of 8 and >= K (ldy=%ld ldw=%ld)",
+              (long)ldy, (long)ldw);
+  PLM_REQUIRE(aligned16({Y, W, workspace}) &&
+                  ((reinterpret_cast<uintptr_t>(logp) | reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(rank)) & 3) == 0 &&
+                  ((reinterpret_cast<uintptr_t>(targets) | reinterpret_cast<uintptr_t>(tok)) & 7) == 0,
+              "plm_head_topk_bf16: Y, W and the workspace must be 16-byte aligned, targets / tok 8-byte, logp / lse / rank 4-byte");
+  const size_t need = plm_head_topk_workspace_bytes(M, V, K, k);
+  if (workspace_bytes < need) {
+    plm_set_error("plm_head_topk_bf16: workspace of %zu bytes required, %zu given", need, workspace_bytes);
+    return PLM_E_WORKSPACE;
+  }
+  const int64_t ld = plm_cdiv(V, 8) * 8;
+  const int slots = persistent_slots();
+  if (slots == 0) return PLM_E_HIP;
+  const NtPlan p = nt_plan(M, V, K, ld, 0, 0, false, NT_EPI_NONE, slots, plan_env());
+  const int variant = p.kernel == NT_PERSISTENT ? kNtTileVariant[p.tile] : (p.kernel == NT_DMA128 ? 2 : 1);
+  const int64_t chunk = ht_chunk_rows();
+  for (int64_t r0 = 0; r0 < M; r0 += chunk) {
+    const int64_t rows = M - r0 < chunk ? M - r0 : chunk;
+    const int rc = plm_gemm_bf16_nt_ws(Y + r0 * ldy, ldy, W, ldw, workspace, ld, rows, V, K, 0, 0, nullptr, variant, nullptr, 0, stream);
+    if (rc != PLM_OK) return rc;
+    const HeadTopkOut o{tok + r0 * k, logp + r0 * k, lse ? lse + r0 : nullptr, rank ? rank + r0 : nullptr};
+    plm_launch_head_topk_rows((const uint16_t*)workspace, ld, targets ? targets + r0 : nullptr, o, k, rows, V, (hipStream_t)stream);
+  }
+  PLM_CHECK_LAUNCH("plm_head_topk_bf16");
+  return PLM_OK;
+}

@@ -53,3 +53,12 @@ void plm_launch_head_predict_combine(const float* part4, const float* xt, const 
                                      int ntc, hipStream_t s);
 void plm_launch_head_predict_rows(const uint16_t* logits, int64_t ld, const int64_t* targets, const HeadPredictOut& out, int64_t rows, int64_t V,
                                   hipStream_t s);
+
+// head_topk.hip: outputs of the top-k head, tok / logp [rows, k], lse / rank [rows]; lse and rank may be null (rank needs targets)
+struct HeadTopkOut {
+  int64_t* tok;
+  float *logp, *lse;
+  int32_t* rank;
+};
+void plm_launch_head_topk_rows(const uint16_t* logits, int64_t ld, const int64_t* targets, const HeadTopkOut& out, int64_t k, int64_t rows,
+                               int64_t V, hipStream_t s);

@@ -28,6 +28,8 @@ static void load_env() {
   g_env.nt_no_hybrid = getenv("PLM_NT_NO_HYBRID") != nullptr;
   g_env.nt_hybrid_min_k = num("PLM_NT_HYBRID_MIN_K");
   g_env.attn_doc_split_min = num("PLM_ATTN_DOC_SPLIT_MIN") >= 0 ? (int)num("PLM_ATTN_DOC_SPLIT_MIN") : 8;
+  const long long hc = num("PLM_HT_CHUNK");
+  g_env.ht_chunk = (hc == 256 || hc == 512 || hc == 1024) ? (int)hc : 0;
 }
 const PlmEnv& plm_env() {
   static const bool once = (load_env(), true);

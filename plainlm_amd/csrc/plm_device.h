@@ -39,6 +39,7 @@ struct PlmEnv {
   bool nt_no_hybrid;          // PLM_NT_NO_HYBRID: no whole-K + stream-K NT schedule
   long long nt_hybrid_min_k;  // PLM_NT_HYBRID_MIN_K: lowers the hybrid schedule's thresholds (-1: defaults)
   int attn_doc_split_min;     // PLM_ATTN_DOC_SPLIT_MIN: tile steps from which a heavy document-mask QUERY tile is split into two 64-row items (default 8; 0: never)
+  int ht_chunk;               // PLM_HT_CHUNK: rows of logits per chunk of plm_head_topk_bf16, 256 / 512 / 1024 (A/B runs; anything else: the library's constant)
 };
 const PlmEnv& plm_env();
 

@@ -452,5 +452,31 @@ class HipEngine(torch.nn.Module):
       raise ValueError('Validation loss is nan')
     return {'loss': loss_sum / batches, 'accuracy': correct / tokens, 'entropy': ent_sum / tokens, 'tokens': int(tokens)}
 
+  @torch.no_grad()
+  def eval_topk(self, dataloader, ks=(1, 5)):
+    """{'top<k>' for k in ks, 'mrr', 'tokens'} of a validation pass through model.predict_topk (no logits buffer): top-k accuracy
+    (rank < k) and the mean reciprocal rank (1 / (rank + 1)) over the non-ignored targets of all batches, from the target's rank alone
+    (a target whose logit is not finite ranks V).  The sums stay on the device and are read once."""
+    ks = tuple(int(k) for k in ks)
+    if not ks or min(ks) < 1:
+      raise ValueError(f'eval_topk: ks must be positive integers (got {ks!r})')
+    self.check_losses()
+    self.model.eval()
+    if hasattr(self.optimizer, 'eval'):
+      self.optimizer.eval()  # schedule-free: at the averaged iterate x, as eval(); step() returns to y
+    acc = torch.zeros(len(ks) + 2, device=self.device, dtype=torch.float64)  # hits per k, reciprocal-rank sum, tokens
+    for batch in dataloader:
+      inputs, targets, doc_start = _move_to_device(batch, self.seq_len, self.device, self.intra_doc_masking, self._stager)
+      rank = self.model.predict_topk(inputs, 1, doc_start, targets=targets).rank  # the rank is over the whole row, whatever k
+      valid = rank >= 0
+      rr = torch.where(valid, 1.0 / (rank.double() + 1.0), torch.zeros((), dtype=torch.float64, device=rank.device))
+      acc += torch.stack([(valid & (rank < k)).sum().double() for k in ks] + [rr.sum(), valid.sum().double()])
+    if dist.is_initialized():
+      dist.all_reduce(acc, op=dist.ReduceOp.SUM)
+    *hits, rr_sum, tokens = acc.tolist()
+    out = {f'top{k}': h / tokens for k, h in zip(ks, hits)}
+    out.update(mrr=rr_sum / tokens, tokens=int(tokens))
+    return out
+
 
 TorchEngine = HipEngine  # the name train.py imports (train.py:44)

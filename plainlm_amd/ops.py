@@ -1165,3 +1165,5 @@ from .ops_paged import (KV_PAGE_ROWS, KV_PAGED_CHUNK, attn_decode_paged, attn_de
 from .ops_muon import (MUON_ADJUST_LR, MUON_EPS, MUON_NS_COEFFICIENTS, NT_BATCH_GROUP, gemm_nt_batched, muon_adjusted_lr, muon_apply,  # noqa: E402,F401
                        muon_arena, muon_blocks, muon_items, muon_layout, muon_ns_flops, muon_orthogonalize, muon_prepare, muon_set_lr,
                        muon_workspace, muon_workspace_bytes)
+# ---- the top-k head: the k best tokens of every row without the logits; its wrappers live in ops_topk.py -------------
+from .ops_topk import HEAD_TOPK_MAX, HeadTopKOut, head_topk, head_topk_chunk_rows  # noqa: E402,F401

@@ -265,6 +265,7 @@ class Block(nn.Module):
 
 
 HeadPrediction = namedtuple('HeadPrediction', ['tokens', 'logprob', 'entropy', 'nll'])  # Transformer.predict
+HeadTopK = namedtuple('HeadTopK', ['tokens', 'logprobs', 'lse', 'rank'])  # Transformer.predict_topk
 
 
 class Transformer(nn.Module, G.Generation):
@@ -531,6 +532,25 @@ class Transformer(nn.Module, G.Generation):
       y = y.view(B, T, self.cfg.dim)[:, -1]  # row stride T * dim
       return self.head(y, False, (B,), None if targets is None else targets[:, -1].contiguous())
     return self.head(y, False, (B, T), None if targets is None else targets.reshape(-1).contiguous())
+
+  @torch.compiler.disable
+  def predict_topk(self, x, k, attn_mask=None, targets=None, last_only=False):
+    """The k most likely next tokens of every position without the [B, T, V] logits (ops.head_topk):
+    HeadTopK(tokens int64 [B, T, k] by probability descending, equal logits by token ascending; logprobs fp32 [B, T, k]; lse fp32 [B, T];
+    rank int32 [B, T] or None) - or [B, k] / [B], the last position alone, with ``last_only``, as ``predict``.  With ``targets`` [B, T]
+    rank is the 0-based place of the target among the position's tokens (0: it is the prediction; -1: ignored target), so top-k accuracy
+    is ``rank < k`` and the reciprocal rank ``1 / (rank + 1)``.  1 <= k <= 64.  Forward-only, like ``predict``: call it under no_grad."""
+    self._refuse(x, forward_only='predict_topk')
+    if targets is not None and isinstance(x, torch.Tensor) and tuple(targets.shape) != tuple(x.shape):
+      raise ValueError(f'predict_topk: targets {tuple(targets.shape)} do not match the inputs {tuple(x.shape)}')
+    y, B, T = self.trunk(x, attn_mask)
+    shape = (B, T)
+    if last_only:
+      y, shape = y.view(B, T, self.cfg.dim)[:, -1], (B,)  # row stride T * dim
+      targets = None if targets is None else targets[:, -1]
+    wb, _ = self.lm_head.shadow()
+    r = ops.head_topk(y, wb, k, None if targets is None else targets.reshape(-1).contiguous(), want_lse=True)
+    return HeadTopK(r.tok.view(shape + (k,)), r.logp.view(shape + (k,)), r.lse.view(shape), None if r.rank is None else r.rank.view(shape))
 
   def token_logprobs(self, x, targets, attn_mask=None):
     """log p(target) per token, fp32 [B, T] (0 where the target is ignored): ``-score(x, targets, attn_mask, 'none')``."""
