@@ -712,6 +712,65 @@ int plm_extend_layer_paged_bf16(float* x, const float* attn_norm_w, const float*
                                 int64_t n_pages, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits, void* workspace,
                                 size_t workspace_bytes, void* stream);
 
+/* ---- ragged steps over the paged KV cache: one packed list of mixed-width rows -----
+ * Every argument check of these entry points comes before any HIP call.  bf16 pages only; pool, table, Lcap, max_pages and n_pages as in
+ * the block above.
+ * The packed-row contract: cu_rows int32 [B+1] (cu[0] = 0, non-decreasing) and row_seq int32 [R], both on the device.  Row r of the R
+ * packed rows is row j = r - cu[b] of sequence b = row_seq[r], at position lens0[b] + j, if 0 <= b < B and cu[b] <= r < cu[b+1].  Any
+ * other row is padding: it stores nothing, its q_out / out rows are zeros and its lse is +INFINITY.  Sequence b contributes
+ * c_b = cu[b+1] - cu[b] rows (0: it takes no part).  The two words are checked against each other wherever a row becomes an address: no
+ * inconsistent input does.  Nothing is read back to the host.
+ *
+ * plm_kv_paged_append_rope_packed: plm_kv_paged_append_rope_rows over packed rows (qkv bf16 [R, ld_qkv], q_out bf16 [R, nh*hd]): the same
+ * RoPE table loads and rotation, so a row's q_out and its stored k | v are that kernel's bits for the same row values at the same
+ * position.  A sequence is refused on the device - nothing of it is stored, its q_out rows are zeros, status[0] = 1 - when lens0[b] < 0,
+ * lens0[b] + c_b > min(max_pages * 64, rope_T), or a page that one of its rows needs is outside [0, n_pages).  One launch.
+ *
+ * plm_attn_ragged_paged: q bf16 [R, nh*hd] rotated, the rows already appended; lens0 int32 [B], the lengths BEFORE the step, clamped to
+ * [0, Lcap].  Row j of sequence b attends keys 0 .. lens0[b] + j.  Writes out bf16 [R, nh*hd] and, unless NULL, lse fp32 [R, nh] (base
+ * 2), padding rows included.  NT: the number of 32-row tiles, sum over b of ceil(c_b / 32), a host integer in [1, R]; a valid row whose
+ * tile index is >= NT comes out as an empty row (out = 0, lse = +INFINITY).  Two launches: a grid of (NT*nh) x ceil(Lcap / chunk)
+ * workgroups, each over one tile of at most 32 rows of one sequence, one head and one chunk of plm_kv_paged_chunk_rows() keys (8 whole
+ * pages, two per wave: the four waves split the keys, never the queries) - a workgroup whose chunk starts beyond its tile's last visible
+ * key writes an empty partial and reads nothing else - then a combine over every row's chunks in key order that skips empty partials.  A
+ * page outside [0, n_pages) contributes no key; rows at and beyond a sequence's length are never loaded.  No atomics: bit-reproducible,
+ * and a row's bits depend on its own sequence's rows, lens0[b] and j alone - not on B, R, the order in which the sequences are packed,
+ * the other sequences, Lcap or where the pages lie.  ceil(Lcap / chunk) > 64 is refused.  workspace:
+ * plm_attn_ragged_paged_workspace_bytes(...) bytes, 16-byte aligned (0 for a shape the launch refuses).
+ *
+ * PLM_E_INVALID before anything is launched: NULL pointers (lse excepted), a head_dim other than 32 / 64 / 128, row strides that are
+ * not multiples of 8 or too short, bases that are not 16-byte aligned (int32 operands: 4-byte), R or B outside [1, 2^20], NT outside
+ * [1, R], max_pages outside [1, 2^18), n_pages outside [1, 2^24), Lcap outside [1, max_pages * 64]; a short workspace gives
+ * PLM_E_WORKSPACE. */
+int plm_kv_paged_append_rope_packed(const uint16_t* qkv, int64_t ld_qkv, const int32_t* lens0, const int32_t* cu_rows, const int32_t* row_seq,
+                                    const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* q_out, uint16_t* pool,
+                                    int64_t ld_kv, const int32_t* table, int32_t* status, int64_t R, int64_t B, int64_t max_pages,
+                                    int64_t n_pages, int64_t nh, int64_t hd, void* stream);
+size_t plm_attn_ragged_paged_workspace_bytes(int64_t R, int64_t nh, int64_t hd, int64_t Lcap);
+int plm_attn_ragged_paged(const uint16_t* q, const uint16_t* pool, int64_t ld_kv, const int32_t* table, const int32_t* lens0,
+                          const int32_t* cu_rows, const int32_t* row_seq, uint16_t* out, float* lse, int64_t R, int64_t B, int64_t NT,
+                          int64_t Lcap, int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
+/* The fused layer over a ragged step: 1 <= R <= 32 packed rows as ever.
+ * plm_ragged_norm_qkv_append_paged_bf16: plm_extend_norm_qkv_append_paged_bf16 under the packed-row map and
+ * plm_kv_paged_append_rope_packed's refusal predicate: q_out and the stored rows are that stage's bits for the same rows at the same
+ * positions.  One launch.
+ * plm_ragged_layer_paged_bf16: that stage, plm_attn_ragged_paged, then the out, fc1 and fc2 stages of plm_decode_layer_bf16 unchanged;
+ * bit-equal to its stages called one after the other.  Every refusal of every stage comes before the first launch; workspace: the
+ * _workspace_bytes query (0 for a refused shape). */
+int plm_ragged_norm_qkv_append_paged_bf16(const float* x, const float* norm_w, float eps, const uint16_t* w_qkv, const int32_t* lens0,
+                                          const int32_t* cu_rows, const int32_t* row_seq, const float* rope_cos, const float* rope_sin,
+                                          int64_t rope_T, uint16_t* q_out, uint16_t* pool, int64_t ld_kv, const int32_t* table, int32_t* status,
+                                          int64_t R, int64_t B, int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd, void* stream);
+size_t plm_ragged_layer_paged_workspace_bytes(int64_t R, int64_t nh, int64_t hd, int64_t hidden, int64_t Lcap);
+int plm_ragged_layer_paged_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                                const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* lens0,
+                                const int32_t* cu_rows, const int32_t* row_seq, const float* rope_cos, const float* rope_sin, int64_t rope_T,
+                                uint16_t* pool, int64_t ld_kv, const int32_t* table, int32_t* status, int64_t R, int64_t B, int64_t NT,
+                                int64_t Lcap, int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- temperature / top-k / top-p sampling of one token per row -----
  * Every argument check comes before any HIP call.
  * logits bf16 [B, ld] (ld >= V; any 2-byte aligned base and any ld: columns >= V are never loaded); u fp32 [B], one uniform per row,

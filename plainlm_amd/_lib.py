@@ -187,6 +187,14 @@ SIGNATURES = {
                                        _I64, _I64, _I, _P, _SZ, _P]),
   'plm_extend_layer_paged_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64,
                                        _I64, _I64, _I64, _I, _I, _P, _SZ, _P]),
+  'plm_kv_paged_append_rope_packed': (_I, [_P, _I64, _P, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
+  'plm_attn_ragged_paged_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64]),
+  'plm_attn_ragged_paged': (_I, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _SZ, _P]),
+  'plm_ragged_norm_qkv_append_paged_bf16': (_I, [_P, _P, _F, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64,
+                                                 _P]),
+  'plm_ragged_layer_paged_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64]),
+  'plm_ragged_layer_paged_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64,
+                                       _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
   'plm_sample_logits_bf16': (_I, [_P, _I64, _P, _F, _I64, _F, _P, _P, _P, _P, _I64, _I64, _P]),
   'plm_spec_verify_bf16': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I64, _I64, _I64, _P]),
   'plm_lookup_draft_i64': (_I, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P]),

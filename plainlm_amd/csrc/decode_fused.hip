@@ -35,7 +35,7 @@
 #define DF_TILE_ELEMS 16640 // 16 x (1024 + 8) = 32 x (512 + 8)
 
 enum { DF_PRO_BF16 = 0, DF_PRO_NORM = 1 };
-enum { DF_EPI_RESIDUAL = 1, DF_EPI_GLU = 2, DF_EPI_SILU = 3, DF_EPI_RELU_SQ = 4, DF_EPI_QKV_ROWS = 5, DF_EPI_QKV_ROWS_KV8 = 6, DF_EPI_QKV_ROWS_PAGED = 7 };
+enum { DF_EPI_RESIDUAL = 1, DF_EPI_GLU = 2, DF_EPI_SILU = 3, DF_EPI_RELU_SQ = 4, DF_EPI_QKV_ROWS = 5, DF_EPI_QKV_ROWS_KV8 = 6, DF_EPI_QKV_ROWS_PAGED = 7, DF_EPI_QKV_PACKED_PAGED = 8 };
 
 struct DfArgs {
   // prologue
@@ -66,6 +66,11 @@ struct DfArgs {
   // table[b, t / 64]; Tmax = max_pages * 64
   const int32_t* table;  // [M / n, max_pages]
   int max_pages, n_pages;
+  // QKV_PACKED_PAGED: QKV_ROWS_PAGED with the packed row -> (sequence, position) map in place of m / n, m % n:
+  // row m is row m - cu_rows[b] of sequence b = row_seq[m] when 0 <= b < B and cu_rows[b] <= m < cu_rows[b + 1], else padding
+  const int32_t* cu_rows;  // [B + 1]
+  const int32_t* row_seq;  // [M]
+  int B;
 };
 
 // (a, b) -> (a cos - b sin, b cos + a sin): the pair arithmetic of rope8 (plm_device.h) at sgn = +1
@@ -182,6 +187,39 @@ __global__ __launch_bounds__(DF_THREADS) void decode_fused_kernel(const DfArgs p
     r.x += bf2f(f2bf(v0));
     r.y += bf2f(f2bf(v1));
     *reinterpret_cast<float2*>(xo) = r;
+  } else if (EPI == DF_EPI_QKV_PACKED_PAGED) {  // plm_kv_paged_append_rope_packed's contract: the paged epilogue below under the packed map
+    const int col = blockIdx.x * DF_TILE_N + c2;
+    const int dm = p.dm;
+    const int b = p.row_seq[m];
+    bool refused = (unsigned)b >= (unsigned)p.B || p.cu_rows[b] > m || m >= p.cu_rows[b + 1];  // padding: nothing stored, nothing reported
+    int t = 0;
+    if (!refused) {
+      const int r = m - p.cu_rows[b];  // 0 <= r <= m < 32
+      const int cb = (int)min((int64_t)p.cu_rows[b + 1] - p.cu_rows[b], (int64_t)DF_MAX_ROWS);  // r < cb; more rows than a launch has: inconsistent
+      const int l0 = p.lens0[b];
+      refused = l0 < 0 || (int64_t)l0 + cb > p.Tmax || (int64_t)l0 + cb > p.rope_T;
+      if (!refused) {
+        const int32_t* trow = p.table + (int64_t)b * p.max_pages;
+        for (int pi = l0 / PLM_KV_PAGE_ROWS; pi <= (l0 + cb - 1) / PLM_KV_PAGE_ROWS; ++pi) refused = refused || (unsigned)trow[pi] >= (unsigned)p.n_pages;
+      }
+      if (refused && col == 0) p.status[0] = 1;
+      t = l0 + r;
+    }
+    if (refused) {
+      if (col < dm) df_st2(p.out + (int64_t)m * dm + col, f2bf(0.f), f2bf(0.f));
+      return;
+    }
+    bf16_t b0 = f2bf(v0), b1 = f2bf(v1);
+    if (col < 2 * dm) {
+      const int64_t ti = (int64_t)t * (p.hd / 2) + (col % p.hd) / 2;
+      df_rope2(b0, b1, p.rcos[ti], p.rsin[ti]);
+    }
+    if (col < dm) {
+      df_st2(p.out + (int64_t)m * dm + col, b0, b1);
+    } else {
+      const int page = p.table[(int64_t)b * p.max_pages + t / PLM_KV_PAGE_ROWS];  // checked above: 0 <= page < n_pages
+      df_st2(p.kv + ((int64_t)page * PLM_KV_PAGE_ROWS + t % PLM_KV_PAGE_ROWS) * p.ld_kv + (col - dm), b0, b1);
+    }
   } else if (EPI == DF_EPI_QKV_ROWS || EPI == DF_EPI_QKV_ROWS_KV8 || EPI == DF_EPI_QKV_ROWS_PAGED) {  // plm_kv_append_rope_rows's contract: row m is chunk row r of sequence b, at position lens0[b] + r
     const int col = blockIdx.x * DF_TILE_N + c2;
     const int dm = p.dm, n = p.n;
@@ -329,7 +367,20 @@ struct DfPaged {
   const int32_t* table;
   const int32_t* live;
   int64_t max_pages, n_pages, Lcap;
+  // a ragged step: R packed rows of B sequences in NT tiles; null / 0 otherwise
+  const int32_t* cu_rows = nullptr;
+  const int32_t* row_seq = nullptr;
+  int64_t R = 0, B = 0, NT = 0;
 };
+
+// what the packed-row words add to a stage's refusals (plm_kv_paged_append_rope_packed's)
+static int df_check_packed(const char* fn, const DfPaged& pg, const int32_t* lens0) {
+  PLM_REQUIRE(pg.cu_rows && pg.row_seq && lens0, "%s: null pointer", fn);
+  PLM_REQUIRE(pg.B >= 1 && pg.B <= (1 << 20), "%s: bad shape B=%ld sequences (1 <= B <= 2^20)", fn, (long)pg.B);
+  PLM_REQUIRE(((reinterpret_cast<uintptr_t>(pg.cu_rows) | reinterpret_cast<uintptr_t>(pg.row_seq) | reinterpret_cast<uintptr_t>(lens0)) & 3) == 0,
+              "%s: lens0, cu_rows and row_seq must be 4-byte aligned", fn);
+  return PLM_OK;
+}
 
 static int df_check_paged(const char* fn, const DfPaged& pg, bool attend) {
   PLM_REQUIRE(pg.table, "%s: null pointer", fn);
@@ -359,7 +410,12 @@ static void df_launch_qkv(const float* x, const float* nw, float eps, const uint
   a.n = (int)n, a.lens0 = lens0, a.n_new = n_new, a.rot0 = rot0, a.depth = depth;
   if (pg != nullptr) {  // Tmax is max_pages * 64 here
     a.table = pg->table, a.max_pages = (int)pg->max_pages, a.n_pages = (int)pg->n_pages;
-    df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS_PAGED>(a, 3 * d / DF_TILE_N, s);
+    if (pg->cu_rows != nullptr) {  // the packed rows of a ragged step: B = 1, n = R here
+      a.cu_rows = pg->cu_rows, a.row_seq = pg->row_seq, a.B = (int)pg->B;
+      df_launch<DF_PRO_NORM, DF_EPI_QKV_PACKED_PAGED>(a, 3 * d / DF_TILE_N, s);
+    } else {
+      df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS_PAGED>(a, 3 * d / DF_TILE_N, s);
+    }
   } else if (kv8) df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS_KV8>(a, 3 * d / DF_TILE_N, s);
   else df_launch<DF_PRO_NORM, DF_EPI_QKV_ROWS>(a, 3 * d / DF_TILE_N, s);
 }
@@ -435,7 +491,7 @@ extern "C" int plm_extend_norm_qkv_append_bf16(const float* x, const float* norm
 
 // The attention stage of a layer: what tells the two layer entry points apart.  The decode layer is n = 1 rows per sequence with
 // DF_ATTN_DECODE (its per-sequence operands: pos, lens); the extend layer any n with DF_ATTN_EXTEND (lens0, n_new - which may be null).
-enum DfAttn { DF_ATTN_DECODE, DF_ATTN_EXTEND };
+enum DfAttn { DF_ATTN_DECODE, DF_ATTN_EXTEND, DF_ATTN_RAGGED };  // RAGGED: B = 1, n = R packed rows, paged only
 
 // Workspace of a layer at M = B*n rows: q bf16 [M, d] | attention output bf16 [M, d] | activation bf16 [M, hidden] | the attention stage's
 // partials, every part a multiple of 16 bytes.  A function of the shapes and the splits argument alone.
@@ -449,8 +505,9 @@ static size_t df_layer_workspace_bytes(DfAttn attn, int64_t B, int64_t n, int64_
     return 0;
   // 0 for a head_dim, Tmax or splits the attention stage refuses
   size_t att;
-  if (paged) att = attn == DF_ATTN_DECODE ? plm_attn_decode_paged_workspace_bytes(B, nh, hd, Tmax)
-                                          : plm_attn_extend_paged_workspace_bytes(B, n, nh, hd, Tmax, splits);
+  if (attn == DF_ATTN_RAGGED) att = plm_attn_ragged_paged_workspace_bytes(n, nh, hd, Tmax);
+  else if (paged) att = attn == DF_ATTN_DECODE ? plm_attn_decode_paged_workspace_bytes(B, nh, hd, Tmax)
+                                               : plm_attn_extend_paged_workspace_bytes(B, n, nh, hd, Tmax, splits);
   else att = attn == DF_ATTN_DECODE ? plm_attn_decode_workspace_bytes(B, nh, hd, Tmax, splits)
                                     : plm_attn_extend_workspace_bytes(B, n, nh, hd, Tmax, splits);
   if (att == 0) return 0;
@@ -473,7 +530,7 @@ static int df_layer(const char* fn, DfAttn attn, float* x, const float* attn_nor
                     const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* kv, int64_t ld_kv, int32_t* status, int64_t B, int64_t n,
                     int64_t Tmax, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, int splits, void* workspace, size_t workspace_bytes,
                     void* stream, bool kv8 = false, const DfPaged* pg = nullptr) {
-  PLM_REQUIRE(x && attn_norm_w && mlp_norm_w && w_qkv && w_out && w_fc1 && w_fc2 && p0 && (attn == DF_ATTN_EXTEND || p1) && rope_cos && rope_sin &&
+  PLM_REQUIRE(x && attn_norm_w && mlp_norm_w && w_qkv && w_out && w_fc1 && w_fc2 && p0 && (attn != DF_ATTN_DECODE || p1) && rope_cos && rope_sin &&
                   kv && status && workspace,
               "%s: null pointer", fn);
   PLM_REQUIRE(df_aligned(workspace), "%s: the workspace must be 16-byte aligned", fn);
@@ -484,6 +541,10 @@ static int df_layer(const char* fn, DfAttn attn, float* x, const float* attn_nor
   // a paged cache (kv: the pool): the qkv stage's rows per sequence are the table's, Tmax is the attention stage's Lcap
   if (pg != nullptr)
     if (const int e = df_check_paged(fn, *pg, true)) return e;
+  if (attn == DF_ATTN_RAGGED) {  // plm_attn_ragged_paged's own refusals
+    if (const int e = df_check_packed(fn, *pg, p0)) return e;
+    PLM_REQUIRE(pg->NT >= 1 && pg->NT <= pg->R, "%s: NT=%ld tiles outside [1, R = %ld] (a tile holds at least one row)", fn, (long)pg->NT, (long)pg->R);
+  }
   const int64_t Tq = pg != nullptr ? pg->max_pages * PLM_KV_PAGE_ROWS : Tmax;
   if (const int e = df_check_qkv(fn, x, attn_norm_w, w_qkv, p0, rope_cos, rope_sin, rope_T, q, kv, ld_kv, status, B, n, Tq, nh, hd, kv8)) return e;
   const int64_t M = B * n;
@@ -509,7 +570,10 @@ static int df_layer(const char* fn, DfAttn attn, float* x, const float* attn_nor
                 ld_kv, status, B, n, Tq, nh, hd, s, kv8, nullptr, nullptr, pg);
   const uint8_t* c8 = reinterpret_cast<const uint8_t*>(kv);
   int e;
-  if (pg != nullptr)
+  if (attn == DF_ATTN_RAGGED)
+    e = plm_attn_ragged_paged(q, kv, ld_kv, pg->table, p0, pg->cu_rows, pg->row_seq, attn_out, nullptr, pg->R, pg->B, pg->NT, Tmax, pg->max_pages,
+                              pg->n_pages, nh, hd, att, att_bytes, stream);
+  else if (pg != nullptr)
     e = attn == DF_ATTN_DECODE
             ? plm_attn_decode_paged(q, kv, ld_kv, pg->table, p1, attn_out, nullptr, B, Tmax, pg->max_pages, pg->n_pages, nh, hd, att, att_bytes, stream)
             : plm_attn_extend_paged(q, kv, ld_kv, pg->table, p0, p1, attn_out, nullptr, B, n, Tmax, pg->max_pages, pg->n_pages, nh, hd, splits, att,
@@ -811,4 +875,40 @@ extern "C" int plm_extend_layer_paged_bf16(float* x, const float* attn_norm_w, c
   return df_layer("plm_extend_layer_paged_bf16", DF_ATTN_EXTEND, x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, lens0, n_new, rope_cos,
                   rope_sin, rope_T, pool, ld_kv, status, B, n, Lcap, nh, hd, hidden, mlp_kind, splits, workspace, workspace_bytes, stream, false,
                   &pg);
+}
+
+// ---- the ragged step over a paged cache: R <= 32 packed rows of B sequences.  The qkv stage's epilogue is
+// DF_EPI_QKV_PACKED_PAGED, the attention stage plm_attn_ragged_paged; the out, fc1 and fc2 stages never look at positions ----
+extern "C" int plm_ragged_norm_qkv_append_paged_bf16(const float* x, const float* norm_w, float eps, const uint16_t* w_qkv, const int32_t* lens0,
+                                                     const int32_t* cu_rows, const int32_t* row_seq, const float* rope_cos, const float* rope_sin,
+                                                     int64_t rope_T, uint16_t* q_out, uint16_t* pool, int64_t ld_kv, const int32_t* table,
+                                                     int32_t* status, int64_t R, int64_t B, int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd,
+                                                     void* stream) {
+  const char* fn = "plm_ragged_norm_qkv_append_paged_bf16";
+  DfPaged pg = {table, nullptr, max_pages, n_pages, 0};
+  pg.cu_rows = cu_rows, pg.row_seq = row_seq, pg.R = R, pg.B = B;
+  if (const int e = df_check_paged(fn, pg, false)) return e;
+  if (const int e = df_check_packed(fn, pg, lens0)) return e;
+  const int64_t Tq = max_pages * PLM_KV_PAGE_ROWS;
+  if (const int e = df_check_qkv(fn, x, norm_w, w_qkv, lens0, rope_cos, rope_sin, rope_T, q_out, pool, ld_kv, status, 1, R, Tq, nh, hd)) return e;
+  df_launch_qkv(x, norm_w, eps, w_qkv, lens0, nullptr, rope_cos, rope_sin, rope_T, q_out, pool, ld_kv, status, 1, R, Tq, nh, hd, (hipStream_t)stream,
+                false, nullptr, nullptr, &pg);
+  PLM_CHECK_LAUNCH(fn);
+  return PLM_OK;
+}
+
+extern "C" size_t plm_ragged_layer_paged_workspace_bytes(int64_t R, int64_t nh, int64_t hd, int64_t hidden, int64_t Lcap) {
+  return df_layer_workspace_bytes(DF_ATTN_RAGGED, 1, R, nh, hd, hidden, Lcap, 0, true);
+}
+
+extern "C" int plm_ragged_layer_paged_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                                           const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* lens0,
+                                           const int32_t* cu_rows, const int32_t* row_seq, const float* rope_cos, const float* rope_sin,
+                                           int64_t rope_T, uint16_t* pool, int64_t ld_kv, const int32_t* table, int32_t* status, int64_t R, int64_t B,
+                                           int64_t NT, int64_t Lcap, int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd, int64_t hidden,
+                                           int mlp_kind, void* workspace, size_t workspace_bytes, void* stream) {
+  DfPaged pg = {table, nullptr, max_pages, n_pages, Lcap};
+  pg.cu_rows = cu_rows, pg.row_seq = row_seq, pg.R = R, pg.B = B, pg.NT = NT;
+  return df_layer("plm_ragged_layer_paged_bf16", DF_ATTN_RAGGED, x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, lens0, nullptr, rope_cos,
+                  rope_sin, rope_T, pool, ld_kv, status, 1, R, Lcap, nh, hd, hidden, mlp_kind, 0, workspace, workspace_bytes, stream, false, &pg);
 }

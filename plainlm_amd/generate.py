@@ -289,6 +289,22 @@ class PagedKVCache:
       self.reserve(bound)
     self._pl += n_new * self.live if isinstance(n_new, int) else n_new
 
+  def admit(self, b):
+    """The idle slot b becomes a live sequence of length 0 that holds no page yet: the start of a prompt fed through ragged steps
+    (DESIGN.md section 26)."""
+    if self._live[b] or self.pages[b]:
+      raise ValueError(f'PagedKVCache.admit: slot {b} holds a sequence (release it first)')
+    self._live[b] = True
+    self._pl[0, b] = -1  # pos = lens - 1, as set_lens keeps it
+    self.live[b] = 1
+
+  def ship(self, *words):
+    """Host int32 tensors -> their device copies, as ONE non-blocking copy from a pinned snapshot (the way ``table`` ships its rows)."""
+    src = torch.cat([w.reshape(-1) for w in words])
+    dev = torch.empty(src.shape, dtype=torch.int32, device=self._table.device)
+    dev.copy_(src.pin_memory() if dev.is_cuda else src, non_blocking=True)
+    return dev.split([w.numel() for w in words])
+
   def release(self, b):
     """Sequence b leaves: its pages go back to the pool, its table row to -1, its length to 0; the slot is idle."""
     self.pool.free(self.pages[b])
@@ -455,6 +471,39 @@ def check_fused_rows(who, B, n, dim):
   if B * n > ops.FUSED_EXTEND_MAX_ROWS:
     raise ValueError(f'{who}: fused=True serves at most {ops.FUSED_EXTEND_MAX_ROWS} chunk rows, got {B} sequences x {n} rows = {B * n}: leave fused off')
   check_fused_dim(who, dim)
+
+
+def check_ragged(tokens, counts, cache, fused, dim):
+  """The refusals of Transformer.step_ragged that need no GPU; returns (R, the counts as a list of cache.B ints)."""
+  who = 'step_ragged'
+  if not isinstance(tokens, torch.Tensor) or tokens.dtype != torch.int64 or tokens.dim() != 1 or tokens.numel() < 1:
+    raise TypeError(f'Transformer.{who}: tokens must be a non-empty int64 [R] tensor, packed in slot order')
+  counts = [int(c) for c in (counts.tolist() if isinstance(counts, torch.Tensor) else counts)]
+  R = tokens.numel()
+  if len(counts) != cache.B or any(c < 0 for c in counts):
+    raise ValueError(f'{who}: need {cache.B} counts (one per slot, none negative), got {counts}')
+  if sum(counts) != R:
+    raise ValueError(f'{who}: the counts {counts} sum to {sum(counts)}, the step has {R} rows')
+  for b, c in enumerate(counts):
+    if c and not cache._live[b]:
+      raise ValueError(f'{who}: slot {b} is idle and must have count 0, got {c}')
+    if cache.bound[b] + c > cache.Tmax:
+      raise ValueError(f'{who}: slot {b} holds {cache.bound[b]} tokens, {c} more do not fit max_len {cache.Tmax}')
+  if fused:
+    if R > ops.FUSED_EXTEND_MAX_ROWS:
+      raise ValueError(f'{who}: fused=True serves at most {ops.FUSED_EXTEND_MAX_ROWS} packed rows, got {R}: leave fused off')
+    check_fused_dim(who, dim)
+  return R, counts
+
+
+def check_prefill_chunk(who, prefill_chunk, max_batch, fused):
+  """serve's prefill_chunk as an int >= 1; with fused, a step's max_batch decode rows + prefill_chunk prompt rows must fit the skinny-M kernels."""
+  if isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int) or prefill_chunk < 1:
+    raise ValueError(f'{who}: prefill_chunk must be None or an int >= 1, got {prefill_chunk!r}')
+  if fused and int(max_batch) + prefill_chunk > ops.FUSED_EXTEND_MAX_ROWS:
+    raise ValueError(f'{who}: fused=True serves at most {ops.FUSED_EXTEND_MAX_ROWS} rows a step, got max_batch {max_batch} + prefill_chunk '
+                     f'{prefill_chunk}: leave fused off or feed smaller chunks')
+  return prefill_chunk
 
 
 def pad4(n):
@@ -1211,8 +1260,116 @@ class Generation:
       return cache, self.head(last_rows(y, B, Tp, cache.lens), logits, (B,))
 
   @torch.compiler.disable
+  def step_ragged(self, tokens, counts, cache, logits=False, all_rows=False, fused=False):
+    """One ragged step on a PagedKVCache: tokens int64 [R], packed in slot order, of which slot b contributes
+    counts[b] (host integers: 0 - the slot takes no part, and an idle slot must have 0; 1 - a decode row; or a chunk of a prompt).
+    Slot b's rows are appended at positions cache.lens[b] .. and attended over its pages in one pass per layer (ops.kv_paged_append_rope_packed
+    / ops.attn_ragged_paged as ``cached_layers``' attention stage); then lens += counts, on the device.  Pages are reserved on the host
+    by the counts, before anything is launched.  Returns the HeadPrediction [B] of the token after each participating slot's last row
+    (a slot with count 0 gets row 0's, which means nothing) - with logits=True the bf16 logits [B, V]; with all_rows=True the [R]
+    predictions or [R, V] logits of every packed row.  fused=True runs every layer as one ops.ragged_layer_paged call and serves
+    R <= ops.FUSED_EXTEND_MAX_ROWS rows, ValueError beyond.  A non-paged cache raises TypeError; an mxfp8 model, counts that do not sum
+    to R and a count that does not fit max_len raise ValueError.  Runs under no_grad."""
+    if not isinstance(cache, PagedKVCache):
+      raise TypeError(f'Transformer.step_ragged: the cache must be a PagedKVCache, got {type(cache).__name__} (ragged steps run on pages only)')
+    refuse_paged_model('step_ragged', self)
+    R, counts = check_ragged(tokens, counts, cache, fused, self.cfg.dim)
+    guard('step_ragged', tokens, self)
+    check_cache('step_ragged', cache, self)
+    nh = self.cfg.n_heads
+    with torch.no_grad():
+      rope = self._rope(tokens.device)
+      lens0 = cache.lens  # the lengths before the step: what every layer's append and attention see; moved once, after the last layer
+      cache.reserve(counts)
+      cu, row_seq, last_row, NT = ops.ragged_plan(counts)
+      cu, row_seq, last_row, adv = cache.ship(cu, row_seq, last_row, torch.tensor(counts, dtype=torch.int32))
+      table, Lcap = cache.table, cache.lcap()
+
+      def attend(i, qkv):
+        q, _ = ops.kv_paged_append_rope_packed(qkv, lens0, cu, row_seq, rope[0], rope[1], cache.kv[i], table, nh, status=cache.status)
+        return ops.attn_ragged_paged(q, cache.kv[i], table, lens0, cu, row_seq, nh, NT, Lcap=Lcap)
+      flat = tokens.contiguous()
+      y = self.fused_layers(flat, cache, rope, ('ragged', lens0, cu, row_seq, NT)) if fused else self.cached_layers(flat, cache, attend)
+      cache.advance_by(adv)
+      if all_rows:
+        return self.head(y, logits, (R,))
+      return self.head(y.index_select(0, last_row.clamp(min=0).long()), logits, (cache.B,))  # the head runs on at most B rows
+
+  def _serve_ragged(self, who, prompts, budget, total, pages, S, pool, eos_id, fused, C):
+    """serve(prefill_chunk=C): every step is one ``step_ragged`` - a row per decoding slot plus, in slot order, up to C prompt rows of
+    the admitted prompts.  A prompt whose last row is in the step gets its first token from it and decodes from the next."""
+    N, dev = len(prompts), prompts[0].device
+    with torch.no_grad():
+      slots = self.new_cache_paged(S, pool, max(total))
+      owner, fed, left, promised = [None] * S, [0] * S, [0] * S, [0] * S  # per slot: its prompt, the prompt rows fed, tokens and pages still due
+      steps, where = [], [[] for _ in range(N)]  # where[i]: (step, slot) of sequence i's tokens
+      cur = torch.zeros((S,), dtype=torch.int64, device=dev)
+      done = torch.zeros((S,), dtype=torch.bool, device=dev)
+      waiting = list(range(N))
+
+      def leave(b):
+        slots.release(b)
+        owner[b], promised[b] = None, 0
+
+      while waiting or any(o is not None for o in owner):
+        for b in range(S):  # admission: in prompt order, into the lowest free slot, while the pool can hold the sequence to its end
+          if owner[b] is None and waiting and pool.n_free - sum(promised) >= pages[waiting[0]]:
+            i = waiting.pop(0)
+            slots.admit(b)
+            owner[b], fed[b], left[b], promised[b] = i, 0, budget[i], pages[i]
+            done[b] = False
+        if all(o is None for o in owner):
+          raise RuntimeError(f'{who}: the pool cannot hold prompt {waiting[0]} ({pages[waiting[0]]} pages, {pool.n_free} free)')
+        counts, parts, room = [0] * S, [], C
+        for b in range(S):  # a row per decoding slot; prompt rows in slot order while the step's C last
+          if owner[b] is None:
+            continue
+          n = prompts[owner[b]].numel()
+          if fed[b] == n:
+            counts[b] = 1
+            parts.append(cur[b:b + 1])
+          elif room:
+            counts[b] = min(n - fed[b], room)
+            room -= counts[b]
+            parts.append(prompts[owner[b]][fed[b]:fed[b] + counts[b]])
+        held = [len(p) for p in slots.pages]
+        cur = self.step_ragged(torch.cat(parts), counts, slots, fused=fused).tokens
+        steps.append(cur)
+        emits = [0] * S
+        for b in range(S):
+          if owner[b] is None:
+            continue
+          promised[b] -= len(slots.pages[b]) - held[b]
+          n = prompts[owner[b]].numel()
+          was_decoding = fed[b] == n
+          fed[b] = min(n, fed[b] + counts[b]) if not was_decoding else n
+          if was_decoding or (counts[b] and fed[b] == n):  # the slot's last row was a decode row or its prompt's last row: a token
+            emits[b] = 1
+            where[owner[b]].append((len(steps) - 1, b))
+            left[b] -= 1
+            if left[b] == 0:
+              leave(b)
+        if eos_id is not None:
+          done = done | ((cur == eos_id) & slots.ship(torch.tensor(emits, dtype=torch.int32))[0].bool())
+          if len(steps) % FINISH_CHECK_EVERY == 0:  # the one device-to-host read
+            for b, d in enumerate(done.tolist()):
+              if d and owner[b] is not None and fed[b] == prompts[owner[b]].numel():
+                leave(b)
+      slots.check()
+      out, grid = [], torch.stack(steps)
+      for i in range(N):
+        st, sl = zip(*where[i])
+        t = grid[torch.tensor(st, device=dev), torch.tensor(sl, device=dev)]
+        if eos_id is not None:
+          hit = (t == eos_id).nonzero()
+          if hit.numel():
+            t = t[:int(hit[0]) + 1]
+        out.append(t)
+      return out
+
+  @torch.compiler.disable
   def serve(self, prompts, max_new_tokens, max_batch, pool=None, eos_id=None, fused=False, temperature=None, top_k=None, top_p=None,
-            sample=None, seed=None):
+            sample=None, seed=None, prefill_chunk=None):
     """Continuous batching: continue every prompt of ``prompts`` - a list of 1-D int64 token tensors of any
     lengths - by up to max_new_tokens tokens (an int, or one int per prompt), greedily, with at most max_batch sequences in flight.
     Returns a list of int64 tensors, the new tokens of every prompt, ended by eos_id when the sequence emitted it.  A waiting prompt is
@@ -1222,7 +1379,10 @@ class Generation:
     only when the pool can hold it to the end of its budget, so a step never runs out of pages; a pool too small for one sequence raises
     RuntimeError.  Greedy only: the on-device sampler's per-call uniforms do not map onto sequences that start at different steps, so
     sampling arguments raise ValueError.  fused=True runs the steps through ops.decode_layer_paged and serves max_batch <=
-    ops.FUSED_DECODE_MAX_ROWS, ValueError beyond."""
+    ops.FUSED_DECODE_MAX_ROWS, ValueError beyond.  prefill_chunk=C (an int >= 1) feeds the prompts in chunks inside
+    the decode steps in place of a prefill call per prompt: every step is one ``step_ragged`` of a row per decoding slot plus, in slot
+    order, up to C prompt rows in total; a prompt whose last row is in the step gets its first token from it.  Admission, release, eos_id
+    and the one read stay as they are; with fused=True it needs max_batch + C <= ops.FUSED_EXTEND_MAX_ROWS, ValueError otherwise."""
     who = 'serve'
     refuse_paged_model(who, self)
     if any(a is not None for a in (temperature, top_k, top_p, sample, seed)):
@@ -1230,6 +1390,8 @@ class Generation:
                        'join at different steps: drop temperature / top_k / top_p / sample / seed')
     if fused:
       check_fused(who, int(max_batch), self.cfg.dim)
+    if prefill_chunk is not None:
+      prefill_chunk = check_prefill_chunk(who, prefill_chunk, max_batch, fused)
     prompts = list(prompts)
     if not prompts or int(max_batch) < 1:
       raise ValueError(f'{who}: need at least one prompt and max_batch >= 1')
@@ -1247,6 +1409,8 @@ class Generation:
       pool = self.new_page_pool(min(S, N) * max(pages))
     if max(pages) > pool.n_free:
       raise RuntimeError(f'{who}: the pool has {pool.n_free} free pages, one sequence needs {max(pages)}')
+    if prefill_chunk is not None:  # prompts enter in chunks inside the decode steps
+      return self._serve_ragged(who, prompts, budget, total, pages, S, pool, eos_id, fused, prefill_chunk)
     dev = prompts[0].device
     with torch.no_grad():
       slots = self.new_cache_paged(S, pool, max(total))

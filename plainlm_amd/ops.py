@@ -1161,6 +1161,9 @@ from .ops_beam import (BEAM_MAX, BeamBuffers, attn_decode_beam, beam_advance, be
 # ---- the paged KV cache: pages behind a block table; its wrappers live in ops_paged.py ---------------------------------
 from .ops_paged import (KV_PAGE_ROWS, KV_PAGED_CHUNK, attn_decode_paged, attn_decode_paged_workspace_bytes, attn_extend_paged,  # noqa: E402,F401
                         decode_layer_paged, extend_layer_paged, extend_norm_qkv_append_paged, kv_paged_append_rope_rows, kv_paged_store_rows)
+# ---- ragged steps over the paged cache: packed mixed-width rows; its wrappers live in ops_ragged.py --------------------
+from .ops_ragged import (RAGGED_TILE_ROWS, attn_ragged_paged, kv_paged_append_rope_packed, ragged_layer_paged,  # noqa: E402,F401
+                         ragged_norm_qkv_append_paged, ragged_plan)
 # ---- the Muon tail: batched NT GEMM, prepare / orthogonalize / apply; its wrappers live in ops_muon.py -------------------
 from .ops_muon import (MUON_ADJUST_LR, MUON_EPS, MUON_NS_COEFFICIENTS, NT_BATCH_GROUP, gemm_nt_batched, muon_adjusted_lr, muon_apply,  # noqa: E402,F401
                        muon_arena, muon_blocks, muon_items, muon_layout, muon_ns_flops, muon_orthogonalize, muon_prepare, muon_set_lr,

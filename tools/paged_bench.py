@@ -6,7 +6,12 @@ process (tools/gen_bench.py's ``alternate``): device ms by HIP events, median of
 attention alone (ops.attn_decode / ops.attn_decode_paged), the pool bytes in use against B * Tmax bytes, and ``serve`` against
 ``generate`` / ``generate_fused`` run in static waves of max_batch prompts on --prompts prompts with mixed lengths and budgets (wall ms,
 one run each after a warm-up run).  --lib: another build of the library (the chunk size is a compile-time constant of it).
-Usage: python tools/paged_bench.py [--runs 20] [--lib path/to/libplainlm_hip.so] --out profiles/paged_bench.txt"""
+--ragged measures the ragged step instead: (a) one layer's attention for 15 decode rows + one 128-row prompt chunk at
+context 1024, ops.attn_ragged_paged on the 143 packed rows against ops.attn_extend_paged on the padded [16, 128] form; (b) an all-decode
+batch at (32, 4096) against ops.attn_decode_paged; (c) ``serve`` on the prompt mix with and without prefill_chunk, fused and unfused,
+against the static waves, --serve-runs wall-clock runs each, the sides alternating.
+Usage: python tools/paged_bench.py [--runs 20] [--lib path/to/libplainlm_hip.so] --out profiles/paged_bench.txt
+       python tools/paged_bench.py --ragged --out profiles/ragged_bench.txt"""
 import argparse
 import os
 import statistics
@@ -28,6 +33,9 @@ def main():
   ap.add_argument('--lib', default=None)
   ap.add_argument('--no-serve', action='store_true')
   ap.add_argument('--out', default=None)
+  ap.add_argument('--ragged', action='store_true')
+  ap.add_argument('--serve-runs', type=int, default=5)
+  ap.add_argument('--prefill-chunk', type=int, default=128, help='--ragged: prompt rows per unfused step (a fused step takes 32 - max_batch)')
   a = ap.parse_args()
   from plainlm_amd import _lib
   if a.lib:
@@ -50,6 +58,83 @@ def main():
       if i >= a.warmup:
         v.append(e)
     return v
+
+  def sides_alternating(sides, measure, runs, warmup):
+    v = {k: [] for k in sides}
+    for i in range(warmup + runs):
+      for k, fn in sides.items():
+        torch.cuda.synchronize()
+        e = measure(fn)
+        if i >= warmup:
+          v[k].append(e)
+    return v
+
+  def wall_ms(fn):
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+  if a.ragged:
+    lines[0] = ('# tools/paged_bench.py --ragged: 160M (12 layers, d 768, 12 heads, V 50280); one process, sides alternating; attention: ms, HIP '
+                'events, median of %d [min max]; serve: wall ms, median of %d [min max]' % (a.runs, a.serve_runs))
+    with torch.no_grad():
+      i32 = lambda v: torch.tensor(v, dtype=torch.int32, device='cuda')  # noqa: E731
+      for tag, lens0, counts in (('(a) 15 decode rows + one 128-row chunk, context 1024', [1024] * 16, [1] * 15 + [128]),
+                                 ('(b) 32 decode rows, context 4096', [4095] * 32, [1] * 32)):
+        B, n = len(counts), max(counts)
+        pool = m.new_page_pool(sum(-(-(l + c) // 64) for l, c in zip(lens0, counts)))
+        cache = m.new_cache_paged(B, pool, max(l + c for l, c in zip(lens0, counts)))
+        cache.set_lens([l + c for l, c in zip(lens0, counts)])  # the step's rows are appended already
+        pool.kv[0].copy_(torch.randn(pool.kv[0].shape, device='cuda') * 0.5)
+        table, l0, Lcap = cache.table, i32(lens0), cache.lcap()
+        cu, row_seq, _, NT = ops.ragged_plan(counts)
+        cu, row_seq = cu.cuda(), row_seq.cuda()
+        q = torch.randn(sum(counts), cfg.dim, device='cuda').to(torch.bfloat16)
+        sides = {'ragged': lambda: ops.attn_ragged_paged(q, pool.kv[0], table, l0, cu, row_seq, nh, NT, Lcap=Lcap)}
+        if n > 1:
+          qp, nn = torch.zeros(B * n, cfg.dim, device='cuda', dtype=torch.bfloat16), i32(counts)
+          for b in range(B):
+            qp[b * n:b * n + counts[b]] = q[cu[b]:cu[b + 1]]
+          sides['extend_paged, padded [%d, %d]' % (B, n)] = lambda: ops.attn_extend_paged(qp, pool.kv[0], table, l0, nh, n_new=nn, Lcap=Lcap)
+        else:
+          lens = i32([l + 1 for l in lens0])
+          sides['decode_paged'] = lambda: ops.attn_decode_paged(q, pool.kv[0], table, lens, nh, Lcap=Lcap)
+        v = sides_alternating(sides, timed, a.runs, a.warmup)
+        (k0, r), (k1, o) = v.items()
+        where = 'overlaps' if min(r) <= max(o) and min(o) <= max(r) else ('lies above' if min(r) > max(o) else 'lies below')
+        lines.append('%s, one layer\'s attention: attn_ragged_paged (%d rows, %d tiles) %s   attn_%s %s' % (tag, sum(counts), NT, med(r), k1, med(o)))
+        lines.append('    ragged / other (medians) %.2f; ragged\'s [min max] %s the other\'s' % (statistics.median(r) / statistics.median(o), where))
+        del cache, pool, sides
+      if not a.no_serve:
+        g = torch.Generator().manual_seed(1)
+        N, S = a.prompts, a.max_batch
+        plen = torch.randint(32, 257, (N,), generator=g).tolist()
+        budget = torch.randint(16, 129, (N,), generator=g).tolist()
+        prompts = [torch.randint(0, cfg.vocab_size, (n,), generator=g).cuda() for n in plen]
+
+        def waves(gen):
+          for w in range(0, N, S):
+            idx = list(range(w, min(w + S, N)))
+            x = torch.zeros((len(idx), max(plen[i] for i in idx)), dtype=torch.int64, device='cuda')
+            for r, i in enumerate(idx):
+              x[r, :plen[i]] = prompts[i]
+            gen(x, max(budget[i] for i in idx), prompt_lens=[plen[i] for i in idx])
+        C, Cf = a.prefill_chunk, 32 - S
+        sides = {'serve': lambda: m.serve(prompts, budget, S), 'serve(prefill_chunk=%d)' % C: lambda: m.serve(prompts, budget, S, prefill_chunk=C),
+                 'generate in static waves': lambda: waves(m.generate), 'serve(fused=True)': lambda: m.serve(prompts, budget, S, fused=True),
+                 'serve(fused=True, prefill_chunk=%d)' % Cf: lambda: m.serve(prompts, budget, S, fused=True, prefill_chunk=Cf),
+                 'generate_fused in static waves': lambda: waves(m.generate_fused)}
+        v = sides_alternating(sides, wall_ms, a.serve_runs, 1)
+        lines.append('(c) %d prompts (32 .. 256 tokens), budgets 16 .. 128 (%d tokens asked for), max_batch %d, wall ms, %d runs each after a warm-up run:'
+                     % (N, sum(budget), S, a.serve_runs))
+        lines += ['  %-40s %s' % (k, med(t)) for k, t in v.items()]
+    text = '\n'.join(lines) + '\n'
+    print(text, end='')
+    if a.out:
+      with open(a.out, 'a') as f:
+        f.write(text)
+    return
 
   with torch.no_grad():
     ragged = [64 + round(i * (4096 - 64) / 31) for i in range(32)]
