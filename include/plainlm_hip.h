@@ -771,6 +771,38 @@ int plm_ragged_layer_paged_bf16(float* x, const float* attn_norm_w, const float*
                                 int64_t Lcap, int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind,
                                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the wide fused layer: the ragged paged layer over 1 <= R <= 256 packed rows -----
+ * Every argument check of these entry points comes before any HIP call.  The stages compute what their skinny-M namesakes compute,
+ * with the same rounding points, on a kernel family of its own: a grid of (N / 16 column tiles) x (row tiles of 16, 32 or 64 rows),
+ * K walked in 256-column chunks split over four waves.  The partition of K is a function of K alone, so a row's output depends on
+ * that row and the weights only - not on M, the row tile, the other rows or the packing - and two runs are bit-equal (no atomics).
+ * The fp32 sums are ordered differently from the skinny-M kernels': close to their results, not their bits.
+ * plm_wide_gemm_residual_bf16: plm_decode_gemm_residual_bf16's contract at 1 <= M <= 256.
+ * plm_wide_norm_fc1_act_bf16: plm_decode_norm_fc1_act_bf16's contract at 1 <= M <= 256.
+ * plm_ragged_norm_qkv_append_paged_wide_bf16: plm_ragged_norm_qkv_append_paged_bf16's contract at 1 <= R <= 256: the packed-row map,
+ * RoPE at lens0[b] + j, q to q_out, k | v through the table, per-sequence refusal (status[0] = 1, zero q rows, nothing stored) over
+ * every page the chunk touches, padding rows store nothing.  One launch each.
+ * plm_ragged_layer_paged_wide_bf16: that stage, plm_attn_ragged_paged, then the wide out, fc1 and fc2 stages: six launches, bit-equal
+ * to its stages called one after the other.  Every refusal of every stage comes before the first launch; workspace: the
+ * _workspace_bytes query, a function of the shapes alone (0 for a refused shape).
+ * PLM_E_INVALID: rows outside [1, 256], K % 32, N % 16, hidden % 32, a head_dim other than 32 / 64 / 128, NULL or misaligned pointers,
+ * and what plm_attn_ragged_paged refuses; a short workspace gives PLM_E_WORKSPACE. */
+int plm_wide_gemm_residual_bf16(float* x, const uint16_t* A, const uint16_t* W, int64_t M, int64_t N, int64_t K, void* stream);
+int plm_wide_norm_fc1_act_bf16(const float* x, const float* norm_w, float eps, const uint16_t* w_fc1, uint16_t* act, int64_t M, int64_t d,
+                               int64_t hidden, int mlp_kind, void* stream);
+int plm_ragged_norm_qkv_append_paged_wide_bf16(const float* x, const float* norm_w, float eps, const uint16_t* w_qkv, const int32_t* lens0,
+                                               const int32_t* cu_rows, const int32_t* row_seq, const float* rope_cos, const float* rope_sin,
+                                               int64_t rope_T, uint16_t* q_out, uint16_t* pool, int64_t ld_kv, const int32_t* table,
+                                               int32_t* status, int64_t R, int64_t B, int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd,
+                                               void* stream);
+size_t plm_ragged_layer_paged_wide_workspace_bytes(int64_t R, int64_t nh, int64_t hd, int64_t hidden, int64_t Lcap);
+int plm_ragged_layer_paged_wide_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                                     const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* lens0,
+                                     const int32_t* cu_rows, const int32_t* row_seq, const float* rope_cos, const float* rope_sin,
+                                     int64_t rope_T, uint16_t* pool, int64_t ld_kv, const int32_t* table, int32_t* status, int64_t R, int64_t B,
+                                     int64_t NT, int64_t Lcap, int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd, int64_t hidden,
+                                     int mlp_kind, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- temperature / top-k / top-p sampling of one token per row -----
  * Every argument check comes before any HIP call.
  * logits bf16 [B, ld] (ld >= V; any 2-byte aligned base and any ld: columns >= V are never loaded); u fp32 [B], one uniform per row,

@@ -195,6 +195,13 @@ SIGNATURES = {
   'plm_ragged_layer_paged_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64]),
   'plm_ragged_layer_paged_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64,
                                        _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
+  'plm_wide_gemm_residual_bf16': (_I, [_P, _P, _P, _I64, _I64, _I64, _P]),
+  'plm_wide_norm_fc1_act_bf16': (_I, [_P, _P, _F, _P, _P, _I64, _I64, _I64, _I, _P]),
+  'plm_ragged_norm_qkv_append_paged_wide_bf16': (_I, [_P, _P, _F, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64,
+                                                      _I64, _P]),
+  'plm_ragged_layer_paged_wide_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64]),
+  'plm_ragged_layer_paged_wide_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64,
+                                            _I64, _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
   'plm_sample_logits_bf16': (_I, [_P, _I64, _P, _F, _I64, _F, _P, _P, _P, _P, _I64, _I64, _P]),
   'plm_spec_verify_bf16': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I64, _I64, _I64, _P]),
   'plm_lookup_draft_i64': (_I, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P]),

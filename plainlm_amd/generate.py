@@ -489,18 +489,39 @@ def check_ragged(tokens, counts, cache, fused, dim):
       raise ValueError(f'{who}: slot {b} is idle and must have count 0, got {c}')
     if cache.bound[b] + c > cache.Tmax:
       raise ValueError(f'{who}: slot {b} holds {cache.bound[b]} tokens, {c} more do not fit max_len {cache.Tmax}')
-  if fused:
+  check_fused_kind(who, fused)
+  if fused == 'wide':
+    if R > ops.FUSED_WIDE_MAX_ROWS:
+      raise ValueError(f'{who}: fused=\'wide\' serves at most {ops.FUSED_WIDE_MAX_ROWS} packed rows, got {R}: leave fused off')
+    check_wide_dim(who, dim)
+  elif fused:
     if R > ops.FUSED_EXTEND_MAX_ROWS:
       raise ValueError(f'{who}: fused=True serves at most {ops.FUSED_EXTEND_MAX_ROWS} packed rows, got {R}: leave fused off')
     check_fused_dim(who, dim)
   return R, counts
 
 
+def check_fused_kind(who, fused):
+  """fused of step_ragged and serve: False, True (the skinny-M kernels) or 'wide' (the wide kernels, section 27)."""
+  if not isinstance(fused, bool) and fused != 'wide':
+    raise ValueError(f'{who}: fused must be False, True or \'wide\', got {fused!r}')
+
+
+def check_wide_dim(who, dim):
+  if dim % 32 != 0:
+    raise ValueError(f'{who}: fused=\'wide\' needs cfg.dim % 32 == 0, got {dim}: leave fused off')
+
+
 def check_prefill_chunk(who, prefill_chunk, max_batch, fused):
-  """serve's prefill_chunk as an int >= 1; with fused, a step's max_batch decode rows + prefill_chunk prompt rows must fit the skinny-M kernels."""
+  """serve's prefill_chunk as an int >= 1; with fused, a step's max_batch decode rows + prefill_chunk prompt rows must fit the skinny-M
+  kernels (True) or the wide ones ('wide')."""
   if isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int) or prefill_chunk < 1:
     raise ValueError(f'{who}: prefill_chunk must be None or an int >= 1, got {prefill_chunk!r}')
-  if fused and int(max_batch) + prefill_chunk > ops.FUSED_EXTEND_MAX_ROWS:
+  if fused == 'wide':
+    if int(max_batch) + prefill_chunk > ops.FUSED_WIDE_MAX_ROWS:
+      raise ValueError(f'{who}: fused=\'wide\' serves at most {ops.FUSED_WIDE_MAX_ROWS} rows a step, got max_batch {max_batch} + prefill_chunk '
+                       f'{prefill_chunk}: feed smaller chunks')
+  elif fused and int(max_batch) + prefill_chunk > ops.FUSED_EXTEND_MAX_ROWS:
     raise ValueError(f'{who}: fused=True serves at most {ops.FUSED_EXTEND_MAX_ROWS} rows a step, got max_batch {max_batch} + prefill_chunk '
                      f'{prefill_chunk}: leave fused off or feed smaller chunks')
   return prefill_chunk
@@ -1268,7 +1289,8 @@ class Generation:
     by the counts, before anything is launched.  Returns the HeadPrediction [B] of the token after each participating slot's last row
     (a slot with count 0 gets row 0's, which means nothing) - with logits=True the bf16 logits [B, V]; with all_rows=True the [R]
     predictions or [R, V] logits of every packed row.  fused=True runs every layer as one ops.ragged_layer_paged call and serves
-    R <= ops.FUSED_EXTEND_MAX_ROWS rows, ValueError beyond.  A non-paged cache raises TypeError; an mxfp8 model, counts that do not sum
+    R <= ops.FUSED_EXTEND_MAX_ROWS rows, ValueError beyond; fused='wide'  one ops.ragged_layer_paged_wide call
+    and R <= ops.FUSED_WIDE_MAX_ROWS rows, at every R, so that a row's bits do not depend on the step's width.  A non-paged cache raises TypeError; an mxfp8 model, counts that do not sum
     to R and a count that does not fit max_len raise ValueError.  Runs under no_grad."""
     if not isinstance(cache, PagedKVCache):
       raise TypeError(f'Transformer.step_ragged: the cache must be a PagedKVCache, got {type(cache).__name__} (ragged steps run on pages only)')
@@ -1289,7 +1311,9 @@ class Generation:
         q, _ = ops.kv_paged_append_rope_packed(qkv, lens0, cu, row_seq, rope[0], rope[1], cache.kv[i], table, nh, status=cache.status)
         return ops.attn_ragged_paged(q, cache.kv[i], table, lens0, cu, row_seq, nh, NT, Lcap=Lcap)
       flat = tokens.contiguous()
-      y = self.fused_layers(flat, cache, rope, ('ragged', lens0, cu, row_seq, NT)) if fused else self.cached_layers(flat, cache, attend)
+      # fused='wide': every step runs the wide kernels, the narrow ones included, so a sequence's bits never depend on what shared its step
+      kind = 'wide' if fused == 'wide' else 'ragged'
+      y = self.fused_layers(flat, cache, rope, (kind, lens0, cu, row_seq, NT)) if fused else self.cached_layers(flat, cache, attend)
       cache.advance_by(adv)
       if all_rows:
         return self.head(y, logits, (R,))
@@ -1382,13 +1406,20 @@ class Generation:
     ops.FUSED_DECODE_MAX_ROWS, ValueError beyond.  prefill_chunk=C (an int >= 1) feeds the prompts in chunks inside
     the decode steps in place of a prefill call per prompt: every step is one ``step_ragged`` of a row per decoding slot plus, in slot
     order, up to C prompt rows in total; a prompt whose last row is in the step gets its first token from it.  Admission, release, eos_id
-    and the one read stay as they are; with fused=True it needs max_batch + C <= ops.FUSED_EXTEND_MAX_ROWS, ValueError otherwise."""
+    and the one read stay as they are; with fused=True it needs max_batch + C <= ops.FUSED_EXTEND_MAX_ROWS, ValueError otherwise.
+    fused='wide'  runs every one of those steps through ops.ragged_layer_paged_wide and needs prefill_chunk and
+    max_batch + C <= ops.FUSED_WIDE_MAX_ROWS; any other value of fused raises ValueError."""
     who = 'serve'
     refuse_paged_model(who, self)
     if any(a is not None for a in (temperature, top_k, top_p, sample, seed)):
       raise ValueError(f'{who}: greedy only - the sampler\'s uniforms are drawn per call for a fixed batch and do not map onto sequences that '
                        'join at different steps: drop temperature / top_k / top_p / sample / seed')
-    if fused:
+    check_fused_kind(who, fused)
+    if fused == 'wide':
+      if prefill_chunk is None:
+        raise ValueError(f'{who}: fused=\'wide\' needs prefill_chunk (there is no wide decode-only path: fused=True serves those steps)')
+      check_wide_dim(who, self.cfg.dim)
+    elif fused:
       check_fused(who, int(max_batch), self.cfg.dim)
     if prefill_chunk is not None:
       prefill_chunk = check_prefill_chunk(who, prefill_chunk, max_batch, fused)

@@ -1164,6 +1164,9 @@ from .ops_paged import (KV_PAGE_ROWS, KV_PAGED_CHUNK, attn_decode_paged, attn_de
 # ---- ragged steps over the paged cache: packed mixed-width rows; its wrappers live in ops_ragged.py --------------------
 from .ops_ragged import (RAGGED_TILE_ROWS, attn_ragged_paged, kv_paged_append_rope_packed, ragged_layer_paged,  # noqa: E402,F401
                          ragged_norm_qkv_append_paged, ragged_plan)
+# ---- the wide fused layer: ragged steps of up to 256 packed rows; its wrappers live in ops_wide.py ----------------------
+from .ops_wide import (FUSED_WIDE_MAX_ROWS, ragged_layer_paged_wide, ragged_norm_qkv_append_paged_wide, wide_gemm_residual,  # noqa: E402,F401
+                       wide_norm_fc1_act)
 # ---- the Muon tail: batched NT GEMM, prepare / orthogonalize / apply; its wrappers live in ops_muon.py -------------------
 from .ops_muon import (MUON_ADJUST_LR, MUON_EPS, MUON_NS_COEFFICIENTS, NT_BATCH_GROUP, gemm_nt_batched, muon_adjusted_lr, muon_apply,  # noqa: E402,F401
                        muon_arena, muon_blocks, muon_items, muon_layout, muon_ns_flops, muon_orthogonalize, muon_prepare, muon_set_lr,

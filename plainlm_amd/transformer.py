@@ -582,7 +582,8 @@ class Transformer(nn.Module, G.Generation):
     B <= ops.FUSED_DECODE_MAX_ROWS, one per sequence at cache.pos (ops.decode_layer).  chunk (lens0, n_new, n): n tokens per sequence,
     tokens int64 [B * n] with B * n <= ops.FUSED_EXTEND_MAX_ROWS (ops.extend_layer: row b * n + r is appended at lens0[b] + r, n_new
     int32 [B] or None as ops.kv_append_rope_rows takes it).  chunk ('ragged', lens0, cu_rows, row_seq, NT) on a PagedKVCache: the packed
-    rows of a ragged step, tokens int64 [R], ops.ragged_layer_paged.  Returns the final normed rows [B, B * n or R, dim]."""
+    rows of a ragged step, tokens int64 [R], ops.ragged_layer_paged; ('wide', ...) the same through
+    ops.ragged_layer_paged_wide (section 27).  Returns the final normed rows [B, B * n or R, dim]."""
     fp8 = cache.kv_dtype == 'fp8'  # DESIGN.md section 20: the same calls over the FP8 cache
     if isinstance(cache, G.SharedPrefixCache):  # a SharedPrefixCache (DESIGN.md section 21): decode steps only, ops.decode_layer_shared per layer
       if chunk is not None:
@@ -600,15 +601,16 @@ class Transformer(nn.Module, G.Generation):
       return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps)[1]
     if isinstance(cache, G.PagedKVCache) and chunk is not None and isinstance(chunk[0], str):
       # ('ragged', lens0, cu_rows, row_seq, NT): the packed rows of a ragged step, ops.ragged_layer_paged per layer
-      if chunk[0] != 'ragged' or len(chunk) != 5 or tokens.shape[0] != chunk[3].shape[0]:
+      if chunk[0] not in ('ragged', 'wide') or len(chunk) != 5 or tokens.shape[0] != chunk[3].shape[0]:
         raise ValueError(f'fused_layers: {tokens.shape[0]} tokens are not the packed rows of a ragged step')
       self.refresh_shadows()
       x = ops.embed_fwd(tokens, self.embed_tokens.weight)
       table, Lcap = cache.table, cache.lcap()
+      ragged_layer = ops.ragged_layer_paged_wide if chunk[0] == 'wide' else ops.ragged_layer_paged  # 'wide': DESIGN.md section 27, R <= 256
       for i, layer in enumerate(self.layers):
-        ops.ragged_layer_paged(x, layer.attn_norm.weight, layer.mlp_norm.weight, layer.attn_norm.eps, layer.attn.w_qkv.shadow()[0],
-                               layer.attn.w_out.shadow()[0], layer.mlp.fc1.shadow()[0], layer.mlp.fc2.shadow()[0], chunk[1], chunk[2], chunk[3],
-                               rope[0], rope[1], cache.kv[i], table, self.cfg.n_heads, layer.mlp.kind, cache.status, chunk[4], Lcap=Lcap)
+        ragged_layer(x, layer.attn_norm.weight, layer.mlp_norm.weight, layer.attn_norm.eps, layer.attn.w_qkv.shadow()[0],
+                     layer.attn.w_out.shadow()[0], layer.mlp.fc1.shadow()[0], layer.mlp.fc2.shadow()[0], chunk[1], chunk[2], chunk[3],
+                     rope[0], rope[1], cache.kv[i], table, self.cfg.n_heads, layer.mlp.kind, cache.status, chunk[4], Lcap=Lcap)
       return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps)[1]
     if isinstance(cache, G.PagedKVCache):  # the pool and the table in the cache's place, ops.*_layer_paged per layer
       if chunk is not None and (len(chunk) != 3 or tokens.shape[0] != cache.B * chunk[2]):

@@ -11,7 +11,12 @@ context 1024, ops.attn_ragged_paged on the 143 packed rows against ops.attn_exte
 batch at (32, 4096) against ops.attn_decode_paged; (c) ``serve`` on the prompt mix with and without prefill_chunk, fused and unfused,
 against the static waves, --serve-runs wall-clock runs each, the sides alternating.
 Usage: python tools/paged_bench.py [--runs 20] [--lib path/to/libplainlm_hip.so] --out profiles/paged_bench.txt
-       python tools/paged_bench.py --ragged --out profiles/ragged_bench.txt"""
+       python tools/paged_bench.py --ragged --out profiles/ragged_bench.txt
+--ragged --wide measures the wide fused layer instead: (a) one ops.ragged_layer_paged_wide call against the unfused
+ops chain on the same packed rows (15 decode rows + a 128-row chunk, and 256 rows, context 1024), device ms and host enqueue ms; (b) ``serve``
+with fused='wide' at prefill_chunk 64 and 128 against serve(fused=True), serve(prefill_chunk=128) and the fused static waves; (c) a
+decode-only step_ragged of 16 rows, fused='wide' against fused=True.
+       python tools/paged_bench.py --ragged --wide --out profiles/wide_bench.txt"""
 import argparse
 import os
 import statistics
@@ -35,6 +40,7 @@ def main():
   ap.add_argument('--out', default=None)
   ap.add_argument('--ragged', action='store_true')
   ap.add_argument('--serve-runs', type=int, default=5)
+  ap.add_argument('--wide', action='store_true', help='--ragged: the wide fused layer (DESIGN.md section 27) in place of the attention sides')
   ap.add_argument('--prefill-chunk', type=int, default=128, help='--ragged: prompt rows per unfused step (a fused step takes 32 - max_batch)')
   a = ap.parse_args()
   from plainlm_amd import _lib
@@ -74,6 +80,90 @@ def main():
     fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) * 1e3
+
+  if a.ragged and a.wide:
+    lines[0] = ('# tools/paged_bench.py --ragged --wide: 160M (12 layers, d 768, 12 heads, V 50280); one process, sides alternating; layer and step: '
+                'ms, median of %d [min max]; serve: wall ms, median of %d [min max]' % (a.runs, a.serve_runs))
+
+    def host_ms(fn):  # the enqueue alone: the device is idle before and drained after
+      t0 = time.perf_counter()
+      fn()
+      e = (time.perf_counter() - t0) * 1e3
+      torch.cuda.synchronize()
+      return e
+    with torch.no_grad():
+      i32 = lambda v: torch.tensor(v, dtype=torch.int32, device='cuda')  # noqa: E731
+      m.refresh_shadows()
+      L0, eps, rope = m.layers[0], m.layers[0].attn_norm.eps, m._rope(torch.device('cuda'))
+      an, mn = L0.attn_norm.weight, L0.mlp_norm.weight
+      wq, wo, w1, w2 = L0.attn.w_qkv.shadow()[0], L0.attn.w_out.shadow()[0], L0.mlp.fc1.shadow()[0], L0.mlp.fc2.shadow()[0]
+      for tag, lens0, counts in (('(a1) 15 decode rows + one 128-row chunk, context 1024', [1024] * 16, [1] * 15 + [128]),
+                                 ('(a2) 256 rows: two 128-row chunks, context 1024', [1024] * 2, [128] * 2)):
+        pool = m.new_page_pool(sum(-(-(l + c) // 64) for l, c in zip(lens0, counts)))
+        cache = m.new_cache_paged(len(counts), pool, max(l + c for l, c in zip(lens0, counts)))
+        cache.set_lens([l + c for l, c in zip(lens0, counts)])  # the pages of the step's rows are held
+        pool.kv[0].copy_(torch.randn(pool.kv[0].shape, device='cuda') * 0.5)
+        table, l0, Lcap = cache.table, i32(lens0), cache.lcap()
+        cu, row_seq, _, NT = ops.ragged_plan(counts)
+        cu, row_seq = cu.cuda(), row_seq.cuda()
+        x0 = torch.randn(sum(counts), cfg.dim, device='cuda')
+
+        def wide():
+          ops.ragged_layer_paged_wide(x0.clone(), an, mn, eps, wq, wo, w1, w2, l0, cu, row_seq, rope[0], rope[1], pool.kv[0], table, nh, 'glu',
+                                      cache.status, NT, Lcap=Lcap)
+
+        def chain():
+          x = x0.clone()
+          q, _ = ops.kv_paged_append_rope_packed(ops.gemm_nt(ops.rmsnorm_fwd(x, an, eps)[1], wq), l0, cu, row_seq, rope[0], rope[1], pool.kv[0], table,
+                                                 nh, status=cache.status)
+          x = x + ops.gemm_nt(ops.attn_ragged_paged(q, pool.kv[0], table, l0, cu, row_seq, nh, NT, Lcap=Lcap), wo).float()
+          x + ops.gemm_nt(ops.swiglu_fwd(ops.gemm_nt(ops.rmsnorm_fwd(x, mn, eps)[1], w1)), w2).float()
+        sides = {'ragged_layer_paged_wide': wide, 'unfused ops chain': chain}
+        dev, host = sides_alternating(sides, timed, a.runs, a.warmup), sides_alternating(sides, host_ms, a.runs, a.warmup)
+        lines.append('%s, one layer (%d rows):' % (tag, sum(counts)))
+        lines += ['  %-26s device %s   host enqueue %s' % (k, med(dev[k]), med(host[k])) for k in sides]
+        del cache, pool, sides
+      S = a.max_batch
+      tok = torch.randint(0, cfg.vocab_size, (S,), device='cuda')
+      pool = m.new_page_pool(S * 17)
+      cache = m.new_cache_paged(S, pool, 1024 + 64)
+
+      def step(fused):
+        cache.set_lens([1024] * S)
+        m.step_ragged(tok, [1] * S, cache, fused=fused)
+      v = sides_alternating({"step_ragged(fused='wide')": lambda: step('wide'), 'step_ragged(fused=True)': lambda: step(True)}, timed, a.runs, a.warmup)
+      lines.append('(c) a decode-only step of %d rows at context 1024 (set_lens included on both sides), the price of the bits rule:' % S)
+      lines += ['  %-26s %s' % (k, med(t)) for k, t in v.items()]
+      del cache, pool
+      if not a.no_serve:
+        g = torch.Generator().manual_seed(1)
+        N = a.prompts
+        plen = torch.randint(32, 257, (N,), generator=g).tolist()
+        budget = torch.randint(16, 129, (N,), generator=g).tolist()
+        prompts = [torch.randint(0, cfg.vocab_size, (n,), generator=g).cuda() for n in plen]
+
+        def waves(gen):
+          for w in range(0, N, S):
+            idx = list(range(w, min(w + S, N)))
+            x = torch.zeros((len(idx), max(plen[i] for i in idx)), dtype=torch.int64, device='cuda')
+            for r, i in enumerate(idx):
+              x[r, :plen[i]] = prompts[i]
+            gen(x, max(budget[i] for i in idx), prompt_lens=[plen[i] for i in idx])
+        sides = {"serve(fused='wide', prefill_chunk=64)": lambda: m.serve(prompts, budget, S, fused='wide', prefill_chunk=64),
+                 "serve(fused='wide', prefill_chunk=128)": lambda: m.serve(prompts, budget, S, fused='wide', prefill_chunk=128),
+                 'serve(fused=True)': lambda: m.serve(prompts, budget, S, fused=True),
+                 'serve(prefill_chunk=128)': lambda: m.serve(prompts, budget, S, prefill_chunk=128),
+                 'generate_fused in static waves': lambda: waves(m.generate_fused)}
+        v = sides_alternating(sides, wall_ms, a.serve_runs, 1)
+        lines.append('(b) %d prompts (32 .. 256 tokens), budgets 16 .. 128 (%d tokens asked for), max_batch %d, wall ms, %d runs each after a warm-up run:'
+                     % (N, sum(budget), S, a.serve_runs))
+        lines += ['  %-40s %s' % (k, med(t)) for k, t in v.items()]
+    text = '\n'.join(lines) + '\n'
+    print(text, end='')
+    if a.out:
+      with open(a.out, 'a') as f:
+        f.write(text)
+    return
 
   if a.ragged:
     lines[0] = ('# tools/paged_bench.py --ragged: 160M (12 layers, d 768, 12 heads, V 50280); one process, sides alternating; attention: ms, HIP '
