@@ -803,6 +803,43 @@ int plm_ragged_layer_paged_wide_bf16(float* x, const float* attn_norm_w, const f
                                      int64_t NT, int64_t Lcap, int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd, int64_t hidden,
                                      int mlp_kind, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- shared-prefix pages: cascade attention over a ragged step -----
+ * Every argument check of these entry points comes before any HIP call.  Operands as plm_attn_ragged_paged, plus the plan of the shared
+ * prefixes, all int32 on the device: key_lo [B], the shared keys of sequence b - a multiple of 64 no larger than lens0[b] and Pcap, 0
+ * for none (any other value reads as 0: the sequence is attended over all its keys by the own part alone); tile_rows [NTg, 32], the
+ * packed rows of group tile t (any other value: a padding column); tile_seq [NTg], a member whose table row names the tile's pages;
+ * tile_keys [NTg], the tile's shared keys.  A listed row counts only if it is a row of the packed list (both words agree) and its
+ * sequence's key_lo equals tile_keys[t]; a tile whose tile_seq is outside [0, B) or whose tile_keys is no positive multiple of 64
+ * within Pcap has no column.  The table rows of a group's members must name the same pages below key_lo: that is the caller's promise.
+ *
+ * plm_attn_ragged_paged_cascade: three launches.  Prefix: a grid of (NTg*nh) x ceil(Pcap / chunk) workgroups, one group tile, one head
+ * and one chunk of the shared keys each - whole visible pages, so no mask and no row clamp; the keys are read once per 32 rows of ALL
+ * member sequences.  Own: plm_attn_ragged_paged's tiles over keys key_lo[b] .. lens0[b] + j; pages below key_lo are not fetched.
+ * Combine: a row's prefix partials in key order, then its own, empty ones skipped.  A row of a sequence with key_lo > 0 that no tile
+ * lists comes out as an empty row (out = 0, lse = +INFINITY), as a padding row does.  No atomics; a row's bits depend on its own
+ * sequence's rows, lens0[b], j and key_lo[b] alone - not on the other members, the group's size, the tile or column the row landed
+ * in, the packing order, Lcap, Pcap or where the pages lie.  workspace: the _workspace_bytes query (0 for a refused shape).
+ * plm_ragged_layer_paged_wide_cascade_bf16: plm_ragged_layer_paged_wide_bf16 with that attention stage: seven launches, bit-equal to
+ * its stages called one after the other.
+ * PLM_E_INVALID: what plm_attn_ragged_paged (and the wide layer) refuse, NULL plan words, NTg outside [1, R], Pcap no positive
+ * multiple of 64 or beyond max_pages * 64, plan words that are not 4-byte aligned; a short workspace gives PLM_E_WORKSPACE. */
+size_t plm_attn_ragged_paged_cascade_workspace_bytes(int64_t R, int64_t nh, int64_t hd, int64_t Lcap, int64_t NTg, int64_t Pcap);
+int plm_attn_ragged_paged_cascade(const uint16_t* q, const uint16_t* pool, int64_t ld_kv, const int32_t* table, const int32_t* lens0,
+                                  const int32_t* key_lo, const int32_t* cu_rows, const int32_t* row_seq, const int32_t* tile_rows,
+                                  const int32_t* tile_seq, const int32_t* tile_keys, uint16_t* out, float* lse, int64_t R, int64_t B,
+                                  int64_t NT, int64_t NTg, int64_t Lcap, int64_t Pcap, int64_t max_pages, int64_t n_pages, int64_t nh,
+                                  int64_t hd, void* workspace, size_t workspace_bytes, void* stream);
+size_t plm_ragged_layer_paged_wide_cascade_workspace_bytes(int64_t R, int64_t nh, int64_t hd, int64_t hidden, int64_t Lcap, int64_t NTg,
+                                                           int64_t Pcap);
+int plm_ragged_layer_paged_wide_cascade_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                                             const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* lens0,
+                                             const int32_t* key_lo, const int32_t* cu_rows, const int32_t* row_seq, const int32_t* tile_rows,
+                                             const int32_t* tile_seq, const int32_t* tile_keys, const float* rope_cos, const float* rope_sin,
+                                             int64_t rope_T, uint16_t* pool, int64_t ld_kv, const int32_t* table, int32_t* status, int64_t R,
+                                             int64_t B, int64_t NT, int64_t NTg, int64_t Lcap, int64_t Pcap, int64_t max_pages, int64_t n_pages,
+                                             int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, void* workspace, size_t workspace_bytes,
+                                             void* stream);
+
 /* ---- temperature / top-k / top-p sampling of one token per row -----
  * Every argument check comes before any HIP call.
  * logits bf16 [B, ld] (ld >= V; any 2-byte aligned base and any ld: columns >= V are never loaded); u fp32 [B], one uniform per row,

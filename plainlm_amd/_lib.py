@@ -202,6 +202,12 @@ SIGNATURES = {
   'plm_ragged_layer_paged_wide_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64]),
   'plm_ragged_layer_paged_wide_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64,
                                             _I64, _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
+  'plm_attn_ragged_paged_cascade_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I64]),
+  'plm_attn_ragged_paged_cascade': (_I, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64,
+                                         _I64, _P, _SZ, _P]),
+  'plm_ragged_layer_paged_wide_cascade_workspace_bytes': (_SZ, [_I64, _I64, _I64, _I64, _I64, _I64, _I64]),
+  'plm_ragged_layer_paged_wide_cascade_bf16': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P,
+                                                    _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P, _SZ, _P]),
   'plm_sample_logits_bf16': (_I, [_P, _I64, _P, _F, _I64, _F, _P, _P, _P, _P, _I64, _I64, _P]),
   'plm_spec_verify_bf16': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I64, _I64, _I64, _P]),
   'plm_lookup_draft_i64': (_I, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P]),

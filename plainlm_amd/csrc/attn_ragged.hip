@@ -127,13 +127,35 @@ __global__ __launch_bounds__(256) void kv_paged_append_rope_packed_kernel(const 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Workspace: ml fp32 [R, nh, NC, 2] then acc fp32 [R, nh, NC, hd], NC = ceil(Lcap / RG_CHUNK); the partial of (row r, head h, chunk c)
 // at index (r * nh + h) * NC + c.  The acc of an empty partial is not written and not read.
-template <int HD>
-__global__ __launch_bounds__(RG_THREADS) void attn_ragged_paged_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ pool,
-                                                                       int64_t ld_kv, const int32_t* __restrict__ table,
-                                                                       const int32_t* __restrict__ lens0, const int32_t* __restrict__ cu,
-                                                                       const int32_t* __restrict__ row_seq, float* __restrict__ ws_ml,
-                                                                       float* __restrict__ ws_acc, int R, int B, int Lcap, int max_pages,
-                                                                       int n_pages, int nh, float scale) {
+//
+// The cascade runs the same body in two more modes.  RG_OWN: the tile walks keys key_lo[b] .. only - a page wholly
+// below key_lo is neither staged nor fetched, a chunk wholly below writes the empty partial.  RG_PREFIX: the tile is a GROUP tile of the
+// plan - column i is packed row tile_rows[t, i] of any member sequence, the keys are the first tile_keys[t] keys (whole pages) of the
+// table row of the representative tile_seq[t]; every key precedes every query, so there is no mask, no per-lane limit and no row clamp.
+enum { RG_PLAIN = 0, RG_OWN = 1, RG_PREFIX = 2 };
+
+struct RgCascade {  // the plan's words; RG_PLAIN reads none of them
+  const int32_t* key_lo;     // [B]
+  const int32_t* tile_rows;  // [NTg, RG_Q]
+  const int32_t* tile_seq;   // [NTg]
+  const int32_t* tile_keys;  // [NTg]
+  int32_t* claim;            // [R] in the workspace: the (tile, column) that computed a row's prefix partials
+  int Pcap;
+};
+
+// The shared keys of sequence b as EVERY cascade kernel reads them: a positive multiple of 64 no larger than the sequence's clamped
+// length and Pcap, else 0 - and a sequence with 0 shared keys is attended by the own part alone, over all its keys.
+__device__ __forceinline__ int rg_key_lo(const int32_t* __restrict__ key_lo, int b, int l0, int Pcap) {
+  const int k = key_lo[b];
+  return (k > 0 && k % RG_ROWS == 0 && k <= l0 && k <= Pcap) ? k : 0;
+}
+
+template <int HD, int MODE>
+__device__ __forceinline__ void rg_tile_body(const uint16_t* __restrict__ q, const uint16_t* __restrict__ pool, int64_t ld_kv,
+                                             const int32_t* __restrict__ table, const int32_t* __restrict__ lens0,
+                                             const int32_t* __restrict__ cu, const int32_t* __restrict__ row_seq, float* __restrict__ ws_ml,
+                                             float* __restrict__ ws_acc, int R, int B, int Lcap, int max_pages, int n_pages, int nh, float scale,
+                                             const RgCascade& cs) {
   using TL = GenTile<HD>;
   constexpr int NKS = HD / 16, NDB = HD / 32, LDO = HD + RG_PAD;
   static_assert(RG_WAVES * RG_Q * LDO * 4 <= RG_WAVES * TL::BYTES, "the merge buffer lies over the V tiles");
@@ -148,50 +170,65 @@ __global__ __launch_bounds__(RG_THREADS) void attn_ragged_paged_kernel(const uin
   const int dm = nh * HD;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
 
-  // ---- which tile is this?  An inclusive scan of the tile counts, 256 sequences a pass; every count is capped at t + 1
-  if (tid == 0) s_found[0] = -1;
-  for (int b0 = 0, base = 0; b0 < B; b0 += RG_THREADS) {  // (base <= t: at most 2^20 * 257 inside the loop)
-    const int i = b0 + tid;
-    const int nt = i < B ? rg_tiles(cu, i, t + 1) : 0;
-    int inc = nt;
+  int b, L, klast, klo = 0, lim = 0x7fffffff;  // the tile's table row, its keys, the last one it sees, the first one it walks
+  int64_t r;
+  bool valid;
+  if constexpr (MODE == RG_PREFIX) {  // the plan names the tile: its representative's table row and its keys (uniform)
+    b = cs.tile_seq[t];
+    L = cs.tile_keys[t];
+    if ((unsigned)b >= (unsigned)B || L <= 0 || L % RG_ROWS != 0 || L > cs.Pcap) return;  // no tile: it has no column and writes nothing
+    klast = L - 1;
+    r = cs.tile_rows[(int64_t)t * RG_Q + l31];
+    const int bq = (r >= 0 && r < R) ? rg_row_seq(cu, row_seq, r, B) : -1;
+    valid = bq >= 0 && rg_key_lo(cs.key_lo, bq, rg_clamp(lens0[bq], 0, Lcap), cs.Pcap) == L;  // a member row, or the column is padding
+    if (h == 0 && ck == 0 && wave == 0 && hi == 0 && valid) cs.claim[r] = t * RG_Q + l31;
+  } else {
+    // ---- which tile is this?  An inclusive scan of the tile counts, 256 sequences a pass; every count is capped at t + 1
+    if (tid == 0) s_found[0] = -1;
+    for (int b0 = 0, base = 0; b0 < B; b0 += RG_THREADS) {  // (base <= t: at most 2^20 * 257 inside the loop)
+      const int i = b0 + tid;
+      const int nt = i < B ? rg_tiles(cu, i, t + 1) : 0;
+      int inc = nt;
 #pragma unroll
-    for (int o = 1; o < PLM_WAVE; o <<= 1) {
-      const int v = __shfl_up(inc, o, PLM_WAVE);
-      if (lane >= o) inc += v;
-    }
-    if (lane == PLM_WAVE - 1) s_scan[wave] = inc;
-    __syncthreads();
-    int before = base, total = base;
+      for (int o = 1; o < PLM_WAVE; o <<= 1) {
+        const int v = __shfl_up(inc, o, PLM_WAVE);
+        if (lane >= o) inc += v;
+      }
+      if (lane == PLM_WAVE - 1) s_scan[wave] = inc;
+      __syncthreads();
+      int before = base, total = base;
 #pragma unroll
-    for (int w = 0; w < RG_WAVES; ++w) {
-      if (w < wave) before += s_scan[w];
-      total += s_scan[w];
+      for (int w = 0; w < RG_WAVES; ++w) {
+        if (w < wave) before += s_scan[w];
+        total += s_scan[w];
+      }
+      const int first = before + inc - nt;  // this sequence's first tile
+      if (nt > 0 && t >= first && t < first + nt) {
+        s_found[0] = i;
+        s_found[1] = t - first;
+      }
+      __syncthreads();
+      if (s_found[0] >= 0 || total > t) break;  // uniform
+      base = total;
     }
-    const int first = before + inc - nt;  // this sequence's first tile
-    if (nt > 0 && t >= first && t < first + nt) {
-      s_found[0] = i;
-      s_found[1] = t - first;
-    }
-    __syncthreads();
-    if (s_found[0] >= 0 || total > t) break;  // uniform
-    base = total;
-  }
-  __syncthreads();  // (B <= 0 never gets here; covers tid 0's store when the loop ran)
-  const int b = s_found[0];
-  if (b < 0) return;  // NT was overstated: no row belongs to this tile
-  const int j0 = s_found[1] * RG_Q;
+    __syncthreads();  // (B <= 0 never gets here; covers tid 0's store when the loop ran)
+    b = s_found[0];
+    if (b < 0) return;  // NT was overstated: no row belongs to this tile
+    const int j0 = s_found[1] * RG_Q;
 
-  const int l0 = rg_clamp(lens0[b], 0, Lcap);
-  const int64_t cb = (int64_t)cu[b + 1] - cu[b];                   // > j0
-  const int L = (int)min((int64_t)l0 + cb, (int64_t)Lcap);         // keys of the sequence; rows at and beyond L are never loaded
-  const int64_t r = (int64_t)cu[b] + j0 + l31;                     // this lane's packed row
-  const bool valid = j0 + l31 < cb && r >= 0 && r < R && row_seq[r] == b;  // both words agree, or the lane is padding
-  const int lim = valid ? min(l0 + j0 + l31, Lcap - 1) : 0x7fffffff;  // the last key this lane's query sees; padding: zero q, no mask
-  const int rlast = (int)min((int64_t)j0 + RG_Q - 1, cb - 1);
-  const int klast = min(l0 + rlast, Lcap - 1);                     // the last key the tile's last row sees; klast <= L - 1
+    const int l0 = rg_clamp(lens0[b], 0, Lcap);
+    const int64_t cb = (int64_t)cu[b + 1] - cu[b];                   // > j0
+    L = (int)min((int64_t)l0 + cb, (int64_t)Lcap);                   // keys of the sequence; rows at and beyond L are never loaded
+    r = (int64_t)cu[b] + j0 + l31;                                   // this lane's packed row
+    valid = j0 + l31 < cb && r >= 0 && r < R && row_seq[r] == b;     // both words agree, or the lane is padding
+    lim = valid ? min(l0 + j0 + l31, Lcap - 1) : 0x7fffffff;         // the last key this lane's query sees; padding: zero q, no mask
+    const int rlast = (int)min((int64_t)j0 + RG_Q - 1, cb - 1);
+    klast = min(l0 + rlast, Lcap - 1);                               // the last key the tile's last row sees; klast <= L - 1
+    if constexpr (MODE == RG_OWN) klo = rg_key_lo(cs.key_lo, b, l0, cs.Pcap);  // the keys below it are the prefix kernel's
+  }
   const int k0 = ck * RG_CHUNK;
   if (tid < RG_Q) s_row[tid] = valid ? (int)r : -1;
-  if (k0 > klast) {  // not a chunk of this tile: the empty partial, nothing else is read
+  if (k0 > klast || k0 + RG_CHUNK <= klo) {  // not a chunk of this tile: the empty partial, nothing else is read
     if (tid < RG_Q && valid) {
       const int64_t part = (r * nh + h) * NC + ck;
       ws_ml[part * 2] = -INFINITY;
@@ -203,7 +240,7 @@ __global__ __launch_bounds__(RG_THREADS) void attn_ragged_paged_kernel(const uin
   // the chunk's page ids, once; an entry that is no page of the pool is kept as -1 and its keys are skipped
   if (tid < RG_CHUNK_PAGES) {
     int pg = -1;
-    if (k0 + tid * RG_ROWS < kend) pg = table[(int64_t)b * max_pages + k0 / RG_ROWS + tid];  // kend <= Lcap <= max_pages * 64
+    if (k0 + tid * RG_ROWS < kend && k0 + (tid + 1) * RG_ROWS > klo) pg = table[(int64_t)b * max_pages + k0 / RG_ROWS + tid];  // kend <= max_pages * 64
     s_page[tid] = rg_page_ok(pg, n_pages) ? pg : -1;
   }
 
@@ -225,7 +262,8 @@ __global__ __launch_bounds__(RG_THREADS) void attn_ragged_paged_kernel(const uin
     const int page = __builtin_amdgcn_readfirstlane(s_page[pi]);
     if (page < 0) continue;
     const uint16_t* kbase = pool + (int64_t)page * RG_ROWS * ld_kv + h * HD;  // + i * ld_kv: k of the page's row i; + dm: its v
-    const int last = min(RG_ROWS - 1, L - 1 - kv0);  // the sequence's last valid row inside the page (>= 0: kv0 <= klast <= L - 1)
+    // the sequence's last valid row inside the page (>= 0: kv0 <= klast <= L - 1); a prefix page is whole
+    const int last = MODE == RG_PREFIX ? RG_ROWS - 1 : min(RG_ROWS - 1, L - 1 - kv0);
     // K: both 32-row blocks of the page straight into A fragments
     bf16x8_t kf[2][NKS];
 #pragma unroll
@@ -252,7 +290,7 @@ __global__ __launch_bounds__(RG_THREADS) void attn_ragged_paged_kernel(const uin
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks) s[kb] = mfma32(kf[kb][ks], qf[ks], s[kb]);
     }
-    if (__ballot(kv0 + RG_ROWS - 1 > lim) != 0) {  // some query does not see the whole page: the mask
+    if (MODE != RG_PREFIX && __ballot(kv0 + RG_ROWS - 1 > lim) != 0) {  // some query does not see the whole page: the mask
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -345,11 +383,48 @@ __global__ __launch_bounds__(RG_THREADS) void attn_ragged_paged_kernel(const uin
   for (int e = 0; e < SL; ++e) ws_acc[part * HD + c + e] = a[e];
 }
 
-// one workgroup per packed row: all heads of the row
-__global__ __launch_bounds__(256) void attn_ragged_combine_kernel(const float* __restrict__ ws_ml, const float* __restrict__ ws_acc,
-                                                                  const int32_t* __restrict__ cu, const int32_t* __restrict__ row_seq,
-                                                                  uint16_t* __restrict__ out, float* __restrict__ lse, int B, int NT, int NC,
-                                                                  int nh, int hd) {
+template <int HD>
+__global__ __launch_bounds__(RG_THREADS) void attn_ragged_paged_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ pool,
+                                                                       int64_t ld_kv, const int32_t* __restrict__ table,
+                                                                       const int32_t* __restrict__ lens0, const int32_t* __restrict__ cu,
+                                                                       const int32_t* __restrict__ row_seq, float* __restrict__ ws_ml,
+                                                                       float* __restrict__ ws_acc, int R, int B, int Lcap, int max_pages,
+                                                                       int n_pages, int nh, float scale) {
+  rg_tile_body<HD, RG_PLAIN>(q, pool, ld_kv, table, lens0, cu, row_seq, ws_ml, ws_acc, R, B, Lcap, max_pages, n_pages, nh, scale, RgCascade{});
+}
+
+// the own part of the cascade: the ragged tiles over keys key_lo[b] .. lens0[b] + j
+template <int HD>
+__global__ __launch_bounds__(RG_THREADS) void attn_ragged_paged_own_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ pool,
+                                                                           int64_t ld_kv, const int32_t* __restrict__ table,
+                                                                           const int32_t* __restrict__ lens0, const int32_t* __restrict__ cu,
+                                                                           const int32_t* __restrict__ row_seq, float* __restrict__ ws_ml,
+                                                                           float* __restrict__ ws_acc, int R, int B, int Lcap, int max_pages,
+                                                                           int n_pages, int nh, float scale, const RgCascade cs) {
+  rg_tile_body<HD, RG_OWN>(q, pool, ld_kv, table, lens0, cu, row_seq, ws_ml, ws_acc, R, B, Lcap, max_pages, n_pages, nh, scale, cs);
+}
+
+// the shared part: grid (NTg * nh) x ceil(Pcap / chunk), one group tile, one head and one chunk of the prefix per workgroup
+template <int HD>
+__global__ __launch_bounds__(RG_THREADS) void attn_prefix_paged_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ pool,
+                                                                       int64_t ld_kv, const int32_t* __restrict__ table,
+                                                                       const int32_t* __restrict__ lens0, const int32_t* __restrict__ cu,
+                                                                       const int32_t* __restrict__ row_seq, float* __restrict__ ws_ml,
+                                                                       float* __restrict__ ws_acc, int R, int B, int Lcap, int max_pages,
+                                                                       int n_pages, int nh, float scale, const RgCascade cs) {
+  rg_tile_body<HD, RG_PREFIX>(q, pool, ld_kv, table, lens0, cu, row_seq, ws_ml, ws_acc, R, B, Lcap, max_pages, n_pages, nh, scale, cs);
+}
+
+// One workgroup per packed row: all heads of the row.  CASCADE: a row of a sequence with shared keys walks its prefix partials
+// (p_ml / p_acc, NCp a row and head) in key order, then its own; it is live only if the prefix kernel computed it - claim[r] names a
+// column of the plan that lists r under the prefix kernel's own predicate, so whatever the word holds, no partial is read that no
+// workgroup wrote.
+template <bool CASCADE>
+__device__ __forceinline__ void rg_combine_body(const float* __restrict__ ws_ml, const float* __restrict__ ws_acc,
+                                                const int32_t* __restrict__ cu, const int32_t* __restrict__ row_seq,
+                                                uint16_t* __restrict__ out, float* __restrict__ lse, int B, int NT, int NC, int nh, int hd,
+                                                const float* __restrict__ p_ml, const float* __restrict__ p_acc,
+                                                const int32_t* __restrict__ lens0, int Lcap, int NTg, int NCp, const RgCascade& cs) {
   __shared__ int s_part[4];
   const int64_t r = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -366,14 +441,33 @@ __global__ __launch_bounds__(256) void attn_ragged_combine_kernel(const float* _
     const int64_t tile = (int64_t)s_part[0] + s_part[1] + s_part[2] + s_part[3] + (r - cu[b]) / RG_Q;
     live = tile < NT;  // beyond the tiles the caller stated: no workgroup computed this row
   }
+  int np = 0;  // the row's prefix partials
+  if (CASCADE && live) {
+    const int klo = rg_key_lo(cs.key_lo, b, rg_clamp(lens0[b], 0, Lcap), cs.Pcap);
+    if (klo > 0) {
+      const int x = cs.claim[r];  // (tile, column), if the prefix kernel wrote it
+      live = (unsigned)x < (unsigned)NTg * RG_Q && cs.tile_rows[x] == r && cs.tile_keys[x / RG_Q] == klo &&
+             (unsigned)cs.tile_seq[x / RG_Q] < (unsigned)B;
+      np = NCp;
+    }
+  }
   for (int e = tid; e < dm; e += 256) {
     const int h = e / hd, d = e - h * hd;
     float mm = -INFINITY;
-    const int64_t p0 = (r * nh + h) * NC;
-    if (live)
+    const int64_t p0 = (r * nh + h) * NC, pp0 = (r * nh + h) * NCp;
+    if (live) {
+      for (int c = 0; c < np; ++c) mm = fmaxf(mm, p_ml[(pp0 + c) * 2]);
       for (int c = 0; c < NC; ++c) mm = fmaxf(mm, ws_ml[(p0 + c) * 2]);
+    }
     float ll = 0.f, acc = 0.f;
     if (mm != -INFINITY) {
+      for (int c = 0; c < np; ++c) {  // the shared keys come first
+        const float mc = p_ml[(pp0 + c) * 2];
+        if (mc == -INFINITY) continue;
+        const float sc = __builtin_amdgcn_exp2f(mc - mm);
+        ll += p_ml[(pp0 + c) * 2 + 1] * sc;
+        acc += p_acc[(pp0 + c) * hd + d] * sc;
+      }
       for (int c = 0; c < NC; ++c) {  // key order; an empty partial is skipped, so the chunk count never reaches the bits
         const float mc = ws_ml[(p0 + c) * 2];
         if (mc == -INFINITY) continue;
@@ -386,6 +480,22 @@ __global__ __launch_bounds__(256) void attn_ragged_combine_kernel(const float* _
     reinterpret_cast<bf16_t*>(out)[r * dm + e] = f2bf(empty ? 0.f : acc / ll);  // (the bits: out is declared uint16_t)
     if (lse != nullptr && d == 0) lse[r * nh + h] = empty ? INFINITY : mm + __builtin_amdgcn_logf(ll);  // base 2
   }
+}
+
+__global__ __launch_bounds__(256) void attn_ragged_combine_kernel(const float* __restrict__ ws_ml, const float* __restrict__ ws_acc,
+                                                                  const int32_t* __restrict__ cu, const int32_t* __restrict__ row_seq,
+                                                                  uint16_t* __restrict__ out, float* __restrict__ lse, int B, int NT, int NC,
+                                                                  int nh, int hd) {
+  rg_combine_body<false>(ws_ml, ws_acc, cu, row_seq, out, lse, B, NT, NC, nh, hd, nullptr, nullptr, nullptr, 0, 0, 0, RgCascade{});
+}
+
+__global__ __launch_bounds__(256) void attn_cascade_combine_kernel(const float* __restrict__ p_ml, const float* __restrict__ p_acc,
+                                                                   const float* __restrict__ ws_ml, const float* __restrict__ ws_acc,
+                                                                   const int32_t* __restrict__ lens0, const int32_t* __restrict__ cu,
+                                                                   const int32_t* __restrict__ row_seq, uint16_t* __restrict__ out,
+                                                                   float* __restrict__ lse, int B, int NT, int NTg, int NC, int NCp, int Lcap,
+                                                                   int nh, int hd, const RgCascade cs) {
+  rg_combine_body<true>(ws_ml, ws_acc, cu, row_seq, out, lse, B, NT, NC, nh, hd, p_ml, p_acc, lens0, Lcap, NTg, NCp, cs);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -477,6 +587,82 @@ extern "C" int plm_attn_ragged_paged(const uint16_t* q, const uint16_t* pool, in
   else ragged_launch<128>(q, pool, ld_kv, table, lens0, cu_rows, row_seq, R, B, NT, Lcap, max_pages, n_pages, nh, (int)NC, ws_ml, ws_acc, s);
   hipLaunchKernelGGL(attn_ragged_combine_kernel, dim3((unsigned)R), dim3(256), 0, s, ws_ml, ws_acc, cu_rows, row_seq, out, lse, (int)B, (int)NT,
                      (int)NC, (int)nh, (int)hd);
+  PLM_CHECK_LAUNCH(fn);
+  return PLM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// plm_attn_ragged_paged_cascade: prefix, own, combine
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Workspace: claim int32 [R] | the prefix partials, ml [R, nh, NCp, 2] then acc [R, nh, NCp, hd], NCp = ceil(Pcap / RG_CHUNK) | the own
+// partials in plm_attn_ragged_paged's layout; every part a multiple of 16 bytes.
+static size_t cascade_part_bytes(int64_t R, int64_t nh, int64_t hd, int64_t chunks) {
+  return ((size_t)R * (size_t)nh * (size_t)chunks * (2 + (size_t)hd) * 4 + 15) / 16 * 16;
+}
+
+extern "C" size_t plm_attn_ragged_paged_cascade_workspace_bytes(int64_t R, int64_t nh, int64_t hd, int64_t Lcap, int64_t NTg, int64_t Pcap) {
+  if (!ragged_attend_shape_ok(R, nh, hd, Lcap) || NTg < 1 || NTg > R || Pcap < RG_ROWS || Pcap % RG_ROWS != 0 ||
+      plm_cdiv(Pcap, RG_CHUNK) > CACHE_MAX_SPLITS)
+    return 0;
+  return ((size_t)R * 4 + 15) / 16 * 16 + cascade_part_bytes(R, nh, hd, plm_cdiv(Pcap, RG_CHUNK)) +
+         cascade_part_bytes(R, nh, hd, plm_cdiv(Lcap, RG_CHUNK));
+}
+
+template <int HD>
+static void cascade_launch(const uint16_t* q, const uint16_t* pool, int64_t ld_kv, const int32_t* table, const int32_t* lens0,
+                           const int32_t* cu_rows, const int32_t* row_seq, int64_t R, int64_t B, int64_t NT, int64_t NTg, int64_t Lcap,
+                           int64_t max_pages, int64_t n_pages, int64_t nh, int NC, int NCp, float* p_ml, float* p_acc, float* ws_ml, float* ws_acc,
+                           const RgCascade& cs, hipStream_t s) {
+  const float scale = 1.f / sqrtf((float)HD);
+  hipLaunchKernelGGL(attn_prefix_paged_kernel<HD>, dim3((unsigned)(NTg * nh), (unsigned)NCp), dim3(RG_THREADS), 0, s, q, pool, ld_kv, table, lens0,
+                     cu_rows, row_seq, p_ml, p_acc, (int)R, (int)B, (int)Lcap, (int)max_pages, (int)n_pages, (int)nh, scale, cs);
+  hipLaunchKernelGGL(attn_ragged_paged_own_kernel<HD>, dim3((unsigned)(NT * nh), (unsigned)NC), dim3(RG_THREADS), 0, s, q, pool, ld_kv, table, lens0,
+                     cu_rows, row_seq, ws_ml, ws_acc, (int)R, (int)B, (int)Lcap, (int)max_pages, (int)n_pages, (int)nh, scale, cs);
+}
+
+extern "C" int plm_attn_ragged_paged_cascade(const uint16_t* q, const uint16_t* pool, int64_t ld_kv, const int32_t* table, const int32_t* lens0,
+                                             const int32_t* key_lo, const int32_t* cu_rows, const int32_t* row_seq, const int32_t* tile_rows,
+                                             const int32_t* tile_seq, const int32_t* tile_keys, uint16_t* out, float* lse, int64_t R, int64_t B,
+                                             int64_t NT, int64_t NTg, int64_t Lcap, int64_t Pcap, int64_t max_pages, int64_t n_pages, int64_t nh,
+                                             int64_t hd, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "plm_attn_ragged_paged_cascade";
+  PLM_REQUIRE(q && out && workspace && key_lo && tile_rows && tile_seq && tile_keys, "%s: null pointer", fn);
+  if (const int e = ragged_check(fn, pool, ld_kv, table, lens0, cu_rows, row_seq, R, B, max_pages, n_pages, nh, hd)) return e;
+  PLM_REQUIRE(NT >= 1 && NT <= R && NT * nh < ((int64_t)1 << 31), "%s: NT=%ld tiles outside [1, R = %ld] (a tile holds at least one row)", fn, (long)NT,
+              (long)R);
+  PLM_REQUIRE(NTg >= 1 && NTg <= R && NTg * nh < ((int64_t)1 << 31), "%s: NTg=%ld group tiles outside [1, R = %ld] (a tile holds at least one row)",
+              fn, (long)NTg, (long)R);
+  PLM_REQUIRE(Lcap >= 1 && Lcap <= max_pages * RG_ROWS, "%s: Lcap=%ld outside [1, max_pages * %d = %ld]", fn, (long)Lcap, RG_ROWS,
+              (long)(max_pages * RG_ROWS));
+  PLM_REQUIRE(Pcap >= RG_ROWS && Pcap % RG_ROWS == 0 && Pcap <= max_pages * RG_ROWS,
+              "%s: Pcap=%ld is no positive multiple of %d within max_pages * %d = %ld (a prefix is whole pages)", fn, (long)Pcap, RG_ROWS, RG_ROWS,
+              (long)(max_pages * RG_ROWS));
+  PLM_REQUIRE(((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0,
+              "%s: q, out and the workspace must be 16-byte aligned", fn);
+  PLM_REQUIRE(((reinterpret_cast<uintptr_t>(key_lo) | reinterpret_cast<uintptr_t>(tile_rows) | reinterpret_cast<uintptr_t>(tile_seq) |
+                reinterpret_cast<uintptr_t>(tile_keys)) & 3) == 0,
+              "%s: key_lo, tile_rows, tile_seq and tile_keys must be 4-byte aligned", fn);
+  const int64_t NC = plm_cdiv(Lcap, RG_CHUNK), NCp = plm_cdiv(Pcap, RG_CHUNK);
+  PLM_REQUIRE(NC <= CACHE_MAX_SPLITS && NCp <= CACHE_MAX_SPLITS, "%s: Lcap=%ld / Pcap=%ld are %ld / %ld chunks of %d keys, more than %d", fn,
+              (long)Lcap, (long)Pcap, (long)NC, (long)NCp, RG_CHUNK, CACHE_MAX_SPLITS);
+  const size_t need = plm_attn_ragged_paged_cascade_workspace_bytes(R, nh, hd, Lcap, NTg, Pcap);
+  if (workspace_bytes < need) {
+    plm_set_error("%s: workspace of %zu bytes required, %zu given", fn, need, workspace_bytes);
+    return PLM_E_WORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace);
+  const size_t parts = (size_t)R * nh;
+  float* p_ml = reinterpret_cast<float*>(ws + ((size_t)R * 4 + 15) / 16 * 16);
+  float* p_acc = p_ml + parts * NCp * 2;
+  float* ws_ml = reinterpret_cast<float*>(reinterpret_cast<char*>(p_ml) + cascade_part_bytes(R, nh, hd, NCp));
+  float* ws_acc = ws_ml + parts * NC * 2;
+  const RgCascade cs = {key_lo, tile_rows, tile_seq, tile_keys, reinterpret_cast<int32_t*>(ws), (int)Pcap};
+  if (hd == 32) cascade_launch<32>(q, pool, ld_kv, table, lens0, cu_rows, row_seq, R, B, NT, NTg, Lcap, max_pages, n_pages, nh, (int)NC, (int)NCp, p_ml, p_acc, ws_ml, ws_acc, cs, s);
+  else if (hd == 64) cascade_launch<64>(q, pool, ld_kv, table, lens0, cu_rows, row_seq, R, B, NT, NTg, Lcap, max_pages, n_pages, nh, (int)NC, (int)NCp, p_ml, p_acc, ws_ml, ws_acc, cs, s);
+  else cascade_launch<128>(q, pool, ld_kv, table, lens0, cu_rows, row_seq, R, B, NT, NTg, Lcap, max_pages, n_pages, nh, (int)NC, (int)NCp, p_ml, p_acc, ws_ml, ws_acc, cs, s);
+  hipLaunchKernelGGL(attn_cascade_combine_kernel, dim3((unsigned)R), dim3(256), 0, s, p_ml, p_acc, ws_ml, ws_acc, lens0, cu_rows, row_seq, out, lse,
+                     (int)B, (int)NT, (int)NTg, (int)NC, (int)NCp, (int)Lcap, (int)nh, (int)hd, cs);
   PLM_CHECK_LAUNCH(fn);
   return PLM_OK;
 }

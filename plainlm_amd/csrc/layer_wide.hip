@@ -352,24 +352,40 @@ extern "C" int plm_ragged_norm_qkv_append_paged_wide_bf16(const float* x, const 
   return PLM_OK;
 }
 
-// Workspace of the layer at R rows: q bf16 [R, d] | attention output bf16 [R, d] | activation bf16 [R, hidden] | plm_attn_ragged_paged's
+// The plan of the shared prefixes; key_lo null: the layer attends through plm_attn_ragged_paged
+struct WlCascade {
+  const int32_t* key_lo;
+  const int32_t* tile_rows;
+  const int32_t* tile_seq;
+  const int32_t* tile_keys;
+  int64_t NTg, Pcap;
+};
+
+// Workspace of the layer at R rows: q bf16 [R, d] | attention output bf16 [R, d] | activation bf16 [R, hidden] | the attention stage's
 // partials, every part a multiple of 16 bytes.  A function of the shapes alone; 0 for a shape the layer refuses.
-extern "C" size_t plm_ragged_layer_paged_wide_workspace_bytes(int64_t R, int64_t nh, int64_t hd, int64_t hidden, int64_t Lcap) {
+static size_t wl_layer_bytes(int64_t R, int64_t nh, int64_t hd, int64_t hidden, size_t att) {
   if (R < 1 || R > WL_MAX_ROWS || nh < 1 || nh * hd > DF_MAX_DIM / 4 || (nh * hd) % 32 != 0 || hidden < 1 || hidden > DF_MAX_DIM / 2 || hidden % 32 != 0)
     return 0;
-  const size_t att = plm_attn_ragged_paged_workspace_bytes(R, nh, hd, Lcap);  // 0 for a head_dim or Lcap the attention stage refuses
-  if (att == 0) return 0;
+  if (att == 0) return 0;  // a head_dim, Lcap or plan the attention stage refuses
   const size_t d = (size_t)(nh * hd);
   return 2 * df_round16((size_t)R * d * 2) + df_round16((size_t)R * (size_t)hidden * 2) + att;
 }
 
-extern "C" int plm_ragged_layer_paged_wide_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
-                                                const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* lens0,
-                                                const int32_t* cu_rows, const int32_t* row_seq, const float* rope_cos, const float* rope_sin,
-                                                int64_t rope_T, uint16_t* pool, int64_t ld_kv, const int32_t* table, int32_t* status, int64_t R,
-                                                int64_t B, int64_t NT, int64_t Lcap, int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd,
-                                                int64_t hidden, int mlp_kind, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* fn = "plm_ragged_layer_paged_wide_bf16";
+extern "C" size_t plm_ragged_layer_paged_wide_workspace_bytes(int64_t R, int64_t nh, int64_t hd, int64_t hidden, int64_t Lcap) {
+  return wl_layer_bytes(R, nh, hd, hidden, plm_attn_ragged_paged_workspace_bytes(R, nh, hd, Lcap));
+}
+
+extern "C" size_t plm_ragged_layer_paged_wide_cascade_workspace_bytes(int64_t R, int64_t nh, int64_t hd, int64_t hidden, int64_t Lcap, int64_t NTg,
+                                                                      int64_t Pcap) {
+  return wl_layer_bytes(R, nh, hd, hidden, plm_attn_ragged_paged_cascade_workspace_bytes(R, nh, hd, Lcap, NTg, Pcap));
+}
+
+static int wl_ragged_layer(const char* fn, float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                           const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* lens0, const int32_t* cu_rows,
+                           const int32_t* row_seq, const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* pool, int64_t ld_kv,
+                           const int32_t* table, int32_t* status, int64_t R, int64_t B, int64_t NT, int64_t Lcap, int64_t max_pages,
+                           int64_t n_pages, int64_t nh, int64_t hd, int64_t hidden, int mlp_kind, const WlCascade& cs, void* workspace,
+                           size_t workspace_bytes, void* stream) {
   PLM_REQUIRE(x && attn_norm_w && mlp_norm_w && w_qkv && w_out && w_fc1 && w_fc2 && lens0 && rope_cos && rope_sin && pool && status && workspace,
               "%s: null pointer", fn);
   PLM_REQUIRE(df_aligned(workspace), "%s: the workspace must be 16-byte aligned", fn);
@@ -385,11 +401,21 @@ extern "C" int plm_ragged_layer_paged_wide_bf16(float* x, const float* attn_norm
                                  nh, hd))
     return e;
   PLM_REQUIRE(NT >= 1 && NT <= R, "%s: NT=%ld tiles outside [1, R = %ld] (a tile holds at least one row)", fn, (long)NT, (long)R);
+  if (cs.key_lo) {  // plm_attn_ragged_paged_cascade's own refusals, under this entry point's name
+    PLM_REQUIRE(cs.NTg >= 1 && cs.NTg <= R, "%s: NTg=%ld group tiles outside [1, R = %ld] (a tile holds at least one row)", fn, (long)cs.NTg, (long)R);
+    PLM_REQUIRE(cs.Pcap >= PLM_KV_PAGE_ROWS && cs.Pcap % PLM_KV_PAGE_ROWS == 0 && cs.Pcap <= max_pages * PLM_KV_PAGE_ROWS,
+                "%s: Pcap=%ld is no positive multiple of %d within max_pages * %d = %ld (a prefix is whole pages)", fn, (long)cs.Pcap,
+                PLM_KV_PAGE_ROWS, PLM_KV_PAGE_ROWS, (long)(max_pages * PLM_KV_PAGE_ROWS));
+    PLM_REQUIRE(((reinterpret_cast<uintptr_t>(cs.key_lo) | reinterpret_cast<uintptr_t>(cs.tile_rows) | reinterpret_cast<uintptr_t>(cs.tile_seq) |
+                  reinterpret_cast<uintptr_t>(cs.tile_keys)) & 3) == 0,
+                "%s: key_lo, tile_rows, tile_seq and tile_keys must be 4-byte aligned", fn);
+  }
   if (const int e = wl_check_residual(fn, x, q, w_out, R, d, d)) return e;
   if (const int e = wl_check_fc1(fn, x, mlp_norm_w, w_fc1, q, R, d, hidden, mlp_kind)) return e;
   if (const int e = wl_check_residual(fn, x, q, w_fc2, R, d, hidden)) return e;
-  // the attention stage's own shape refusals are its workspace query's: 0 for anything plm_attn_ragged_paged would refuse
-  const size_t need = plm_ragged_layer_paged_wide_workspace_bytes(R, nh, hd, hidden, Lcap);
+  // the attention stage's own shape refusals are its workspace query's: 0 for anything it would refuse
+  const size_t need = cs.key_lo ? plm_ragged_layer_paged_wide_cascade_workspace_bytes(R, nh, hd, hidden, Lcap, cs.NTg, cs.Pcap)
+                                : plm_ragged_layer_paged_wide_workspace_bytes(R, nh, hd, hidden, Lcap);
   PLM_REQUIRE(need != 0, "%s: bad shape R=%ld Lcap=%ld nh=%ld hd=%ld hidden=%ld", fn, (long)R, (long)Lcap, (long)nh, (long)hd, (long)hidden);
   if (workspace_bytes < need) {
     plm_set_error("%s: workspace of %zu bytes required, %zu given", fn, need, workspace_bytes);
@@ -400,12 +426,43 @@ extern "C" int plm_ragged_layer_paged_wide_bf16(float* x, const float* attn_norm
   uint16_t* act = reinterpret_cast<uint16_t*>(ws + 2 * qb);
   hipStream_t s = (hipStream_t)stream;
   wl_launch_qkv(x, attn_norm_w, eps, w_qkv, lens0, rope_cos, rope_sin, rope_T, q, pool, ld_kv, status, R, nh, hd, pg, s);
-  if (const int e = plm_attn_ragged_paged(q, pool, ld_kv, table, lens0, cu_rows, row_seq, attn_out, nullptr, R, B, NT, Lcap, max_pages, n_pages, nh, hd,
-                                          ws + 2 * qb + ab, need - 2 * qb - ab, stream))
-    return e;
+  const int e = cs.key_lo ? plm_attn_ragged_paged_cascade(q, pool, ld_kv, table, lens0, cs.key_lo, cu_rows, row_seq, cs.tile_rows, cs.tile_seq,
+                                                          cs.tile_keys, attn_out, nullptr, R, B, NT, cs.NTg, Lcap, cs.Pcap, max_pages, n_pages, nh, hd,
+                                                          ws + 2 * qb + ab, need - 2 * qb - ab, stream)
+                          : plm_attn_ragged_paged(q, pool, ld_kv, table, lens0, cu_rows, row_seq, attn_out, nullptr, R, B, NT, Lcap, max_pages, n_pages,
+                                                  nh, hd, ws + 2 * qb + ab, need - 2 * qb - ab, stream);
+  if (e) return e;
   wl_launch_residual(x, attn_out, w_out, R, d, d, s);
   wl_launch_fc1(x, mlp_norm_w, eps, w_fc1, act, R, d, hidden, mlp_kind, s);
   wl_launch_residual(x, act, w_fc2, R, d, hidden, s);
   PLM_CHECK_LAUNCH(fn);
   return PLM_OK;
 }
+
+extern "C" int plm_ragged_layer_paged_wide_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                                                const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* lens0,
+                                                const int32_t* cu_rows, const int32_t* row_seq, const float* rope_cos, const float* rope_sin,
+                                                int64_t rope_T, uint16_t* pool, int64_t ld_kv, const int32_t* table, int32_t* status, int64_t R,
+                                                int64_t B, int64_t NT, int64_t Lcap, int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd,
+                                                int64_t hidden, int mlp_kind, void* workspace, size_t workspace_bytes, void* stream) {
+  return wl_ragged_layer("plm_ragged_layer_paged_wide_bf16", x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, lens0, cu_rows, row_seq,
+                         rope_cos, rope_sin, rope_T, pool, ld_kv, table, status, R, B, NT, Lcap, max_pages, n_pages, nh, hd, hidden, mlp_kind,
+                         WlCascade{}, workspace, workspace_bytes, stream);
+}
+
+// the wide layer with the cascade attention stage: seven launches
+extern "C" int plm_ragged_layer_paged_wide_cascade_bf16(float* x, const float* attn_norm_w, const float* mlp_norm_w, float eps, const uint16_t* w_qkv,
+                                                        const uint16_t* w_out, const uint16_t* w_fc1, const uint16_t* w_fc2, const int32_t* lens0,
+                                                        const int32_t* key_lo, const int32_t* cu_rows, const int32_t* row_seq,
+                                                        const int32_t* tile_rows, const int32_t* tile_seq, const int32_t* tile_keys,
+                                                        const float* rope_cos, const float* rope_sin, int64_t rope_T, uint16_t* pool, int64_t ld_kv,
+                                                        const int32_t* table, int32_t* status, int64_t R, int64_t B, int64_t NT, int64_t NTg,
+                                                        int64_t Lcap, int64_t Pcap, int64_t max_pages, int64_t n_pages, int64_t nh, int64_t hd,
+                                                        int64_t hidden, int mlp_kind, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "plm_ragged_layer_paged_wide_cascade_bf16";
+  PLM_REQUIRE(key_lo && tile_rows && tile_seq && tile_keys, "%s: null pointer", fn);
+  return wl_ragged_layer(fn, x, attn_norm_w, mlp_norm_w, eps, w_qkv, w_out, w_fc1, w_fc2, lens0, cu_rows, row_seq, rope_cos, rope_sin, rope_T, pool,
+                         ld_kv, table, status, R, B, NT, Lcap, max_pages, n_pages, nh, hd, hidden, mlp_kind,
+                         WlCascade{key_lo, tile_rows, tile_seq, tile_keys, NTg, Pcap}, workspace, workspace_bytes, stream);
+}
+

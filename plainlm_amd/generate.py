@@ -28,9 +28,12 @@ cache is ``PagePool`` - per-layer pages of ops.KV_PAGE_RO
 device block table with a host mirror, host upper bounds of the lengths, release / adopt; ``prefill_paged`` / ``new_cache_paged`` make one,
 decode_step and extend dispatch on it to ops.kv_paged_append_rope_rows / ops.attn_decode_paged / ops.attn_extend_paged, and ``serve`` is
 continuous batching over it (refuse_paged and refuse_paged_model hold its refusals); fused=True runs ops.decode_layer_paged /
-ops.extend_layer_paged per layer.
+ops.extend_layer_paged per layer.  Shared-prefix pages: ``PagePool`` counts a page's holders, ``prefill_prefix``
+keeps a prompt prefix's whole pages once (``PagedPrefix``), ``PagedKVCache.admit_prefix`` starts sequences on them, ``step_ragged``
+dispatches on such a cache to ops.attn_ragged_paged_cascade, and ``serve_shared`` is the chunked-prefill serving loop over it.
 """
 
+import itertools
 import math
 
 import torch
@@ -150,7 +153,9 @@ class SharedPrefixCache:
 class PagePool:
   """The pages of a paged KV cache: per layer ``kv`` bf16 [n_pages, ops.KV_PAGE_ROWS, 2*dim] in KVCache's row
   layout, and a host free list.  One page id means the same page in every layer.  ``alloc(k)`` hands out k page ids and raises
-  RuntimeError when fewer are free - on the host, before anything is launched; ``free(ids)`` takes them back.  bf16 pages only."""
+  RuntimeError when fewer are free - on the host, before anything is launched; ``free(ids)`` takes them back.  Pages are counted by
+  their holders: ``share(ids)`` adds one, ``free`` drops one, and a page is free again when none is left; ``n_free`` and
+  ``bytes_in_use`` count a shared page once.  bf16 pages only."""
 
   def __init__(self, n_layers, n_pages, n_heads, head_dim, device, kv_dtype='bf16'):
     if check_kv_dtype(kv_dtype) != 'bf16':
@@ -161,7 +166,7 @@ class PagePool:
     shape = (self.n_pages, ops.KV_PAGE_ROWS, 2 * n_heads * head_dim)
     self.kv = [torch.empty(shape, dtype=torch.bfloat16, device=device) for _ in range(n_layers)]  # rows >= a sequence's length are never read
     self._free = list(range(self.n_pages - 1, -1, -1))  # a stack: page 0 goes out first, a freed page is reused first
-    self._used = [False] * self.n_pages
+    self._used = [0] * self.n_pages  # holders of every page: alloc makes one, share adds one, free drops one
 
   @property
   def n_free(self):
@@ -173,20 +178,46 @@ class PagePool:
                          'make a larger pool')
     ids = [self._free.pop() for _ in range(k)]
     for p in ids:
-      self._used[p] = True
+      self._used[p] = 1
     return ids
 
-  def free(self, ids):
+  def _held(self, what, ids):
     ids = list(ids)
     if any(not 0 <= p < self.n_pages or not self._used[p] for p in ids) or len(set(ids)) != len(ids):
-      raise ValueError(f'PagePool.free: {ids} are not all pages in use')
+      raise ValueError(f'PagePool.{what}: {ids} are not all pages in use')
+    return ids
+
+  def share(self, ids):
+    """One more holder of pages in use: they return to the free list when every holder has freed them."""
+    for p in self._held('share', ids):
+      self._used[p] += 1
+
+  def free(self, ids):
+    ids = self._held('free', ids)
     for p in ids:
-      self._used[p] = False
-    self._free.extend(reversed(ids))
+      self._used[p] -= 1
+    self._free.extend(p for p in reversed(ids) if not self._used[p])
 
   def bytes_in_use(self):
     """Bytes of the pages handed out, all layers."""
     return (self.n_pages - len(self._free)) * sum(t[0].numel() * t.element_size() for t in self.kv)
+
+
+class PagedPrefix:
+  """A prompt prefix kept once in a PagePool (DESIGN.md section 28): ``pages``, the ids of its whole pages, held by this object;
+  ``n_tokens`` = 64 * len(pages), the tokens they hold; ``rest``, the tokens past the last whole page, which every member sequence
+  feeds itself.  ``PagedKVCache.admit_prefix`` starts sequences on the pages; ``release()`` drops this object's hold (the pages are
+  free again once the last member has left).  Made by ``Transformer.prefill_prefix``."""
+  _ids = itertools.count()
+
+  def __init__(self, pool, pages, rest):
+    self.pool, self.pages, self.rest = pool, list(pages), rest
+    self.n_tokens = ops.KV_PAGE_ROWS * len(self.pages)
+    self.group = next(PagedPrefix._ids)  # what cascade_plan groups the members by
+
+  def release(self):
+    self.pool.free(self.pages)
+    self.pages, self.n_tokens = [], 0
 
 
 class PagedKVCache:
@@ -212,6 +243,8 @@ class PagedKVCache:
     self.pages = [[] for _ in range(self.B)]
     self.bound = [0] * self.B
     self._live = [False] * self.B
+    self.key_lo = [0] * self.B     # the keys slot b shares with its group (whole pages; 0: none) ...
+    self.group = [None] * self.B   # ... and the group: the PagedPrefix's id
     self._pl = torch.zeros((2, self.B), dtype=torch.int32, device=dev)
     self.live = torch.zeros((self.B,), dtype=torch.int32, device=dev)
     self.status = torch.zeros((1,), dtype=torch.int32, device=dev)
@@ -263,6 +296,8 @@ class PagedKVCache:
     vals = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
     if len(vals) != self.B or any(v < 0 or v > self.Tmax for v in vals):
       raise ValueError(f'PagedKVCache.set_lens: need {self.B} lengths in [0, {self.Tmax}], got {vals}')
+    if any(v < k for v, k in zip(vals, self.key_lo)):
+      raise ValueError(f'PagedKVCache.set_lens: {vals} cut into the shared prefixes {self.key_lo} (release the slot instead)')
     for b, v in enumerate(vals):
       keep = -(-v // ops.KV_PAGE_ROWS)
       if len(self.pages[b]) > keep:
@@ -298,6 +333,28 @@ class PagedKVCache:
     self._pl[0, b] = -1  # pos = lens - 1, as set_lens keeps it
     self.live[b] = 1
 
+  def admit_prefix(self, b, prefix):
+    """The idle slot b becomes a live sequence of length prefix.n_tokens on the prefix's pages: its first
+    table entries are the prefix's page ids, of which it is one more holder; its key_lo and group say so to ``step_ragged``.  Its
+    appends take fresh pages - the length starts at a page edge - so a shared page is never written.  A prefix without a whole
+    page is ``admit``."""
+    if not isinstance(prefix, PagedPrefix) or prefix.pool is not self.pool:
+      raise ValueError('PagedKVCache.admit_prefix: the prefix must be a PagedPrefix on the same pool')
+    if self._live[b] or self.pages[b]:
+      raise ValueError(f'PagedKVCache.admit_prefix: slot {b} holds a sequence (release it first)')
+    n = prefix.n_tokens
+    if n >= self.Tmax:
+      raise ValueError(f'PagedKVCache.admit_prefix: the prefix holds {n} tokens, this cache {self.Tmax} per sequence')
+    if not n:
+      return self.admit(b)
+    self.pool.share(prefix.pages)
+    self.pages[b] = list(prefix.pages)
+    self._mirror[b, :len(self.pages[b])] = torch.tensor(self.pages[b], dtype=torch.int32)
+    self._touch(b)
+    self.bound[b], self._live[b], self.key_lo[b], self.group[b] = n, True, n, prefix.group
+    self._pl[:, b] = torch.tensor([n - 1, n], dtype=torch.int32)
+    self.live[b] = 1
+
   def ship(self, *words):
     """Host int32 tensors -> their device copies, as ONE non-blocking copy from a pinned snapshot (the way ``table`` ships its rows)."""
     src = torch.cat([w.reshape(-1) for w in words])
@@ -306,9 +363,10 @@ class PagedKVCache:
     return dev.split([w.numel() for w in words])
 
   def release(self, b):
-    """Sequence b leaves: its pages go back to the pool, its table row to -1, its length to 0; the slot is idle."""
+    """Sequence b leaves: its pages go back to the pool (a shared page loses one holder), its table row to -1, its length to 0; the
+    slot is idle."""
     self.pool.free(self.pages[b])
-    self.pages[b] = []
+    self.pages[b], self.key_lo[b], self.group[b] = [], 0, None
     self._mirror[b] = -1
     self._touch(b)
     self.bound[b], self._live[b] = 0, False
@@ -324,6 +382,7 @@ class PagedKVCache:
     if len(other.pages[j]) > self.max_pages or other.bound[j] > self.Tmax:
       raise ValueError(f'PagedKVCache.adopt: the sequence holds {other.bound[j]} tokens, this cache {self.Tmax} per sequence')
     self.pages[b], other.pages[j] = other.pages[j], []
+    self.key_lo[b], self.group[b], other.key_lo[j], other.group[j] = other.key_lo[j], other.group[j], 0, None
     self._mirror[b, :len(self.pages[b])] = torch.tensor(self.pages[b], dtype=torch.int32)
     other._mirror[j] = -1
     self._touch(b)
@@ -490,6 +549,9 @@ def check_ragged(tokens, counts, cache, fused, dim):
     if cache.bound[b] + c > cache.Tmax:
       raise ValueError(f'{who}: slot {b} holds {cache.bound[b]} tokens, {c} more do not fit max_len {cache.Tmax}')
   check_fused_kind(who, fused)
+  if fused is True and any(cache.key_lo):
+    raise ValueError(f'{who}: fused=True has no cascade variant and the cache holds sequences on shared prefix pages: pass fused=\'wide\' or '
+                     'leave fused off')
   if fused == 'wide':
     if R > ops.FUSED_WIDE_MAX_ROWS:
       raise ValueError(f'{who}: fused=\'wide\' serves at most {ops.FUSED_WIDE_MAX_ROWS} packed rows, got {R}: leave fused off')
@@ -1281,6 +1343,26 @@ class Generation:
       return cache, self.head(last_rows(y, B, Tp, cache.lens), logits, (B,))
 
   @torch.compiler.disable
+  def prefill_prefix(self, tokens, pool):
+    """A prompt prefix kept once on ``pool``: tokens int64 [n]; its first 64 * floor(n / 64) tokens are
+    prefilled as a one-sequence paged cache whose pages the returned ``PagedPrefix`` holds, the tokens past the last whole page are
+    its ``rest``.  Sequences start on it through ``PagedKVCache.admit_prefix`` / ``serve_shared``; ``release()`` it afterwards.  A
+    prefix shorter than a page holds no page: rest is all of it."""
+    refuse_paged_model('prefill_prefix', self)
+    if not isinstance(tokens, torch.Tensor) or tokens.dtype != torch.int64 or tokens.dim() != 1:
+      raise TypeError('Transformer.prefill_prefix: tokens must be a 1-D int64 tensor')
+    if not isinstance(pool, PagePool):
+      raise TypeError(f'Transformer.prefill_prefix: pool must be a PagePool, got {type(pool).__name__}')
+    n = tokens.numel() // ops.KV_PAGE_ROWS * ops.KV_PAGE_ROWS
+    if not n:
+      return PagedPrefix(pool, [], tokens)
+    cache, _ = self.prefill_paged(tokens[:n].view(1, -1), pool, max_len=n)
+    cache.check()
+    prefix = PagedPrefix(pool, cache.pages[0], tokens[n:])
+    cache.pages[0] = []  # the prefix object is the pages' holder now
+    return prefix
+
+  @torch.compiler.disable
   def step_ragged(self, tokens, counts, cache, logits=False, all_rows=False, fused=False):
     """One ragged step on a PagedKVCache: tokens int64 [R], packed in slot order, of which slot b contributes
     counts[b] (host integers: 0 - the slot takes no part, and an idle slot must have 0; 1 - a decode row; or a chunk of a prompt).
@@ -1290,7 +1372,9 @@ class Generation:
     (a slot with count 0 gets row 0's, which means nothing) - with logits=True the bf16 logits [B, V]; with all_rows=True the [R]
     predictions or [R, V] logits of every packed row.  fused=True runs every layer as one ops.ragged_layer_paged call and serves
     R <= ops.FUSED_EXTEND_MAX_ROWS rows, ValueError beyond; fused='wide'  one ops.ragged_layer_paged_wide call
-    and R <= ops.FUSED_WIDE_MAX_ROWS rows, at every R, so that a row's bits do not depend on the step's width.  A non-paged cache raises TypeError; an mxfp8 model, counts that do not sum
+    and R <= ops.FUSED_WIDE_MAX_ROWS rows, at every R, so that a row's bits do not depend on the step's width.  A cache with a live
+    slot on shared prefix pages (``admit_prefix``) attends through ops.attn_ragged_paged_cascade - fused='wide':
+    ops.ragged_layer_paged_wide_cascade; fused=True: ValueError.  A non-paged cache raises TypeError; an mxfp8 model, counts that do not sum
     to R and a count that does not fit max_len raise ValueError.  Runs under no_grad."""
     if not isinstance(cache, PagedKVCache):
       raise TypeError(f'Transformer.step_ragged: the cache must be a PagedKVCache, got {type(cache).__name__} (ragged steps run on pages only)')
@@ -1303,23 +1387,32 @@ class Generation:
       rope = self._rope(tokens.device)
       lens0 = cache.lens  # the lengths before the step: what every layer's append and attention see; moved once, after the last layer
       cache.reserve(counts)
-      cu, row_seq, last_row, NT = ops.ragged_plan(counts)
-      cu, row_seq, last_row, adv = cache.ship(cu, row_seq, last_row, torch.tensor(counts, dtype=torch.int32))
+      adv, cascade = torch.tensor(counts, dtype=torch.int32), ()
+      if any(cache.key_lo):  # a live slot stands on shared pages - every step of this cache attends by the cascade
+        cu, row_seq, last_row, NT, key_lo, tile_rows, tile_seq, tile_keys, NTg, Pcap = ops.cascade_plan(counts, cache.key_lo, cache.group)
+        cu, row_seq, last_row, adv, key_lo, tile_rows, tile_seq, tile_keys = cache.ship(cu, row_seq, last_row, adv, key_lo, tile_rows, tile_seq,
+                                                                                         tile_keys)
+        cascade = (key_lo, tile_rows.view(NTg, -1), tile_seq, tile_keys, NTg, Pcap)
+      else:
+        cu, row_seq, last_row, NT = ops.ragged_plan(counts)
+        cu, row_seq, last_row, adv = cache.ship(cu, row_seq, last_row, adv)
       table, Lcap = cache.table, cache.lcap()
 
       def attend(i, qkv):
         q, _ = ops.kv_paged_append_rope_packed(qkv, lens0, cu, row_seq, rope[0], rope[1], cache.kv[i], table, nh, status=cache.status)
+        if cascade:
+          return ops.attn_ragged_paged_cascade(q, cache.kv[i], table, lens0, cascade[0], cu, row_seq, *cascade[1:4], nh, NT, *cascade[4:], Lcap=Lcap)
         return ops.attn_ragged_paged(q, cache.kv[i], table, lens0, cu, row_seq, nh, NT, Lcap=Lcap)
       flat = tokens.contiguous()
       # fused='wide': every step runs the wide kernels, the narrow ones included, so a sequence's bits never depend on what shared its step
       kind = 'wide' if fused == 'wide' else 'ragged'
-      y = self.fused_layers(flat, cache, rope, (kind, lens0, cu, row_seq, NT)) if fused else self.cached_layers(flat, cache, attend)
+      y = self.fused_layers(flat, cache, rope, (kind, lens0, cu, row_seq, NT) + cascade) if fused else self.cached_layers(flat, cache, attend)
       cache.advance_by(adv)
       if all_rows:
         return self.head(y, logits, (R,))
       return self.head(y.index_select(0, last_row.clamp(min=0).long()), logits, (cache.B,))  # the head runs on at most B rows
 
-  def _serve_ragged(self, who, prompts, budget, total, pages, S, pool, eos_id, fused, C):
+  def _serve_ragged(self, who, prompts, budget, total, pages, S, pool, eos_id, fused, C, prefix=None):
     """serve(prefill_chunk=C): every step is one ``step_ragged`` - a row per decoding slot plus, in slot order, up to C prompt rows of
     the admitted prompts.  A prompt whose last row is in the step gets its first token from it and decodes from the next."""
     N, dev = len(prompts), prompts[0].device
@@ -1339,7 +1432,7 @@ class Generation:
         for b in range(S):  # admission: in prompt order, into the lowest free slot, while the pool can hold the sequence to its end
           if owner[b] is None and waiting and pool.n_free - sum(promised) >= pages[waiting[0]]:
             i = waiting.pop(0)
-            slots.admit(b)
+            slots.admit(b) if prefix is None else slots.admit_prefix(b, prefix)  # serve_shared: on the shared pages
             owner[b], fed[b], left[b], promised[b] = i, 0, budget[i], pages[i]
             done[b] = False
         if all(o is None for o in owner):
@@ -1502,6 +1595,57 @@ class Generation:
             t = t[:int(hit[0]) + 1]
         out.append(t)
       return out
+
+  @torch.compiler.disable
+  def serve_shared(self, prefix, prompts, max_new_tokens, max_batch, pool=None, eos_id=None, fused=False, prefill_chunk=128):
+    """``serve(prefill_chunk=...)`` for prompts that start alike: every sequence is ``prefix`` - a 1-D int64
+    tensor, prefilled here once and released at the end, or a ``PagedPrefix`` of ``prefill_prefix``, which stays the caller's - followed
+    by its own prompt.  The prefix's whole pages are held once for the call and every sequence is admitted onto them
+    (``admit_prefix``); its fed rows are prefix.rest, then its prompt, and every step attends through the cascade.  Admission
+    promises a sequence's OWN pages only.  Returns serve's list of new tokens.  Greedy only; fused is False or 'wide' (the 32-row
+    fused layer has no cascade variant: fused=True raises ValueError); an mxfp8 model and cfg.kv_cache = 'fp8' are refused as in serve."""
+    who = 'serve_shared'
+    refuse_paged_model(who, self)
+    check_fused_kind(who, fused)
+    if fused is True:
+      raise ValueError(f'{who}: fused=True has no cascade variant: pass fused=\'wide\' or leave fused off')
+    if fused == 'wide':
+      check_wide_dim(who, self.cfg.dim)
+    prefill_chunk = check_prefill_chunk(who, prefill_chunk, max_batch, fused)
+    prompts = list(prompts)
+    if not prompts or int(max_batch) < 1:
+      raise ValueError(f'{who}: need at least one prompt and max_batch >= 1')
+    for t in prompts:
+      if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or t.numel() < 1:
+        raise TypeError(f'{who}: every prompt must be a non-empty 1-D int64 tensor')
+    held = isinstance(prefix, PagedPrefix)
+    if not held and (not isinstance(prefix, torch.Tensor) or prefix.dtype != torch.int64 or prefix.dim() != 1):
+      raise TypeError(f'{who}: the prefix must be a 1-D int64 tensor or a PagedPrefix')
+    if held and pool is not None and pool is not prefix.pool:
+      raise ValueError(f'{who}: the PagedPrefix lives on another pool')
+    guard(who, prompts[0], self, forward_only=True)
+    N, S = len(prompts), int(max_batch)
+    budget = [int(max_new_tokens)] * N if isinstance(max_new_tokens, int) else [int(v) for v in max_new_tokens]
+    if len(budget) != N:
+      raise ValueError(f'{who}: {len(budget)} budgets for {N} prompts')
+    n_prefix = prefix.n_tokens + prefix.rest.numel() if held else prefix.numel()
+    shared = n_prefix // ops.KV_PAGE_ROWS  # the pages held once
+    total = [_check_new_tokens(who, n_prefix + prompts[i].numel(), budget[i], 0, '', [('', self.cfg.seq_len)]) for i in range(N)]
+    pages = [-(-t // ops.KV_PAGE_ROWS) - shared for t in total]  # what sequence i holds of its own at the end of its budget
+    if held:
+      pool = prefix.pool
+    elif pool is None:
+      pool = self.new_page_pool(shared + min(S, N) * max(pages))
+    if not held:
+      prefix = self.prefill_prefix(prefix, pool)
+    try:
+      if max(pages) > pool.n_free:
+        raise RuntimeError(f'{who}: the pool has {pool.n_free} free pages beside the prefix, one sequence needs {max(pages)}')
+      return self._serve_ragged(who, [torch.cat([prefix.rest, t]) for t in prompts], budget, total, pages, S, pool, eos_id, fused, prefill_chunk,
+                                prefix=prefix)
+    finally:
+      if not held:
+        prefix.release()
 
   def fork(self, cache, n_samples, max_new_tokens):
     """A SharedPrefixCache for n_samples continuations of every prompt of the prefilled bf16 ``cache``, max_new_tokens suffix rows each.

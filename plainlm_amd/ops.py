@@ -1167,6 +1167,8 @@ from .ops_ragged import (RAGGED_TILE_ROWS, attn_ragged_paged, kv_paged_append_ro
 # ---- the wide fused layer: ragged steps of up to 256 packed rows; its wrappers live in ops_wide.py ----------------------
 from .ops_wide import (FUSED_WIDE_MAX_ROWS, ragged_layer_paged_wide, ragged_norm_qkv_append_paged_wide, wide_gemm_residual,  # noqa: E402,F401
                        wide_norm_fc1_act)
+# ---- shared-prefix pages: cascade attention over a ragged step; its wrappers live in ops_cascade.py -------------------
+from .ops_cascade import attn_ragged_paged_cascade, cascade_plan, ragged_layer_paged_wide_cascade  # noqa: E402,F401
 # ---- the Muon tail: batched NT GEMM, prepare / orthogonalize / apply; its wrappers live in ops_muon.py -------------------
 from .ops_muon import (MUON_ADJUST_LR, MUON_EPS, MUON_NS_COEFFICIENTS, NT_BATCH_GROUP, gemm_nt_batched, muon_adjusted_lr, muon_apply,  # noqa: E402,F401
                        muon_arena, muon_blocks, muon_items, muon_layout, muon_ns_flops, muon_orthogonalize, muon_prepare, muon_set_lr,

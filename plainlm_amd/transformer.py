@@ -601,16 +601,22 @@ class Transformer(nn.Module, G.Generation):
       return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps)[1]
     if isinstance(cache, G.PagedKVCache) and chunk is not None and isinstance(chunk[0], str):
       # ('ragged', lens0, cu_rows, row_seq, NT): the packed rows of a ragged step, ops.ragged_layer_paged per layer
-      if chunk[0] not in ('ragged', 'wide') or len(chunk) != 5 or tokens.shape[0] != chunk[3].shape[0]:
+      # ('wide', ..., key_lo, tile_rows, tile_seq, tile_keys, NTg, Pcap): the same step over shared prefix pages (section 28)
+      cascade = chunk[0] == 'wide' and len(chunk) == 11
+      if chunk[0] not in ('ragged', 'wide') or not (len(chunk) == 5 or cascade) or tokens.shape[0] != chunk[3].shape[0]:
         raise ValueError(f'fused_layers: {tokens.shape[0]} tokens are not the packed rows of a ragged step')
       self.refresh_shadows()
       x = ops.embed_fwd(tokens, self.embed_tokens.weight)
       table, Lcap = cache.table, cache.lcap()
       ragged_layer = ops.ragged_layer_paged_wide if chunk[0] == 'wide' else ops.ragged_layer_paged  # 'wide': DESIGN.md section 27, R <= 256
       for i, layer in enumerate(self.layers):
-        ragged_layer(x, layer.attn_norm.weight, layer.mlp_norm.weight, layer.attn_norm.eps, layer.attn.w_qkv.shadow()[0],
-                     layer.attn.w_out.shadow()[0], layer.mlp.fc1.shadow()[0], layer.mlp.fc2.shadow()[0], chunk[1], chunk[2], chunk[3],
-                     rope[0], rope[1], cache.kv[i], table, self.cfg.n_heads, layer.mlp.kind, cache.status, chunk[4], Lcap=Lcap)
+        w = (x, layer.attn_norm.weight, layer.mlp_norm.weight, layer.attn_norm.eps, layer.attn.w_qkv.shadow()[0], layer.attn.w_out.shadow()[0],
+             layer.mlp.fc1.shadow()[0], layer.mlp.fc2.shadow()[0])
+        tail = (rope[0], rope[1], cache.kv[i], table, self.cfg.n_heads, layer.mlp.kind, cache.status, chunk[4])
+        if cascade:
+          ops.ragged_layer_paged_wide_cascade(*w, chunk[1], chunk[5], chunk[2], chunk[3], *chunk[6:9], *tail, chunk[9], chunk[10], Lcap=Lcap)
+        else:
+          ragged_layer(*w, chunk[1], chunk[2], chunk[3], *tail, Lcap=Lcap)
       return ops.rmsnorm_fwd(x, self.out_norm.weight, self.out_norm.eps)[1]
     if isinstance(cache, G.PagedKVCache):  # the pool and the table in the cache's place, ops.*_layer_paged per layer
       if chunk is not None and (len(chunk) != 3 or tokens.shape[0] != cache.B * chunk[2]):
